@@ -27,6 +27,12 @@ the same JSON line:
 
 Rank 0 prints ONE JSON line.  `value` = uncompressed MiB that went through encode AND decode per second
 (whole job, all ranks), inputs resident in HBM.
+
+A plain run times the headline alone: set-up, warm-up, the timed steps, the round-trip check of every block on
+the device, the line.  Everything else -- the `configs` above, the event-probe pass behind the per-kernel times and
+the rooflines, the encoder bytes against the CPU reference, the host-inclusive figures, the CPU baseline and
+bench_detail.json -- runs with --full.  --dump-outputs DIR writes what the last timed step handed its caller
+(see dump_outputs) as .npy files, so that two builds can be compared output for output.
 """
 import argparse
 import datetime
@@ -57,6 +63,10 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true", help="besides the headline: the `configs`, the event-probe pass (per-kernel times, rooflines), the encoder "
+                                                        "bytes against the CPU reference, the host-inclusive figures, the CPU baseline and bench_detail.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed to DIR/<name>.npy "
+                                                                        "(float32 / float64; see dump_outputs)")
     ap.add_argument("--blocks", type=int, default=100000, help="32 KB blocks per GPU (headline)")
     ap.add_argument("--proba", type=int, default=14)
     ap.add_argument("--workload", choices=["single", "mixed"], default="single", help="headline corpus: one distribution (--proba) or the config-5 mix")
@@ -247,14 +257,14 @@ def checker_lib():
         return None
 
 
-def check_parity(cd, rank, n_check=0):
-    """untimed gates: round trip on every block; encoder bytes and return values of EVERY block (n_check = 0; else a strided sample)
-    against the compiled reference (or the oracle when oracle/_ref is absent)"""
+def check_parity(cd, rank, n_check=0, reference=True):
+    """untimed gates: round trip on every block; with `reference`, encoder bytes and return values of EVERY block (n_check = 0; else a
+    strided sample) against the compiled reference (or the oracle when oracle/_ref is absent)"""
     nb = cd.src.shape[0]
     assert bool((cd.dres == BLOCK).all()), "%s decode return values wrong" % cd.name
     assert torch.equal(cd.out, cd.src), "%s decode(encode(x)) != x" % cd.name
     parity = "roundtrip-all-blocks"
-    if rank != 0:
+    if rank != 0 or not reference:
         return parity, 0
     lib = checker_lib()
     if lib is None:
@@ -485,13 +495,53 @@ def ragged_case(hip, dev, n_blocks=20000, reps=5):
     return rec
 
 
-PLAIN = False          # --plain: see parse()
+DUMP_SEED = 20240601       # the fixed sample of --dump-outputs
+DUMP_SAMPLE_BLOCKS = 96    # blocks per codec whose slots and decoded bytes are written (about 25 MB per codec in float32)
+DUMP_MAX_SIZES = 262144    # blocks per codec whose sizes are written; a larger batch writes a fixed sample of this many
+DUMP_LIMIT = 64 << 20
 
 
-def run_case(hip, codecs, steps, warmup, barrier, rank, check=True, n_check=0):
+def dump_outputs(path, codecs):
+    """--dump-outputs: what the last timed step handed its caller, per codec `<c>` in `codecs` (rank 0's batch):
+        <c>_compressed_sizes.npy   float64 [n]         the encoder's return value per block
+        <c>_decoded_sizes.npy      float64 [n]         the decoder's return value per block
+        <c>_compressed_sample.npy  float32 [k, cap]    the compressed slots of k sampled blocks; bytes past a block's return value
+                                                       are not part of the result and are written as 0
+        <c>_decoded_sample.npy     float32 [k, 32768]  the decoded blocks of the same k
+    n = every block up to DUMP_MAX_SIZES, k = DUMP_SAMPLE_BLOCKS; samples are drawn with the fixed seed DUMP_SEED, so that runs
+    with the same arguments write the same blocks."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for cd in codecs:
+        nb = cd.src.shape[0]
+        rng = np.random.default_rng(DUMP_SEED)
+        rows = np.arange(nb) if nb <= DUMP_MAX_SIZES else np.sort(rng.choice(nb, DUMP_MAX_SIZES, replace=False))
+        sample = np.sort(rng.choice(nb, min(DUMP_SAMPLE_BLOCKS, nb), replace=False))
+        res = cd.res.cpu().numpy()
+        arrays[cd.name + "_compressed_sizes"] = res[rows].astype(np.float64)
+        arrays[cd.name + "_decoded_sizes"] = cd.dres.cpu().numpy()[rows].astype(np.float64)
+        sel = torch.from_numpy(sample).to(cd.src.device)
+        slots = cd.dst[sel].cpu().numpy()
+        used = res[sample]
+        used = np.where((used >= 0) & (used <= cd.cap), used, 0)
+        slots[np.arange(cd.cap)[None, :] >= used[:, None]] = 0
+        arrays[cd.name + "_compressed_sample"] = slots.astype(np.float32)
+        arrays[cd.name + "_decoded_sample"] = cd.out[sel].cpu().numpy().astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, "--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+PLAIN = False          # --plain, or a run without --full: see parse()
+FULL = False           # --full: see parse()
+
+
+def run_case(hip, codecs, steps, warmup, barrier, rank, check=True, n_check=0, on_timed=None):
     """time `steps` steps (each: encode + decode of every codec in `codecs`), bracketed by barrier + synchronize, with the
-    kernel probe OFF; then the same steps once more with every launch of the library bracketed by HIP events on its stream
-    (FSEHIP_probe_*) for the per-kernel table and the roofline.  Returns the raw timings of this rank and the per-kernel probe."""
+    kernel probe OFF; `on_timed(codecs)` sees the buffers as the last timed step left them; then (unless PLAIN) the same steps
+    once more with every launch of the library bracketed by HIP events on its stream (FSEHIP_probe_*) for the per-kernel table
+    and the roofline.  Returns the raw timings of this rank and the per-kernel probe."""
     for _ in range(warmup):
         for cd in codecs:
             cd.encode(); cd.decode()
@@ -507,6 +557,8 @@ def run_case(hip, codecs, steps, warmup, barrier, rank, check=True, n_check=0):
             cd.decode(); ev[k].record(); k += 1
     barrier()
     elapsed = time.perf_counter() - t0
+    if on_timed is not None:
+        on_timed(codecs)
     # probe pass (not part of `value`)
     ms = (C.c_double * 16)(); launches = (C.c_uint * 16)()
     probe_elapsed = 0.0
@@ -531,7 +583,7 @@ def run_case(hip, codecs, steps, warmup, barrier, rank, check=True, n_check=0):
     for cd in codecs:
         out["csize"][cd.name] = float(cd.res.sum().item()) / cd.src.shape[0]
         if check:
-            out["parity"][cd.name], n = check_parity(cd, rank, n_check)
+            out["parity"][cd.name], n = check_parity(cd, rank, n_check, reference=FULL)
             out["parity_blocks_checked"] += n
     return out
 
@@ -792,10 +844,13 @@ def summarize(r, codecs, nb, steps, world, reduce_max, total_blocks=None, traffi
 
 def main():
     args = parse()
-    global PLAIN
-    PLAIN = args.plain
+    global PLAIN, FULL
+    FULL = args.full
+    PLAIN = args.plain or not FULL
     if PLAIN:
         args.no_host_inclusive = args.no_cpu_baseline = True
+    if not FULL:
+        args.no_configs = True
     launch_ranks_if_needed(args)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -887,15 +942,21 @@ def main():
     src = gen(head_proba, nb, rank * nb)
     head_names = ("fse", "huf") if args.codec == "both" else (args.codec,)
     codecs = [Codec(hip, n, src, pools, args.table_log, args.max_log) for n in head_names]
-    r = run_case(hip, codecs, args.steps, args.warmup, barrier, rank, n_check=args.parity_blocks)
+    dump = None
+    if args.dump_outputs and rank == 0:
+        def dump(cds):
+            dump_outputs(args.dump_outputs, cds)
+    r = run_case(hip, codecs, args.steps, args.warmup, barrier, rank, n_check=args.parity_blocks, on_timed=dump)
     head, vals = summarize(r, codecs, nb, args.steps, world, reduce_max)
     elapsed = vals[0]
     dom_codec = max(head_names, key=lambda n: max(r["per"].get(k, (0, 0))[0] for k in HOT[n]))
-    head_roof = roofline(r["per"], dom_codec, r["csize"][dom_codec], nb, args.steps, traffic_tag="")
-    enc_roof = roofline(r["per"], dom_codec, r["csize"][dom_codec], nb, args.steps, traffic_tag="",
-                        kernels=[k for k in HOT[dom_codec] if "encode" in k])
-    head_roof["measured_over"] = ("%d steps repeated with the event probe on, directly after the timed region (%.3f ms per step with the probe, %.3f without)"
-                                  % (args.steps, r["probe_elapsed"] / args.steps * 1e3, r["elapsed"] / args.steps * 1e3))
+    head_roof = enc_roof = None
+    if FULL:
+        head_roof = roofline(r["per"], dom_codec, r["csize"][dom_codec], nb, args.steps, traffic_tag="")
+        enc_roof = roofline(r["per"], dom_codec, r["csize"][dom_codec], nb, args.steps, traffic_tag="",
+                            kernels=[k for k in HOT[dom_codec] if "encode" in k])
+        head_roof["measured_over"] = ("%d steps repeated with the event probe on, directly after the timed region (%.3f ms per step with the probe, %.3f without)"
+                                      % (args.steps, r["probe_elapsed"] / args.steps * 1e3, r["elapsed"] / args.steps * 1e3))
     if rank == 0 and dom_codec == "fse" and not PLAIN:
         try:
             sec = secondary_roofline(hip, codecs[head_names.index("fse")], hip.device_info())
@@ -1033,9 +1094,9 @@ def main():
                    "blocks_per_gpu": nb, "block_bytes": BLOCK, "codec": args.codec, "parity": head.get("parity"),
                    "compressed_bytes_per_block": head["%s_compressed_bytes_per_block" % head_names[0]]},
         "encode_GBps": head["%s_encode_GBps" % head_names[0]], "decode_GBps": head["%s_decode_GBps" % head_names[0]],
-        "roofline": head_roof, "roofline_encode": enc_roof,
-        "kernel_ms_per_step": head["kernel_ms_per_step"],
     }
+    if FULL:
+        line.update({"roofline": head_roof, "roofline_encode": enc_roof, "kernel_ms_per_step": head["kernel_ms_per_step"]})
     if rccl is not None:
         line["rccl"] = rccl
     if len(head_names) > 1:
@@ -1066,7 +1127,7 @@ def main():
                                           "gather_GBps": links.get("gather"), "roundtrip_ok": wc.get("roundtrip_ok")}
                     if wc.get("error"):
                         extra["with_comm"]["error"] = wc["error"][:160]
-        print(compact_line(line, extra, write_detail(line)))
+        print(compact_line(line, extra, write_detail(line) if FULL else None))
         sys.stdout.flush()
 
     if comm_leg is not None:
@@ -1207,7 +1268,8 @@ def compact_line(full, extra=None, detail_path=None):
     cfg = full["config"]
     line["config"] = {k: cfg[k] for k in ("workload", "blocks_per_gpu", "block_bytes", "codec", "parity") if k in cfg}
     line["encode_GBps"], line["decode_GBps"] = full["encode_GBps"], full["decode_GBps"]
-    line["roofline"] = {k: full["roofline"].get(k) for k in ROOF_KEYS}
+    if full.get("roofline"):
+        line["roofline"] = {k: full["roofline"].get(k) for k in ROOF_KEYS}
     if full.get("roofline_encode"):
         line["roofline_encode"] = {k: full["roofline_encode"].get(k) for k in ROOF_KEYS}
     cb = full.get("cpu_baseline")

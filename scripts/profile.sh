@@ -2,7 +2,8 @@
 # Collects the rocprofv3 evidence behind profiles/ on the GPU box (run through gpurun from the repository root):
 #   scripts/profile.sh <run-name>        ->  gpurun_out/<run-name>_{fse,huf}/{trace,pmc_fetch,pmc_write,pmc_rd,pmc_wr,pmc_sq1,pmc_sq2}
 # then, back in the container:  python scripts/pmc_summary.py gpurun_out/<run>_fse r03_fse 20000   (and _huf)
-# bench.py runs with --plain: warm-up + timed steps only, so every kernel is launched exactly warmup + steps times.
+# bench.py runs with --plain: warm-up + timed steps only, so every kernel is launched exactly warmup + steps times (with --full where a
+# record of `configs` is wanted).
 # Counters are collected in passes of their own (--pmc never together with tracing domains other than the kernel trace).
 #   pmc_fetch / pmc_write : FETCH_SIZE / WRITE_SIZE, the derived counters MI355X_MICROARCH.md prescribes (FETCH_SIZE x2 on gfx950)
 #   pmc_rd / pmc_wr       : the L2's memory-side request counters by request size (32 / 64 / 128 B), an exact byte count that
@@ -51,14 +52,14 @@ fi
 # the 16-bit-symbol coder: its kernels (k_u16_*) beside the headline's in one run
 O=$R/gpurun_out/${RUN}_u16pmc
 mkdir -p $O
-B="python $R/bench.py --codec fse --configs fse_u16 --u16-blocks 20000 --plain"
+B="python $R/bench.py --codec fse --configs fse_u16 --u16-blocks 20000 --plain --full"
 timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o bench -- $B $P > $O/fetch.log 2>&1
 timeout 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o bench -- $B $P > $O/write.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- $B --steps 5 --warmup 2 > $O/trace.log 2>&1
 for extra in fse_u16 ${PROFILE_U16_ONLY:+} $([ -z "$PROFILE_U16_ONLY" ] && echo using_tables); do
     O=$R/gpurun_out/${RUN}_$extra
     mkdir -p $O
-    timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- python $R/bench.py --codec fse --configs $extra --plain --steps 5 --warmup 2 > $O/trace.log 2>&1
+    timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- python $R/bench.py --codec fse --configs $extra --plain --full --steps 5 --warmup 2 > $O/trace.log 2>&1
 done
 # the using-table calls, one record per run (the headline of the same run uses the record's distribution, so that kernels both of them launch see one kind
 # of data); python scripts/pmc_summary.py --ut gpurun_out/<run> <tag> 20000 turns them into profiles/traffic_<kernel>_ut_<key>.json
@@ -67,7 +68,7 @@ for rec in fse_p14:fse:14 fse_p80:fse:80 huf_p14:fse:14; do
     key=${rec%%:*}; rest=${rec#*:}; codec=${rest%%:*}; proba=${rest#*:}
     O=$R/gpurun_out/${RUN}_ut_$key
     mkdir -p $O
-    B="python $R/bench.py --codec $codec --proba $proba --configs using_tables --ut-keys $key --plain"
+    B="python $R/bench.py --codec $codec --proba $proba --configs using_tables --ut-keys $key --plain --full"
     timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o bench -- $B $P > $O/fetch.log 2>&1
     timeout 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o bench -- $B $P > $O/write.log 2>&1
 done

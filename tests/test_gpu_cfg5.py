@@ -67,7 +67,7 @@ def _run_bench(extra, env=None, timeout=900):
 def test_bench_two_ranks_start_from_gpus_flag():
     """`python bench.py --gpus 2` with no launcher around it starts two ranks itself, reports n_gpus == 2, codes the fixed corpus of
     config 5 as two shards (strong scaling) and round-trips the with-comm variant (scatter, both codecs, gather)."""
-    short, line = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--blocks", "4096", "--cfg5-blocks", "3000", "--cfg5-total", "8001",
+    short, line = _run_bench(["--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--blocks", "4096", "--cfg5-blocks", "3000", "--cfg5-total", "8001",
                        "--configs", "cfg5_mixed_shard,cfg5_mixed_1M", "--no-cpu-baseline", "--no-host-inclusive", "--comm-passes", "2",
                        "--parity-blocks", "512"],
                       env={"FSEHIP_BENCH_BACKEND": "gloo"})
@@ -97,7 +97,7 @@ def test_bench_two_ranks_start_from_gpus_flag():
 def test_bench_two_ranks_comm_watchdog_keeps_the_line():
     """the with-comm leg runs last, under a watchdog: when it does not finish in time (here: at once) rank 0 still prints the line --
     every other figure in place, an error record where the leg's would be -- and every rank leaves"""
-    short, line = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--blocks", "2048", "--cfg5-total", "6001",
+    short, line = _run_bench(["--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--blocks", "2048", "--cfg5-total", "6001",
                        "--configs", "cfg5_mixed_1M", "--no-cpu-baseline", "--no-host-inclusive", "--comm-passes", "2", "--parity-blocks", "256",
                        "--comm-timeout", "0"],
                       env={"FSEHIP_BENCH_BACKEND": "gloo"})
@@ -109,7 +109,7 @@ def test_bench_two_ranks_comm_watchdog_keeps_the_line():
 
 
 def test_bench_one_gpu_line_has_the_contract_fields():
-    short, line = _run_bench(["--steps", "2", "--warmup", "1", "--blocks", "8192", "--configs", "cfg5_mixed_1M", "--cfg5-total", "9000",
+    short, line = _run_bench(["--full", "--steps", "2", "--warmup", "1", "--blocks", "8192", "--configs", "cfg5_mixed_1M", "--cfg5-total", "9000",
                               "--cpu-sample-blocks", "1024", "--cpu-seconds", "0.2", "--parity-blocks", "256"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline",
               "roofline_encode", "cpu_baseline", "configs", "detail"):
@@ -136,3 +136,37 @@ def test_bench_one_gpu_line_has_the_contract_fields():
     pk = hi["packed"]                              # the same pipeline with packed results: fewer bytes over the link, same bytes back
     assert pk.get("error") is None and pk["roundtrip_ok"] is True and pk["pcie_bytes"]["encode"] < hi["pcie_bytes"]["encode"]
     assert line["configs"]["cfg5_mixed_1M"]["corpus_blocks"] == 9000 and line["configs"]["cfg5_mixed_1M"]["scaling"] == "strong"
+
+
+def test_bench_plain_run_times_the_headline_and_dumps_its_outputs(hip, tmp_path):
+    """a run without --full: the headline alone (no configs, rooflines, CPU legs or detail file), exactly --steps timed steps, and
+    --dump-outputs writes what the last step computed -- float arrays within 64 MB that match the same call made here"""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--blocks", "2048", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1 and p.stdout.rstrip("\n").splitlines()[-1] == lines[0], p.stdout[-2000:]
+    short = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in short, k
+    assert short["steps"] == 3 and short["warmup"] == 1 and short["ms_per_step"] > 0 and short["value"] > 0 and short["dtype"] == "u8"
+    assert short["higher_is_better"] is True and short["config"]["blocks_per_gpu"] == 2048
+    for k in ("configs", "cpu_baseline", "roofline", "roofline_encode", "host_inclusive"):
+        assert k not in short, k
+    assert short["detail"] is None
+    files = {f.name: np.load(f) for f in tmp_path.iterdir()}
+    assert set(files) == {"fse_compressed_sizes.npy", "fse_decoded_sizes.npy", "fse_compressed_sample.npy", "fse_decoded_sample.npy"}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    src = hip.probagen_batch(14, 2048, 32768, first_seed=1)
+    dst, res = hip.fse_compress_batch(src, table_log=11)
+    assert (files["fse_compressed_sizes.npy"] == res.cpu().numpy().astype(np.float64)).all()
+    assert (files["fse_decoded_sizes.npy"] == 32768).all()
+    rows = {bytes(r): b for b, r in enumerate(src.cpu().numpy())}
+    dec, comp = files["fse_decoded_sample.npy"], files["fse_compressed_sample.npy"]
+    assert dec.shape == (96, 32768) and comp.shape[0] == 96
+    dh, rh = dst.cpu().numpy(), res.cpu().numpy()
+    for k in range(dec.shape[0]):
+        b = rows[bytes(dec[k].astype(np.uint8))]          # every sampled decoded block is one of the sources ...
+        n = int(rh[b])                                     # ... and its compressed slot is that block's bytes, zero past its size
+        assert (comp[k][:n] == dh[b][:n]).all() and not comp[k][n:].any()
