@@ -124,7 +124,7 @@ __global__ __launch_bounds__(64) void k_fse_cprep(FseCPrepArgs a, u32 capTs)
 //                  internal.h and leaves the counters in scratch;
 //   k_fse_dbuild : one wave per block -- FSE_buildDTable (lib/fse_decompress.c:71-126) with the wave-cooperative
 //                  spread / rank of fse_wave_build.h, emitting the decoder's compact cell formats (u16 cell, symbol in
-//                  a separate byte table; bit-reversed layout when maxLog <= 11, see fse_decode.hip) with coalesced stores.
+//                  a separate byte table; bit-reversed layout when maxLog <= 11, see fse_decode.hip) straight to global memory.
 __global__ __launch_bounds__(64) void k_fse_dparse(FseDPrepArgs a)
 {
     const size_t b = (size_t)blockIdx.x * 64 + threadIdx.x;
@@ -214,35 +214,21 @@ __global__ __launch_bounds__(64) void k_fse_dbuild(FseDPrepArgs a, u32 capTs, in
     __syncthreads();
     const u32 tl = m.tableLog, ts = 1u << tl;
     const bool rev = ((m.state >> 2) & 3u) != FSE_DCLS_PLAIN;              // uniform
+    u16* const A = a.atab + b * capTs;
+    u8* const S = a.symtab + b * capTs;
     const bool fast = wave_spread_rank(w, m.maxSV, tl, lane, [&](u32 s) { return (u32)(int)w.nrm[s]; }, [&](u32 u, u32 s, u32 r, u32 nrm) {
-        (void)s;
         const int n = (int)nrm;
         const u32 next = (n > 0 ? (u32)n : 1u) + r;                        // symbolNext[s]++, fse_decompress.c:117-122
         const u32 nb = tl - hibit32(next);
         const u32 ns = (next << nb) - ts;
         // bit-reversed format (see fse_decode.hip): nbBits | rev_tl(newState) << 5 (rev_tl(newState) < 2048: tableLog <= 11, or
-        // tableLog 12 with nbBits >= 1, i.e. newState even); the cell of state u goes to position rev_tl(u), which the copy-out
-        // below takes care of
-        if (rev) w.cell[wb_ci(u)] = (u16)(nb | ((__brev(ns) >> (32u - tl)) << 5));
-        else     w.cell[wb_ci(u)] = (u16)((ns & 0xFFFu) | (nb << 12));
+        // tableLog 12 with nbBits >= 1, i.e. newState even), the cell of state u at position rev_tl(u).  Stored straight to the
+        // block's tables: lane l emits cells l*C + i, whose positions rev_tl(l*C + i) = rev(i) * 64 + rev(l) make every store
+        // instruction of the wave one contiguous run of 64 cells.  (The plain layout's stores are scattered; it is off the hot path.)
+        const u32 x = rev ? __brev(u) >> (32u - tl) : u;
+        A[x] = rev ? (u16)(nb | ((__brev(ns) >> (32u - tl)) << 5)) : (u16)((ns & 0xFFFu) | (nb << 12));
+        S[x] = (u8)s;
     });
-    u32* const A32 = (u32*)(a.atab + b * capTs);
-    u32* const S32 = (u32*)(a.symtab + b * capTs);
-    if (ts < 4u) {                                                         // uniform: a table of two cells (FSE_buildDTable on a caller's counters; no header says tableLog 1)
-        if (lane < ts) { const u32 x = rev ? __brev(lane) >> (32u - tl) : lane; (a.atab + b * capTs)[lane] = w.cell[wb_ci(x)]; (a.symtab + b * capTs)[lane] = w.symTab[wb_si(x)]; }
-    } else if (rev) {
-        const u32 rs = 32u - tl;                                           // tl >= FSE_MIN_TABLELOG = 5
-        for (u32 i = lane; i < ts / 2; i += 64)
-            A32[i] = (u32)w.cell[wb_ci(__brev(2u * i) >> rs)] | ((u32)w.cell[wb_ci(__brev(2u * i + 1u) >> rs)] << 16);
-        for (u32 i = lane; i < ts / 4; i += 64) {
-            u32 y = 0;
-            for (u32 k = 0; k < 4; ++k) y |= (u32)w.symTab[wb_si(__brev(4u * i + k) >> rs)] << (8u * k);
-            S32[i] = y;
-        }
-    } else {
-        for (u32 i = lane; i < ts / 2; i += 64) A32[i] = *(const u32*)(w.cell + wb_ci(2u * i));
-        for (u32 i = lane; i < ts / 4; i += 64) S32[i] = *(const u32*)(w.symTab + wb_si(4u * i));
-    }
     if (lane == 0) a.meta[b].state = m.state | (fast ? 2u : 0u);
 }
 

@@ -36,28 +36,37 @@ __device__ unsigned long long g_wbTiming[4096 * 8];
 #else
 #define WBT(k)
 #endif
-struct WaveBuildLds {        // LDS scratch of one wave, tableSize = 1 << tl <= capTs
+// LDS of one wave, tableSize = 1 << tl <= capTs.  Two pairs of arrays share their bytes, each pair being used in phases that a
+// barrier separates: the spread's marks and the rank matrix (the marks are dead once the spread is done), the cells' symbols and
+// the running sums (every lane holds the symbols of its own cells in registers from the first rank pass on).  The local ranks
+// never go to LDS: they stay in the lane's registers from the rank pass to the emit pass.
+struct WaveBuildLds {
     s16* nrm;                // [256] normalized counters, zero beyond maxSV (input)
     u16* cumP;               // [257] (unused by the core; callers may use it)
     u8*  symP;               // [256] symbols in use (counter != 0), ascending
-    u8*  symTab;             // [wb_si(capTs)] symbol of every cell (output of the spread), index through wb_si()
-    u16* cell;               // [wb_ci(capTs)] rank inside the lane range, index through wb_ci(); the emitter may overwrite cell[wb_ci(u)] with its result
+    u8*  symTab;             // [wb_si(capTs)] symbol of every cell (output of the spread), index through wb_si(); shares its bytes with coarse
+    u16* marks;              // [wb_ci(capTs)] scratch of the spread, index through wb_ci(); shares its bytes with cnt
     u32* cnt;                // [WB_WIN * 16] byte matrix cnt[symbol - window base][lane]
     u16* coarse;             // [WB_WIN * 16] per symbol of the window: cells before lane group j (4 lanes per group)
 };
-// cell[] / symTab[] are indexed through wb_ci() / wb_si(): every row of 32 cells is followed by 4 bytes of padding.  Lane l
+// marks[] / symTab[] are indexed through wb_ci() / wb_si(): every row of 32 cells is followed by 4 bytes of padding.  Lane l
 // works on cells [l*C, (l+1)*C) (C = 32 at tableLog 11), so without the padding the 64 lanes of one LDS instruction
 // would sit 64 (or 32) bytes apart -- on 2 (4) of the 32 banks; with it they are 17 (9) dwords apart: conflict-free.
-__host__ __device__ inline u32 wb_ci(u32 u) { return u + ((u >> 5) << 1); }     // u16 arrays (cell, marks)
+__host__ __device__ inline u32 wb_ci(u32 u) { return u + ((u >> 5) << 1); }     // u16 array (marks)
 __host__ __device__ inline u32 wb_si(u32 u) { return u + ((u >> 5) << 2); }     // u8 array (symTab)
-__host__ __device__ inline size_t wave_build_lds_bytes(u32 capTs) { return WB_WIN * 64 + WB_WIN * 32 + 2 * (size_t)wb_ci(capTs) + wb_si(capTs) + 512 + 520 + 256; }
+// A/B aid: unused LDS per build, i.e. fewer waves per CU (how much do the builders live on residency?)
+#ifndef WB_EXTRA_LDS
+#define WB_EXTRA_LDS 0u
+#endif
+__host__ __device__ inline size_t wb_part_a(u32 capTs) { const size_t m = 2 * (size_t)wb_ci(capTs); return m > WB_WIN * 64 ? m : WB_WIN * 64; }   // cnt | marks
+__host__ __device__ inline size_t wb_part_b(u32 capTs) { const size_t t = wb_si(capTs); return t > WB_WIN * 32 ? t : WB_WIN * 32; }           // symTab | coarse
+// 7,944 bytes at tableLog 11 (20 builds per CU by LDS; the kernels' 113 VGPRs allow 16), 14,600 at tableLog 12
+__host__ __device__ inline size_t wave_build_lds_bytes(u32 capTs) { return wb_part_a(capTs) + wb_part_b(capTs) + 512 + 520 + 256 + WB_EXTRA_LDS; }
 DEV WaveBuildLds wave_build_carve(u8* base, u32 capTs)
 {
     WaveBuildLds w;
-    w.cnt = (u32*)base; base += WB_WIN * 64;             // 16-byte aligned parts first
-    w.coarse = (u16*)base; base += WB_WIN * 32;
-    w.cell = (u16*)base; base += 2 * (size_t)wb_ci(capTs);
-    w.symTab = base; base += wb_si(capTs);
+    w.cnt = (u32*)base; w.marks = (u16*)base; base += wb_part_a(capTs);   // 16-byte aligned parts first (both sizes are multiples of 16)
+    w.coarse = (u16*)base; w.symTab = base; base += wb_part_b(capTs);
     w.nrm = (s16*)base; base += 512;
     w.cumP = (u16*)base; base += 520;
     w.symP = base;
@@ -79,6 +88,11 @@ DEV u32 wb_scan_excl(u32 v, u32 lane, u32* total)         // exclusive prefix su
     return incl - v;
 }
 
+// an empty asm that "changes" v: what is computed from v per group cannot be hoisted out of the window loop (the compiler would
+// otherwise keep the symbols, addresses and masks of all 64 cells live at once: 256 VGPRs)
+DEV void wb_opaque(u32& v) { asm volatile("" : "+v"(v)); }
+#define WB_MAXC ((1u << FSEHIP_FSE_MAX_TABLELOG) >> 6)                   // cells per lane at the largest table (64)
+
 // All 64 lanes of one wave call this with uniform arguments; w.nrm holds the counters.  Uses __syncthreads(), so the
 // workgroup must be exactly this wave.  Returns the fastMode flag of FSE_buildDTable (no counter >= tableSize/2).
 template <class Payload, class Emit>
@@ -92,7 +106,7 @@ DEV bool wave_spread_rank(const WaveBuildLds& w, u32 maxSV, u32 tl, u32 lane, Pa
     const u32 C = ts >= 64 ? ts >> 6 : 1;                                 // cells (and visits) per lane
     const bool act = lane * C < ts;
     const u32 m0 = lane * C;
-    u16* const marks = w.cell;                                            // [ts] scratch of the spread (cell[] is not in use yet)
+    u16* const marks = w.marks;                                           // [ts] scratch of the spread (cnt[] is not in use yet)
     // ---- per symbol: lane l looks after symbols 4l .. 4l+3
     int n[4];
     {   const uint2 raw = *(const uint2*)(w.nrm + 4 * lane);
@@ -111,7 +125,7 @@ DEV bool wave_spread_rank(const WaveBuildLds& w, u32 maxSV, u32 tl, u32 lane, Pa
     u32 posBase = base3 & 0x1FFFu, lowBase = (base3 >> 13) & 0x1FFu, anyBase = base3 >> 22;
     const u32 nLow = (totals >> 13) & 0x1FFu, nAny = totals >> 22;
     const int high = (int)ts - 1 - (int)nLow;                             // highThreshold (-1: every cell is a low-probability one)
-    // clear the spread marks and the count matrix rows in use
+    // clear the spread marks
     if (act) { if (C >= 2) for (u32 i = 0; i < C; i += 2) *(u32*)(marks + wb_ci(m0 + i)) = 0; else marks[wb_ci(m0)] = 0; }
     __syncthreads();
     WBT(1)
@@ -172,9 +186,27 @@ DEV bool wave_spread_rank(const WaveBuildLds& w, u32 maxSV, u32 tl, u32 lane, Pa
     __syncthreads();
     WBT(3)
 
+    // ---- the symbols of my cells, four to a register (sym[c >> 2] byte c & 3 = symbol of cell m0 + c), and their ranks inside
+    //      my range, packed the same way (a rank is < C <= 64).  Cells go in groups of eight; C is 1, 2 or 4 (one partial group)
+    //      or a multiple of 8.  The loops over the groups are unrolled so that the arrays stay in registers.
+    const u32 nj = C < 8 ? C : 8;                                         // cells per group
+    u32 sym[WB_MAXC / 4], lr[WB_MAXC / 4];
+#pragma unroll
+    for (u32 q = 0; q < WB_MAXC / 4; ++q) { sym[q] = 0; lr[q] = 0; }
+    if (act) {
+        if (C >= 8) {
+#pragma unroll
+            for (u32 g = 0; g < WB_MAXC / 8; ++g)
+                if (8 * g < C) {
+                    const u32* const syp = (const u32*)(w.symTab + wb_si(m0 + 8 * g));   // 8 cells of one row: two aligned dwords
+                    sym[2 * g] = syp[0]; sym[2 * g + 1] = syp[1];
+                }
+        } else {
+#pragma unroll
+            for (u32 j = 0; j < 4; ++j) if (j < C) sym[0] |= (u32)w.symTab[wb_si(m0 + j)] << (8 * j);
+        }
+    }
     // ---- per window of WB_WIN symbols: rank inside the lane range, running sums over the lane groups, emit.
-    //      (The emitter may overwrite cell[wb_ci(u)] of the cells it is called for; the other cells still hold their
-    //      local rank, which later windows read.)
     const u32 sh8 = 8 * (lane & 3u), grp = lane >> 2;
     const u32 belowMask = (1u << sh8) - 1u;
     const bool single = maxSV < WB_WIN;                                   // uniform: one window, nothing to predicate
@@ -184,36 +216,29 @@ DEV bool wave_spread_rank(const WaveBuildLds& w, u32 maxSV, u32 tl, u32 lane, Pa
         }
         __syncthreads();
         // rank inside the lane range: LDS atomics return the previous count, in program order.  Eight cells at a time so
-        // that the LDS round trips overlap (the symbols of a lane's cells are contiguous bytes).
+        // that the LDS round trips overlap.  A cell of a later window keeps the rank an earlier window gave it.
         if (act) {
-            u32 i = 0;
-            for (; i + 8 <= C; i += 8) {
-                const u32* const syp = (const u32*)(w.symTab + wb_si(m0 + i));    // 8 cells of one row: two aligned dwords
-                const uint2 sy = make_uint2(syp[0], syp[1]);
-                u32* const cp = (u32*)(w.cell + wb_ci(m0 + i));
-                uint4 prev = make_uint4(0, 0, 0, 0);
-                if (!single) prev = make_uint4(cp[0], cp[1], cp[2], cp[3]);        // local ranks written by earlier windows
+#pragma unroll
+            for (u32 g = 0; g < WB_MAXC / 8; ++g) {
+                if (8 * g >= C) break;                                    // uniform
+                wb_opaque(sym[2 * g]); wb_opaque(sym[2 * g + 1]);
                 u32 old[8]; bool in[8];
 #pragma unroll
                 for (u32 j = 0; j < 8; ++j) {
-                    const u32 s = (((j < 4 ? sy.x : sy.y) >> (8 * (j & 3))) & 0xFFu) - base;
-                    in[j] = single || s < WB_WIN;
+                    const u32 s = ((sym[2 * g + (j >> 2)] >> (8 * (j & 3))) & 0xFFu) - base;
+                    in[j] = j < nj && (single || s < WB_WIN);
                     old[j] = 0;
                     if (in[j]) old[j] = atomicAdd(&w.cnt[s * 16 + grp], 1u << sh8);
                 }
 #pragma unroll
-                for (u32 j = 0; j < 8; ++j) {
-                    const u32 pw = j < 2 ? prev.x : j < 4 ? prev.y : j < 6 ? prev.z : prev.w;
-                    old[j] = in[j] ? (old[j] >> sh8) & 0xFFu : (pw >> (16 * (j & 1))) & 0xFFFFu;
-                }
-                cp[0] = old[0] | (old[1] << 16); cp[1] = old[2] | (old[3] << 16); cp[2] = old[4] | (old[5] << 16); cp[3] = old[6] | (old[7] << 16);
-            }
-            for (; i < C; ++i) {
-                const u32 u = m0 + i;
-                const u32 s = (u32)w.symTab[wb_si(u)] - base;
-                if (single || s < WB_WIN) {
-                    const u32 old = atomicAdd(&w.cnt[s * 16 + grp], 1u << sh8);
-                    w.cell[wb_ci(u)] = (u16)((old >> sh8) & 0xFFu);
+                for (u32 h = 0; h < 2; ++h) {
+                    u32 r = lr[2 * g + h];
+#pragma unroll
+                    for (u32 k = 0; k < 4; ++k) {
+                        const u32 j = 4 * h + k;
+                        if (in[j]) r = (r & ~(0xFFu << (8 * k))) | (((old[j] >> sh8) & 0xFFu) << (8 * k));
+                    }
+                    lr[2 * g + h] = r;
                 }
             }
         }
@@ -239,35 +264,24 @@ DEV bool wave_spread_rank(const WaveBuildLds& w, u32 maxSV, u32 tl, u32 lane, Pa
         WBT(5)
         // emit: everything a cell needs is gathered for eight cells before the first one is emitted
         if (act) {
-            u32 i = 0;
-            for (; i + 8 <= C; i += 8) {
-                const u32* const syp = (const u32*)(w.symTab + wb_si(m0 + i));
-                const uint2 sy = make_uint2(syp[0], syp[1]);
-                const u32* const cp = (const u32*)(w.cell + wb_ci(m0 + i));
-                const uint4 lr = make_uint4(cp[0], cp[1], cp[2], cp[3]);
+#pragma unroll
+            for (u32 g = 0; g < WB_MAXC / 8; ++g) {
+                if (8 * g >= C) break;                                    // uniform
+                wb_opaque(sym[2 * g]); wb_opaque(sym[2 * g + 1]);
+                u32 mg = m0 + 8 * g; wb_opaque(mg);
                 u32 sf[8], co[8], cn[8], pl[8]; bool in[8];
 #pragma unroll
                 for (u32 j = 0; j < 8; ++j) {
-                    sf[j] = ((j < 4 ? sy.x : sy.y) >> (8 * (j & 3))) & 0xFFu;
+                    sf[j] = (sym[2 * g + (j >> 2)] >> (8 * (j & 3))) & 0xFFu;
                     const u32 sw = sf[j] - base;
-                    in[j] = single || sw < WB_WIN;
+                    in[j] = j < nj && (single || sw < WB_WIN);
                     const u32 row = in[j] ? sw : 0u;
                     co[j] = w.coarse[row * 16 + grp]; cn[j] = w.cnt[row * 16 + grp]; pl[j] = payload(sf[j]);
                 }
 #pragma unroll
                 for (u32 j = 0; j < 8; ++j) {
-                    const u32 lrw = j < 2 ? lr.x : j < 4 ? lr.y : j < 6 ? lr.z : lr.w;
-                    const u32 local = (lrw >> (16 * (j & 1))) & 0xFFFFu;
-                    if (in[j]) emit(m0 + i + j, sf[j], local + co[j] + wb_bytesum(cn[j] & belowMask), pl[j]);
-                }
-            }
-            for (; i < C; ++i) {
-                const u32 u = m0 + i;
-                const u32 sfull = w.symTab[wb_si(u)];
-                const u32 sw = sfull - base;
-                if (single || sw < WB_WIN) {
-                    const u32 r = (u32)w.cell[wb_ci(u)] + (u32)w.coarse[sw * 16 + grp] + wb_bytesum(w.cnt[sw * 16 + grp] & belowMask);
-                    emit(u, sfull, r, payload(sfull));
+                    const u32 local = (lr[2 * g + (j >> 2)] >> (8 * (j & 3))) & 0xFFu;
+                    if (in[j]) emit(mg + j, sf[j], local + co[j] + wb_bytesum(cn[j] & belowMask), pl[j]);
                 }
             }
         }
