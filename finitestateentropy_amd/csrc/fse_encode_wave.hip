@@ -415,10 +415,11 @@ __global__ __launch_bounds__(64 * FSE_WV_WAVES) void k_fse_encode_wave(FseEncArg
     // ---- verification / repair per chain: start[k] must equal end[k-1]; super-range 0 (and every one that ran from the block end) is exact.
     //      A lane keeps the sample it had before its last re-run (start -> end, mid, counts: WV_SAMPLE_CACHE).  For a fixed run of symbols the
     //      map start state -> (bits, end state) is a monotone step function with a handful of steps (a composition of degree-1 circle maps;
-    //      2 .. 8 distinct values per 1024-symbol super-range on Proba80, never one: scripts/sim_repair_policies.py), so while the links
-    //      above a lane are still settling its predecessor's end flips between the same few states -- A, B, A again -- and the lane has
+    //      1 .. 10 distinct values per 1024-symbol super-range on Proba80, 3.1 on average: scripts/sim/repair_policies.py), so while the
+    //      links above a lane are still settling its predecessor's end flips between the same few states -- A, B, A again -- and the lane has
     //      already walked from A: it takes the sample back instead of re-running (free rounds of look-ups between two rounds of runs;
-    //      simulated on P80: 3.9 -> 3.1 rounds per wave; P14 has one round and does not get here).
+    //      P80: 4.4 -> 3.5 rounds per wave in the lane-exact model scripts/sim/wave_encoder_sim.py, 4.49 -> 3.40 measured; P14 has one round
+    //      and does not get here).
 #ifndef WV_SAMPLE_CACHE
 #define WV_SAMPLE_CACHE 1
 #endif

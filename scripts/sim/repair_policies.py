@@ -1,4 +1,5 @@
-"""CPU model of k_fse_encode_wave's speculate / verify / repair scheme (csrc/fse_encode_wave.hip) on probagen blocks: what the map
+"""CPU model of k_fse_encode_wave's speculate / verify / repair scheme (csrc/fse_encode_wave.hip) on probagen blocks, cut as the kernel
+cuts them (the lane-exact model wave_encoder_sim.py, checked against the device): what the map
 "start state -> (bits emitted, end state)" of a super-range looks like, and how many repair rounds different policies need.
 Development aid (uses the oracle for the generator and the reference's table builders only):
 
@@ -9,7 +10,7 @@ Facts the kernel rests on, checked here on every super-range:
     (every FSE_encodeSymbol, lib/fse.h:514-521, is a degree-1 monotone map of the circle of states: a state in the upper part of
     the symbol's interval emits one bit more and lands on the lower sub-states; compositions stay monotone);
   * it is a step function with few steps: the number of distinct (bits, end) values per super-range is printed per distribution
-    (Proba80: 2 .. 8 over 1024 steps per chain, never 1 -- the reason a speculated start is wrong so often and stays wrong for long).
+    (Proba80: 2 .. 8 over 1024 steps per chain, 1 only on a short super-range -- the reason a speculated start is wrong so often and stays wrong for long).
 Policies compared (rounds = rounds of re-runs a wave of two blocks pays, the maximum over its four chains):
   current   a lane whose start differs from its predecessor's end re-runs from that end (rounds 2-5 of the build);
   cache     the same, but a lane keeps the sample it had before its last re-run and takes it back when the predecessor's end
@@ -22,6 +23,9 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
 from oracle.oracle import Oracle
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import wave_encoder_sim as wsim                           # noqa: E402  (the cut, the warm-up and the exact-start rule: the checked model's)
 
 LANES = 32
 
@@ -53,22 +57,24 @@ def init_state(s, st, dfs, dnb):           # FSE_initCState2, lib/fse.h:503-512
     return st[((((nb << 16) - dnb[s])) >> nb) + dfs[s]]
 
 
-def block_maps(orc, src8, warm_factor):
-    """per chain: full maps of every super-range (end state, lifted end, lifted mid) and the warmed-up guesses, as the kernel cuts them"""
+def block_maps(orc, src8, warm_factor, addr=0):
+    """per chain: full maps of every super-range (end state, lifted end, lifted mid) and the warmed-up guesses, cut as the kernel cuts
+    them (wave_encoder_sim.cut: both roundings of C, delta from the source address `addr`, the last super-range to the block end)"""
     src = src8.astype(np.int64)
     tl, present, st, dfs, dnb = tables(orc, src8)
     T = 1 << tl
     n = src.size
     warm = int(warm_factor * T) // present
-    warm = min(max((warm + 63) & ~63, 64), 4096)
-    C = (((n - 2 + LANES - 1) // LANES) + 63) & ~63
+    warm = min(max((warm + 63) & ~63, wsim.WARM_MIN), wsim.WARM_MAX)
+    _, C, delta, _, _ = wsim.cut(n, addr)
     allx = np.arange(T, 2 * T)
     chains = []
     for c in range(2):
         E, LE, LM, g = [], [], [], []
         for k in range(LANES // 2):
-            lo = 2 + 2 * k * C if k else 2
-            mid, hi = min(n, 2 + (2 * k + 1) * C), min(n, 2 + (2 * k + 2) * C)
+            lo = min(2 + 2 * k * C - delta, n) if k else 2
+            mid = min(n, 2 + (2 * k + 1) * C - delta)
+            hi = n if (2 * k + 2 >= LANES or 2 + (2 * k + 2) * C - delta > n) else 2 + (2 * k + 2) * C - delta
             if lo >= n:
                 break
             x1, b1 = walk(allx.copy(), np.arange(lo + ((c - lo) % 2), mid, 2), src, st, dfs, dnb)
@@ -136,8 +142,9 @@ def rounds(T, chains, cache_size, bracket, helpers):
                     s = (best[0] + best[1]) // 2
                     samp[c][k].append(s - T if s >= 2 * T else s); idle -= 1
         for c, k in hard:
+            old = cs[c][k]                                              # the kernel keeps the start the lane holds, which may be a sample it took back
             cs[c][k] = ce[c][k - 1]
-            samp[c][k] = (samp[c][k] + [cs[c][k]])[-cache_size:] if not helpers else samp[c][k] + [cs[c][k]]
+            samp[c][k] = ([a for a in samp[c][k] if a != old] + [old, cs[c][k]])[-cache_size:] if not helpers else samp[c][k] + [cs[c][k]]
             full[c][k] = True
         for c, k in pend:
             full[c][k] = True; samp[c][k].append(cs[c][k])

@@ -29,5 +29,11 @@ def test_lifted_map_is_a_monotone_step_function_and_the_kept_sample_never_costs_
         cur = model.rounds(T, chains, 1, False, False)
         kept = model.rounds(T, chains, 2, False, False)
         assert kept <= cur
+        # the policy model rests on the lane-exact one: its kernel policy needs the rounds the kernel's model needs (one block per wave)
+        _, msv, cnt = orc.hist_count(blocks[b])
+        tl = orc.fse_optimal_tablelog(11, blocks[b].size, msv)
+        _, norm = orc.fse_normalize_count(tl, cnt, blocks[b].size, msv)
+        _, ct = orc.fse_build_ctable(norm, msv, tl)
+        assert kept == model.wsim.simulate_wave([model.wsim.Block(blocks[b], ct, 0, 11)])["rounds"]
         if proba == 14:
             assert cur <= 2 and all(len(np.unique(E[k])) == 1 for E, _, _, _ in chains for k in range(1, len(E)))   # fast mixing: the end forgets the start
