@@ -194,11 +194,7 @@ DEV u32 lshl_or(u32 v, u32 sh, u32 o) { u32 r; __asm__("v_lshl_or_b32 %0, %1, %2
 DEV u32 ring_dword(u32 P) { u32 r; __asm__("v_bfe_u32 %0, %1, 5, %2" : "=v"(r) : "v"(P), "n"(FSE_IN_RING_LOG - 2)); return r; }              // (P >> 5) mod ring dwords
 // PheadRef: the cursor at the head of the phase's LAST iteration (the reference's reader state between two loop-head reloads is
 // fixed by the bits unread at the last reload and the bits unread now: k_fse_decode rebuilds it from the two).
-#ifndef FSE_SCHED
-#define FSE_SCHED 1
-#endif
-#if FSE_SCHED
-// The phase with its issue order written out (sched_barrier between the groups) -- the compiler's own schedule (FSE_SCHED 0, below)
+// The phase with its issue order written out (sched_barrier between the groups) -- the compiler's own schedule
 // requested a cell only after the window reads and waited for the window behind a cursor update that itself waited for the cell.
 // Per iteration there are two LDS round trips nothing can hide (cell of symbol pair 1 -> cell of pair 2 -> next iteration's cell); the
 // rest is arranged around them:
@@ -211,55 +207,12 @@ DEV u32 ring_dword(u32 P) { u32 r; __asm__("v_bfe_u32 %0, %1, 5, %2" : "=v"(r) :
 // Per 100k Proba14 blocks (decode call = dparse + dbuild + this kernel): compiler's schedule 11.59 ms; cell requested early, cell-only
 // work before the window wait 11.27; with the window requested one iteration ahead 10.72.
 #define SB __builtin_amdgcn_sched_barrier(0)
-// Measurement aid (EXPERIMENTS.md, "what a smaller table cell may cost"): FSE_EXTRA_CHAIN_OPS dependent no-op VALU instructions behind every
-// next-state computation -- the slope ms per instruction on the chain, against which any cell format that saves LDS but adds work
-// between a cell's arrival and the next request has to be weighed.  0 in the product.
-#ifndef FSE_EXTRA_CHAIN_OPS
-#define FSE_EXTRA_CHAIN_OPS 0
-#endif
-DEV u32 fse_chain_pad(u32 s)
-{
-#pragma unroll
-    for (int i = 0; i < FSE_EXTRA_CHAIN_OPS / 2; ++i) __asm__ volatile("v_xor_b32 %0, 1, %0\n\tv_xor_b32 %0, 1, %0" : "+v"(s));
-    return s;
-}
-// Measurement aid (EXPERIMENTS.md, "the state ring in global memory"): FSE_PROBE_GSTORE 1 = the decoder lanes ALSO store every record pair to
-// global memory (one global_store_dwordx2 per lane and two iterations, SGPR base + VGPR offset), 2 = INSTEAD of the LDS ring (results wrong:
-// timing only) -- what would a state ring outside LDS (36 instead of 33 blocks per CU) cost the decoder wave's instruction stream?
-#ifndef FSE_PROBE_GSTORE
-#define FSE_PROBE_GSTORE 0
-#endif
-#if FSE_PROBE_GSTORE
-__device__ u8 g_probeRing[512u * 64u * 2u * 4096u];                 // 512 workgroup slots x 64 lanes x 2 decoder waves x 4 KiB
-DEV void fse_probe_gstore(u32 off, u32 a, u32 b)
-{
-    typedef u32 v2 __attribute__((ext_vector_type(2)));
-    __attribute__((address_space(1))) u8* const base = (__attribute__((address_space(1))) u8*)g_probeRing;
-    *(__attribute__((address_space(1))) v2*)(base + off) = (v2){ a, b };
-}
-#endif
-// Measurement aid (EXPERIMENTS.md section 1, round 6): FSE_PEEK_IN_PHASE 1 requests the service's progress words {srvFlushed, srvValidLo} the NEXT round
-// looks at HERE, a few iterations before the phase ends, instead of in the round's poll loop.  Reason to try: that loop is a do-while, and the
-// compiler waits for the words requested in it at the bottom of the loop body on the exit path too (the loop-carried copy needs the data: s_waitcnt
-// lgkmcnt(0) + v_mov_b64 in front of the loop's branch), so every round pays part of an LDS round trip that the request "one round ahead" was meant
-// to hide.  Measured: 3700 -> 3671 cycles per productive round, and the decode call 0.3 - 0.8 % SLOWER on every distribution.  0 in the product.
-#ifndef FSE_PEEK_IN_PHASE
-#define FSE_PEEK_IN_PHASE 0
-#endif
-#ifndef FSE_PEEK_AT
-#define FSE_PEEK_AT 4            // iterations before the end of the phase
-#endif
 template <int NITER>
-DEV void fse_bulk_phase_rev(u32& sMine, u32& Pref, u32& PheadRef, u32 K, u32 cellShift, u32 tabOff, u32 myIn, u32 maskB, uint2* ringMine,
-                            const u32* peekAt = nullptr, u64* peekOut = nullptr)
+DEV void fse_bulk_phase_rev(u32& sMine, u32& Pref, u32& PheadRef, u32 K, u32 cellShift, u32 tabOff, u32 myIn, u32 maskB, uint2* ringMine)
 {
     u32 s = sMine, P = Pref;
     u32 prev = 0;
     __asm__ volatile("" : "+v"(myIn));
-#if FSE_PROBE_GSTORE
-    // (a 4 KiB stretch per lane, the position inside it following the LDS ring's: 512 bytes of it are ever touched)
-    const u32 probeOff = (((blockIdx.x & 511u) * 128u + (threadIdx.x & 127u)) << 12) + ((u32)(uintptr_t)ringMine & 0x1F8u);
-#endif
     u32 c = lds_cell(s);
     u32 Pw = P;
     lds_u32_ptr wp = (lds_u32_ptr)(uintptr_t)(myIn + (ring_dword(P) << 2));
@@ -275,7 +228,7 @@ DEV void fse_bulk_phase_rev(u32& sMine, u32& Pref, u32& PheadRef, u32 K, u32 cel
         __asm__ volatile("" : "+v"(lo), "+v"(hi));
         SB;
         const u32 sStart = s;
-        s = fse_chain_pad(lshl_or(__builtin_amdgcn_ubfe(lo, dpp_swap_and(c, maskB), c), K - c, (c >> cellShift) | tabOff));
+        s = lshl_or(__builtin_amdgcn_ubfe(lo, dpp_swap_and(c, maskB), c), K - c, (c >> cellShift) | tabOff);
         const u32 c2 = lds_cell(s);
         SB;
         const u32 n1 = dpp_swap_add(c, c);
@@ -288,18 +241,9 @@ DEV void fse_bulk_phase_rev(u32& sMine, u32& Pref, u32& PheadRef, u32 K, u32 cel
         u32 lo2 = __builtin_amdgcn_alignbit(hi, lo, n1);
         u32 rec = __builtin_amdgcn_perm(s, sStart, 0x05040100u);
         __asm__ volatile("" : "+v"(lo2), "+v"(rec));
-#if FSE_PROBE_GSTORE == 2
-        if (it & 1) fse_probe_gstore(probeOff + 8u * (u32)(it & ~1), prev, rec); else prev = rec;
-#elif FSE_PROBE_GSTORE == 1
-        if (it & 1) { ringMine[it & ~1] = make_uint2(prev, rec); fse_probe_gstore(probeOff + 8u * (u32)(it & ~1), prev, rec); } else prev = rec;
-#else
-        if (it & 1) ringMine[it & ~1] = make_uint2(prev, rec); else prev = rec;
-#endif
-#if FSE_PEEK_IN_PHASE
-        if (peekOut && it == (NITER > FSE_PEEK_AT ? NITER - FSE_PEEK_AT : 0)) *peekOut = __hip_atomic_load((const u64*)peekAt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
+        if (it & 1) ringMine[it & ~1] = make_uint2(prev, rec); else prev = rec;      // this lane's half of slot pair (it >> 1): its states of both iterations
         SB;
-        s = fse_chain_pad(lshl_or(__builtin_amdgcn_ubfe(lo2, dpp_swap_and(c2, maskB), c2), K - c2, (c2 >> cellShift) | tabOff));
+        s = lshl_or(__builtin_amdgcn_ubfe(lo2, dpp_swap_and(c2, maskB), c2), K - c2, (c2 >> cellShift) | tabOff);
         if (it + 1 < NITER) c = lds_cell(s);
         SB;
         const u32 n2 = dpp_swap_add(c2, c2);
@@ -308,40 +252,6 @@ DEV void fse_bulk_phase_rev(u32& sMine, u32& Pref, u32& PheadRef, u32 K, u32 cel
     sMine = s; Pref = P;
 }
 #undef SB
-#else
-template <int NITER>
-DEV void fse_bulk_phase_rev(u32& sMine, u32& Pref, u32& PheadRef, u32 K, u32 cellShift, u32 tabOff, u32 myIn, u32 maskB, uint2* ringMine,
-                            const u32* peekAt = nullptr, u64* peekOut = nullptr)
-{
-    u32 s = sMine, P = Pref;
-    u32 prev = 0;
-    if (peekOut) *peekOut = __hip_atomic_load((const u64*)peekAt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    __asm__ volatile("" : "+v"(myIn));                           // one register: the three window reads then differ by their immediate offsets
-#pragma unroll FSE_PHASE_UNROLL
-    for (int it = 0; it < NITER; ++it) {
-        if (it == NITER - 1) PheadRef = P;
-        const u32 c = lds_cell(s);                               // lane A: state 1's cell, lane B: state 2's
-        const lds_u32_ptr wp = (lds_u32_ptr)(uintptr_t)(myIn + (ring_dword(P) << 2));
-        const u32 d0 = wp[0], d1 = wp[1], d2 = wp[2];
-        const u32 lo = __builtin_amdgcn_alignbit(d1, d0, P), hi = __builtin_amdgcn_alignbit(d2, d1, P);
-        const u32 sStart = s;
-        {   const u32 bits = __builtin_amdgcn_ubfe(lo, dpp_swap_and(c, maskB), c);
-            s = lshl_or(bits, K - c, (c >> cellShift) | tabOff); }
-        const u32 c2 = lds_cell(s);
-        const u32 n1 = dpp_swap_add(c, c);                       // low 5 bits: bits of this symbol pair
-        const u32 lo2 = __builtin_amdgcn_alignbit(hi, lo, n1);
-        const u32 rec = __builtin_amdgcn_perm(s, sStart, 0x05040100u);   // low 16 bits of the two cell addresses this lane decoded from
-        {   const u32 bits = __builtin_amdgcn_ubfe(lo2, dpp_swap_and(c2, maskB), c2);
-            s = lshl_or(bits, K - c2, (c2 >> cellShift) | tabOff); }
-        const u32 n2 = dpp_swap_add(c2, c2);
-        P += (n1 & 31u) + (n2 & 31u);
-        // two iterations per ring slot pair: this lane's half of slot pair (it >> 1) holds its states of both iterations
-        if (it & 1) ringMine[it & ~1] = make_uint2(prev, rec); else prev = rec;
-    }
-    sMine = s; Pref = P;
-}
-
-#endif
 
 // Per-block control words in LDS: the decoder wave and the service wave of a workgroup talk through these only.
 struct DecCtl {
@@ -391,6 +301,25 @@ DEV void fse_ring_put(u32* rg, int off, u32 w)
 // to ring offset (Stop - 4 - o) mod FSE_IN_RING (Stop = payload size rounded up to 4).  Either way ring byte x <-> payload
 // byte is a bijection on windows of FSE_IN_RING aligned-dword bytes, so the validLo protocol is the same.
 DEV void fse_ring_put_rev(u32* rg, int Sg, int off, u32 w) { fse_ring_put(rg, ((Sg + 3) & ~3) - 4 - off, __brev(w)); }
+// caller tables: thread 0 claims a slot of the library's symbol scratch for the workgroup (FseDecArgs::slotBitmap; at most one workgroup of
+// this kernel is resident per CU, so with 2 x CUs slots the search finds a free one at once) and leaves its index in flagsSh[6]
+DEV u32 fse_scratch_slot_claim(const FseDecArgs& a, u32* flagsSh)
+{
+    u32 slot = (u32)blockIdx.x % a.nSlots;
+    for (;;) {
+        const u32 bit = 1u << (slot & 31u);
+        const u32 old = __hip_atomic_fetch_or(a.slotBitmap + (slot >> 5), bit, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+        if (!(old & bit)) break;
+        slot = slot + 1 == a.nSlots ? 0 : slot + 1;
+    }
+    flagsSh[6] = slot;
+#if FSE_SYM_L1
+    // the slot may have been used from this CU before (by a workgroup long gone): whatever the CU's vector cache still holds of it
+    // is dropped before this workgroup writes and reads it
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+#endif
+    return slot;
+}
 // caller tables: the workgroup's slot of the symbol scratch goes back when the LAST of its waves is through with it -- the service waves
 // gather from it during the bulk, the decoder waves' literal tails read it after that (FseCellsRev / FseCellsCompact take their symbols
 // there), so every wave of the workgroup reports here once, after its last access (flagsSh[7] counts them), and the last one releases.
@@ -401,9 +330,6 @@ DEV void fse_scratch_slot_done(const FseDecArgs& a, u32* flagsSh, int lane)
         __hip_atomic_fetch_and(a.slotBitmap + (slot >> 5), ~(1u << (slot & 31u)), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
-#ifndef FSE_SRV_READLANE
-#define FSE_SRV_READLANE 1
-#endif
 DEV u32 srv_rl(u32 v, int l) { return (u32)__builtin_amdgcn_readlane((int)v, l); }
 DEV unsigned long long srv_rl64(unsigned long long v, int l) { return (unsigned long long)srv_rl((u32)v, l) | ((unsigned long long)srv_rl((u32)(v >> 32), l) << 32); }
 template <bool TIMED, bool CALLER>
@@ -485,18 +411,13 @@ DEV void fse_decode_service(const FseDecArgs& a, u8* ldsb, DecCtl* ctlAll, u32 s
             }
         }
         // (2) issue the symbol gathers of every block with enough records
-        // (FSE_SRV_READLANE: the per-block values of lane l reach the wave through v_readlane -- the lane index is a constant of the unrolled loop --
+        // (the per-block values of lane l reach the wave through v_readlane -- the lane index is a constant of the unrolled loop --
         //  instead of __shfl = ds_bpermute: eight LDS-pipe instructions per flushed block were about half of all LDS instructions of the CU)
 #pragma unroll
         for (int l = 0; l < FSE_SRV_G; ++l) {
             if (!((fm >> l) & 1ull)) continue;               // uniform
-#if FSE_SRV_READLANE
             const u32 cnt = srv_rl(avail, l), fp_g = srv_rl(fpos, l);
             const gbl_u8_ptr tg = (gbl_u8_ptr)(uintptr_t)srv_rl64(tabBits, l);
-#else
-            const u32 cnt = (u32)__shfl((int)avail, l, WAVE), fp_g = (u32)__shfl((int)fpos, l, WAVE);
-            const gbl_u8_ptr tg = (gbl_u8_ptr)(uintptr_t)__shfl(tabBits, l, WAVE);
-#endif
             if ((u32)lane < cnt) {
                 // iteration i lives in slot pair (i >> 1): 16 bytes = lane A's {iteration 2p, 2p+1} words, then lane B's
                 u32 ri = fp_g + (u32)lane;
@@ -521,13 +442,8 @@ DEV void fse_decode_service(const FseDecArgs& a, u8* ldsb, DecCtl* ctlAll, u32 s
 #pragma unroll
         for (int l = 0; l < FSE_SRV_G; ++l) {
             if (!((fm >> l) & 1ull)) continue;               // uniform
-#if FSE_SRV_READLANE
             const u32 cnt = srv_rl(avail, l), fl_g = srv_rl(flushed, l);
             gbl_u8_w_ptr const og = (gbl_u8_w_ptr)(uintptr_t)(srv_rl64(outBits, l) + 4ull * fl_g);
-#else
-            const u32 cnt = (u32)__shfl((int)avail, l, WAVE), fl_g = (u32)__shfl((int)flushed, l, WAVE);
-            gbl_u8_w_ptr const og = (gbl_u8_w_ptr)(uintptr_t)(__shfl(outBits, l, WAVE) + 4ull * fl_g);
-#endif
             if ((u32)lane < cnt) {
                 const u32 w = yq[l][0] | (yq[l][1] << 8) | (yq[l][2] << 16) | (yq[l][3] << 24);
                 gbl_store_u32(og + 4u * lane, w);
@@ -584,6 +500,21 @@ DEV size_t fse_tail(const Cells& t, u32 s1, u32 s2, BitReader& r, u8* out, long 
 // of a block follows its input rate.
 // LDS: G tables A[2^ldsLog] (u16) on table-size aligned addresses | DecCtl[G] | per block: state ring
 // (FSE_DEC_RING x 8 B), input ring (256 + 16 B) | two flag words
+//
+// The kernel in its phases (each starts at a `// ----` comment below), with every barrier and every way out:
+//   1. slot lookup          all threads, uniform.  WAY OUT: the whole workgroup, if its first slot lies beyond the list (before any barrier).
+//   2. table staging        barrier (the flag words are zero).  Caller tables only: wave 1 marks the tables that are this launch's while
+//                           thread 0 claims a slot of the symbol scratch; barrier; WAY OUT: the whole workgroup, if none of its tables is
+//                           this launch's.  Then the copy (one-shot path: all waves) or the conversion (caller tables: the service waves;
+//                           the decoder waves go on to 3 meanwhile) -- no barrier inside.
+//   3. block set-up         every lane computes along, only lanes of the decoder waves own a block; then s_waitcnt vmcnt(0) + barrier (all
+//                           waves: tables and flag words are staged); bulk eligibility, ring coordinates, control words; barrier (all waves:
+//                           the control words are written).  WAY OUT: each service wave, through fse_decode_service, when the bulk of its
+//                           blocks is over.  No barrier after this point: the two sides talk through the control words.
+//   4. bulk rounds          decoder waves; bit-reversed cells (FAST): wave-uniform rounds of long phases, then of finishing phases; plain
+//                           cells: divergent rounds of long phases.
+//   5. hand-back and tail   the even lane of every pair that owns a block; the wave stays whole to the end (caller tables: it reports to
+//                           fse_scratch_slot_done as a whole).
 template <bool FAST, bool TIMED, bool CALLER>
 __global__ __launch_bounds__(FSE_DEC_THREADS) void k_fse_decode(FseDecArgs a)
 {
@@ -592,7 +523,7 @@ __global__ __launch_bounds__(FSE_DEC_THREADS) void k_fse_decode(FseDecArgs a)
     unsigned long long tBorn = 0, wBorn = 0;
     (void)tBorn; (void)wBorn;
     TIMING(tBorn = __builtin_readcyclecounter(); wBorn = wall_clock64(););
-    // slot g of this workgroup = entry first + g of the launch's block list (or simply block first + g)
+    // ---- 1. slot lookup: slot g of this workgroup = entry first + g of the launch's block list (or simply block first + g)
     const size_t first = (size_t)blockIdx.x * a.G;
     // The one-shot path hands over a class's FSE_DBINS size-bin lists (internal.h), walked one after the other as if they were one
     // list sorted by compressed size.  Their lengths come in one 16-byte load; where the workgroup's first slot falls is uniform, and
@@ -636,7 +567,7 @@ __global__ __launch_bounds__(FSE_DEC_THREADS) void k_fse_decode(FseDecArgs a)
     const u32 ringOff = 0;                                       // state ring offset inside a slot
     const u32 inOff = FSE_DEC_RING * 8;                          // input ring offset inside a slot
 
-    // ---- stage: reference cells {u16 newState; u8 symbol; u8 nbBits} -> compact u16 (uniform control flow, both waves).
+    // ---- 2. table staging: reference cells {u16 newState; u8 symbol; u8 nbBits} -> compact u16 (uniform control flow, both waves).
     //      A table whose fields do not fit 12+4 bits (cannot come from FSE_buildDTable) is flagged and decoded
     //      by the literal path only.
     u32* const flagsSh = (u32*)(ldsb + (size_t)a.G * slotBytes);  // behind the slots: [0] any nbBits == 0, [1] some table is this launch's (caller tables), [2..3] bad-table mask, [4..5] decline mask,
@@ -649,8 +580,8 @@ __global__ __launch_bounds__(FSE_DEC_THREADS) void k_fse_decode(FseDecArgs a)
         // block, 33 blocks per CU, 32 CUs per L2 -- 8.6 MB of tables in flight on a 4 MB L2 (measured: 20.5 ms per 100k blocks against
         // 12.2 with the one-shot path's byte tables).  The staging pass below therefore writes the symbols of the workgroup's tables
         // into one slot of a small scratch the LIBRARY keeps per device (FseDecArgs::symScratch: 2 x CUs slots of 72 KB, allocated at the
-        // first such call); a slot is claimed here and handed back by the last service wave.  At most one workgroup of this kernel is
-        // resident per CU (160 KB of LDS), so with 2 x CUs slots the search below finds a free one at once.
+        // first such call); a slot is claimed here (fse_scratch_slot_claim) and handed back by the workgroup's last wave
+        // (fse_scratch_slot_done).
         // Meanwhile wave 1 looks at the headers of the workgroup's tables: which of them are this launch's (FseDecArgs: tlMin, ldsLog,
         // onlyDeclined)?  A workgroup without any returns at once -- the launches for the classes a batch does not contain cost next to nothing.
         __syncthreads();                                                 // (the flag words are zero)
@@ -671,21 +602,7 @@ __global__ __launch_bounds__(FSE_DEC_THREADS) void k_fse_decode(FseDecArgs a)
         }
         if (mine) flagsSh[1] = 1u;                                       // (plain stores of the same value; no __syncthreads_or: it brings static LDS)
         u32 slot = 0;
-        if (tid == 0) {
-            slot = (u32)blockIdx.x % a.nSlots;
-            for (;;) {
-                const u32 bit = 1u << (slot & 31u);
-                const u32 old = __hip_atomic_fetch_or(a.slotBitmap + (slot >> 5), bit, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-                if (!(old & bit)) break;
-                slot = slot + 1 == a.nSlots ? 0 : slot + 1;
-            }
-            flagsSh[6] = slot;
-#if FSE_SYM_L1
-            // the slot may have been used from this CU before (by a workgroup long gone): whatever the CU's vector cache still holds of it
-            // is dropped before this workgroup writes and reads it
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
-        }
+        if (tid == 0) slot = fse_scratch_slot_claim(a, flagsSh);
         __syncthreads();
         if (!flagsSh[1]) {                                               // uniform: nothing of this launch's here
             if (tid == 0) __hip_atomic_fetch_and(a.slotBitmap + (slot >> 5), ~(1u << (slot & 31u)), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
@@ -839,7 +756,7 @@ __global__ __launch_bounds__(FSE_DEC_THREADS) void k_fse_decode(FseDecArgs a)
         if (declBits) { atomicOr(&flagsSh[4], (u32)declBits); atomicOr(&flagsSh[5], (u32)(declBits >> 32)); }
         if (anyNb0) atomicOr(&flagsSh[0], 1u);
     }
-    // ---- per-block set-up by the decoder waves, BEFORE the staged tables are waited for (the readers' first loads overlap the staging): lanes 2g and 2g+1 walk block first+g together and both run this set-up
+    // ---- 3. block set-up by the decoder waves, BEFORE the staged tables are waited for (the readers' first loads overlap the staging): lanes 2g and 2g+1 walk block first+g together and both run this set-up
     //      (identical values in both; only the even lane publishes, finishes the block and writes its result)
     //      (decoder wave w takes the slots [w * ppw, (w+1) * ppw))
     const int ppw = (a.G + FSE_DEC_WAVES - 1) / FSE_DEC_WAVES;
@@ -894,7 +811,7 @@ __global__ __launch_bounds__(FSE_DEC_THREADS) void k_fse_decode(FseDecArgs a)
     // a launch that may hand blocks on marks the tables it leaves to the plain-cell launch (tableLog 12 with a cell of nbBits 0)
     if (CALLER && owner && a.declineNb0 && ((declMask >> gsl) & 1ull)) { if (half == 0) a.results[b] = FSE_DECLINED; owner = false; }
 
-    // ---- bulk: iterations of fse_decompress.c:201-218 whose loop-head reload is provably the fast one.
+    // ---- (3, after the barrier) bulk eligibility: iterations of fse_decompress.c:201-218 whose loop-head reload is provably the fast one.
     //      The decoder lane touches only registers and LDS:
     //        * input: the 8 bytes below the window come from this block's LDS input ring;
     //        * output: each iteration appends the 4 states it decoded FROM to the block's state ring.
@@ -953,6 +870,7 @@ __global__ __launch_bounds__(FSE_DEC_THREADS) void k_fse_decode(FseDecArgs a)
     __syncthreads();
     if (!decWave) { fse_decode_service<TIMED, CALLER>(a, ldsb, ctlAll, slotBytes, ringOff, inOff, lane, (wave - FSE_DEC_WAVES) * FSE_SRV_G, FAST, flagsSh); return; }
 
+    // ---- 4. bulk rounds
     __builtin_amdgcn_s_setprio(3);                   // the decoder wave is the critical path of the workgroup
     uint2* const myRing = (uint2*)(ldsb + (size_t)(gsl < a.G ? gsl : 0) * slotBytes + ringOff) + half;   // my half of every slot pair
     const u32 myIn = (u32)(uintptr_t)(__attribute__((address_space(3))) u8*)(ldsb + (size_t)(gsl < a.G ? gsl : 0) * slotBytes + inOff);   // absolute LDS address of my input ring
@@ -996,17 +914,6 @@ __global__ __launch_bounds__(FSE_DEC_THREADS) void k_fse_decode(FseDecArgs a)
             // stream start is ever consumed: once the ring reaches down to it (validLo <= 0) the phase may run.
             const int lowest = (int)bs.q - 4 * ((48 * (FSE_CHECK_EVERY - 1) + 31) / 32);
             const int need = lowest > 0 ? lowest : 0;
-#if FSE_PEEK_IN_PHASE
-            // srvNext was requested inside the previous phase (fse_bulk_phase_rev) and arrived long ago: the common round looks at it and goes on
-            // without an LDS round trip of its own; only a round that has to poll asks again and waits.
-            {   bool rdy = !can | ((iters + FSE_CHECK_EVERY - (u32)srvNext <= FSE_DEC_RING) & (need >= (int)(u32)(srvNext >> 32)));
-                while (!__all(rdy)) {                                            // uniform: poll until every chain of the wave may run
-                    TIMING(const unsigned long long tB = __builtin_readcyclecounter(); tWait += tB - tA; ++nWait; tA = tB;);
-                    srvNext = ctl_peek2(&ctl->srvFlushed);
-                    rdy = !can | ((iters + FSE_CHECK_EVERY - (u32)srvNext <= FSE_DEC_RING) & (need >= (int)(u32)(srvNext >> 32)));
-                }
-            }
-#else
             bool rdy;
             do {                                                                 // uniform: poll until every chain of the wave may run
                 const u32 fl = (u32)srvNext;
@@ -1015,17 +922,12 @@ __global__ __launch_bounds__(FSE_DEC_THREADS) void k_fse_decode(FseDecArgs a)
                 rdy = !can | ((iters + FSE_CHECK_EVERY - fl <= FSE_DEC_RING) & (need >= vlo));
                 TIMING(if (!__all(rdy)) { const unsigned long long tB = __builtin_readcyclecounter(); tWait += tB - tA; ++nWait; tA = tB; });
             } while (!__all(rdy));
-#endif
             if (!__any(can)) break;                                              // uniform
             uint2* const ring = can ? myRing + rpos : dummyRing;
             u32 sN = bs.s, Pn = P, PhN = Phead;
             unsigned long long tI = 0; (void)tI;
             TIMING(tI = __builtin_readcyclecounter(););
-#if FSE_PEEK_IN_PHASE
-            fse_bulk_phase_rev<FSE_CHECK_EVERY>(sN, Pn, PhN, tl + 1u, 4u, tabOff, myIn, maskB & 31u, ring, &ctl->srvFlushed, &srvNext);
-#else
             fse_bulk_phase_rev<FSE_CHECK_EVERY>(sN, Pn, PhN, tl + 1u, 4u, tabOff, myIn, maskB & 31u, ring);
-#endif
             TIMING(tInner += __builtin_readcyclecounter() - tI;);
             bs.s = can ? sN : bs.s; P = can ? Pn : P; Phead = can ? PhN : Phead;
             const u32 adv = can ? (u32)FSE_CHECK_EVERY : 0u;
@@ -1046,26 +948,17 @@ __global__ __launch_bounds__(FSE_DEC_THREADS) void k_fse_decode(FseDecArgs a)
         for (;;) {                                   // ---- finishing phases of FSE_FINISH_EVERY iterations (every lane is through with the long ones)
             const u32 fl = (u32)srvNext;
             const int vlo = (int)(u32)(srvNext >> 32);
-#if !FSE_PEEK_IN_PHASE
             srvNext = ctl_peek2(&ctl->srvFlushed);
-#endif
             const int lowest = (int)bs.q - 8;                                    // the second iteration's window starts at most two dwords further down
             const bool rdy = !can2 | ((iters + FSE_FINISH_EVERY - fl <= FSE_DEC_RING) & ((lowest > 0 ? lowest : 0) >= vlo));
             if (!__all(rdy)) {
                 TIMING(const unsigned long long tB = __builtin_readcyclecounter(); tWait += tB - tA; ++nWait; tA = tB;);
-#if FSE_PEEK_IN_PHASE
-                srvNext = ctl_peek2(&ctl->srvFlushed);
-#endif
                 continue;
             }
             if (!__any(can2)) break;
             uint2* const ring = can2 ? myRing + rpos : dummyRing;
             u32 sN = bs.s, Pn = P, PhN = Phead;
-#if FSE_PEEK_IN_PHASE
-            fse_bulk_phase_rev<FSE_FINISH_EVERY>(sN, Pn, PhN, tl + 1u, 4u, tabOff, myIn, maskB & 31u, ring, &ctl->srvFlushed, &srvNext);
-#else
             fse_bulk_phase_rev<FSE_FINISH_EVERY>(sN, Pn, PhN, tl + 1u, 4u, tabOff, myIn, maskB & 31u, ring);
-#endif
             bs.s = can2 ? sN : bs.s; P = can2 ? Pn : P; Phead = can2 ? PhN : Phead;
             rpos = can2 ? (rpos + FSE_FINISH_EVERY) & (FSE_DEC_RING - 1) : rpos;
             iters += can2 ? FSE_FINISH_EVERY : 0u; grp -= can2 ? FSE_FINISH_EVERY : 0;
@@ -1078,64 +971,33 @@ __global__ __launch_bounds__(FSE_DEC_THREADS) void k_fse_decode(FseDecArgs a)
         }
         }
     } else {
+    // ---- plain cells only (caller tables of log 12 with a cell of nbBits 0, k_fse_dbuild's plain class): divergent rounds, no finishing phases
     while (__any(can)) {                             // ---- phases of FSE_CHECK_EVERY iterations
         const u32 fl = (u32)srvNext;
         const int vlo = (int)(u32)(srvNext >> 32);
         srvNext = ctl_peek2(&ctl->srvFlushed);
-        // room for 16 more records, and the lowest byte this phase can read is in the ring: its last iteration starts at most
-        // 15 * 48 bits further down (23 dwords) and reads the three dwords from there -> 92 bytes below q (plain loop: 6 bytes per
-        // iteration and a window of 8).  Nothing below the stream start is ever consumed: once the ring reaches down to it
-        // (validLo <= 0) the phase may run.
-        const int lowest = (int)bs.q - (FAST ? 4 * ((48 * (FSE_CHECK_EVERY - 1) + 31) / 32) : 6 * FSE_CHECK_EVERY + 8);
+        // room for 16 more records, and the lowest byte this phase can read is in the ring: 6 bytes per iteration and a window of 8.
+        // Nothing below the stream start is ever consumed: once the ring reaches down to it (validLo <= 0) the phase may run.
+        const int lowest = (int)bs.q - (6 * FSE_CHECK_EVERY + 8);
         // (bitwise &: ONE divergent branch per round -- the compiler turns && chains into nested branches with a copy of every
         //  loop-carried register at each level)
         const bool ready = can & (iters + FSE_CHECK_EVERY - fl <= FSE_DEC_RING) & ((lowest > 0 ? lowest : 0) >= vlo);
         if (ready) {
             uint2* const ring = myRing + rpos;                               // 16 consecutive slots: a phase never wraps
             rpos = (rpos + FSE_CHECK_EVERY) & (FSE_DEC_RING - 1);
-            if (FAST) {
-                unsigned long long tI = 0; (void)tI;
-                TIMING(tI = __builtin_readcyclecounter(););
-                fse_bulk_phase_rev<FSE_CHECK_EVERY>(bs.s, P, Phead, tl + 1u, 4u, tabOff, myIn, maskB & 31u, ring);
-                TIMING(tInner += __builtin_readcyclecounter() - tI;);
-                const u32 B = R8 - P;
-                bs.q = 4u * (B >> 5) - 8u; bs.bq = B & 31u;
-            }
-            else if (nb0) fse_bulk_phase<true>(bs.s, bs.q, bs.bq, tabOff, myIn, half, maskB, ring);
-            else          fse_bulk_phase<false>(bs.s, bs.q, bs.bq, tabOff, myIn, half, maskB, ring);
+            if (nb0) fse_bulk_phase<true>(bs.s, bs.q, bs.bq, tabOff, myIn, half, maskB, ring);
+            else     fse_bulk_phase<false>(bs.s, bs.q, bs.bq, tabOff, myIn, half, maskB, ring);
             iters += FSE_CHECK_EVERY; grp -= FSE_CHECK_EVERY;
-            if (FAST) {
-                const u32 Bp = R8 - P - inA8;                                 // unread bits of the payload proper
-                can = (Bp >= 65u + 48u * (FSE_CHECK_EVERY - 1)) & (grp >= FSE_CHECK_EVERY);
-                can2 = (Bp >= 65u + 48u * (FSE_FINISH_EVERY - 1)) & (grp >= FSE_FINISH_EVERY);
-            }
-            // plain loop: the reference's ptr offset after its next reload is >= 4*dp - 8 = q: keep 16 more fast reloads certain
-            else can = (bs.q >= 24u + 6u * FSE_CHECK_EVERY + 4u) & (grp >= FSE_CHECK_EVERY);     // (+4: q counts from the aligned base)
-            if (half == 0) ctl_store2(&ctl->pubIters, iters, (can | can2) ? bs.q + 8u : ((bs.q + 8u) | 0x80000000u));
+            // the reference's ptr offset after its next reload is >= 4*dp - 8 = q: keep 16 more fast reloads certain
+            can = (bs.q >= 24u + 6u * FSE_CHECK_EVERY + 4u) & (grp >= FSE_CHECK_EVERY);     // (+4: q counts from the aligned base)
+            if (half == 0) ctl_store2(&ctl->pubIters, iters, can ? bs.q + 8u : ((bs.q + 8u) | 0x80000000u));
         }
         TIMING(const unsigned long long tB = __builtin_readcyclecounter(); if (__any(ready)) { tRun += tB - tA; ++nRun; } else { tWait += tB - tA; ++nWait; } tA = tB;);
-    }
-    if (false) while (__any(can2)) {                  // ---- finishing phases of FSE_FINISH_EVERY iterations (every lane is through with the long ones)
-        const u32 fl = (u32)srvNext;
-        const int vlo = (int)(u32)(srvNext >> 32);
-        srvNext = ctl_peek2(&ctl->srvFlushed);
-        const int lowest = (int)bs.q - 8;                                    // the second iteration's window starts at most two dwords further down
-        const bool ready = can2 & (iters + FSE_FINISH_EVERY - fl <= FSE_DEC_RING) & ((lowest > 0 ? lowest : 0) >= vlo);
-        if (ready) {
-            uint2* const ring = myRing + rpos;
-            rpos = (rpos + FSE_FINISH_EVERY) & (FSE_DEC_RING - 1);
-            fse_bulk_phase_rev<FSE_FINISH_EVERY>(bs.s, P, Phead, tl + 1u, 4u, tabOff, myIn, maskB & 31u, ring);
-            const u32 B = R8 - P;
-            bs.q = 4u * (B >> 5) - 8u; bs.bq = B & 31u;
-            iters += FSE_FINISH_EVERY; grp -= FSE_FINISH_EVERY;
-            can2 = (B - inA8 >= 65u + 48u * (FSE_FINISH_EVERY - 1)) & (grp >= FSE_FINISH_EVERY);
-            if (half == 0) ctl_store2(&ctl->pubIters, iters, can2 ? bs.q + 8u : ((bs.q + 8u) | 0x80000000u));
-        }
-        TIMING(const unsigned long long tB = __builtin_readcyclecounter(); if (__any(ready)) { tFin += tB - tA; ++nFin; } else { tWait += tB - tA; ++nWait; } tA = tB;);
     }
     }
     TIMING(if (lane == 0) { atomicAdd(&g_decTiming[0], tRun); atomicAdd(&g_decTiming[1], tWait); atomicAdd(&g_decTiming[2], nRun); atomicAdd(&g_decTiming[3], nWait); atomicAdd(&g_decTiming[4], 1ull);
                             atomicAdd(&g_decTiming[13], tBulk0 - tBorn); atomicAdd(&g_decTiming[15], tFin); atomicAdd(&g_decTiming[10], nFin); atomicAdd(&g_decTiming[7], tInner); });
+    // ---- 5. hand-back and literal tail
     const u32 sOther = dpp_swap(bs.s);               // (all lanes of the wave are still here)
     const unsigned long long tBulk1 = tA;
     (void)tBulk1;
@@ -1226,11 +1088,7 @@ static hipError_t fse_sym_scratch(FseDecArgs& a, hipStream_t s)
 
 static hipError_t fse_decode_launch(FseDecArgs a, bool rev, hipStream_t s)
 {
-#ifdef FSE_DEC_LDS12_KB             // A/B aid: another workgroup size for the classes with 8 KiB tables
-    const size_t ldsBytes = a.ldsLog >= 12 ? FSE_DEC_LDS12_KB * 1024 : FSE_DEC_LDS;
-#else
     const size_t ldsBytes = FSE_DEC_LDS;
-#endif
     const bool caller = a.atab == nullptr;
     {   hipError_t e = ensure_dyn_lds((const void*)k_fse_decode<true, false, false>, FSE_DEC_LDS);
         if (e == hipSuccess) e = ensure_dyn_lds((const void*)k_fse_decode<false, false, false>, FSE_DEC_LDS);

@@ -164,7 +164,7 @@ DEV void u16d_service(u8* ldsb, U16Ctl* ctlAll, u32 slotBytes, int G, int lane, 
         for (int l = 0; l < U16D_SRV_G; ++l) {
             if (!((fm >> l) & 1ull)) continue;
             // (v_readlane instead of __shfl = ds_bpermute: the lane index is a constant of the unrolled loop, and the LDS pipe is what the
-            //  decoder wave's chain waits on -- fse_decode.hip, FSE_SRV_READLANE)
+            //  decoder wave's chain waits on -- fse_decode.hip, fse_decode_service)
             const u32 cnt = u16d_rl(avail, l), fp_g = u16d_rl(fpos, l);
             const g_u8 tg = (g_u8)(uintptr_t)u16d_rl64(symBits, l);
             if ((u32)lane < cnt) {

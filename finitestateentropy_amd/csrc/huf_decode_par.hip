@@ -143,44 +143,6 @@ DEV u32 hpar_run_keep(u32 arr, u32& C, u32 limit, u32 tabOff, u32 mask2, u32 (&s
     return n;
 }
 
-// pass 2 from the registers: lane's n symbols to p -- single bytes up to a 4-byte boundary, then the register stream shifted by that many
-// bytes (v_alignbyte) in 16-byte stores, the last 1..15 bytes as dwords and bytes.  Static register indices throughout (unrolled).
-__device__ __attribute__((always_inline)) void hpar_store_kept(u8* p, u32 n, const u32 (&sym)[HPAR_KEEP])
-{
-    u32 a = (0u - (u32)(uintptr_t)p) & 3u;
-    a = a < n ? a : n;
-    {   const u32 w = sym[0];
-        if (a > 0) p[0] = (u8)w;
-        if (a > 1) p[1] = (u8)(w >> 8);
-        if (a > 2) p[2] = (u8)(w >> 16); }
-    p += a;
-    u32 left = n - a;
-#pragma unroll
-    for (int g = 0; g < HPAR_KEEP / 4; ++g) {
-        if (left == 0) continue;
-        u32 w[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int k = 4 * g + t;
-            const u32 hi = k + 1 < HPAR_KEEP ? sym[k + 1 < HPAR_KEEP ? k + 1 : k] : 0u;
-            w[t] = __builtin_amdgcn_alignbyte(hi, sym[k], a);
-        }
-        if (left >= 16) { __builtin_memcpy(p, w, 16); p += 16; left -= 16; }
-        else {
-            if (left >= 4) __builtin_memcpy(p, &w[0], 4);
-            if (left >= 8) __builtin_memcpy(p + 4, &w[1], 4);
-            if (left >= 12) __builtin_memcpy(p + 8, &w[2], 4);
-            const u32 r = left >= 12 ? w[3] : left >= 8 ? w[2] : left >= 4 ? w[1] : w[0];
-            u8* const t = p + (left & ~3u);
-            const u32 m = left & 3u;
-            if (m > 0) t[0] = (u8)r;
-            if (m > 1) t[1] = (u8)(r >> 8);
-            if (m > 2) t[2] = (u8)(r >> 16);
-            left = 0;
-        }
-    }
-}
-
 // pass 2 through an LDS line buffer (the stream's staging area, idle once its links are verified): the piece's output is taken in chunks of
 // CH bytes of the 16-byte grid of the DESTINATION (logical byte x of the piece <-> global address gBase + x, gBase 16-byte aligned, the
 // piece's first byte at x = h).  A lane's run is [s, s + n): `a` single bytes up to the dword grid, then its register stream shifted by `a`
@@ -236,10 +198,6 @@ DEV void hpar_flush_kept(u32 bufOff, u8* gBase, u32 h, u32 total, u32 s, u32 n, 
             if (x + 16u <= h || x >= end) continue;
             typedef u32 hpar_v4 __attribute__((ext_vector_type(4)));
             const hpar_v4 v = *(const __attribute__((address_space(3))) hpar_v4*)(uintptr_t)(chunk + (x - c0));
-#ifdef HPAR_ABL_NOGSTORE   // measurement aid: the line buffer is filled and read, the global stores are left out (results wrong)
-            if (v.x == 0x12345u && v.y == 0x777u) gBase[x] = 0;
-            continue;
-#endif
             if (x >= h && x + 16u <= end) *(hpar_v4*)(gBase + x) = v;
             else {
                 const u32 w[4] = { v.x, v.y, v.z, v.w };
@@ -251,8 +209,7 @@ DEV void hpar_flush_kept(u32 bufOff, u8* gBase, u32 h, u32 total, u32 s, u32 n, 
 }
 
 // ---- staging of (a piece of) a stream: consumption order -- array dword m = bit-reversed stream dword dTop - m, zeros below the stream's first
-// bit -- in units of four dwords.  Two steps so that a stream's loads can be issued EARLY (before the stores of the stream in front of it:
-// loads and stores share one in-order counter, a load issued behind a burst of stores is not seen before the stores are acknowledged):
+// bit -- in units of four dwords.  Two steps: the loads go out before the fence that ends the previous piece's use of the LDS array, the stores behind it:
 //   hpar_stage_load   : one 16-byte load per unit into registers, every load of a lane issued before anything waits; the units that touch either
 //                       end of the stream (dwords beyond its last byte, the partial top dword: one or two lanes) are put together afterwards;
 //   hpar_stage_commit : bit reversal and the LDS stores.
@@ -475,12 +432,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(X2CAP ? 2 : 
     // hold the stream's next dwords instead of zeros.  One piece is the common case (the classes of k_huf_dprep fit their streams).
     constexpr u32 PDW = DATA / 4u - 24u;                                 // dwords of a piece: DATA bytes hold them, 16 dwords of slack and rounding to units
     constexpr u32 MAXU = (DATA / 16 + 63) / 64;
-#ifndef HPAR_EARLY_LOADS
-#define HPAR_EARLY_LOADS 0
-#endif
-    constexpr bool EARLY = HPAR_EARLY_LOADS && DATA < 8192u;                                  // the next stream's loads in front of this stream's stores (registers permitting)
     uint4 buf[MAXU];
-    bool staged = false;                                                 // buf holds the next piece to stage already
     __syncthreads();                                                     // (the table is staged)
 #pragma unroll 1
     for (int q = 0; q < nStreams; ++q) {                                 // uniform: stream after stream
@@ -502,16 +454,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(X2CAP ? 2 : 
             const u32 rest = Sd - mTop, nPc = (rest + PDW - 1u) / PDW;   // what is left of the stream goes in pieces of equal size
             const u32 nd = nPc <= 1u ? rest : (rest + nPc - 1u) / nPc;   // dwords of this piece (<= PDW)
             const bool lastPiece = mTop + nd == Sd;
-            if (!staged) hpar_stage_load<MAXU>(buf, sp, L, Sd, mTop, nd, lane);
-            staged = false;
+            hpar_stage_load<MAXU>(buf, sp, L, Sd, mTop, nd, lane);
             hpar_wave_sync();                                            // (table staged / previous piece done: one wave, its LDS operations run in order)
             hpar_stage_commit<MAXU>(buf, data, nd, lane);
             hpar_wave_sync();
             HST({ const unsigned long long tB = __builtin_readcyclecounter(); tStage += tB - tA; tA = tB; })
-#if defined(HPAR_ABL) && HPAR_ABL == 1     // measurement aid: staging only (results wrong)
-            if (data[lane] == 0x12345u) out[lane] = 0;
-            break;
-#endif
             // cursors below are local to the piece's array: local = global - 32 * mTop
             const u32 C0 = Cstart - 32u * mTop;                          // exact: the stream's first code bit, or where the piece before ended
             const u32 CendL = (lastPiece ? Cend : 32u * (mTop + nd)) - 32u * mTop;
@@ -551,23 +498,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(X2CAP ? 2 : 
             // the last piece must regenerate exactly what is left of the segment and end exactly on the stream's first bit; a piece before
             // it must leave symbols to regenerate
             if (lastPiece ? (outBase + total != want || endC != CendL) : (outBase + total >= want)) { good = false; break; }   // uniform: not a stream the reference accepts as is
-            // ---- the next stream's loads go out now, in front of this one's stores
-            if (EARLY && lastPiece && q + 1 < nStreams) {
-                const u32 L2 = len[q + 1], Sd2 = (L2 + 3) / 4, Cs2 = 32u * Sd2 - T0[q + 1];
-                const u32 mTop2 = (Cs2 - 1u) >> 5, rest2 = Sd2 - mTop2, nPc2 = (rest2 + PDW - 1u) / PDW, nd2 = nPc2 <= 1u ? rest2 : (rest2 + nPc2 - 1u) / nPc2;
-                hpar_stage_load<MAXU>(buf, sp + L, L2, Sd2, mTop2, nd2, lane);
-                staged = true;
-            }
             // ---- pass 2: my symbols out of the registers; only a piece with a spilled lane decodes them again
-#if defined(HPAR_ABL) && HPAR_ABL == 2     // measurement aid: no stores (results wrong)
-            if (!__any(spill)) { u32 x = 0;
-#pragma unroll
-                for (int k = 0; k < HPAR_KEEP; ++k) x ^= sym[k];
-                if (x == 0x12345u) out[lane] = 0; }
-#else
-#if defined(HPAR_DIRECT_STORE)              // A/B aid (EXPERIMENTS.md): every lane stores its own run straight from the registers
-            if (!__any(spill)) hpar_store_kept(out + (size_t)q * seg + outBase + (incl - n), n, sym);
-#else
             if (!__any(spill)) {
                 u8* const g0 = out + (size_t)q * seg + outBase;
                 const u32 h = (u32)(uintptr_t)g0 & 15u;
@@ -575,14 +506,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(X2CAP ? 2 : 
                 static_assert(CH + 2u * HPAR_FLUSH_SLACK <= DATA, "the line buffer must fit the stream's staging area");
                 hpar_flush_kept<CH>(arr, g0 - h, h, total, h + (incl - n), n, sym, lane);
             }
-#endif
-#endif
             else {
                 u8* p = out + (size_t)q * seg + outBase + (incl - n);
                 u32 left = n, C = S;
-#ifdef HPAR_NO_STORE
-                u32 dummyAcc = 0;
-#endif
                 while (left && ((uintptr_t)p & 3u)) { const u32 c = hpar_single(arr, C, tabOff, mask2); *p++ = (u8)(c >> 8); --left; }
                 if (left >= 16) {
                     HparBulk bk; bk.open(arr, C);
@@ -590,20 +516,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(X2CAP ? 2 : 
                         u32 w[4];
 #pragma unroll
                         for (int t = 0; t < 4; ++t) w[t] = bk.iter(tabOff, mask2);
-#ifdef HPAR_NO_STORE      // measurement aid (EXPERIMENTS.md): pass 2 without its 16-byte stores -- is the scattered store pattern what bounds the kernel?
-                        dummyAcc ^= w[0] ^ w[1] ^ w[2] ^ w[3];
-#else
                         __builtin_memcpy(p, w, 16);
-#endif
                         p += 16; left -= 16;
                     } while (left >= 16);
                     while (left >= 4) { const u32 w = bk.iter(tabOff, mask2); __builtin_memcpy(p, &w, 4); p += 4; left -= 4; }
                     C = bk.cursor();
                 }
                 while (left) { const u32 c = hpar_single(arr, C, tabOff, mask2); *p++ = (u8)(c >> 8); --left; }
-#ifdef HPAR_NO_STORE
-                if (dummyAcc == 0x12345u) *p = 0;
-#endif
             }
             outBase += total;
             Cstart = endC + 32u * mTop;
