@@ -5,6 +5,7 @@ pointers on torch's current stream.  ``results`` tensors are ``torch.int64`` vie
 ``size_t`` return values: a negative value ``-c`` is the error code ``c`` of lib/error_public.h:45-56.
 Single-block functions take numpy arrays (host pointers) and have the reference's exact signatures.
 """
+import contextlib
 import ctypes as C
 import numbers
 
@@ -257,6 +258,21 @@ class FseHip:
         if g:
             g.check("FSE_decompress_batch")
         return dst, results
+
+    @contextlib.contextmanager
+    def decode_timing(self):
+        """Between entry and exit the bit-reversed classes of both FSE decoders run through the TIMED instantiation of k_fse_decode
+        (FSEHIP_debug_decodeTiming, csrc/fse_decode.hip).  Yields a list that holds the 16 counters of g_decTiming once the block has been
+        left -- [2] rounds that ran a long phase, [10] rounds of finishing phases, [4] decoder waves that went through the bulk.  The switch
+        is process-wide and goes back off whatever happens inside; both ends synchronise the device.  A measurement and test aid."""
+        out = []
+        _check(self.lib.FSEHIP_debug_decodeTiming(1, None), "debug_decodeTiming(1)")
+        buf = (C.c_ulonglong * 16)()
+        try:
+            yield out
+        finally:
+            _check(self.lib.FSEHIP_debug_decodeTiming(0, buf), "debug_decodeTiming(0)")
+            out.extend(int(v) for v in buf)
 
     # ------------------------------------------------------------------ tables built on the device (g1-g3)
     def fse_build_ctable_batch(self, src, table_log=11, max_symbol_value=255, sizes=None, header_capacity=512, ctables=None):
