@@ -753,6 +753,120 @@ def _frame_methods():
 _frame_methods()
 
 
+def _frame_dev_methods():
+    # .fse frames on DEVICE buffers (csrc/frame_dev.hip): many contents <-> many frames in one flat CUDA uint8 tensor each, cut by offsets
+    # (n + 1 entries).  Offsets come as a host sequence / numpy array (uploaded here) or as a CUDA int64 tensor (used as it is: with
+    # max_total_blocks, dst, results and workspace given too, the call is launches only and can be captured into a graph).
+    def _offsets(self, offsets, device, need_host):
+        if isinstance(offsets, torch.Tensor) and offsets.is_cuda:
+            dev = offsets.to(torch.int64).contiguous()
+            return dev, (dev.cpu().numpy().astype(np.uint64) if need_host else None)
+        host = np.ascontiguousarray(np.asarray(offsets.cpu() if isinstance(offsets, torch.Tensor) else offsets), dtype=np.uint64)
+        if host.ndim != 1 or host.size < 1:
+            raise ValueError("offsets: one entry more than items")
+        return torch.from_numpy(host.astype(np.int64)).to(device), host
+
+    def _flat(t, what):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
+            raise TypeError("%s must be a contiguous 1-D CUDA uint8 tensor" % what)
+        return t
+
+    def frame_block_count(self, n, block_size_id=5):
+        self.lib.FSEHIP_frame_blockCount.restype = SZ
+        return int(self.lib.FSEHIP_frame_blockCount(SZ(int(n)), C.c_uint(block_size_id)))
+
+    def frame_dbatch_plan(self, sizes, block_size_id=5):
+        """destination offsets of frame_compress_dbatch for contents of these sizes: every frame gets exactly FSEHIP_frame_compressBound bytes"""
+        self.lib.FSEHIP_frame_compressBound.restype = SZ
+        bounds = [int(self.lib.FSEHIP_frame_compressBound(SZ(int(n)), C.c_uint(block_size_id))) for n in sizes]
+        if any(b >= (1 << 62) for b in bounds):
+            raise ValueError("block_size_id %r" % (block_size_id,))
+        return np.concatenate([[0], np.cumsum(np.asarray(bounds, dtype=np.uint64), dtype=np.uint64)]).astype(np.uint64)
+
+    def frame_dbatch_workspace(self, n_frames, max_total_blocks, block_size_id=None, codec=0, device="cuda"):
+        """block_size_id None: the reader's workspace"""
+        if block_size_id is None:
+            self.lib.FSEHIP_frame_decompress_dbatch_workspaceSize.restype = SZ
+            n = int(self.lib.FSEHIP_frame_decompress_dbatch_workspaceSize(SZ(n_frames), SZ(max_total_blocks)))
+        else:
+            self.lib.FSEHIP_frame_compress_dbatch_workspaceSize.restype = SZ
+            n = int(self.lib.FSEHIP_frame_compress_dbatch_workspaceSize(SZ(n_frames), SZ(max_total_blocks), C.c_uint(block_size_id), C.c_int(codec)))
+            if n >= (1 << 62):
+                raise ValueError("block_size_id %r / codec %r" % (block_size_id, codec))
+        return torch.empty(max(n, 1), dtype=torch.uint8, device=device)
+
+    def xxh32_batch(self, data, offsets, seed=0):
+        """hashes[i] = XXH32(data[offsets[i]:offsets[i+1]], seed), as an int64 tensor of values below 2**32"""
+        _flat(data, "data")
+        off, _ = self._offsets(offsets, data.device, False)
+        n = off.numel() - 1
+        h = torch.zeros(max(n, 1), dtype=torch.int32, device=data.device)
+        _check(self.lib.FSEHIP_XXH32_batch(_ptr(h), _ptr(data), _ptr(off), SZ(n), C.c_uint32(seed & 0xFFFFFFFF), _stream()), "XXH32_batch")
+        return h[:n].to(torch.int64) & 0xFFFFFFFF
+
+    def frame_compress_dbatch(self, src, src_offsets, block_size_id=5, codec=0, dst=None, dst_offsets=None, max_total_blocks=None, workspace=None, results=None):
+        """-> (frames, dst_offsets, results): frame i = frames[dst_offsets[i] : dst_offsets[i] + results[i]]; a negative result -c is error code c"""
+        _flat(src, "src")
+        need_host = dst_offsets is None or max_total_blocks is None
+        soff, shost = self._offsets(src_offsets, src.device, need_host)
+        n = soff.numel() - 1
+        if dst_offsets is None:
+            dst_offsets = self.frame_dbatch_plan(np.diff(shost), block_size_id)
+        doff, dhost = self._offsets(dst_offsets, src.device, dst is None)
+        if doff.numel() != n + 1:
+            raise ValueError("dst_offsets: one entry per frame and one more")
+        if max_total_blocks is None:
+            max_total_blocks = sum(self.frame_block_count(int(x), block_size_id) for x in np.diff(shost)) if block_size_id <= 6 else 0
+        g = None
+        if dst is None:
+            total = int(dhost[-1])
+            dst, g = self._dst(1, total, src.device)
+            dst = dst[0]
+        res = torch.zeros(max(n, 1), dtype=torch.int64, device=src.device)[:n] if results is None else results
+        ws = workspace if workspace is not None else self.frame_dbatch_workspace(n, max_total_blocks, min(block_size_id, 6), codec if codec in (0, 1) else 0, src.device)
+        _check(self.lib.FSEHIP_frame_compress_dbatch(_ptr(dst), _ptr(doff), _ptr(res), _ptr(src), _ptr(soff), SZ(n), SZ(max_total_blocks),
+                                                     C.c_uint(block_size_id), C.c_int(codec), _ptr(ws), SZ(ws.numel()), _stream()), "frame_compress_dbatch")
+        if g is not None:
+            g.check("frame_compress_dbatch")
+            # ... and inside the slots: the writer's contract is the frame's bytes and nothing else (include/fsehip.h)
+            total = int(dhost[-1])
+            if total:
+                idx = torch.arange(total, device=src.device)
+                slot = torch.searchsorted(doff[1:].contiguous(), idx, right=True).clamp(max=n - 1)
+                beyond = (idx - doff[slot]) >= res[slot].clamp(min=0)
+                assert bool((g.full[0, :total][beyond] == g.fill).all()), "frame_compress_dbatch wrote behind a frame's last byte"
+        return dst, doff, res
+
+    def frame_decompress_dbatch(self, frames, frame_offsets, dst_offsets, dst=None, max_total_blocks=None, workspace=None, results=None):
+        """-> (dst, results): content i = dst[dst_offsets[i] : dst_offsets[i] + results[i]]; capacity of slot i = dst_offsets[i+1] - dst_offsets[i]"""
+        _flat(frames, "frames")
+        foff, fhost = self._offsets(frame_offsets, frames.device, max_total_blocks is None)
+        n = foff.numel() - 1
+        doff, dhost = self._offsets(dst_offsets, frames.device, dst is None)
+        if doff.numel() != n + 1:
+            raise ValueError("dst_offsets: one entry per frame and one more")
+        if max_total_blocks is None:                      # a frame of F bytes: at most (F - 8) / 2 blocks
+            max_total_blocks = int(sum(max(int(x) - 8, 0) // 2 for x in np.diff(fhost)))
+        g = None
+        if dst is None:
+            dst, g = self._dst(1, int(dhost[-1]), frames.device)
+            dst = dst[0]
+        res = torch.zeros(max(n, 1), dtype=torch.int64, device=frames.device)[:n] if results is None else results
+        ws = workspace if workspace is not None else self.frame_dbatch_workspace(n, max_total_blocks, None, 0, frames.device)
+        _check(self.lib.FSEHIP_frame_decompress_dbatch(_ptr(dst), _ptr(doff), _ptr(res), _ptr(frames), _ptr(foff), SZ(n), SZ(max_total_blocks),
+                                                       _ptr(ws), SZ(ws.numel()), _stream()), "frame_decompress_dbatch")
+        if g is not None:
+            g.check("frame_decompress_dbatch")
+        return dst, res
+
+    FseHip._flat = staticmethod(_flat)
+    for f in (_offsets, frame_block_count, frame_dbatch_plan, frame_dbatch_workspace, xxh32_batch, frame_compress_dbatch, frame_decompress_dbatch):
+        setattr(FseHip, f.__name__, f)
+
+
+_frame_dev_methods()
+
+
 # ---------------------------------------------------------------------------------------------------------
 #  FSE for 16-bit symbols (lib/fseU16.h): sizes of the uncompressed side are in symbols
 # ---------------------------------------------------------------------------------------------------------

@@ -151,6 +151,13 @@ static inline BlockView mkview(const void* base, size_t stride, const size_t* si
 {
     BlockView v; v.base = (const u8*)base; v.stride = stride; v.sizes = sizes; v.uniform = uniform; v.offsets = nullptr; return v;
 }
+static inline BlockView subview(const BlockView& v, size_t b0)      // blocks b0.. of a view
+{
+    BlockView r = v;
+    if (v.offsets) r.offsets = v.offsets + b0;
+    else { r.base = v.base + b0 * v.stride; r.sizes = v.sizes ? v.sizes + b0 : nullptr; }
+    return r;
+}
 
 // =====================================================================================================
 //  workload generator
@@ -334,6 +341,14 @@ extern "C" int FSEHIP_FSE_compress_batch(void* d_dst, size_t dstStride, size_t d
         if (ctBytes <= wksp && wksp - ctBytes < 4096)
             return batch_arg_error(d_results, d_sizes, uniformSize, dstCapacity, nBlocks, FSEHIP_ERROR(workSpace_tooSmall), 2, s);
     }
+    return fse_compress_view(d_dst, dstStride, dstCapacity, d_results, mkview(d_src, srcStride, d_sizes, uniformSize), maxSymbolValue, tableLog, nBlocks,
+                             d_workspace, workspaceBytes, s);
+}
+// the pipeline itself, on any view of the source blocks (strided, or packed: BlockView::offsets -- the device frame writer, frame_dev.hip);
+// arguments already checked
+int fse_compress_view(void* d_dst, size_t dstStride, size_t dstCapacity, size_t* d_results, const BlockView& srcAll, unsigned maxSymbolValue, unsigned tableLog,
+                      size_t nBlocks, void* d_workspace, size_t workspaceBytes, hipStream_t s)
+{
     const FseCWs w = fse_cws(tableLog);
     if (workspaceBytes < w.perBlock + WS_SLACK) return (int)hipErrorInvalidValue;
     size_t chunk = (workspaceBytes - WS_SLACK) / w.perBlock;
@@ -357,7 +372,7 @@ extern "C" int FSEHIP_FSE_compress_batch(void* d_dst, size_t dstStride, size_t d
     if (msv > 255) msv = 255;
     for (size_t b0 = 0; b0 < nBlocks; b0 += chunk) {
         const size_t nb = (nBlocks - b0) < chunk ? (nBlocks - b0) : chunk;
-        const BlockView src = mkview((const u8*)d_src + b0 * srcStride, srcStride, d_sizes ? d_sizes + b0 : nullptr, uniformSize);
+        const BlockView src = subview(srcAll, b0);
         HistArgs h;
         h.counts = counts; h.maxSVs = maxSVs; h.uniformMaxSV = msv; h.useUniformIn = 1; h.results = hres; h.src = src; h.nBlocks = nb;
         CK(launch_hist(h, s));
@@ -388,19 +403,13 @@ extern "C" size_t FSEHIP_FSE_decompress_batch_workspaceSize(size_t nBlocks, unsi
     return c * fse_dws_per_block(clamp_maxlog(maxLog)) + WS_SLACK;
 }
 
-static inline BlockView subview(const BlockView& v, size_t b0)      // blocks b0.. of a view
-{
-    BlockView r = v;
-    if (v.offsets) r.offsets = v.offsets + b0;
-    else { r.base = v.base + b0 * v.stride; r.sizes = v.sizes ? v.sizes + b0 : nullptr; }
-    return r;
-}
 // rawRle: the bench loop's treatment of blocks the compressor declined (programs/bench.c:393-406) -- a record as long as the block is the
 // block itself, a record of one byte is that byte repeated -- applied by k_rawrle_expand (compact.hip); k_fse_dparse then leaves those alone
 hipError_t launch_rawrle_expand(u8* dst, size_t dstStride, size_t dstCapacity, size_t* results, const BlockView& csrc, const size_t* origSizes, size_t uniformOrig,
                                 size_t nBlocks, hipStream_t s);
 static int fse_decompress_impl(void* d_dst, size_t dstStride, size_t dstCapacity, size_t* d_results, const BlockView& csAll, unsigned maxLog, size_t nBlocks,
-                               void* d_workspace, size_t workspaceBytes, hipStream_t s, const size_t* d_origSizes, size_t uniformOrig, int rawRle)
+                               void* d_workspace, size_t workspaceBytes, hipStream_t s, const size_t* d_origSizes, size_t uniformOrig, int rawRle,
+                               const u64* d_dstOffsets = nullptr, const size_t* d_dstCaps = nullptr)
 {
     if ((uintptr_t)d_workspace & 255u) return (int)hipErrorInvalidValue;          // include/fsehip.h: workspaces are 256-byte aligned; checked before anything else
     if (nBlocks == 0) return 0;
@@ -431,6 +440,7 @@ static int fse_decompress_impl(void* d_dst, size_t dstStride, size_t dstCapacity
         e.csrc = cs; e.dtables = nullptr; e.dtStrideU32 = 0; e.atab = atab; e.symtab = symtab; e.meta = meta;
         e.maxTableLog = maxLog; e.G = 0; e.slotU32 = 0; e.nBlocks = nb; e.tlMin = 0; e.declineNb0 = 0; e.onlyDeclined = 0;
         e.symScratch = nullptr; e.slotBitmap = nullptr; e.nSlots = 0; e.scratchSlotBytes = 0;
+        if (d_dstOffsets) { e.dst = (u8*)d_dst; e.dstOffsets = d_dstOffsets + b0; e.dstCaps = d_dstCaps + b0; }
         CK(launch_fse_decode_classes(e, lists, counts, s));
     }
     return 0;
@@ -442,6 +452,11 @@ extern "C" int FSEHIP_FSE_decompress_batch(void* d_dst, size_t dstStride, size_t
 {
     return fse_decompress_impl(d_dst, dstStride, dstCapacity, d_results, mkview(d_cSrc, cStride, d_cSizes, uniformCSize), maxLog, nBlocks,
                                d_workspace, workspaceBytes, (hipStream_t)stream, nullptr, 0, 0);
+}
+int fse_decompress_view(void* d_dst, const u64* d_dstOffsets, const size_t* d_dstCaps, size_t* d_results, const BlockView& csrc, unsigned maxLog, size_t nBlocks,
+                        void* d_workspace, size_t workspaceBytes, hipStream_t s)
+{
+    return fse_decompress_impl(d_dst, 0, 0, d_results, csrc, maxLog, nBlocks, d_workspace, workspaceBytes, s, nullptr, 0, 0, d_dstOffsets, d_dstCaps);
 }
 // FSE_decompress over a PACKED batch (FSEHIP_compact_batch), with the bench loop's treatment of declined blocks
 extern "C" int FSEHIP_FSE_decompress_packed_batch(void* d_dst, size_t dstStride, size_t dstCapacity, size_t* d_results,
@@ -1215,6 +1230,13 @@ static int huf_compress_impl(int streams, void* d_dst, size_t dstStride, size_t 
     if (tableLog > FSEHIP_HUF_TABLELOG_MAX || maxSymbolValue > 255)               // huf_compress.c:656-660, in the reference's order, per block
         return batch_arg_error(d_results, d_sizes, uniformSize, dstCapacity, nBlocks,
                                tableLog > FSEHIP_HUF_TABLELOG_MAX ? FSEHIP_ERROR(tableLog_tooLarge) : FSEHIP_ERROR(maxSymbolValue_tooLarge), 1, s);
+    return huf_compress_view(streams, d_dst, dstStride, dstCapacity, d_results, mkview(d_src, srcStride, d_sizes, uniformSize), maxSymbolValue, tableLog, nBlocks,
+                             d_workspace, workspaceBytes, s);
+}
+// (as fse_compress_view)
+int huf_compress_view(int streams, void* d_dst, size_t dstStride, size_t dstCapacity, size_t* d_results, const BlockView& srcAll, unsigned maxSymbolValue,
+                      unsigned tableLog, size_t nBlocks, void* d_workspace, size_t workspaceBytes, hipStream_t s)
+{
     if (workspaceBytes < HUF_CWS_PER_BLOCK + HUF_CWS_NODE_PAD + WS_SLACK) return (int)hipErrorInvalidValue;
     size_t chunk = (workspaceBytes - WS_SLACK - HUF_CWS_NODE_PAD) / HUF_CWS_PER_BLOCK;
     if (chunk >= nBlocks) chunk = nBlocks;
@@ -1229,7 +1251,7 @@ static int huf_compress_impl(int streams, void* d_dst, size_t dstStride, size_t 
     const unsigned msv = maxSymbolValue ? maxSymbolValue : 255;   // huf_compress.c:661
     for (size_t b0 = 0; b0 < nBlocks; b0 += chunk) {
         const size_t nb = (nBlocks - b0) < chunk ? (nBlocks - b0) : chunk;
-        const BlockView src = mkview((const u8*)d_src + b0 * srcStride, srcStride, d_sizes ? d_sizes + b0 : nullptr, uniformSize);
+        const BlockView src = subview(srcAll, b0);
         HistArgs h;
         h.counts = counts; h.maxSVs = maxSVs; h.uniformMaxSV = msv; h.useUniformIn = 1; h.results = hres; h.src = src; h.nBlocks = nb;
         CK(launch_hist(h, s));
@@ -1265,7 +1287,7 @@ extern "C" size_t FSEHIP_HUF_decompress_batch_workspaceSize(size_t nBlocks)
 }
 
 static int huf_decompress_impl(void* d_dst, size_t dstStride, const size_t* d_dstSizes, size_t uniformDstSize, size_t* d_results, const BlockView& csAll,
-                               size_t nBlocks, void* d_workspace, size_t workspaceBytes, hipStream_t s)
+                               size_t nBlocks, void* d_workspace, size_t workspaceBytes, hipStream_t s, const u64* d_dstOffsets = nullptr)
 {
     if ((uintptr_t)d_workspace & 255u) return (int)hipErrorInvalidValue;          // include/fsehip.h: workspaces are 256-byte aligned; checked before anything else
     if (nBlocks == 0) return 0;
@@ -1286,11 +1308,13 @@ static int huf_decompress_impl(void* d_dst, size_t dstStride, const size_t* d_ds
         d.csrc = cs; d.dstSizes = ds; d.dst = (u8*)d_dst + b0 * dstStride; d.dstStride = dstStride;
         d.dtables = dtables; d.dtStrideU32 = dtU32; d.meta = meta; d.lists = lists; d.counts = counts; d.results = d_results + b0; d.nBlocks = nb;
         d.tableOnly = 0; d.dtMaxLog = FSEHIP_HUF_TABLELOG_MAX - 1;
+        if (d_dstOffsets) { d.dst = (u8*)d_dst; d.dstOffsets = d_dstOffsets + b0; }
         CK(launch_huf_dprep(d, s));
         HufDecArgs e;
         e.dst = (u8*)d_dst + b0 * dstStride; e.dstStride = dstStride; e.dstSizes = ds; e.results = d_results + b0;
         e.csrc = cs; e.dtables = dtables; e.dtStrideU32 = dtU32; e.meta = meta;
         e.maxTableLog = FSEHIP_HUF_TABLELOG_MAX; e.G = 0; e.slotU32 = 0; e.streams = 4; e.acceptX2 = 0; e.onlyDeclined = 0; e.classLo = 0; e.nBlocks = nb;
+        if (d_dstOffsets) { e.dst = (u8*)d_dst; e.dstOffsets = d_dstOffsets + b0; }
         CK(launch_huf_decode_classes(e, lists, counts, s));
     }
     return 0;
@@ -1301,6 +1325,11 @@ extern "C" int FSEHIP_HUF_decompress_batch(void* d_dst, size_t dstStride, const 
 {
     return huf_decompress_impl(d_dst, dstStride, d_dstSizes, uniformDstSize, d_results, mkview(d_cSrc, cStride, d_cSizes, uniformCSize), nBlocks,
                                d_workspace, workspaceBytes, (hipStream_t)stream);
+}
+int huf_decompress_view(void* d_dst, const u64* d_dstOffsets, const size_t* d_dstSizes, size_t* d_results, const BlockView& csrc, size_t nBlocks,
+                        void* d_workspace, size_t workspaceBytes, hipStream_t s)
+{
+    return huf_decompress_impl(d_dst, 0, d_dstSizes, 0, d_results, csrc, nBlocks, d_workspace, workspaceBytes, s, d_dstOffsets);
 }
 // HUF_decompress over a PACKED batch (FSEHIP_compact_batch): HUF_decompress itself takes a record as long as the block for the block and
 // a record of one byte for that byte repeated (lib/huf_decompress.c:1063-1066), which is how the compaction stores what HUF_compress declined

@@ -26,6 +26,7 @@ DEV u64 ld64(const u8* p) { return (u64)ld32(p) | ((u64)ld32(p + 4) << 32); }
 
 // A strided batch of byte blocks: block b = base + b*stride, size sizes[b] (or `uniform` when sizes == nullptr).
 // Packed form (FSEHIP_compact_batch): `offsets` (nBlocks + 1 entries) instead -- block b = base + offsets[b], offsets[b+1] - offsets[b] bytes.
+// Both set (the device frame reader: headers lie between the blocks): block b = base + offsets[b], sizes[b] bytes, nBlocks offsets.
 struct BlockView {
     const u8* base;
     size_t stride;
@@ -33,7 +34,7 @@ struct BlockView {
     size_t uniform;
     const u64* offsets;
 };
-DEV size_t view_size(const BlockView& v, size_t b) { return v.offsets ? (size_t)(v.offsets[b + 1] - v.offsets[b]) : v.sizes ? v.sizes[b] : v.uniform; }
+DEV size_t view_size(const BlockView& v, size_t b) { return v.offsets ? (v.sizes ? v.sizes[b] : (size_t)(v.offsets[b + 1] - v.offsets[b])) : v.sizes ? v.sizes[b] : v.uniform; }
 DEV const u8* view_ptr(const BlockView& v, size_t b) { return v.offsets ? v.base + v.offsets[b] : v.base + b * v.stride; }
 
 // ---- cross-lane scans and reductions on the VALU's DPP path (round 6) ----------------------------------------------------------------------

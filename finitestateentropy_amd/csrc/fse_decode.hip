@@ -515,7 +515,9 @@ DEV size_t fse_tail(const Cells& t, u32 s1, u32 s2, BitReader& r, u8* out, long 
 //                           cells: divergent rounds of long phases.
 //   5. hand-back and tail   the even lane of every pair that owns a block; the wave stays whole to the end (caller tables: it reports to
 //                           fse_scratch_slot_done as a whole).
-template <bool FAST, bool TIMED, bool CALLER>
+// VIEW (the device frame reader, frame_dev.hip): block b is written at dst + dstOffsets[b] with its own capacity dstCaps[b] instead of into slot b of a
+// strided batch with one capacity -- an instantiation of its own, so that the batch kernels keep the capacity in a scalar register.
+template <bool FAST, bool TIMED, bool CALLER, bool VIEW = false>
 __global__ __launch_bounds__(FSE_DEC_THREADS) void k_fse_decode(FseDecArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) u32 lds[];
@@ -787,14 +789,14 @@ __global__ __launch_bounds__(FSE_DEC_THREADS) void k_fse_decode(FseDecArgs a)
     const u32 tabOff = ldsBase + (u32)(gsl < a.G ? gsl : 0) * tabStride;
     const u16* const A = (const u16*)(lds8 + (tabOff - ldsBase));
     const u8* in = nullptr; size_t S = 0; u8* out = nullptr;
-    const long omax = (long)a.dstCapacity;
+    const long omax = VIEW ? (long)a.dstCaps[owner ? b : 0] : (long)a.dstCapacity;
     long op = 0;
     BitReader r; r.base = nullptr; r.size = 0; r.at = 0; r.win = 0; r.used = 0;
     u32 s1 = 0, s2 = 0;
     if (owner) {
         in = view_ptr(a.csrc, b) + hdr;
         S = view_size(a.csrc, b) - hdr;              // hdr <= cSrcSize (FSE_readNCount never returns more)
-        out = a.dst + b * a.dstStride;
+        out = VIEW ? a.dst + a.dstOffsets[b] : a.dst + b * a.dstStride;
         const size_t e = r.init(in, S);
         if (is_err(e)) { a.results[b] = e; owner = false; }
         else {
@@ -1102,6 +1104,15 @@ static hipError_t fse_decode_launch(FseDecArgs a, bool rev, hipStream_t s)
     if (a.G < 1) return hipErrorInvalidValue;
     if (caller && ((size_t)a.G << a.ldsLog) > FSE_SYM_SLOT_BYTES) return hipErrorInvalidValue;
     const size_t groups = (a.nBlocks + a.G - 1) / a.G;
+    if (a.dstOffsets) {                                              // destination view: one-shot path only
+        if (caller || !a.dstCaps) return hipErrorInvalidValue;
+        hipError_t e = ensure_dyn_lds((const void*)k_fse_decode<true, false, false, true>, FSE_DEC_LDS);
+        if (e == hipSuccess) e = ensure_dyn_lds((const void*)k_fse_decode<false, false, false, true>, FSE_DEC_LDS);
+        if (e != hipSuccess) return e;
+        if (rev) hipLaunchKernelGGL((k_fse_decode<true, false, false, true>), dim3((unsigned)groups), dim3(FSE_DEC_THREADS), ldsBytes, s, a);
+        else     hipLaunchKernelGGL((k_fse_decode<false, false, false, true>), dim3((unsigned)groups), dim3(FSE_DEC_THREADS), ldsBytes, s, a);
+        return hipGetLastError();
+    }
     if (caller) {
         if (rev && g_decTimingOn.load(std::memory_order_relaxed)) {
             hipError_t e = ensure_dyn_lds((const void*)k_fse_decode<true, true, true>, FSE_DEC_LDS);

@@ -79,8 +79,9 @@ __global__ __launch_bounds__(64) void k_fse_encode(FseEncArgs a)
     const u32* const tt = lds + (size_t)lane * a.slotU32 + 1 + (tl ? (1u << (tl - 1)) : 1u);
 
     // uniform base + 32-bit lane offset addressing (launcher guarantees G*stride + size < 4 GiB)
-    const u8* const sbase = a.src.base + first * a.src.stride;
-    const u32 soff = lane * (u32)a.src.stride;
+    // (a packed view -- BlockView::offsets -- has no common base: the block's own address, lane offset 0)
+    const u8* const sbase = a.src.offsets ? a.src.base + a.src.offsets[b] : a.src.base + first * a.src.stride;
+    const u32 soff = a.src.offsets ? 0u : lane * (u32)a.src.stride;
     u8* const dbase = a.dst + first * a.dstStride;
     const u32 doff = lane * (u32)a.dstStride + hdr;
     const size_t n64 = view_size(a.src, b);

@@ -292,7 +292,7 @@ __global__ __launch_bounds__(HD_THREADS) void k_huf_decode(HufDecArgs a)
         const u8* const in = view_ptr(a.csrc, b) + hdr;
         const size_t cSize = view_size(a.csrc, b) - hdr;
         dstSize = view_size(a.dstSizes, b);
-        out = a.dst + b * a.dstStride;
+        out = a.dstOffsets ? a.dst + a.dstOffsets[b] : a.dst + b * a.dstStride;
         if (((desc >> 8) & 0xFFu) != 0) blockErr = FERR(GENERIC);                       // X2 table: huf_decompress.c:411-412 (4X1 entry point)
         else if (dtLog > a.maxTableLog) blockErr = FERR(tableLog_tooLarge);
         else if (dtLog < 1) blockErr = FERR(corruption_detected);                       // no table has tableLog 0 (a zero-filled DTable): the reference's look-up
@@ -456,7 +456,7 @@ __global__ __launch_bounds__(64) void k_huf_decode_x2(HufDecArgs a)
     const u32* const cells = gt + 1;
     const u8* const in = view_ptr(a.csrc, b);
     const size_t cSize = view_size(a.csrc, b), dstSize = view_size(a.dstSizes, b);
-    u8* const ostart = a.dst + b * a.dstStride;
+    u8* const ostart = a.dstOffsets ? a.dst + a.dstOffsets[b] : a.dst + b * a.dstStride;
     size_t result;
     do {
         if (dtLog > a.maxTableLog) { result = FERR(tableLog_tooLarge); break; }
@@ -505,7 +505,7 @@ __global__ __launch_bounds__(64) void k_huf_decode_1x(HufDecArgs a)
     const u32 tableType = (desc >> 8) & 0xFFu, dtLog = (desc >> 16) & 0xFFu;
     const u8* const in = view_ptr(a.csrc, b);
     const size_t cSize = view_size(a.csrc, b), dstSize = view_size(a.dstSizes, b);
-    u8* const ostart = a.dst + b * a.dstStride;
+    u8* const ostart = a.dstOffsets ? a.dst + a.dstOffsets[b] : a.dst + b * a.dstStride;
     size_t result;
     do {
         if (tableType != 0 && !(a.acceptX2 && tableType == 1)) { result = FERR(GENERIC); break; }   // :367-369 (the 1X1 entry point)

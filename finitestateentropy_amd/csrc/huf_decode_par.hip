@@ -285,7 +285,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(X2CAP ? 2 : 
     const u8* const in = view_ptr(a.csrc, b) + hdr;
     const size_t cSize = view_size(a.csrc, b) - hdr;
     const size_t dstSize = view_size(a.dstSizes, b);
-    u8* const out = a.dst + b * a.dstStride;
+    u8* const out = a.dstOffsets ? a.dst + a.dstOffsets[b] : a.dst + b * a.dstStride;
 
     // ---- can this block take the parallel path?  (uniform)  Anything unusual is the serial decoder's business.
     const u32 tableType = (desc >> 8) & 0xFFu;                           // 0: single-symbol cells (X1); 1: double-symbol cells (X2), caller-built only

@@ -817,7 +817,7 @@ __global__ __launch_bounds__(64) void k_huf_dprep(HufDPrepArgs a)
         HufMeta m; m.state = 0; m.hdrSize = 0; m.tableLog = 0; m.maxSV = 0;
         if (state == 2 || state == 3) {                                    // coalesced copy / fill of the whole block
             const u8* const in = view_ptr(a.csrc, b);
-            u8* const dst = a.dst + b * a.dstStride;
+            u8* const dst = a.dstOffsets ? a.dst + a.dstOffsets[b] : a.dst + b * a.dstStride;
             const size_t dstSize = view_size(a.dstSizes, b);
             const u32 fill = (u32)in[0] * 0x01010101u;
             const size_t head = dstSize < 4 ? dstSize : (size_t)((0 - (uintptr_t)dst) & 3u);

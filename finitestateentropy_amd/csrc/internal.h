@@ -163,6 +163,9 @@ struct FseDecArgs {              // a3: FSE_decompress_usingDTable, one lane per
     unsigned tlMin; int declineNb0; int onlyDeclined;
     // ... and their symbols go through a scratch the library keeps per device (set by the launcher, fse_decode.hip)
     u8* symScratch; u32* slotBitmap; u32 nSlots; u32 scratchSlotBytes;
+    // destination view (one-shot path only; both or neither): block b is written at dst + dstOffsets[b] and may take dstCaps[b] bytes --
+    // dstStride and dstCapacity are then unused
+    const u64* dstOffsets = nullptr; const size_t* dstCaps = nullptr;
 };
 // marker in results[] between the launches of the caller-table batch (no size_t a decoder returns, cf. HUF_DECLINED)
 #define FSE_DECLINED ((size_t)0 - (size_t)0x7001)
@@ -231,6 +234,7 @@ struct HufDPrepArgs {            // glue g6: HUF_readStats + HUF_readDTableX1 (+
     u32* counts;
     size_t* results;
     size_t nBlocks;
+    const u64* dstOffsets = nullptr;   // destination view: block b at dst + dstOffsets[b] (dstStride unused), or nullptr
     int tableOnly;               // HUF_readDTableX1 over a batch (lib/huf_decompress.c:118-185): no raw / RLE decisions, nothing of the payload
                                  // looked at; results[b] = header size (HUF_readStats' return value) or its error
     unsigned dtMaxLog;           // DTableDesc.maxTableLog of the tables (the one-shot path: HUF_TABLELOG_MAX - 1, lib/huf_decompress.c:1030)
@@ -259,6 +263,7 @@ struct HufDecArgs {              // a5: HUF_decompress4X1_usingDTable, 4 lanes p
     unsigned classLo;            // usingDTable batch only (no workspace, hence no class lists): a launch of the stream-parallel decoder takes the blocks whose
                                  // longest stream needs more than classLo bytes of LDS (and fits its own budget, or it is the largest class)
     size_t nBlocks;
+    const u64* dstOffsets = nullptr;   // destination view: block b at dst + dstOffsets[b] (dstStride unused), or nullptr
 };
 // The caller-table batch has no workspace for a list of declined blocks: the stream-parallel decoder marks a block it declines with
 // this value in results[b] (no size_t a decoder returns: sizes are below 2^28 there, error codes above (size_t)-9), and the
@@ -321,6 +326,17 @@ private:
 struct DevProps { int cus; int ldsPerCU; bool ok; };
 const DevProps& dev_props();
 hipError_t ensure_dyn_lds(const void* kernel, int bytes);
+// the one-shot pipelines on views (capi.hip): the batch calls with the source blocks, or the compressed blocks and the destinations, anywhere in one
+// buffer -- what the device frame calls (frame_dev.hip) need.  Same workspaces as the batch calls of the same name.
+int fse_compress_view(void* d_dst, size_t dstStride, size_t dstCapacity, size_t* d_results, const BlockView& src, unsigned maxSymbolValue, unsigned tableLog,
+                      size_t nBlocks, void* d_workspace, size_t workspaceBytes, hipStream_t s);
+int huf_compress_view(int streams, void* d_dst, size_t dstStride, size_t dstCapacity, size_t* d_results, const BlockView& src, unsigned maxSymbolValue,
+                      unsigned tableLog, size_t nBlocks, void* d_workspace, size_t workspaceBytes, hipStream_t s);
+int fse_decompress_view(void* d_dst, const u64* d_dstOffsets, const size_t* d_dstCaps, size_t* d_results, const BlockView& csrc, unsigned maxLog, size_t nBlocks,
+                        void* d_workspace, size_t workspaceBytes, hipStream_t s);
+int huf_decompress_view(void* d_dst, const u64* d_dstOffsets, const size_t* d_dstSizes, size_t* d_results, const BlockView& csrc, size_t nBlocks,
+                        void* d_workspace, size_t workspaceBytes, hipStream_t s);
+hipError_t launch_xxh32(u32* hashes, const u8* data, const u64* starts, const u64* lens, size_t nItems, u32 seed, hipStream_t s);   // frame_dev.hip; lens == nullptr: starts[i + 1] - starts[i]
 int release_thread_scratch(void);          // capi.hip: gives the calling thread's host-call arena back
 int frame_pool_release_scratch(void);       // frame.hip: the same for the idle helper threads of the batched frame calls (0, a hipError_t, or FSEHIP_SCRATCH_BUSY)
 int frame_pool_shutdown(void);              // frame.hip: ends and joins those threads

@@ -401,6 +401,50 @@ FSEHIP_API size_t FSEHIP_frame_compress_batch(void* const* dsts, const size_t* d
 FSEHIP_API size_t FSEHIP_frame_decompress_batch(void* const* dsts, const size_t* dstCapacities, const void* const* srcs, const size_t* srcSizes,
                                                 size_t* results, size_t nFrames, unsigned nThreads);
 
+/* ---- .fse frames on DEVICE buffers (frame_dev.hip): the same container (programs/fileio.c:266-285), written and read without the bytes
+ * leaving the device.  Like every batched call: kernel launches on `stream` and nothing else (no synchronisation, no read-back, no
+ * allocation, no memset / copy nodes), so the calls can be captured into a HIP graph; all pointers are DEVICE pointers, workspaces
+ * 256-byte aligned; the return value is a hipError_t (0 = launched; hipErrorInvalidValue: blockSizeId > 6, codec not 0 / 1, workspace
+ * misaligned or too small), a frame's own outcome is its d_results entry.
+ *
+ *   FSEHIP_XXH32_batch   d_hashes[i] = XXH32(d_data[d_offsets[i] .. d_offsets[i+1]), seed) -- the checksum the tool streams over the
+ *                        content (fileio.c:303,339,408), here as a call of its own (per-block or per-tensor checksums on the device).
+ *                        nItems + 1 offsets; items start at any alignment; one lane quad per item (the hash is four serial chains: the
+ *                        parallel axis is the items).  Reads exactly the items' bytes.
+ *
+ *   FSEHIP_frame_blockCount   host arithmetic: blocks of a content of srcSize bytes, ceil(srcSize / (1 KB << blockSizeId)); id > 6: GENERIC.
+ *
+ *   FSEHIP_frame_compress_dbatch   (FIO_compressFilename, fileio.c:286-432, over many contents)
+ *     content i = d_src[d_srcOffsets[i] .. d_srcOffsets[i+1])  (contents back to back), frame i is written at d_dst + d_dstOffsets[i],
+ *     its capacity is d_dstOffsets[i+1] - d_dstOffsets[i] (nFrames + 1 entries each).  d_results[i] = what FSEHIP_frame_compress returns
+ *     for that content and capacity, byte for byte the same frame: dstSize_tooSmall below FSEHIP_frame_compressBound, a block coder's
+ *     error otherwise.  maxTotalBlocks is the caller's promise >= sum of FSEHIP_frame_blockCount(size_i): it sizes the launches, so that no
+ *     size is read back.  A frame whose blocks do not all lie inside the promise gets GENERIC; the others are unaffected.  All blocks of all
+ *     frames go through ONE call of the one-shot coder.
+ *     Memory: reads the contents; writes exactly the bytes of every frame that succeeds -- nothing into the slot of a frame that fails,
+ *     nothing behind a frame's last byte.
+ *
+ *   FSEHIP_frame_decompress_dbatch   (FIO_decompressFilename, fileio.c:462-626, over many frames)
+ *     frame i = d_frames[d_frameOffsets[i] .. d_frameOffsets[i+1]), regenerated at d_dst + d_dstOffsets[i], capacity d_dstOffsets[i+1] -
+ *     d_dstOffsets[i].  Frames describe themselves: codecs and block-size ids may differ inside one call.  d_results[i] = what
+ *     FSEHIP_frame_decompress(dst, capacity_i, frame_i, size_i) returns, with the same regenerated bytes, for intact and damaged frames
+ *     alike -- blocks in order (per block dstSize_tooSmall before its decoding error), then the structural error of the header walk, then
+ *     the checksum.  maxTotalBlocks >= the number of blocks in all frames (a frame of F bytes has at most (F - 8) / 2); a frame beyond the
+ *     promise gets GENERIC and writes nothing.
+ *     Memory: a frame's result depends on nothing outside its [offset, next offset) -- the header walk reads nothing else; the block
+ *     decoders fetch aligned 64-byte pieces and may touch, without using them, bytes of the neighbouring frames inside d_frames.  Nothing is
+ *     written outside a frame's destination slot; inside the slot, bytes behind the regenerated size are undefined.
+ */
+FSEHIP_API int FSEHIP_XXH32_batch(uint32_t* d_hashes, const void* d_data, const uint64_t* d_offsets, size_t nItems, uint32_t seed, void* stream);
+FSEHIP_API size_t FSEHIP_frame_blockCount(size_t srcSize, unsigned blockSizeId);
+FSEHIP_API size_t FSEHIP_frame_compress_dbatch_workspaceSize(size_t nFrames, size_t maxTotalBlocks, unsigned blockSizeId, int codec);
+FSEHIP_API int FSEHIP_frame_compress_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_src, const uint64_t* d_srcOffsets,
+                                            size_t nFrames, size_t maxTotalBlocks, unsigned blockSizeId, int codec,
+                                            void* d_workspace, size_t workspaceBytes, void* stream);
+FSEHIP_API size_t FSEHIP_frame_decompress_dbatch_workspaceSize(size_t nFrames, size_t maxTotalBlocks);
+FSEHIP_API int FSEHIP_frame_decompress_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_frames, const uint64_t* d_frameOffsets,
+                                              size_t nFrames, size_t maxTotalBlocks, void* d_workspace, size_t workspaceBytes, void* stream);
+
 /* ---- FSE for 16-bit symbols (lib/fseU16.h:62-80, lib/fseU16.c) -- SURVEY 8(f) rank 4.  Alphabets of up to
  * FSEHIP_FSEU16_MAX_SYMBOL_VALUE + 1 symbols, table logs up to 13 (default 12), ONE tANS state per stream: a different format from
  * the byte coder's.  Sizes of the uncompressed side are in SYMBOLS (as in the reference), strides in bytes.

@@ -25,6 +25,9 @@ sqtable = "\n".join(lines)
 
 num = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "design_table.py"), os.path.join(ROOT, "profiles", "%s_bench_detail.json" % tag)], stdout=subprocess.PIPE, check=True).stdout.decode()
 numtable = num.split("\n\nroofline:")[0].rstrip()
+extra = os.path.join(ROOT, "profiles", "framedev_numtable.md")          # rows measured by scripts/framedevbench.py, not by bench.py
+if os.path.exists(extra):
+    numtable += "\n" + open(extra).read().rstrip()
 
 r, re_, s = d["roofline"], d["roofline_encode"], d["roofline"].get("secondary") or {}
 w = s.get("where_the_rest_goes") or {}
