@@ -127,7 +127,7 @@ class FseHip:
                      "FSEHIP_FSE_countU16", "FSEHIP_FSE_compressU16", "FSEHIP_FSE_decompressU16",
                      "FSEHIP_FSE_compressU16_batch_workspaceSize", "FSEHIP_FSE_decompressU16_batch_workspaceSize",
                      "FSEHIP_FSE_buildCTable_batch_workspaceSize", "FSEHIP_FSE_buildDTable_batch_workspaceSize",
-                     "FSEHIP_HUF_buildCTable_batch_workspaceSize", "FSEHIP_HUF_readDTableX1_batch_workspaceSize",
+                     "FSEHIP_HUF_buildCTable_batch_workspaceSize", "FSEHIP_HUF_readDTableX1_batch_workspaceSize", "FSEHIP_HUF_readDTableX2_batch_workspaceSize",
                      "FSEHIP_compact_batch_workspaceSize", "FSEHIP_compact_batch_bound", "FSEHIP_HUF_compress1X",
                      "FSEHIP_HUF_decompress4X1", "FSEHIP_HUF_decompress1X1"):
             if hasattr(L, name):
@@ -601,6 +601,33 @@ def _huf_methods():
                                                       SZ(n), _ptr(ws), SZ(ws.numel()), _stream()), "HUF_readDTableX1_batch")
         return dt, res
 
+    def huf_read_dtable_x2_batch(self, csrc, csizes, max_table_log=12, dtables=None, results=None, workspace=None):
+        """HUF_readDTableX2_batch: (dtables (n, 1 + (1 << max_table_log)) int32 -- double-symbol cells --, results = header bytes or error).
+        max_table_log is DTableDesc.maxTableLog as the reference reads it (above 12: every block fails, nothing is written)"""
+        n = _blocks(csrc, "csrc").shape[0]
+        g = None
+        if dtables is None:
+            dtables, g = self._dst(n, 1 + (1 << min(max_table_log, 12)), csrc.device, zero=True, dtype=torch.int32)
+        res = torch.zeros(n, dtype=torch.int64, device=csrc.device) if results is None else results
+        if workspace is None:
+            workspace = torch.empty(int(self.lib.FSEHIP_HUF_readDTableX2_batch_workspaceSize(SZ(n))), dtype=torch.uint8, device=csrc.device)
+        ps, uni, keep = _sizes_arg(csizes, csrc)
+        _check(self.lib.FSEHIP_HUF_readDTableX2_batch(_ptr(dtables), SZ(dtables.stride(0)), C.c_uint(max_table_log), _ptr(res), _ptr(csrc), SZ(csrc.stride(0)),
+                                                      ps, uni, SZ(n), _ptr(workspace), SZ(workspace.numel()), _stream()), "HUF_readDTableX2_batch")
+        if g:
+            g.check("HUF_readDTableX2_batch")
+        return dtables, res
+
+    def huf_decompress4x2_using_dtable_batch(self, csrc, csizes, dtables, dst_sizes, max_table_log=12, shared_table=False, dst=None, results=None):
+        """HUF_decompress4X2_usingDTable over a batch: double-symbol tables only (a tableType 0 table: GENERIC)"""
+        return self.huf_decompress4x1_using_dtable_batch(csrc, csizes, dtables, dst_sizes, max_table_log, shared_table, dst=dst, results=results,
+                                                         _fn="FSEHIP_HUF_decompress4X2_usingDTable_batch")
+
+    def huf_decompress1x2_using_dtable_batch(self, csrc, csizes, dtables, dst_sizes, max_table_log=12, shared_table=False, dst=None, results=None):
+        """HUF_decompress1X2_usingDTable over a batch: one stream per block, double-symbol tables only"""
+        return self.huf_decompress4x1_using_dtable_batch(csrc, csizes, dtables, dst_sizes, max_table_log, shared_table, dst=dst, results=results,
+                                                         _fn="FSEHIP_HUF_decompress1X2_usingDTable_batch")
+
     def huf_decompress_packed_batch(self, packed, offsets, dst_sizes, dst=None, results=None, workspace=None):
         n = offsets.numel() - 1
         width = int(dst_sizes) if isinstance(dst_sizes, numbers.Integral) else int(dst_sizes.max().item())
@@ -659,6 +686,56 @@ def _huf_methods():
         self.lib.FSEHIP_HUF_readDTableX1.restype = SZ
         return int(self.lib.FSEHIP_HUF_readDTableX1(dt.ctypes.data_as(VP), src.ctypes.data_as(VP), SZ(src.size))), dt
 
+    def huf_read_dtable_x2(self, src, max_table_log=12, wksp_bytes=None, dtable=None):
+        """HUF_readDTableX2 (wksp_bytes None) / HUF_readDTableX2_wksp into a DTable made by HUF_CREATE_STATIC_DTABLEX2(DTable, max_table_log), or into
+        `dtable` (uint32, written in place): (header size or error, DTable)"""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        if dtable is None:
+            dtable = np.zeros(1 + (1 << 12), dtype=np.uint32)
+            dtable[0] = max_table_log * 0x01000001
+        if wksp_bytes is None:
+            self.lib.FSEHIP_HUF_readDTableX2.restype = SZ
+            return int(self.lib.FSEHIP_HUF_readDTableX2(dtable.ctypes.data_as(VP), src.ctypes.data_as(VP), SZ(src.size))), dtable
+        ws = np.zeros(max(wksp_bytes, 4) // 4 + 1, dtype=np.uint32)
+        self.lib.FSEHIP_HUF_readDTableX2_wksp.restype = SZ
+        return int(self.lib.FSEHIP_HUF_readDTableX2_wksp(dtable.ctypes.data_as(VP), src.ctypes.data_as(VP), SZ(src.size), ws.ctypes.data_as(VP), SZ(wksp_bytes))), dtable
+
+    def _huf_x2(self, base, csrc, dst_size, dctx, wksp_bytes):
+        if dctx is None:
+            fname, extra = base, ()
+        elif wksp_bytes is None:
+            fname, extra = base + "_DCtx", ()
+        else:
+            self._x2_ws = np.zeros(max(wksp_bytes, 4) // 4 + 1, dtype=np.uint32)
+            fname, extra = base + "_DCtx_wksp", (self._x2_ws.ctypes.data_as(VP), SZ(wksp_bytes))
+        getattr(self.lib, fname).restype = SZ
+        if dctx is None:
+            return self._single(fname, dst_size, csrc)
+        csrc = np.ascontiguousarray(csrc, dtype=np.uint8)
+        out = np.zeros(max(dst_size, 1) + 16, dtype=np.uint8)
+        out[dst_size:] = 0xA5
+        r = int(getattr(self.lib, fname)(dctx.ctypes.data_as(VP), out.ctypes.data_as(VP), SZ(dst_size), csrc.ctypes.data_as(VP), SZ(csrc.size), *extra))
+        assert (out[dst_size:] == 0xA5).all(), "%s wrote past dstSize" % fname
+        return r, out[:dst_size]
+
+    def huf_decompress4x2(self, csrc, dst_size, dctx=None, wksp_bytes=None):
+        """HUF_decompress4X2 / HUF_decompress4X2_DCtx (dctx: uint32 DTable, receives the table) / HUF_decompress4X2_DCtx_wksp (wksp_bytes too)"""
+        return self._huf_x2("FSEHIP_HUF_decompress4X2", csrc, dst_size, dctx, wksp_bytes)
+
+    def huf_decompress1x2(self, csrc, dst_size, dctx=None, wksp_bytes=None):
+        """HUF_decompress1X2 / HUF_decompress1X2_DCtx / HUF_decompress1X2_DCtx_wksp: one stream per block"""
+        return self._huf_x2("FSEHIP_HUF_decompress1X2", csrc, dst_size, dctx, wksp_bytes)
+
+    def huf_decompress4x2_using_dtable(self, csrc, dt, dst_size):
+        dt = np.ascontiguousarray(dt, dtype=np.uint32)
+        self.lib.FSEHIP_HUF_decompress4X2_usingDTable.restype = SZ
+        return self._single("FSEHIP_HUF_decompress4X2_usingDTable", dst_size, csrc, dt.ctypes.data_as(VP))
+
+    def huf_decompress1x2_using_dtable(self, csrc, dt, dst_size):
+        dt = np.ascontiguousarray(dt, dtype=np.uint32)
+        self.lib.FSEHIP_HUF_decompress1X2_usingDTable.restype = SZ
+        return self._single("FSEHIP_HUF_decompress1X2_usingDTable", dst_size, csrc, dt.ctypes.data_as(VP))
+
     def huf_compress1x(self, src, max_sv=255, huff_log=11, cap=None):
         return self._single("FSEHIP_HUF_compress1X", huf_compress_bound(len(src)) if cap is None else cap, src, C.c_uint(max_sv), C.c_uint(huff_log))
 
@@ -697,7 +774,9 @@ def _huf_methods():
               huf_decompress_packed_batch, huf_build_ctable_batch, huf_read_dtable_x1_batch, huf_workspace, huf_compress_batch, huf_decompress_batch, huf_compress4x_using_ctable_batch, huf_compress1x_using_ctable_batch,
               huf_decompress4x1_using_dtable_batch, huf_decompress4x_using_dtable_batch, huf_compress2, huf_decompress, huf_compress1x_using_ctable,
               huf_compress4x_using_ctable, huf_decompress4x1_using_dtable, huf_decompress4x_using_dtable,
-              huf_build_ctable, huf_write_ctable, huf_read_dtable_x1, huf_compress1x, huf_decompress4x1, huf_decompress1x1):
+              huf_build_ctable, huf_write_ctable, huf_read_dtable_x1, huf_compress1x, huf_decompress4x1, huf_decompress1x1,
+              huf_read_dtable_x2_batch, huf_decompress4x2_using_dtable_batch, huf_decompress1x2_using_dtable_batch, huf_read_dtable_x2, _huf_x2,
+              huf_decompress4x2, huf_decompress1x2, huf_decompress4x2_using_dtable, huf_decompress1x2_using_dtable):
         setattr(FseHip, f.__name__, f)
 
 

@@ -739,6 +739,36 @@ extern "C" int FSEHIP_HUF_readDTableX1_batch(FSEHIP_HUF_DTable* d_dtables, size_
     return 0;
 }
 
+// HUF_readDTableX2 over a batch (lib/huf_decompress.c:551-649): double-symbol cells, 1 << maxTableLog of them behind the descriptor.  maxTableLog is
+// DTableDesc.maxTableLog as the reference reads it: above 12 every block fails with tableLog_tooLarge (:587), a header deeper than it likewise (:594).
+extern "C" size_t FSEHIP_HUF_readDTableX2_batch_workspaceSize(size_t nBlocks) { return FSEHIP_HUF_readDTableX1_batch_workspaceSize(nBlocks); }
+extern "C" int FSEHIP_HUF_readDTableX2_batch(FSEHIP_HUF_DTable* d_dtables, size_t dtableStrideU32, unsigned maxTableLog, size_t* d_results,
+                                             const void* d_src, size_t srcStride, const size_t* d_srcSizes, size_t uniformSrcSize,
+                                             size_t nBlocks, void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if ((uintptr_t)d_workspace & 255u) return (int)hipErrorInvalidValue;
+    if (nBlocks == 0) return 0;
+    if (maxTableLog <= FSEHIP_HUF_TABLELOG_MAX && dtableStrideU32 < 1 + ((size_t)1 << maxTableLog)) return (int)hipErrorInvalidValue;   // HUF_DTABLE_SIZE(maxTableLog)
+    if (workspaceBytes < HUF_RDT_PER_BLOCK + WS_SLACK) return (int)hipErrorInvalidValue;
+    size_t chunk = (workspaceBytes - WS_SLACK) / HUF_RDT_PER_BLOCK;
+    if (chunk > nBlocks) chunk = nBlocks;
+    u8* p = (u8*)d_workspace;
+    HufMeta* meta = (HufMeta*)p; p += align_up(chunk * sizeof(HufMeta), 256);
+    u32* lists = (u32*)p; p += align_up(chunk * HUF_DCLS_COUNT * sizeof(u32), 256);
+    u32* counts = (u32*)p;
+    for (size_t b0 = 0; b0 < nBlocks; b0 += chunk) {
+        const size_t nb = (nBlocks - b0) < chunk ? (nBlocks - b0) : chunk;
+        HufDPrepArgs d;
+        d.csrc = mkview((const u8*)d_src + b0 * srcStride, srcStride, d_srcSizes ? d_srcSizes + b0 : nullptr, uniformSrcSize);
+        d.dstSizes = mkview(nullptr, 0, nullptr, 0); d.dst = nullptr; d.dstStride = 0;
+        d.dtables = d_dtables + b0 * dtableStrideU32; d.dtStrideU32 = dtableStrideU32; d.meta = meta; d.lists = lists; d.counts = counts;
+        d.results = d_results + b0; d.nBlocks = nb; d.tableOnly = 1; d.dtMaxLog = maxTableLog;
+        CK(launch_huf_dprep_x2(d, s));
+    }
+    return 0;
+}
+
 // =====================================================================================================
 //  Layer 1: single-block calls on host pointers = batch of one (H2D, kernels, D2H)
 // =====================================================================================================
@@ -1207,6 +1237,38 @@ extern "C" int FSEHIP_HUF_decompress1X_usingDTable_batch(void* d_dst, size_t dst
     return huf_1x_dtable_batch(1, d_dst, dstStride, d_dstSizes, uniformDstSize, d_results, d_cSrc, cStride, d_cSizes, uniformCSize, d_dtables, dtableStrideU32, maxTableLog, nBlocks, stream);
 }
 
+// HUF_decompress4X2_usingDTable / HUF_decompress1X2_usingDTable over a batch (lib/huf_decompress.c:867-875, :907-915): the dispatching routes above, after
+// which a block whose table is not a double-symbol one has GENERIC for its result (:873, :913) -- what such a block's destination holds is unspecified
+__global__ void k_huf_x2_strict(size_t* results, const u32* dtables, size_t dtStrideU32, size_t nBlocks)
+{
+    const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < nBlocks && ((dtables[b * dtStrideU32] >> 8) & 0xFFu) != 1u) results[b] = FERR(GENERIC);
+}
+static int huf_x2_strict(size_t* d_results, const FSEHIP_HUF_DTable* d_dtables, size_t dtableStrideU32, size_t nBlocks, void* stream)
+{
+    if (nBlocks == 0) return 0;
+    hipLaunchKernelGGL(k_huf_x2_strict, dim3((unsigned)((nBlocks + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_results, d_dtables, dtableStrideU32, nBlocks);
+    return (int)hipGetLastError();
+}
+extern "C" int FSEHIP_HUF_decompress4X2_usingDTable_batch(void* d_dst, size_t dstStride, const size_t* d_dstSizes, size_t uniformDstSize,
+                                                          size_t* d_results, const void* d_cSrc, size_t cStride, const size_t* d_cSizes, size_t uniformCSize,
+                                                          const FSEHIP_HUF_DTable* d_dtables, size_t dtableStrideU32, unsigned maxTableLog,
+                                                          size_t nBlocks, void* stream)
+{
+    const int e = FSEHIP_HUF_decompress4X_usingDTable_batch(d_dst, dstStride, d_dstSizes, uniformDstSize, d_results, d_cSrc, cStride, d_cSizes, uniformCSize,
+                                                            d_dtables, dtableStrideU32, maxTableLog, nBlocks, stream);
+    return e ? e : huf_x2_strict(d_results, d_dtables, dtableStrideU32, nBlocks, stream);
+}
+extern "C" int FSEHIP_HUF_decompress1X2_usingDTable_batch(void* d_dst, size_t dstStride, const size_t* d_dstSizes, size_t uniformDstSize,
+                                                          size_t* d_results, const void* d_cSrc, size_t cStride, const size_t* d_cSizes, size_t uniformCSize,
+                                                          const FSEHIP_HUF_DTable* d_dtables, size_t dtableStrideU32, unsigned maxTableLog,
+                                                          size_t nBlocks, void* stream)
+{
+    const int e = FSEHIP_HUF_decompress1X_usingDTable_batch(d_dst, dstStride, d_dstSizes, uniformDstSize, d_results, d_cSrc, cStride, d_cSizes, uniformCSize,
+                                                            d_dtables, dtableStrideU32, maxTableLog, nBlocks, stream);
+    return e ? e : huf_x2_strict(d_results, d_dtables, dtableStrideU32, nBlocks, stream);
+}
+
 // =====================================================================================================
 //  one-shot Huff0 block API over a batch
 // =====================================================================================================
@@ -1573,6 +1635,104 @@ extern "C" size_t FSEHIP_HUF_readDTableX1(FSEHIP_HUF_DTable* DTable, const void*
 {
     u32 ws[FSEHIP_HUF_DECOMPRESS_WORKSPACE_SIZE / 4];
     return FSEHIP_HUF_readDTableX1_wksp(DTable, src, srcSize, ws, sizeof(ws));
+}
+// The double-symbol family, lib/huf.h:157,166-167,271-272,280,304,314-315,323 (lib/huf_decompress.c:551-656, :867-952).
+// HUF_readDTableX2_wksp (:551-649) on a block that is in device memory already.  The workspace is checked as :570-581 check it -- rankVal, rankStats,
+// rankStart0, sortedSymbol, weightList -- and then left alone; then the descriptor's limit (:587), then the header.  dctx (host) receives the descriptor
+// {maxTableLog and reserved byte as found, tableType 1, tableLog = maxTableLog} and all 1 << maxTableLog cells, ddt (device) the same table.
+static const size_t HUF_X2_WKSP_BYTES = 4 * ((FSEHIP_HUF_TABLELOG_MAX + 1) * FSEHIP_HUF_TABLELOG_MAX + (FSEHIP_HUF_TABLELOG_MAX + 1) + (FSEHIP_HUF_TABLELOG_MAX + 2) + 2 * 256 / 4 + 256 / 4);
+static size_t huf_read_x2_host(FSEHIP_HUF_DTable* dctx, const void* d_src, size_t cSrcSize, DevBuf& ddt, size_t wkspSize)
+{
+    if (wkspSize < HUF_X2_WKSP_BYTES) return FSEHIP_ERROR(tableLog_tooLarge);      // :581
+    const u32 desc = dctx[0];
+    const unsigned mtl = desc & 0xFFu;
+    if (mtl > FSEHIP_HUF_TABLELOG_MAX) return FSEHIP_ERROR(tableLog_tooLarge);      // :587
+    const size_t dtU32 = 1 + ((size_t)1 << mtl);
+    const size_t wsB = FSEHIP_HUF_readDTableX2_batch_workspaceSize(1);
+    DevBuf dws, dres;
+    HK(ddt.alloc(4 * dtU32)); HK(dws.alloc(wsB)); HK(dres.alloc(8));
+    HK((hipError_t)FSEHIP_HUF_readDTableX2_batch((u32*)ddt.p, dtU32, mtl, (size_t*)dres.p, d_src, cSrcSize, nullptr, cSrcSize, 1, dws.p, wsB, nullptr));
+    size_t hSize = 0;
+    HK(hipMemcpy(&hSize, dres.p, 8, hipMemcpyDeviceToHost));
+    if (FSEHIP_isError(hSize)) return hSize;
+    HK(hipMemcpy(dctx + 1, (const u32*)ddt.p + 1, (size_t)4 << mtl, hipMemcpyDeviceToHost));
+    dctx[0] = (desc & 0xFF0000FFu) | 0x100u | ((u32)mtl << 16);     // :645-647
+    const u32 dNew = dctx[0];
+    HK(hipMemcpy(ddt.p, &dNew, 4, hipMemcpyHostToDevice));
+    return hSize;
+}
+// HUF_decompress4X2_DCtx_wksp / HUF_decompress1X2_DCtx_wksp (:877-890, :917-930): the table from the block's header into dctx, then the streams behind it
+// through the table-dispatching route -- the lock-step double-symbol decoder, which returns what the reference's X2 decoder returns on damaged streams too
+static size_t huf_x2_dctx_host(int streams, FSEHIP_HUF_DTable* dctx, void* dst, size_t dstSize, const void* cSrc, size_t cSrcSize, size_t wkspSize)
+{
+    DevBuf dsrc, ddst, dres, ddt;                                   // (in the order they are carved: ddt inside huf_read_x2_host)
+    HK(dsrc.alloc(cSrcSize)); HK(ddst.alloc(dstSize)); HK(dres.alloc(8));
+    HK(hipMemcpy(dsrc.p, cSrc, cSrcSize, hipMemcpyHostToDevice));
+    const size_t hSize = huf_read_x2_host(dctx, dsrc.p, cSrcSize, ddt, wkspSize);
+    if (FSEHIP_isError(hSize)) return hSize;
+    if (hSize >= cSrcSize) return FSEHIP_ERROR(srcSize_wrong);     // :886, :926
+    HK((hipError_t)(streams == 4 ? FSEHIP_HUF_decompress4X_usingDTable_batch : FSEHIP_HUF_decompress1X_usingDTable_batch)(
+        ddst.p, dstSize, nullptr, dstSize, (size_t*)dres.p, (const u8*)dsrc.p + hSize, cSrcSize - hSize, nullptr, cSrcSize - hSize,
+        (const u32*)ddt.p, 0, FSEHIP_HUF_TABLELOG_MAX, 1, nullptr));
+    size_t r = 0;
+    HK(hipMemcpy(&r, dres.p, 8, hipMemcpyDeviceToHost));
+    if (!FSEHIP_isError(r) && r > 0) HK(hipMemcpy(dst, ddst.p, r <= dstSize ? r : dstSize, hipMemcpyDeviceToHost));
+    return r;
+}
+extern "C" size_t FSEHIP_HUF_readDTableX2_wksp(FSEHIP_HUF_DTable* DTable, const void* src, size_t srcSize, void* workSpace, size_t wkspSize)
+{
+    (void)workSpace;
+    DevBuf dsrc, ddt;
+    HK(dsrc.alloc(srcSize));
+    HK(hipMemcpy(dsrc.p, src, srcSize, hipMemcpyHostToDevice));
+    return huf_read_x2_host(DTable, dsrc.p, srcSize, ddt, wkspSize);
+}
+extern "C" size_t FSEHIP_HUF_readDTableX2(FSEHIP_HUF_DTable* DTable, const void* src, size_t srcSize)    // :651-656
+{
+    u32 ws[FSEHIP_HUF_DECOMPRESS_WORKSPACE_SIZE / 4];
+    return FSEHIP_HUF_readDTableX2_wksp(DTable, src, srcSize, ws, sizeof(ws));
+}
+extern "C" size_t FSEHIP_HUF_decompress4X2_DCtx_wksp(FSEHIP_HUF_DTable* dctx, void* dst, size_t dstSize, const void* cSrc, size_t cSrcSize,
+                                                     void* workSpace, size_t wkspSize)
+{
+    (void)workSpace;
+    return huf_x2_dctx_host(4, dctx, dst, dstSize, cSrc, cSrcSize, wkspSize);
+}
+extern "C" size_t FSEHIP_HUF_decompress4X2_DCtx(FSEHIP_HUF_DTable* dctx, void* dst, size_t dstSize, const void* cSrc, size_t cSrcSize)   // :940-946
+{
+    return huf_x2_dctx_host(4, dctx, dst, dstSize, cSrc, cSrcSize, FSEHIP_HUF_DECOMPRESS_WORKSPACE_SIZE);
+}
+extern "C" size_t FSEHIP_HUF_decompress4X2(void* dst, size_t dstSize, const void* cSrc, size_t cSrcSize)   // :948-952: HUF_CREATE_STATIC_DTABLEX2(DTable, HUF_TABLELOG_MAX)
+{
+    std::vector<u32> dt(FSEHIP_HUF_DTABLE_SIZE_U32(FSEHIP_HUF_TABLELOG_MAX), 0);
+    dt[0] = (u32)FSEHIP_HUF_TABLELOG_MAX * 0x01000001u;
+    return huf_x2_dctx_host(4, dt.data(), dst, dstSize, cSrc, cSrcSize, FSEHIP_HUF_DECOMPRESS_WORKSPACE_SIZE);
+}
+extern "C" size_t FSEHIP_HUF_decompress1X2_DCtx_wksp(FSEHIP_HUF_DTable* dctx, void* dst, size_t dstSize, const void* cSrc, size_t cSrcSize,
+                                                     void* workSpace, size_t wkspSize)
+{
+    (void)workSpace;
+    return huf_x2_dctx_host(1, dctx, dst, dstSize, cSrc, cSrcSize, wkspSize);
+}
+extern "C" size_t FSEHIP_HUF_decompress1X2_DCtx(FSEHIP_HUF_DTable* dctx, void* dst, size_t dstSize, const void* cSrc, size_t cSrcSize)   // :893-899
+{
+    return huf_x2_dctx_host(1, dctx, dst, dstSize, cSrc, cSrcSize, FSEHIP_HUF_DECOMPRESS_WORKSPACE_SIZE);
+}
+extern "C" size_t FSEHIP_HUF_decompress1X2(void* dst, size_t dstSize, const void* cSrc, size_t cSrcSize)   // :901-905
+{
+    std::vector<u32> dt(FSEHIP_HUF_DTABLE_SIZE_U32(FSEHIP_HUF_TABLELOG_MAX), 0);
+    dt[0] = (u32)FSEHIP_HUF_TABLELOG_MAX * 0x01000001u;
+    return huf_x2_dctx_host(1, dt.data(), dst, dstSize, cSrc, cSrcSize, FSEHIP_HUF_DECOMPRESS_WORKSPACE_SIZE);
+}
+extern "C" size_t FSEHIP_HUF_decompress4X2_usingDTable(void* dst, size_t maxDstSize, const void* cSrc, size_t cSrcSize, const FSEHIP_HUF_DTable* DTable)
+{
+    if (((DTable[0] >> 8) & 0xFFu) != 1u) return FSEHIP_ERROR(GENERIC);              // :913
+    return huf_using_dtable_host(true, dst, maxDstSize, cSrc, cSrcSize, DTable);
+}
+extern "C" size_t FSEHIP_HUF_decompress1X2_usingDTable(void* dst, size_t maxDstSize, const void* cSrc, size_t cSrcSize, const FSEHIP_HUF_DTable* DTable)
+{
+    if (((DTable[0] >> 8) & 0xFFu) != 1u) return FSEHIP_ERROR(GENERIC);              // :873
+    return huf_using_dtable_host(true, dst, maxDstSize, cSrc, cSrcSize, DTable, 1);
 }
 // lib/huf.h:204-218 (lib/huf_compress.c:334-421): HUF_buildCTable[_wksp] on the caller's counters, HUF_writeCTable (lib/huf.h:205, lib/huf_compress.c:113-148) on the
 // caller's table -- batches of one on the phases of k_huf_cprep (huf_prep.hip).  The workspace is checked as the reference checks it (:345-348) and left alone.

@@ -1,5 +1,5 @@
 /* dropin_alias.c -- libfse_dropin.so: the reference's OWN symbol names (lib/hist.h:30,46,54, lib/fse.h:76,90,104,119-163,174,222-247,315,335,341,
- * lib/huf.h:66,82,95,164,190,275-277,289-290, lib/error_public.h / fse.h:124-128) as real exported functions that forward to libfsehip.so.
+ * lib/huf.h:66,82,95,157,164,166-167,190,271-272,275-277,280,289-290,304,314-315,323, lib/error_public.h / fse.h:124-128) as real exported functions that forward to libfsehip.so.
  * include/fsehip.h renames at COMPILE time (FSEHIP_DROPIN_NAMES); this is the LINK-time form: an object file or application already
  * compiled against the reference's headers is relinked with `-lfse_dropin -lfsehip` instead of the reference's lib/ *.o and runs on
  * the MI355X unchanged.  It must not be linked beside the reference's own objects (same names), which is why it is a separate
@@ -60,6 +60,17 @@ DROPIN size_t HUF_decompress4X1_DCtx(FSEHIP_HUF_DTable* dctx, void* dst, size_t 
 DROPIN size_t HUF_decompress1X1(void* dst, size_t dn, const void* src, size_t n) { return FSEHIP_HUF_decompress1X1(dst, dn, src, n); }
 DROPIN size_t HUF_decompress1X1_DCtx(FSEHIP_HUF_DTable* dctx, void* dst, size_t dn, const void* src, size_t n) { return FSEHIP_HUF_decompress1X1_DCtx(dctx, dst, dn, src, n); }
 DROPIN size_t HUF_decompress1X1_DCtx_wksp(FSEHIP_HUF_DTable* dctx, void* dst, size_t dn, const void* src, size_t n, void* ws, size_t wsn) { return FSEHIP_HUF_decompress1X1_DCtx_wksp(dctx, dst, dn, src, n, ws, wsn); }
+/* the double-symbol family, lib/huf.h:157,166-167,271-272,280,304,314-315,323 */
+DROPIN size_t HUF_readDTableX2(FSEHIP_HUF_DTable* dt, const void* src, size_t n) { return FSEHIP_HUF_readDTableX2(dt, src, n); }
+DROPIN size_t HUF_readDTableX2_wksp(FSEHIP_HUF_DTable* dt, const void* src, size_t n, void* ws, size_t wsn) { return FSEHIP_HUF_readDTableX2_wksp(dt, src, n, ws, wsn); }
+DROPIN size_t HUF_decompress4X2(void* dst, size_t dn, const void* src, size_t n) { return FSEHIP_HUF_decompress4X2(dst, dn, src, n); }
+DROPIN size_t HUF_decompress4X2_DCtx(FSEHIP_HUF_DTable* dctx, void* dst, size_t dn, const void* src, size_t n) { return FSEHIP_HUF_decompress4X2_DCtx(dctx, dst, dn, src, n); }
+DROPIN size_t HUF_decompress4X2_DCtx_wksp(FSEHIP_HUF_DTable* dctx, void* dst, size_t dn, const void* src, size_t n, void* ws, size_t wsn) { return FSEHIP_HUF_decompress4X2_DCtx_wksp(dctx, dst, dn, src, n, ws, wsn); }
+DROPIN size_t HUF_decompress1X2(void* dst, size_t dn, const void* src, size_t n) { return FSEHIP_HUF_decompress1X2(dst, dn, src, n); }
+DROPIN size_t HUF_decompress1X2_DCtx(FSEHIP_HUF_DTable* dctx, void* dst, size_t dn, const void* src, size_t n) { return FSEHIP_HUF_decompress1X2_DCtx(dctx, dst, dn, src, n); }
+DROPIN size_t HUF_decompress1X2_DCtx_wksp(FSEHIP_HUF_DTable* dctx, void* dst, size_t dn, const void* src, size_t n, void* ws, size_t wsn) { return FSEHIP_HUF_decompress1X2_DCtx_wksp(dctx, dst, dn, src, n, ws, wsn); }
+DROPIN size_t HUF_decompress4X2_usingDTable(void* dst, size_t cap, const void* src, size_t n, const FSEHIP_HUF_DTable* dt) { return FSEHIP_HUF_decompress4X2_usingDTable(dst, cap, src, n, dt); }
+DROPIN size_t HUF_decompress1X2_usingDTable(void* dst, size_t cap, const void* src, size_t n, const FSEHIP_HUF_DTable* dt) { return FSEHIP_HUF_decompress1X2_usingDTable(dst, cap, src, n, dt); }
 DROPIN size_t HUF_compress1X_usingCTable(void* dst, size_t cap, const void* src, size_t n, const FSEHIP_HUF_CElt* ct) { return FSEHIP_HUF_compress1X_usingCTable(dst, cap, src, n, ct); }
 DROPIN size_t HUF_compress4X_usingCTable(void* dst, size_t cap, const void* src, size_t n, const FSEHIP_HUF_CElt* ct) { return FSEHIP_HUF_compress4X_usingCTable(dst, cap, src, n, ct); }
 DROPIN size_t HUF_decompress4X_usingDTable(void* dst, size_t cap, const void* src, size_t n, const FSEHIP_HUF_DTable* dt) { return FSEHIP_HUF_decompress4X_usingDTable(dst, cap, src, n, dt); }

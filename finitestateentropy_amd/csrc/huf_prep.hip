@@ -698,8 +698,10 @@ DEV size_t hp_decode_weights(u8* w, long omax, const u8* in, size_t n, const u32
 #define HD_CBASE  HP_NRM
 enum { DS_STATE = 0, DS_HDR, DS_NSYM, DS_FSE, DS_RESULT_LO, DS_RESULT_HI, DS_AUX, DS_CLS };   // DS_STATE: 0 done, 1 table pending, 2 raw copy, 3 rle fill
 
-template <int G_>
-__global__ __launch_bounds__(64) void k_huf_dprep(HufDPrepArgs a)
+// X2_ = 0: single-symbol cells (HUF_readDTableX1).  X2_ = 1: double-symbol cells (HUF_readDTableX2_wksp, lib/huf_decompress.c:551-649; table only) -- the
+// same header reader, checks and symbol ranks, another phase D
+template <int G_, int X2_>
+DEV void hp_dprep(const HufDPrepArgs& a)
 {
     constexpr u32 HP_G = G_;
     extern __shared__ __attribute__((aligned(16))) u8 hpLds[];
@@ -719,7 +721,8 @@ __global__ __launch_bounds__(64) void k_huf_dprep(HufDPrepArgs a)
             const u8* const in = view_ptr(a.csrc, b);
             const size_t cSize = view_size(a.csrc, b), dstSize = view_size(a.dstSizes, b);
             u8* const w = slot + HD_WGT;
-            if (a.tableOnly && cSize == 0) result = FERR(srcSize_wrong);  // HUF_readStats, entropy_common.c:165
+            if (X2_ && a.dtMaxLog > HUF_MAX_TL) result = FERR(tableLog_tooLarge);   // huf_decompress.c:587: before the header is read
+            else if (a.tableOnly && cSize == 0) result = FERR(srcSize_wrong);  // HUF_readStats, entropy_common.c:165
             else if (!a.tableOnly && dstSize == 0) result = FERR(dstSize_tooSmall);            // huf_decompress.c:1063-1066
             else if (!a.tableOnly && cSize > dstSize) result = FERR(corruption_detected);
             else if (!a.tableOnly && cSize == dstSize) { state = 2; result = dstSize; }   // not compressed: copied below, coalesced
@@ -858,7 +861,7 @@ __global__ __launch_bounds__(64) void k_huf_dprep(HufDPrepArgs a)
                 const Pk tot = pk_rank(cls, rank, lane);
                 const u32 cnt1 = pk_get(tot, 1);
                 if (cnt1 < 2 || (cnt1 & 1u)) err = FERR(corruption_detected);   // entropy_common.c:208
-                else if (tl > a.dtMaxLog + 1) err = FERR(tableLog_tooLarge);   // huf_decompress.c:137 (one-shot path: the DTable of HUF_CREATE_STATIC_DTABLEX1(.., HUF_TABLELOG_MAX))
+                else if (X2_ ? tl > a.dtMaxLog : tl > a.dtMaxLog + 1) err = FERR(tableLog_tooLarge);   // huf_decompress.c:137 (one-shot path: the DTable of HUF_CREATE_STATIC_DTABLEX1(.., HUF_TABLELOG_MAX)); X2: :594
                 else {
                     // X1 cells {byte, nbBits} (huf_decompress.c:158-183): symbol n owns (1 << w) >> 1 consecutive cells, the symbols of
                     // a weight follow each other in symbol order, the weights in ascending order.  Restated by cell: the symbols are
@@ -882,6 +885,48 @@ __global__ __launch_bounds__(64) void k_huf_dprep(HufDPrepArgs a)
                     __syncthreads();
                     u32* const dt = a.dtables + b * a.dtStrideU32;
                     u32* const out = dt + 1;
+                    if constexpr (X2_) {
+                    // X2 cells {u16 sequence; u8 nbBits; u8 length} (huf_decompress.c:468-549, :596-647), by cell.  L = maxTableLog, B = tl + 1.
+                    // First level: the same classes and list as above, every run 1 << (L - tl) times as long (rankVal0, :622-630).  A cell finds
+                    // its symbol s1 (n1 = B - w1 bits, run of 1 << lg1 cells, lg1 = L - n1) and its offset v in the run.  Runs shorter than
+                    // 1 << minBits hold {s1, n1, 1} (:529, :538-546).  Otherwise v indexes a second level whose class starts are the first
+                    // level's >> n1 (:637; the shift floors, exactly so from class minWeight on): below class minWeight = max(1, n1 + B - L)
+                    // the cell is the skip cell {s1, n1, 1} (:480-487), else {s1 | s2 << 8, n1 + B - w2, 2} with s2 by position (:490-505).
+                    const u32 L = a.dtMaxLog, B = tl + 1, sh = L - tl, N = 1u << L;
+                    u32 maxW = 1;
+                    for (u32 v = 2; v <= tl; ++v) if (pk_get(tot, v)) maxW = v;    // uniform (:597)
+                    const u32 minBits = B - maxW;
+                    const u16* const cb16 = cbase;
+                    u32 rv[HUF_MAX_TL + 1];                                 // first-level class starts in registers (uniform)
+#pragma unroll
+                    for (u32 t = 2; t <= HUF_MAX_TL; ++t) rv[t] = t <= tl ? (u32)cstart[t] << sh : 0xFFFFFFFFu;
+                    auto cell = [&](u32 u) -> u32 {
+                        u32 w1 = 1, st = 0;
+#pragma unroll
+                        for (u32 t = 2; t <= HUF_MAX_TL; ++t) { const bool in = u >= rv[t]; w1 = in ? t : w1; st = in ? rv[t] : st; }
+                        const u32 r = u - st, lg1 = w1 - 1 + sh, n1 = B - w1;
+                        const u32 s1 = sorted[cb16[w1] + (r >> lg1)], one = s1 | (n1 << 16) | (1u << 24);
+                        if (lg1 < minBits) return one;
+                        const u32 v = r & ((1u << lg1) - 1u);
+                        u32 w2 = 1, st2 = 0;
+#pragma unroll
+                        for (u32 t = 2; t <= HUF_MAX_TL; ++t) { const u32 s2 = rv[t] >> n1; const bool in = v >= s2; w2 = in ? t : w2; st2 = in ? s2 : st2; }
+                        if ((int)w2 < (int)n1 + (int)B - (int)L) return one;     // (w2 >= 1 always)
+                        const u32 n2 = B - w2;
+                        const u32 s2 = sorted[cb16[w2] + ((v - st2) >> (lg1 - n2))];
+                        return s1 | (s2 << 8) | ((n1 + n2) << 16) | (2u << 24);
+                    };
+                    // whole 16-byte pieces from the first 16-byte boundary of the table on; the (at most six) cells around them singly
+                    const u32 head0 = (u32)((0 - ((uintptr_t)out >> 2)) & 3u), head = head0 < N ? head0 : N;
+                    const u32 pieces = (N - head) >> 2, tail0 = head + 4 * pieces;
+                    for (u32 q = lane; q < pieces; q += 64) {
+                        const u32 u = head + 4 * q;
+                        *(uint4*)(out + u) = make_uint4(cell(u), cell(u + 1), cell(u + 2), cell(u + 3));
+                    }
+                    {   const u32 u = lane < head ? lane : tail0 + (lane - head);
+                        if (u < N) out[u] = cell(u); }
+                    if (lane == 0) dt[0] = ((L & 0xFFu) * 0x01010001u) | 0x100u;   // {maxTableLog, tableType 1, tableLog = maxTableLog (:645), reserved as HUF_CREATE_STATIC_DTABLEX2 leaves it}
+                    } else {
                     const u32 pairs = 1u << (tl - 1);
                     u32 csr[HUF_MAX_TL + 1];                                // class starts in registers (uniform)
 #pragma unroll
@@ -898,6 +943,7 @@ __global__ __launch_bounds__(64) void k_huf_dprep(HufDPrepArgs a)
                         out[q] = (lo | nbits) | ((hi | nbits) << 16);
                     }
                     if (lane == 0) dt[0] = ((a.dtMaxLog & 0xFFu) * 0x01000001u) | (tl << 16);   // {maxTableLog, tableType 0, tableLog, reserved as HUF_CREATE_STATIC_DTABLEX1 leaves it}
+                    }
                 }
             }
             const u32 hdr = sc[DS_HDR];
@@ -929,6 +975,11 @@ __global__ __launch_bounds__(64) void k_huf_dprep(HufDPrepArgs a)
     }
 }
 
+template <int G_>
+__global__ __launch_bounds__(64) void k_huf_dprep(HufDPrepArgs a) { hp_dprep<G_, 0>(a); }
+template <int G_>
+__global__ __launch_bounds__(64) void k_huf_dprep_x2(HufDPrepArgs a) { hp_dprep<G_, 1>(a); }
+
 hipError_t launch_huf_cprep(const HufCPrepArgs& a, hipStream_t s, void* /*unused*/)
 {
     if (a.nBlocks == 0) return hipSuccess;
@@ -954,5 +1005,13 @@ hipError_t launch_huf_dprep(const HufDPrepArgs& a, hipStream_t s)
     probe_before(PK_HUF_DPREP, s);
     hipLaunchKernelGGL(k_huf_dprep<HP_G_DECOMPRESS>, dim3((unsigned)((a.nBlocks + HP_G_DECOMPRESS - 1) / HP_G_DECOMPRESS)), dim3(64), HP_G_DECOMPRESS * HP_SLOT, s, a);
     probe_after(PK_HUF_DPREP, s);
+    return hipGetLastError();
+}
+// HUF_readDTableX2 over a batch: a.tableOnly set, a.dtMaxLog = DTableDesc.maxTableLog as the caller's descriptor has it (any value)
+hipError_t launch_huf_dprep_x2(const HufDPrepArgs& a, hipStream_t s)
+{
+    if (a.nBlocks == 0) return hipSuccess;
+    {   const hipError_t e = launch_zero_u32(a.counts, HUF_DCLS_COUNT, s); if (e != hipSuccess) return e; }
+    hipLaunchKernelGGL(k_huf_dprep_x2<HP_G_DECOMPRESS>, dim3((unsigned)((a.nBlocks + HP_G_DECOMPRESS - 1) / HP_G_DECOMPRESS)), dim3(64), HP_G_DECOMPRESS * HP_SLOT, s, a);
     return hipGetLastError();
 }

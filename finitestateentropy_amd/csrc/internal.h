@@ -240,6 +240,7 @@ struct HufDPrepArgs {            // glue g6: HUF_readStats + HUF_readDTableX1 (+
     unsigned dtMaxLog;           // DTableDesc.maxTableLog of the tables (the one-shot path: HUF_TABLELOG_MAX - 1, lib/huf_decompress.c:1030)
 };
 hipError_t launch_huf_dprep(const HufDPrepArgs& a, hipStream_t s);
+hipError_t launch_huf_dprep_x2(const HufDPrepArgs& a, hipStream_t s);   // HUF_readDTableX2 (double-symbol cells): tableOnly, dtMaxLog as the descriptor has it
 // results[b] = meta[b].hdrSize for every block a prepare kernel left pending (state != 0): the table-building batch calls
 hipError_t launch_hdr_results(const void* meta, size_t metaStride, size_t* results, size_t nBlocks, hipStream_t s);
 // FSE_buildDTable over a batch: the decoder-format tables of k_fse_dbuild written out in the reference's layout (lib/fse.h:565-575)

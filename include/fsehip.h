@@ -7,6 +7,8 @@
  *   lib/huf.h:54-98       HUF_compress / HUF_decompress / HUF_compress2
  *   lib/huf.h:190,290     HUF_compress4X_usingCTable, HUF_compress1X_usingCTable
  *   lib/huf.h:275-277     HUF_decompress4X_usingDTable, HUF_decompress4X1_usingDTable
+ *   lib/huf.h:157-167,271-280,304-323   the double-symbol family: HUF_readDTableX2[_wksp], HUF_decompress4X2 / 1X2[_DCtx[_wksp]],
+ *                         HUF_decompress4X2_usingDTable, HUF_decompress1X2_usingDTable -- the table is built on the device
  *
  * Every function keeps the reference's signature, argument meaning, in-memory table layouts
  * (FSE_CTable / FSE_DTable = unsigned[], HUF_CElt = {U16 val; BYTE nbBits;} stride 4,
@@ -157,6 +159,23 @@ FSEHIP_API size_t FSEHIP_HUF_decompress4X1_DCtx_wksp(FSEHIP_HUF_DTable* dctx, vo
 /* the rest of the single-symbol family (lib/huf.h:141-143 HUF_decompress4X1, :161-163 its DCtx form, :209-211 HUF_readDTableX1[_wksp], :299-304 the 1X1
  * forms; lib/huf_decompress.c:118-192, :377-404, :439-452): the header's table into the caller's DTable / DCtx, then the four streams (4X1) or the single
  * stream (1X1) behind it.  Workspaces are checked as the reference checks them ((16 + 64) words, tableLog_tooLarge) and then left alone. */
+/* the double-symbol family, lib/huf.h:157 HUF_decompress4X2, :166-167 its DCtx forms, :271-272 HUF_readDTableX2[_wksp], :280 HUF_decompress4X2_usingDTable,
+ * :304 HUF_decompress1X2, :314-315 its DCtx forms, :323 HUF_decompress1X2_usingDTable (lib/huf_decompress.c:551-656, :867-952).  The table -- descriptor
+ * {maxTableLog as found, tableType 1, tableLog = maxTableLog} and 1 << maxTableLog cells {U16 sequence; BYTE nbBits; BYTE length} -- is built on the device
+ * from the weights header and is word for word the reference's.  workSpace: smaller than the 1500 bytes lib/huf_decompress.c:570-581 lay out ->
+ * tableLog_tooLarge, before the descriptor's maxTableLog > 12 -> tableLog_tooLarge (:587), before the header is read; otherwise left alone.  The
+ * _usingDTable forms refuse a table of tableType 0 with GENERIC (:873, :913).  Streams are decoded by the double-symbol decoder, so damaged ones
+ * get the verdict of the reference's X2 functions (which is not always that of its X1 functions). */
+FSEHIP_API size_t FSEHIP_HUF_readDTableX2(FSEHIP_HUF_DTable* DTable, const void* src, size_t srcSize);
+FSEHIP_API size_t FSEHIP_HUF_readDTableX2_wksp(FSEHIP_HUF_DTable* DTable, const void* src, size_t srcSize, void* workSpace, size_t wkspSize);
+FSEHIP_API size_t FSEHIP_HUF_decompress4X2(void* dst, size_t dstSize, const void* cSrc, size_t cSrcSize);
+FSEHIP_API size_t FSEHIP_HUF_decompress4X2_DCtx(FSEHIP_HUF_DTable* dctx, void* dst, size_t dstSize, const void* cSrc, size_t cSrcSize);
+FSEHIP_API size_t FSEHIP_HUF_decompress4X2_DCtx_wksp(FSEHIP_HUF_DTable* dctx, void* dst, size_t dstSize, const void* cSrc, size_t cSrcSize, void* workSpace, size_t wkspSize);
+FSEHIP_API size_t FSEHIP_HUF_decompress1X2(void* dst, size_t dstSize, const void* cSrc, size_t cSrcSize);
+FSEHIP_API size_t FSEHIP_HUF_decompress1X2_DCtx(FSEHIP_HUF_DTable* dctx, void* dst, size_t dstSize, const void* cSrc, size_t cSrcSize);
+FSEHIP_API size_t FSEHIP_HUF_decompress1X2_DCtx_wksp(FSEHIP_HUF_DTable* dctx, void* dst, size_t dstSize, const void* cSrc, size_t cSrcSize, void* workSpace, size_t wkspSize);
+FSEHIP_API size_t FSEHIP_HUF_decompress4X2_usingDTable(void* dst, size_t maxDstSize, const void* cSrc, size_t cSrcSize, const FSEHIP_HUF_DTable* DTable);
+FSEHIP_API size_t FSEHIP_HUF_decompress1X2_usingDTable(void* dst, size_t maxDstSize, const void* cSrc, size_t cSrcSize, const FSEHIP_HUF_DTable* DTable);
 /* lib/huf.h:204-218 (lib/huf_compress.c:113-148, :334-421): the compress-side table calls on the caller's own statistics -- HUF_buildCTable[_wksp] from
  * count[0 .. maxSymbolValue] (returns the table log; tree[0 .. maxSymbolValue] receives the codes), HUF_writeCTable from such a table (returns the header
  * size).  Refused where the reference is undefined: no symbol in use, a count of 2^23 or more (blocks are at most HUF_BLOCKSIZE_MAX = 128 KB), more
@@ -260,6 +279,16 @@ FSEHIP_API int FSEHIP_HUF_decompress1X_usingDTable_batch(void* d_dst, size_t dst
                                                          size_t* d_results, const void* d_cSrc, size_t cStride, const size_t* d_cSizes, size_t uniformCSize,
                                                          const FSEHIP_HUF_DTable* d_dtables, size_t dtableStrideU32, unsigned maxTableLog,
                                                          size_t nBlocks, void* stream);
+/* HUF_decompress4X2_usingDTable / HUF_decompress1X2_usingDTable over a batch (lib/huf.h:280, :323; lib/huf_decompress.c:867-875, :907-915): the two
+ * dispatching calls above, except that a block whose table has tableType 0 gets GENERIC (:873, :913; what its destination then holds is unspecified). */
+FSEHIP_API int FSEHIP_HUF_decompress4X2_usingDTable_batch(void* d_dst, size_t dstStride, const size_t* d_dstSizes, size_t uniformDstSize,
+                                                          size_t* d_results, const void* d_cSrc, size_t cStride, const size_t* d_cSizes, size_t uniformCSize,
+                                                          const FSEHIP_HUF_DTable* d_dtables, size_t dtableStrideU32, unsigned maxTableLog,
+                                                          size_t nBlocks, void* stream);
+FSEHIP_API int FSEHIP_HUF_decompress1X2_usingDTable_batch(void* d_dst, size_t dstStride, const size_t* d_dstSizes, size_t uniformDstSize,
+                                                          size_t* d_results, const void* d_cSrc, size_t cStride, const size_t* d_cSizes, size_t uniformCSize,
+                                                          const FSEHIP_HUF_DTable* d_dtables, size_t dtableStrideU32, unsigned maxTableLog,
+                                                          size_t nBlocks, void* stream);
 FSEHIP_API size_t FSEHIP_HUF_compress_batch_workspaceSize(size_t nBlocks);
 FSEHIP_API int FSEHIP_HUF_compress_batch(void* d_dst, size_t dstStride, size_t dstCapacity, size_t* d_results,
                                          const void* d_src, size_t srcStride, const size_t* d_sizes, size_t uniformSize,
@@ -309,6 +338,16 @@ FSEHIP_API int FSEHIP_HUF_writeCTable_batch(void* d_headers, size_t headerStride
                                             const unsigned* d_maxSymbolValues, unsigned huffLog, size_t nBlocks, size_t* d_results, void* stream);
 FSEHIP_API size_t FSEHIP_HUF_readDTableX1_batch_workspaceSize(size_t nBlocks);
 FSEHIP_API int FSEHIP_HUF_readDTableX1_batch(FSEHIP_HUF_DTable* d_dtables, size_t dtableStrideU32, unsigned maxTableLog, size_t* d_results,
+                                             const void* d_src, size_t srcStride, const size_t* d_srcSizes, size_t uniformSrcSize,
+                                             size_t nBlocks, void* d_workspace, size_t workspaceBytes, void* stream);
+/*   HUF_readDTableX2_batch = HUF_readDTableX2 per block (lib/huf_decompress.c:551-649): the double-symbol DTable -- descriptor {maxTableLog, tableType 1,
+ *                            tableLog = maxTableLog, reserved as HUF_CREATE_STATIC_DTABLEX2 leaves it} and 1 << maxTableLog cells {U16 sequence; BYTE nbBits;
+ *                            BYTE length}, word for word the reference's -- for the dispatching / 4X2 / 1X2 _usingDTable batch calls.  d_dtables 4-byte
+ *                            aligned, dtableStrideU32 >= 1 + (1 << maxTableLog); d_results[b] = header size or the reference's error, and a failing block
+ *                            writes nothing to its table.  maxTableLog is DTableDesc.maxTableLog as the reference reads it, NOT a request with a default:
+ *                            above 12 every block fails with tableLog_tooLarge (:587), a header with a larger tableLog likewise (:594). */
+FSEHIP_API size_t FSEHIP_HUF_readDTableX2_batch_workspaceSize(size_t nBlocks);
+FSEHIP_API int FSEHIP_HUF_readDTableX2_batch(FSEHIP_HUF_DTable* d_dtables, size_t dtableStrideU32, unsigned maxTableLog, size_t* d_results,
                                              const void* d_src, size_t srcStride, const size_t* d_srcSizes, size_t uniformSrcSize,
                                              size_t nBlocks, void* d_workspace, size_t workspaceBytes, void* stream);
 
@@ -555,7 +594,7 @@ FSEHIP_API const char* FSEHIP_versionString(void);
 #define HUF_compress1X FSEHIP_HUF_compress1X
 #define HUF_decompress4X1_DCtx_wksp FSEHIP_HUF_decompress4X1_DCtx_wksp
 #endif
-#ifdef FSEHIP_DROPIN_GLUE_NAMES      /* separate switch: the table glue and the header-reading single-symbol decoders (a program that wants the reference's own builders beside the device's hot loops leaves it off) */
+#ifdef FSEHIP_DROPIN_GLUE_NAMES      /* separate switch: the table glue and the header-reading single- and double-symbol decoders (a program that wants the reference's own builders beside the device's hot loops leaves it off) */
 #define FSE_optimalTableLog FSEHIP_FSE_optimalTableLog
 #define FSE_normalizeCount FSEHIP_FSE_normalizeCount
 #define FSE_NCountWriteBound FSEHIP_FSE_NCountWriteBound
@@ -574,6 +613,16 @@ FSEHIP_API const char* FSEHIP_versionString(void);
 #define HUF_decompress1X1 FSEHIP_HUF_decompress1X1
 #define HUF_decompress1X1_DCtx FSEHIP_HUF_decompress1X1_DCtx
 #define HUF_decompress1X1_DCtx_wksp FSEHIP_HUF_decompress1X1_DCtx_wksp
+#define HUF_readDTableX2 FSEHIP_HUF_readDTableX2
+#define HUF_readDTableX2_wksp FSEHIP_HUF_readDTableX2_wksp
+#define HUF_decompress4X2 FSEHIP_HUF_decompress4X2
+#define HUF_decompress4X2_DCtx FSEHIP_HUF_decompress4X2_DCtx
+#define HUF_decompress4X2_DCtx_wksp FSEHIP_HUF_decompress4X2_DCtx_wksp
+#define HUF_decompress1X2 FSEHIP_HUF_decompress1X2
+#define HUF_decompress1X2_DCtx FSEHIP_HUF_decompress1X2_DCtx
+#define HUF_decompress1X2_DCtx_wksp FSEHIP_HUF_decompress1X2_DCtx_wksp
+#define HUF_decompress4X2_usingDTable FSEHIP_HUF_decompress4X2_usingDTable
+#define HUF_decompress1X2_usingDTable FSEHIP_HUF_decompress1X2_usingDTable
 #endif
 #ifdef FSEHIP_DROPIN_U16_NAMES       /* separate switch: programs/fuzzer.c declares FSE_countU16 with another (stale) prototype */
 #define FSE_countU16 FSEHIP_FSE_countU16
