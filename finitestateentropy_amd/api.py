@@ -832,6 +832,16 @@ def _frame_methods():
 _frame_methods()
 
 
+class FrameInfo(C.Structure):
+    """FSEHIP_FrameInfo (include/fsehip.h): what a frame says about itself without a block being decoded"""
+    _fields_ = [("contentBound", C.c_uint64), ("nBlocks", C.c_uint64), ("status", C.c_uint32), ("checksum22", C.c_uint32),
+                ("codec", C.c_uint8), ("blockSizeId", C.c_uint8), ("reserved", C.c_uint8 * 6)]
+
+
+FRAME_INFO_DTYPE = np.dtype([("contentBound", "<u8"), ("nBlocks", "<u8"), ("status", "<u4"), ("checksum22", "<u4"),
+                             ("codec", "u1"), ("blockSizeId", "u1"), ("reserved", "u1", (6,))])
+
+
 def _frame_dev_methods():
     # .fse frames on DEVICE buffers (csrc/frame_dev.hip): many contents <-> many frames in one flat CUDA uint8 tensor each, cut by offsets
     # (n + 1 entries).  Offsets come as a host sequence / numpy array (uploaded here) or as a CUDA int64 tensor (used as it is: with
@@ -938,8 +948,82 @@ def _frame_dev_methods():
             g.check("frame_decompress_dbatch")
         return dst, res
 
+    # ---- frames of unknown size (fsehip.h, FSEHIP_FrameInfo): what a frame announces, the plan made from it, and the reader behind the plan
+    def _align_log(align_log):
+        if not isinstance(align_log, numbers.Integral) or not 0 <= align_log <= 12:
+            raise ValueError("align_log %r: slots are aligned to 1 << 0 .. 1 << 12 bytes" % (align_log,))
+        return int(align_log)
+
+    def frame_inspect(self, frame):
+        """-> (result, info): result = the content bound (a capacity, not a size) or, >= 2**64 - 8, an error code; info = the FSEHIP_FrameInfo
+        fields as a dict.  Host arithmetic: needs no device."""
+        frame = np.ascontiguousarray(frame, dtype=np.uint8)
+        fi = FrameInfo()
+        self.lib.FSEHIP_frame_inspect.restype = SZ
+        r = int(self.lib.FSEHIP_frame_inspect(C.byref(fi), frame.ctypes.data_as(VP), SZ(frame.size)))
+        return r, dict(content_bound=int(fi.contentBound), n_blocks=int(fi.nBlocks), status=int(fi.status), checksum22=int(fi.checksum22),
+                       codec=int(fi.codec), block_size_id=int(fi.blockSizeId), reserved=bytes(fi.reserved))
+
+    def frame_plan_dbatch(self, frames, frame_offsets, capacity=None, align_log=0, with_infos=False, dst_offsets=None, block_first=None, workspace=None):
+        """-> (dst_offsets, block_first[, infos]): int64 CUDA tensors of n + 1 entries -- dst_offsets[i] = min(U[i], capacity) with U the running
+        sum of the frames' content bounds rounded up to 1 << align_log, block_first[i] = the blocks of the frames before i; infos: an (n, 32)
+        uint8 tensor, `infos.cpu().numpy().view(FRAME_INFO_DTYPE)[:, 0]` names its fields.  capacity None: the sizing query (dst_offsets[n] =
+        the capacity all frames need, block_first[n] = the exact max_total_blocks).  Launches only."""
+        align_log = _align_log(align_log)
+        _flat(frames, "frames")
+        foff, _ = self._offsets(frame_offsets, frames.device, False)
+        n = foff.numel() - 1
+        doff = torch.empty(n + 1, dtype=torch.int64, device=frames.device) if dst_offsets is None else dst_offsets
+        bfirst = torch.empty(n + 1, dtype=torch.int64, device=frames.device) if block_first is None else block_first
+        infos = torch.empty((max(n, 1), C.sizeof(FrameInfo)), dtype=torch.uint8, device=frames.device)[:n] if with_infos else None
+        if workspace is None:
+            self.lib.FSEHIP_frame_plan_dbatch_workspaceSize.restype = SZ
+            workspace = torch.empty(max(int(self.lib.FSEHIP_frame_plan_dbatch_workspaceSize(SZ(n))), 1), dtype=torch.uint8, device=frames.device)
+        cap = (1 << 64) - 1 if capacity is None else int(capacity)
+        _check(self.lib.FSEHIP_frame_plan_dbatch(_ptr(doff), _ptr(bfirst), _ptr(infos), _ptr(frames), _ptr(foff), SZ(n), C.c_uint64(cap), C.c_uint(align_log),
+                                                 _ptr(workspace), SZ(workspace.numel()), _stream()), "frame_plan_dbatch")
+        return (doff, bfirst, infos) if with_infos else (doff, bfirst)
+
+    def frame_decompress_packed_dbatch(self, frames, frame_offsets, dst=None, capacity=None, max_total_blocks=None, align_log=0, dst_offsets=None,
+                                       workspace=None, results=None):
+        """-> (dst, dst_offsets, results): content i = dst[dst_offsets[i] : dst_offsets[i] + results[i]], its slot what frame_plan_dbatch gives it
+        for `capacity` (default: dst's size).  dst None: a sizing query first, whose two totals are read back -- the destination (guarded in guard
+        mode) holds every frame's bound and the block promise is exact.  With dst, max_total_blocks, dst_offsets, workspace and results given the
+        call is launches only and can be captured into a graph."""
+        align_log = _align_log(align_log)
+        _flat(frames, "frames")
+        foff, _ = self._offsets(frame_offsets, frames.device, False)
+        n = foff.numel() - 1
+        if dst is None or max_total_blocks is None:
+            doff, bfirst = self.frame_plan_dbatch(frames, foff, None, align_log)
+            need, blocks = (int(x) for x in torch.stack([doff[n], bfirst[n]]).cpu())
+            if max_total_blocks is None:
+                max_total_blocks = blocks
+        g = None
+        if dst is None:
+            capacity = need if capacity is None else int(capacity)
+            dst, g = self._dst(1, capacity, frames.device)
+            dst = dst[0]
+        else:
+            _flat(dst, "dst")
+            capacity = dst.numel() if capacity is None else int(capacity)
+            if capacity > dst.numel():
+                raise ValueError("capacity %d: dst holds %d bytes" % (capacity, dst.numel()))
+        doff = torch.empty(n + 1, dtype=torch.int64, device=frames.device) if dst_offsets is None else dst_offsets
+        res = torch.zeros(max(n, 1), dtype=torch.int64, device=frames.device)[:n] if results is None else results
+        if workspace is None:
+            self.lib.FSEHIP_frame_decompress_packed_dbatch_workspaceSize.restype = SZ
+            workspace = torch.empty(max(int(self.lib.FSEHIP_frame_decompress_packed_dbatch_workspaceSize(SZ(n), SZ(max_total_blocks))), 1),
+                                    dtype=torch.uint8, device=frames.device)
+        _check(self.lib.FSEHIP_frame_decompress_packed_dbatch(_ptr(dst), SZ(capacity), _ptr(doff), _ptr(res), _ptr(frames), _ptr(foff), SZ(n), SZ(max_total_blocks),
+                                                              C.c_uint(align_log), _ptr(workspace), SZ(workspace.numel()), _stream()), "frame_decompress_packed_dbatch")
+        if g is not None:
+            g.check("frame_decompress_packed_dbatch")
+        return dst, doff, res
+
     FseHip._flat = staticmethod(_flat)
-    for f in (_offsets, frame_block_count, frame_dbatch_plan, frame_dbatch_workspace, xxh32_batch, frame_compress_dbatch, frame_decompress_dbatch):
+    for f in (_offsets, frame_block_count, frame_dbatch_plan, frame_dbatch_workspace, xxh32_batch, frame_compress_dbatch, frame_decompress_dbatch,
+              frame_inspect, frame_plan_dbatch, frame_decompress_packed_dbatch):
         setattr(FseHip, f.__name__, f)
 
 

@@ -354,6 +354,49 @@ extern "C" size_t FSEHIP_frame_decompress(void* dst, size_t dstCapacity, const v
     catch (...) { return FSEHIP_ERROR(GENERIC); }
 }
 
+// ---- what a frame says about itself without a block being decoded (fsehip.h, FSEHIP_FrameInfo): the header walk of pass 1 above as a
+// function of its own, summing what the blocks announce.  Host arithmetic only; reads [src, src + srcSize).
+namespace {
+static_assert(sizeof(FSEHIP_FrameInfo) == 32, "FSEHIP_FrameInfo is part of the ABI: 32 bytes");
+void frame_inspect_walk(FSEHIP_FrameInfo& fi, const u8* in, size_t srcSize)
+{
+    memset(&fi, 0, sizeof fi);
+    if (srcSize < 5 + 3) { fi.status = FSEHIP_error_srcSize_wrong; return; }
+    const u32 magic = rd32(in);
+    if ((magic != MAGIC_FSE && magic != MAGIC_HUF) || in[4] > MAX_BSID) { fi.status = FSEHIP_error_GENERIC; return; }
+    fi.codec = magic == MAGIC_HUF ? 1 : 0;
+    fi.blockSizeId = in[4];
+    const size_t bs = block_size(in[4]);
+    size_t ip = 5;
+    for (;;) {
+        if (ip >= srcSize) { fi.status = FSEHIP_error_srcSize_wrong; return; }
+        const unsigned b0 = in[ip++];
+        const unsigned bt = b0 >> 6;
+        size_t rSize = bs, cSize;
+        if (bt == BT_CRC) {
+            if (ip + 2 > srcSize) { fi.status = FSEHIP_error_srcSize_wrong; return; }
+            fi.checksum22 = in[ip + 1] + ((u32)in[ip] << 8) + ((u32)(b0 & 0x3F) << 16);
+            return;
+        }
+        if (!(b0 & 0x20)) { if (ip + 2 > srcSize) { fi.status = FSEHIP_error_srcSize_wrong; return; } rSize = ((size_t)in[ip] << 8) + in[ip + 1]; ip += 2; }
+        if (bt == BT_COMPRESSED) { if (ip + 2 > srcSize) { fi.status = FSEHIP_error_srcSize_wrong; return; } cSize = ((size_t)in[ip] << 8) + in[ip + 1]; ip += 2; }
+        else cSize = bt == BT_RAW ? rSize : 1;
+        if (ip + cSize > srcSize) { fi.status = FSEHIP_error_srcSize_wrong; return; }
+        if (rSize > bs) { fi.status = FSEHIP_error_corruption_detected; return; }
+        fi.contentBound += rSize; ++fi.nBlocks;
+        ip += cSize;
+    }
+}
+}   // namespace
+
+extern "C" size_t FSEHIP_frame_inspect(FSEHIP_FrameInfo* info, const void* src, size_t srcSize)
+{
+    FSEHIP_FrameInfo fi;
+    frame_inspect_walk(fi, (const u8*)src, srcSize);
+    if (info) *info = fi;
+    return fi.status ? (size_t)0 - fi.status : (size_t)fi.contentBound;
+}
+
 // ---- many frames per call.  One frame is bound by one host thread's XXH32 (about 6 GB/s) and its pageable copies whatever the device
 // does, so frames are handed to a pool of host threads: each worker takes the next frame, runs the single-frame code above on a stream
 // of its own (its copies and kernels overlap the other workers') with its own scratch arena, and writes that frame's result.  A

@@ -13,6 +13,10 @@
 //                                   place at the position its predecessors ANNOUNCE -> k_fr_expand (raw / RLE blocks) -> k_fr_settle (per
 //                                   frame: the reader's walk over results, frame.hip:325-341; repairs a frame in which a block
 //                                   regenerated less than announced) -> k_xxh32 -> k_fr_final
+//   FSEHIP_frame_plan_dbatch      : k_fr_plan (the same header walk, summing what the blocks announce) -> scan of the aligned bounds, scan of
+//                                   the block counts -> k_fr_clamp: destination offsets and the exact block total of frames of unknown size
+//   FSEHIP_frame_decompress_packed_dbatch: k_fr_plan in place of k_fr_count, the two scans, k_fr_clamp -- then the reader from k_fr_clear on
+//                                   over the offsets just produced (fr_decode, shared with FSEHIP_frame_decompress_dbatch)
 // A caller's promise `maxTotalBlocks` sizes every per-block launch; what lies beyond the real block count is a block of size 0.
 #include "internal.h"
 #include "ncount_reader.h"
@@ -354,6 +358,39 @@ __global__ void k_fr_count(FrFrame* frames, u64* first, const u8* src, const u64
     frames[f] = m;
     first[f] = n;
 }
+// k_fr_count for frames whose regenerated sizes nobody knows: the same walk, which also sums what the blocks ANNOUNCE -- the frame's
+// content bound (fsehip.h: a capacity with which the reader decides what it decides with any larger one, not the content size), rounded
+// up to the slot alignment in slots[f] -- and tells what it saw (infos, may be null; frames may be null: the plan alone keeps no FrFrame).
+__global__ void k_fr_plan(FrFrame* frames, u64* first, u64* slots, FSEHIP_FrameInfo* infos, const u8* src, const u64* frameOff, size_t nFrames, u32 alignLog)
+{
+    const size_t f = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= nFrames) return;
+    const u8* const in = src + frameOff[f];
+    const size_t srcSize = (size_t)(frameOff[f + 1] - frameOff[f]);
+    FrFrame m; m.soft = 0; m.crc = 0; m.pad = 0;
+    m.hard = fr_head(in, srcSize, m.codec, m.bsLog);
+    u64 n = 0, bound = 0;
+    if (!m.hard) m.soft = fr_walk(in, srcSize, (size_t)1 << m.bsLog, m.crc, [&](u32, size_t rSize, size_t, size_t) { ++n; bound += rSize; });
+    if (frames) frames[f] = m;
+    first[f] = n;
+    const u64 a = ((u64)1 << alignLog) - 1;
+    slots[f] = (bound + a) & ~a;
+    if (infos) {
+        FSEHIP_FrameInfo fi;
+        fi.contentBound = bound; fi.nBlocks = n;
+        fi.status = (u32)(0 - (m.hard ? m.hard : m.soft));
+        fi.checksum22 = m.crc;
+        fi.codec = m.hard ? 0 : (u8)m.codec; fi.blockSizeId = m.hard ? 0 : (u8)(m.bsLog - 10);
+        for (int k = 0; k < 6; ++k) fi.reserved[k] = 0;
+        infos[f] = fi;
+    }
+}
+// off[i] = min(off[i], cap), i < n: the slots behind the capacity become empty, the one across it short
+__global__ void k_fr_clamp(u64* off, size_t n, u64 cap)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && off[i] > cap) off[i] = cap;
+}
 // The block table, one entry per promised block:
 //   at / csize : the record's bytes in d_frames;  dpos : where the block lands in d_dst if every block before it regenerates what it announces;
 //   kind       : type | inPlace << 2 (dpos + rSize fits the frame's slot: decoded / expanded there at once) | codec << 3, or FD_NONE: no block
@@ -524,6 +561,15 @@ FrLayout fr_layout(size_t nFrames, size_t maxBlocks)
     L.total = p;
     return L;
 }
+struct FpLayout { size_t first, partials, total; };
+FpLayout fp_layout(size_t nFrames)
+{
+    FpLayout L; size_t p = 0;
+    auto carve = [&](size_t bytes) { const size_t r = p; p += up256(bytes); return r; };
+    L.first = carve((nFrames + 1) * 8); L.partials = carve(scan_partials(nFrames) * 8);
+    L.total = p;
+    return L;
+}
 }   // namespace
 
 #define CKE(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return (int)e_; } while (0)
@@ -596,28 +642,15 @@ extern "C" int FSEHIP_frame_compress_dbatch(void* d_dst, const uint64_t* d_dstOf
 
 extern "C" size_t FSEHIP_frame_decompress_dbatch_workspaceSize(size_t nFrames, size_t maxTotalBlocks) { return fr_layout(nFrames, maxTotalBlocks).total; }
 
-extern "C" int FSEHIP_frame_decompress_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_frames, const uint64_t* d_frameOffsets,
-                                              size_t nFrames, size_t maxTotalBlocks, void* d_workspace, size_t workspaceBytes, void* stream)
+// the reader behind its header walk and first scan: `frames` and `first` (scanned) are in the workspace, dstOff in device memory
+static int fr_decode(void* d_dst, const u64* dstOff, size_t* d_results, const u8* src, const u64* frameOff, size_t nFrames, size_t nb, u8* ws, const FrLayout& L, hipStream_t s)
 {
-    hipStream_t s = (hipStream_t)stream;
-    if ((uintptr_t)d_workspace & 255u) return (int)hipErrorInvalidValue;
-    if (nFrames == 0) return 0;
-    if (maxTotalBlocks >= ((size_t)1 << 31) || nFrames >= ((size_t)1 << 31)) return (int)hipErrorInvalidValue;
-    const FrLayout L = fr_layout(nFrames, maxTotalBlocks);
-    if (workspaceBytes < L.total) return (int)hipErrorInvalidValue;
-    u8* const ws = (u8*)d_workspace;
     FrFrame* const frames = (FrFrame*)(ws + L.frames); u64* const first = (u64*)(ws + L.first); u32* const hashes = (u32*)(ws + L.hashes);
-    size_t* const verdict = (size_t*)(ws + L.verdict); u64* const olen = (u64*)(ws + L.olen); u64* const partials = (u64*)(ws + L.partials);
+    size_t* const verdict = (size_t*)(ws + L.verdict); u64* const olen = (u64*)(ws + L.olen);
     FrTable t;
     t.at = (u64*)(ws + L.at); t.dpos = (u64*)(ws + L.dpos); t.csize = (u32*)(ws + L.csize); t.rsize = (u32*)(ws + L.rsize); t.kind = (u32*)(ws + L.kind);
     t.fseCs = (size_t*)(ws + L.fseCs); t.fseCap = (size_t*)(ws + L.fseCap); t.hufCs = (size_t*)(ws + L.hufCs); t.hufDs = (size_t*)(ws + L.hufDs);
     t.fseRes = (size_t*)(ws + L.fseRes); t.hufRes = (size_t*)(ws + L.hufRes);
-    const u8* const src = (const u8*)d_frames;
-    const u64* const frameOff = (const u64*)d_frameOffsets; const u64* const dstOff = (const u64*)d_dstOffsets;
-    const size_t nb = maxTotalBlocks;
-
-    hipLaunchKernelGGL(k_fr_count, dim3(grid_for(nFrames)), dim3(FD_THREADS), 0, s, frames, first, src, frameOff, nFrames);
-    CKE(launch_exscan(first, nFrames, partials, s));
     if (nb) {
         hipLaunchKernelGGL(k_fr_clear, dim3(grid_for(nb)), dim3(FD_THREADS), 0, s, t, nb);
         hipLaunchKernelGGL(k_fr_fill, dim3(grid_for(nFrames)), dim3(FD_THREADS), 0, s, t, (const FrFrame*)frames, (const u64*)first, src, frameOff, dstOff, nFrames, nb);
@@ -640,4 +673,68 @@ extern "C" int FSEHIP_frame_decompress_dbatch(void* d_dst, const uint64_t* d_dst
     hipLaunchKernelGGL(k_fr_final, dim3(grid_for(nFrames)), dim3(FD_THREADS), 0, s, d_results, (const size_t*)verdict, (const u64*)olen, (const u32*)hashes,
                        (const FrFrame*)frames, nFrames);
     return (int)hipGetLastError();
+}
+
+extern "C" int FSEHIP_frame_decompress_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_frames, const uint64_t* d_frameOffsets,
+                                              size_t nFrames, size_t maxTotalBlocks, void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if ((uintptr_t)d_workspace & 255u) return (int)hipErrorInvalidValue;
+    if (nFrames == 0) return 0;
+    if (maxTotalBlocks >= ((size_t)1 << 31) || nFrames >= ((size_t)1 << 31)) return (int)hipErrorInvalidValue;
+    const FrLayout L = fr_layout(nFrames, maxTotalBlocks);
+    if (workspaceBytes < L.total) return (int)hipErrorInvalidValue;
+    u8* const ws = (u8*)d_workspace;
+    FrFrame* const frames = (FrFrame*)(ws + L.frames); u64* const first = (u64*)(ws + L.first); u64* const partials = (u64*)(ws + L.partials);
+    const u8* const src = (const u8*)d_frames;
+    const u64* const frameOff = (const u64*)d_frameOffsets;
+
+    hipLaunchKernelGGL(k_fr_count, dim3(grid_for(nFrames)), dim3(FD_THREADS), 0, s, frames, first, src, frameOff, nFrames);
+    CKE(launch_exscan(first, nFrames, partials, s));
+    return fr_decode(d_dst, (const u64*)d_dstOffsets, d_results, src, frameOff, nFrames, maxTotalBlocks, ws, L, s);
+}
+
+// k_fr_plan, the scan of the slots (in place in dstOff: nFrames + 1 entries) and of the block counts, the clamp
+static int fr_plan(FrFrame* frames, u64* first, u64* dstOff, FSEHIP_FrameInfo* infos, const u8* src, const u64* frameOff, size_t nFrames, u64 dstCapacity,
+                   unsigned alignLog, u64* partials, hipStream_t s)
+{
+    if (nFrames) hipLaunchKernelGGL(k_fr_plan, dim3(grid_for(nFrames)), dim3(FD_THREADS), 0, s, frames, first, dstOff, infos, src, frameOff, nFrames, (u32)alignLog);
+    CKE(launch_exscan(dstOff, nFrames, partials, s));
+    CKE(launch_exscan(first, nFrames, partials, s));
+    hipLaunchKernelGGL(k_fr_clamp, dim3(grid_for(nFrames + 1)), dim3(FD_THREADS), 0, s, dstOff, nFrames + 1, dstCapacity);
+    return (int)hipGetLastError();
+}
+
+extern "C" size_t FSEHIP_frame_plan_dbatch_workspaceSize(size_t nFrames) { return fp_layout(nFrames).total; }
+
+extern "C" int FSEHIP_frame_plan_dbatch(uint64_t* d_dstOffsets, uint64_t* d_blockFirst, FSEHIP_FrameInfo* d_infos, const void* d_frames, const uint64_t* d_frameOffsets,
+                                        size_t nFrames, uint64_t dstCapacity, unsigned slotAlignLog, void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    if (slotAlignLog > 12 || ((uintptr_t)d_workspace & 255u) || nFrames >= ((size_t)1 << 31)) return (int)hipErrorInvalidValue;
+    const FpLayout L = fp_layout(nFrames);
+    if (workspaceBytes < L.total) return (int)hipErrorInvalidValue;
+    u8* const ws = (u8*)d_workspace;
+    u64* const first = d_blockFirst ? (u64*)d_blockFirst : (u64*)(ws + L.first);
+    return fr_plan(nullptr, first, (u64*)d_dstOffsets, d_infos, (const u8*)d_frames, (const u64*)d_frameOffsets, nFrames, dstCapacity, slotAlignLog,
+                   (u64*)(ws + L.partials), (hipStream_t)stream);
+}
+
+extern "C" size_t FSEHIP_frame_decompress_packed_dbatch_workspaceSize(size_t nFrames, size_t maxTotalBlocks) { return fr_layout(nFrames, maxTotalBlocks).total; }
+
+extern "C" int FSEHIP_frame_decompress_packed_dbatch(void* d_dst, size_t dstCapacity, uint64_t* d_dstOffsets, size_t* d_results, const void* d_frames,
+                                                     const uint64_t* d_frameOffsets, size_t nFrames, size_t maxTotalBlocks, unsigned slotAlignLog,
+                                                     void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (slotAlignLog > 12 || ((uintptr_t)d_workspace & 255u)) return (int)hipErrorInvalidValue;
+    if (maxTotalBlocks >= ((size_t)1 << 31) || nFrames >= ((size_t)1 << 31)) return (int)hipErrorInvalidValue;
+    const FrLayout L = fr_layout(nFrames, maxTotalBlocks);
+    if (workspaceBytes < L.total) return (int)hipErrorInvalidValue;
+    u8* const ws = (u8*)d_workspace;
+    const u8* const src = (const u8*)d_frames;
+    const u64* const frameOff = (const u64*)d_frameOffsets;
+    CKI(fr_plan((FrFrame*)(ws + L.frames), (u64*)(ws + L.first), (u64*)d_dstOffsets, nullptr, src, frameOff, nFrames, (u64)dstCapacity, slotAlignLog,
+                (u64*)(ws + L.partials), s));
+    if (nFrames == 0) return 0;
+    return fr_decode(d_dst, (const u64*)d_dstOffsets, d_results, src, frameOff, nFrames, maxTotalBlocks, ws, L, s);
 }

@@ -473,7 +473,50 @@ FSEHIP_API size_t FSEHIP_frame_decompress_batch(void* const* dsts, const size_t*
  *     Memory: a frame's result depends on nothing outside its [offset, next offset) -- the header walk reads nothing else; the block
  *     decoders fetch aligned 64-byte pieces and may touch, without using them, bytes of the neighbouring frames inside d_frames.  Nothing is
  *     written outside a frame's destination slot; inside the slot, bytes behind the regenerated size are undefined.
+ *
+ * Frames of UNKNOWN size (a file, another rank, the reference's tool): a frame does not store its content size (fileio.c:266-285), so the
+ * caller of the reader above has neither d_dstOffsets nor a promise better than (F - 8) / 2 blocks.  What a frame does say without a
+ * block being decoded is what its block headers ANNOUNCE:
+ *
+ *   FSEHIP_FrameInfo   contentBound = the sum of the announced regenerated sizes of the blocks the header walk passes (it stops at the end
+ *                      mark or at the first structural problem), nBlocks = their number.  The bound is a CAPACITY, not a size:
+ *                      FSEHIP_frame_decompress with capacity contentBound returns what it returns with any larger capacity, but a
+ *                      compressed FSE block may regenerate less than it announces (then the content is shorter than the bound), and a block
+ *                      decoder may still report dstSize_tooSmall of its own.  For every frame the tool or this library writes the bound
+ *                      equals the content size.  status = 0 or the FSEHIP_ErrorCode of what the reader decides without decoding a block:
+ *                      GENERIC (bad magic or block-size id; contentBound = nBlocks = 0), srcSize_wrong (shorter than 8 bytes, or
+ *                      truncated), corruption_detected (a block announces more than the block size) -- contentBound and nBlocks then
+ *                      cover the blocks in front of that point.  checksum22 = the end mark's 22 bits (0 without one), codec and
+ *                      blockSizeId as the first five bytes give them (0 where status is GENERIC or the frame is shorter than 8 bytes).
+ *
+ *   FSEHIP_frame_inspect   HOST pointer, host arithmetic only (works without a device): fills *info (may be NULL) and returns contentBound,
+ *                      or (size_t)-status.
+ *
+ *   FSEHIP_frame_plan_dbatch   the same walk for every frame of a device batch, one lane per frame, and two scans.  With
+ *                      U[i] = sum over j < i of roundup(contentBound_j, 1 << slotAlignLog):  d_dstOffsets[i] = min(U[i], dstCapacity) and
+ *                      d_blockFirst[i] = the blocks of the frames before i (nFrames + 1 entries each; d_blockFirst[nFrames] is the exact
+ *                      maxTotalBlocks of the reader), d_infos[i] = frame i's record.  d_blockFirst and d_infos may be NULL.  dstCapacity =
+ *                      UINT64_MAX is the sizing query: d_dstOffsets[nFrames] is then the capacity all frames need.  slotAlignLog > 12:
+ *                      hipErrorInvalidValue.  nFrames == 0 writes entry 0 (= 0) of both arrays.  Reads nothing outside a frame's
+ *                      [offset, next offset).
+ *
+ *   FSEHIP_frame_decompress_packed_dbatch   the plan followed by FSEHIP_frame_decompress_dbatch's decoding in one call (no frame is walked a
+ *                      third time): d_dstOffsets is an OUTPUT (nFrames + 1 entries, as the plan writes them for dstCapacity and
+ *                      slotAlignLog), d_results[i] = what FSEHIP_frame_decompress(d_dst + off[i], off[i+1] - off[i], frame_i, size_i)
+ *                      returns, with the same bytes.  A frame that straddles dstCapacity therefore gets a short (or empty) slot and the host
+ *                      call's verdict for that slot; nothing is written at or behind d_dst + dstCapacity.  maxTotalBlocks is the same
+ *                      promise as above -- exact from a sizing query's d_blockFirst[nFrames], or any upper bound; a frame beyond it gets
+ *                      GENERIC and writes nothing.  Memory contract of the reader above.
  */
+typedef struct {
+    uint64_t contentBound;
+    uint64_t nBlocks;
+    uint32_t status;
+    uint32_t checksum22;
+    uint8_t  codec;
+    uint8_t  blockSizeId;
+    uint8_t  reserved[6];   /* zero */
+} FSEHIP_FrameInfo;
 FSEHIP_API int FSEHIP_XXH32_batch(uint32_t* d_hashes, const void* d_data, const uint64_t* d_offsets, size_t nItems, uint32_t seed, void* stream);
 FSEHIP_API size_t FSEHIP_frame_blockCount(size_t srcSize, unsigned blockSizeId);
 FSEHIP_API size_t FSEHIP_frame_compress_dbatch_workspaceSize(size_t nFrames, size_t maxTotalBlocks, unsigned blockSizeId, int codec);
@@ -483,6 +526,14 @@ FSEHIP_API int FSEHIP_frame_compress_dbatch(void* d_dst, const uint64_t* d_dstOf
 FSEHIP_API size_t FSEHIP_frame_decompress_dbatch_workspaceSize(size_t nFrames, size_t maxTotalBlocks);
 FSEHIP_API int FSEHIP_frame_decompress_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_frames, const uint64_t* d_frameOffsets,
                                               size_t nFrames, size_t maxTotalBlocks, void* d_workspace, size_t workspaceBytes, void* stream);
+FSEHIP_API size_t FSEHIP_frame_inspect(FSEHIP_FrameInfo* info, const void* src, size_t srcSize);
+FSEHIP_API size_t FSEHIP_frame_plan_dbatch_workspaceSize(size_t nFrames);
+FSEHIP_API int FSEHIP_frame_plan_dbatch(uint64_t* d_dstOffsets, uint64_t* d_blockFirst, FSEHIP_FrameInfo* d_infos, const void* d_frames, const uint64_t* d_frameOffsets,
+                                        size_t nFrames, uint64_t dstCapacity, unsigned slotAlignLog, void* d_workspace, size_t workspaceBytes, void* stream);
+FSEHIP_API size_t FSEHIP_frame_decompress_packed_dbatch_workspaceSize(size_t nFrames, size_t maxTotalBlocks);
+FSEHIP_API int FSEHIP_frame_decompress_packed_dbatch(void* d_dst, size_t dstCapacity, uint64_t* d_dstOffsets, size_t* d_results, const void* d_frames,
+                                                     const uint64_t* d_frameOffsets, size_t nFrames, size_t maxTotalBlocks, unsigned slotAlignLog,
+                                                     void* d_workspace, size_t workspaceBytes, void* stream);
 
 /* ---- FSE for 16-bit symbols (lib/fseU16.h:62-80, lib/fseU16.c) -- SURVEY 8(f) rank 4.  Alphabets of up to
  * FSEHIP_FSEU16_MAX_SYMBOL_VALUE + 1 symbols, table logs up to 13 (default 12), ONE tANS state per stream: a different format from

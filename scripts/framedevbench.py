@@ -1,8 +1,13 @@
 """development aid: .fse frames written and read on DEVICE buffers (FSEHIP_frame_compress_dbatch / _decompress_dbatch, FSEHIP_XXH32_batch)
 next to the host-buffer batch calls (FSEHIP_frame_compress_batch / _decompress_batch, pinned host memory, 4 threads) on the same contents.
   (a) 1024 frames of 1 MiB   (b) one frame of 256 MiB   (c) the checksum kernel alone on both shapes      P14, block-size id 5, both codecs
+  (d) 100k frames of 4 KB, device calls only
+On every shape the frames are also read as frames of UNKNOWN size: the plan alone (FSEHIP_frame_plan_dbatch: header walk, two scans, clamp)
+and the packed call (FSEHIP_frame_decompress_packed_dbatch) beside the known-offset call on the same frames -- "extra_ms" is the packed call
+minus the known-offset call of the same run.
 Device calls: device events around the calls, repeated until the timed region is at least MIN_MS long, after one warm-up call of the same
-shape.  GB/s = content bytes / time.  Prints one JSON line per figure.  Usage: framedevbench.py [--frames 1024] [--frame-mib 1] [--big-mib 256]"""
+shape.  GB/s = content bytes / time.  Prints one JSON line per figure.  Usage: framedevbench.py [--frames 1024] [--frame-mib 1] [--big-mib 256]
+[--small-frames 100000] [--small-kib 4] [--no-host]"""
 import argparse, ctypes as C, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -12,6 +17,7 @@ from finitestateentropy_amd.api import FseHip
 MIN_MS = 300.0
 ap = argparse.ArgumentParser()
 ap.add_argument("--frames", type=int, default=1024); ap.add_argument("--frame-mib", type=int, default=1); ap.add_argument("--big-mib", type=int, default=256)
+ap.add_argument("--small-frames", type=int, default=100000); ap.add_argument("--small-kib", type=int, default=4)
 ap.add_argument("--no-host", action="store_true")
 args = ap.parse_args()
 hip = FseHip()
@@ -63,8 +69,21 @@ def device_side(shape, n_frames, frame_bytes):
         poff = torch.from_numpy(poff_h).cuda()
         dws = hip.frame_dbatch_workspace(n_frames, nblk)
         r = lambda: hip.frame_decompress_dbatch(packed, poff, soff, dst=back, max_total_blocks=nblk, workspace=dws, results=dres)
-        report(shape, "device read", name, total, timed(r))
+        known = timed(r)
+        report(shape, "device read", name, total, known)
         assert bool((dres == frame_bytes).all()) and torch.equal(back, src)
+        # the same frames as frames of unknown size: exact promise, exact capacity (what a sizing query returns)
+        pws = torch.empty(int(hip.lib.FSEHIP_frame_plan_dbatch_workspaceSize(C.c_size_t(n_frames))), dtype=torch.uint8, device="cuda")
+        pd = torch.zeros(n_frames + 1, dtype=torch.int64, device="cuda"); pb = torch.zeros_like(pd)
+        plan = timed(lambda: hip.frame_plan_dbatch(packed, poff, None, 0, dst_offsets=pd, block_first=pb, workspace=pws))
+        assert torch.equal(pd, soff) and int(pb[-1].item()) == nblk
+        report(shape, "device plan (header walk, scans)", name, total, plan)
+        dres.zero_(); back.zero_(); pd.zero_()
+        u = lambda: hip.frame_decompress_packed_dbatch(packed, poff, dst=back, capacity=total, max_total_blocks=nblk, dst_offsets=pd, workspace=dws, results=dres)
+        unknown = timed(u)
+        report(shape, "device read, sizes unknown (packed call)", name, total, unknown, extra_ms=round(unknown - known, 3), plan_ms=round(plan, 3))
+        assert bool((dres == frame_bytes).all()) and torch.equal(back, src) and torch.equal(pd, soff)
+        del pws
         del cws, dws, packed
     return src
 
@@ -96,9 +115,14 @@ def host_side(shape, src, n_frames, frame_bytes, threads=4):
         assert all(int(res2[i]) == frame_bytes for i in range(n_frames)) and torch.equal(backs, pin)
 
 
-for shape, n_frames, frame_bytes in (("a: %d x %d MiB" % (args.frames, args.frame_mib), args.frames, args.frame_mib << 20), ("b: 1 x %d MiB" % args.big_mib, 1, args.big_mib << 20)):
+hip.lib.FSEHIP_frame_plan_dbatch_workspaceSize.restype = C.c_size_t
+for shape, n_frames, frame_bytes, host in (("a: %d x %d MiB" % (args.frames, args.frame_mib), args.frames, args.frame_mib << 20, True),
+                                           ("b: 1 x %d MiB" % args.big_mib, 1, args.big_mib << 20, True),
+                                           ("d: %d x %d KiB" % (args.small_frames, args.small_kib), args.small_frames, args.small_kib << 10, False)):
+    if n_frames == 0:
+        continue
     src = device_side(shape, n_frames, frame_bytes)
-    if not args.no_host:
+    if host and not args.no_host:
         host_side(shape, src, n_frames, frame_bytes)
     del src
     torch.cuda.empty_cache()
