@@ -1021,9 +1021,65 @@ def _frame_dev_methods():
             g.check("frame_decompress_packed_dbatch")
         return dst, doff, res
 
+    # ---- the packed writer (fsehip.h, FSEHIP_frame_compress_packed_dbatch): frames back to back at their real sizes, offsets from the device
+    def frame_packed_bound(self, total_src_bytes, n_frames, total_blocks, align_log=0):
+        """a capacity of frame_compress_packed_dbatch at which no frame fails for lack of room.  Host arithmetic: needs no device."""
+        self.lib.FSEHIP_frame_packedBound.restype = SZ
+        r = int(self.lib.FSEHIP_frame_packedBound(SZ(int(total_src_bytes)), SZ(int(n_frames)), SZ(int(total_blocks)), C.c_uint(_align_log(align_log))))
+        if r >= (1 << 62):
+            raise ValueError("frame_packed_bound(%r, %r, %r, %r)" % (total_src_bytes, n_frames, total_blocks, align_log))
+        return r
+
+    def frame_compress_packed_dbatch(self, src, src_offsets, block_size_id=5, codec=0, dst=None, capacity=None, max_total_blocks=None, align_log=0, dst_offsets=None,
+                                     workspace=None, results=None):
+        """-> (dst, dst_offsets, results): frame i = dst[dst_offsets[i] : dst_offsets[i] + results[i]], the frames back to back with every start
+        rounded up to 1 << align_log; dst_offsets (int64, n + 1 entries) comes from the device and is what frame_decompress_packed_dbatch takes
+        as frame_offsets.  `capacity` defaults to dst's size; dst None: a destination (guarded in guard mode) of `capacity` bytes, by default
+        frame_packed_bound(...) of the contents, which no frame can miss.  A frame the capacity cuts short gets -2 (dstSize_tooSmall) and is not
+        written.  With dst, max_total_blocks, dst_offsets, workspace and results given the call is launches only and can be captured into a graph."""
+        align_log = _align_log(align_log)
+        _flat(src, "src")
+        soff, shost = self._offsets(src_offsets, src.device, max_total_blocks is None or (dst is None and capacity is None))
+        n = soff.numel() - 1
+        if shost is not None:
+            blocks = sum(self.frame_block_count(int(x), block_size_id) for x in np.diff(shost)) if block_size_id <= 6 else 0
+        if max_total_blocks is None:
+            max_total_blocks = blocks
+        g = None
+        if dst is None:
+            if capacity is None:
+                capacity = self.frame_packed_bound(int(shost[-1] - shost[0]), n, blocks, align_log)
+            dst, g = self._dst(1, int(capacity), src.device)
+            dst = dst[0]
+        else:
+            _flat(dst, "dst")
+            capacity = dst.numel() if capacity is None else int(capacity)
+            if capacity > dst.numel():
+                raise ValueError("capacity %d: dst holds %d bytes" % (capacity, dst.numel()))
+        doff = torch.empty(n + 1, dtype=torch.int64, device=src.device) if dst_offsets is None else dst_offsets
+        res = torch.zeros(max(n, 1), dtype=torch.int64, device=src.device)[:n] if results is None else results
+        if workspace is None:
+            self.lib.FSEHIP_frame_compress_packed_dbatch_workspaceSize.restype = SZ
+            need = int(self.lib.FSEHIP_frame_compress_packed_dbatch_workspaceSize(SZ(n), SZ(max_total_blocks), C.c_uint(min(block_size_id, 6)),
+                                                                                  C.c_int(codec if codec in (0, 1) else 0)))
+            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=src.device)
+        _check(self.lib.FSEHIP_frame_compress_packed_dbatch(_ptr(dst), C.c_uint64(int(capacity)), _ptr(doff), _ptr(res), _ptr(src), _ptr(soff), SZ(n),
+                                                            SZ(max_total_blocks), C.c_uint(block_size_id), C.c_int(codec), C.c_uint(align_log),
+                                                            _ptr(workspace), SZ(workspace.numel()), _stream()), "frame_compress_packed_dbatch")
+        if g is not None:
+            g.check("frame_compress_packed_dbatch")
+            # ... and between the frames: the writer's contract is the frames' bytes and nothing else, the padding included (include/fsehip.h)
+            total = int(doff[n].item())
+            if total:
+                idx = torch.arange(total, device=src.device)
+                slot = torch.searchsorted(doff[1:].contiguous(), idx, right=True).clamp(max=n - 1)
+                beyond = (idx - doff[slot]) >= res[slot].clamp(min=0)
+                assert bool((g.full[0, :total][beyond] == g.fill).all()), "frame_compress_packed_dbatch wrote outside a frame's bytes"
+        return dst, doff, res
+
     FseHip._flat = staticmethod(_flat)
     for f in (_offsets, frame_block_count, frame_dbatch_plan, frame_dbatch_workspace, xxh32_batch, frame_compress_dbatch, frame_decompress_dbatch,
-              frame_inspect, frame_plan_dbatch, frame_decompress_packed_dbatch):
+              frame_inspect, frame_plan_dbatch, frame_decompress_packed_dbatch, frame_packed_bound, frame_compress_packed_dbatch):
         setattr(FseHip, f.__name__, f)
 
 

@@ -8,6 +8,10 @@
 //                                   size / error as the frame writer switches on them, frame.hip:160-177) -> k_fw_lens -> scan (record
 //                                   positions; a frame's own = the difference to its first block's) -> k_xxh32 (trailers)
 //                                   -> k_fw_verdict (per frame: result, magic, trailer) -> k_fw_assemble (per block: header + record)
+//   FSEHIP_frame_compress_packed_dbatch: the same up to the record positions (fw_encode, shared with FSEHIP_frame_compress_dbatch) -> k_fw_sizes
+//                                   (per frame: its result without a capacity; the size rounded up to the slot alignment) -> scan of those
+//                                   -> k_fr_clamp: the destination offsets, an OUTPUT -> k_fw_place (per frame: does it fit its slot; magic,
+//                                   trailer) -> k_fw_assemble over the offsets just produced
 //   FSEHIP_frame_decompress_dbatch: k_fr_count (header walk per frame) -> scan -> k_fr_clear + k_fr_fill (the block table) -> the one-shot
 //                                   FSE and Huff0 decoders over (offset, size) views of the compressed blocks, writing every block in
 //                                   place at the position its predecessors ANNOUNCE -> k_fr_expand (raw / RLE blocks) -> k_fr_settle (per
@@ -244,6 +248,22 @@ __global__ void k_fw_lens(u64* pos, const size_t* cres, const u64* blkOff, const
     }
     pos[g] = len;
 }
+// what FSEHIP_frame_compress returns for content f at a capacity of FSEHIP_frame_compressBound (frame.hip:132-133,167,177): the frame's size, a
+// block coder's error, or GENERIC for a frame beyond the caller's promise
+DEV size_t fw_result(u64 b0, u64 b1, const u64* pos, const size_t* cres, size_t maxBlocks)
+{
+    if (b1 > b0 && b1 > maxBlocks) return FERR(GENERIC);                                       // beyond the caller's promise
+    for (u64 g = b0; g < b1; ++g) if (is_err(cres[g])) return cres[g];                         // fileio.c:341
+    return (size_t)(5 + (b1 > b0 ? pos[b1] - pos[b0] : 0) + 3);
+}
+// magic and block-size id in front of a frame of `size` bytes, the end mark behind its records
+DEV void fw_ends(u8* out, u64 size, u32 hash, u32 bsid, int codec)
+{
+    const u32 magic = codec == 1 ? MAGIC_HUF : MAGIC_FSE;
+    out[0] = (u8)magic; out[1] = (u8)(magic >> 8); out[2] = (u8)(magic >> 16); out[3] = (u8)(magic >> 24); out[4] = (u8)bsid;
+    const u32 checksum = (hash >> 5) & ((1u << 22) - 1);                                        // fileio.c:408-416
+    out[size - 3] = (u8)((checksum >> 16) + (BT_CRC << 6)); out[size - 2] = (u8)(checksum >> 8); out[size - 1] = (u8)checksum;
+}
 // per frame: the result of FSEHIP_frame_compress for this content (frame.hip:132-133,167,177); a good frame gets its magic and trailer here
 __global__ void k_fw_verdict(u8* dst, const u64* dstOff, size_t* results, const u64* srcOff, const u64* first, const u64* pos, const size_t* cres,
                              const u32* hashes, size_t nFrames, size_t maxBlocks, u32 bsid, int codec)
@@ -253,15 +273,33 @@ __global__ void k_fw_verdict(u8* dst, const u64* dstOff, size_t* results, const 
     const u64 n = srcOff[f + 1] - srcOff[f], cap = dstOff[f + 1] - dstOff[f];
     const u64 b0 = first[f], b1 = first[f + 1];
     if (cap < 5 + n + 5 * (b1 - b0) + 3) { results[f] = FERR(dstSize_tooSmall); return; }      // FSEHIP_frame_compressBound
-    if (b1 > b0 && b1 > maxBlocks) { results[f] = FERR(GENERIC); return; }                     // beyond the caller's promise
-    for (u64 g = b0; g < b1; ++g) if (is_err(cres[g])) { results[f] = cres[g]; return; }       // fileio.c:341
-    const u64 size = 5 + (b1 > b0 ? pos[b1] - pos[b0] : 0) + 3;
-    u8* const out = dst + dstOff[f];
-    const u32 magic = codec == 1 ? MAGIC_HUF : MAGIC_FSE;
-    out[0] = (u8)magic; out[1] = (u8)(magic >> 8); out[2] = (u8)(magic >> 16); out[3] = (u8)(magic >> 24); out[4] = (u8)bsid;
-    const u32 checksum = (hashes[f] >> 5) & ((1u << 22) - 1);                                   // fileio.c:408-416
-    out[size - 3] = (u8)((checksum >> 16) + (BT_CRC << 6)); out[size - 2] = (u8)(checksum >> 8); out[size - 1] = (u8)checksum;
-    results[f] = (size_t)size;
+    const size_t r = fw_result(b0, b1, pos, cres, maxBlocks);
+    if (!is_err(r)) fw_ends(dst + dstOff[f], r, hashes[f], bsid, codec);
+    results[f] = r;
+}
+// the packed writer, per frame: k_fw_verdict's result without the capacity test into fsize, and what the frame takes of the destination -- its
+// size rounded up to the slot alignment, 0 for a frame that fails -- into slots (scanned in place afterwards: the destination offsets)
+__global__ void k_fw_sizes(size_t* fsize, u64* slots, const u64* first, const u64* pos, const size_t* cres, size_t nFrames, size_t maxBlocks, u32 alignLog)
+{
+    const size_t f = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= nFrames) return;
+    const size_t r = fw_result(first[f], first[f + 1], pos, cres, maxBlocks);
+    fsize[f] = r;
+    const u64 a = ((u64)1 << alignLog) - 1;
+    slots[f] = is_err(r) ? 0 : ((u64)r + a) & ~a;
+}
+// ... and behind the scan and the clamp: a frame whose slot holds it gets its size, magic and trailer (dst == nullptr: the size alone), one
+// whose slot the capacity cut short dstSize_tooSmall
+__global__ void k_fw_place(u8* dst, const u64* dstOff, size_t* results, const size_t* fsize, const u32* hashes, size_t nFrames, u32 bsid, int codec)
+{
+    const size_t f = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= nFrames) return;
+    size_t r = fsize[f];
+    if (!is_err(r)) {
+        if (dstOff[f + 1] - dstOff[f] < (u64)r) r = FERR(dstSize_tooSmall);
+        else if (dst) fw_ends(dst + dstOff[f], r, hashes[f], bsid, codec);
+    }
+    results[f] = r;
 }
 // one workgroup per block: its header and record at its place in its frame (frame.hip:163-174)
 __global__ __launch_bounds__(FD_THREADS) void k_fw_assemble(u8* dst, const u64* dstOff, const size_t* results, const u8* src, const u64* blkOff, const u32* blkFrame,
@@ -288,8 +326,9 @@ __global__ __launch_bounds__(FD_THREADS) void k_fw_assemble(u8* dst, const u64* 
     else if (bt == BT_COMPRESSED) fd_copy(out + hdr, slots + g * slotStride, r, tid, -1);
 }
 
-struct FwLayout { size_t first, hashes, blkOff, blkFrame, cres, pos, partials, slots, codec, total, slotStride, codecBytes; };
-FwLayout fw_layout(size_t nFrames, size_t maxBlocks, unsigned bsid, int codec)
+struct FwLayout { size_t first, hashes, blkOff, blkFrame, cres, pos, partials, slots, codec, fsize, total, slotStride, codecBytes; };
+// packed: the packed writer's layout -- the fixed-slot one with the frames' results behind it
+FwLayout fw_layout(size_t nFrames, size_t maxBlocks, unsigned bsid, int codec, bool packed = false)
 {
     FwLayout L; size_t p = 0;
     auto carve = [&](size_t bytes) { const size_t r = p; p += up256(bytes); return r; };
@@ -300,6 +339,7 @@ FwLayout fw_layout(size_t nFrames, size_t maxBlocks, unsigned bsid, int codec)
     L.blkOff = carve((maxBlocks + 1) * 8); L.blkFrame = carve(maxBlocks * 4); L.cres = carve(maxBlocks * 8); L.pos = carve((maxBlocks + 1) * 8);
     L.partials = carve(scan_partials(nFrames > maxBlocks ? nFrames : maxBlocks) * 8);
     L.slots = carve(maxBlocks * L.slotStride); L.codec = carve(L.codecBytes);
+    L.fsize = packed ? carve((nFrames + 1) * 8) : 0;
     L.total = p;
     return L;
 }
@@ -600,6 +640,37 @@ extern "C" size_t FSEHIP_frame_compress_dbatch_workspaceSize(size_t nFrames, siz
     return fw_layout(nFrames, maxTotalBlocks, blockSizeId, codec).total;
 }
 
+// the writer up to the record positions: block counts and their scan (`first`), the trailers' hashes, every block of every content through the
+// one-shot coder into its workspace slot (`cres`), the records' lengths and their scan (`pos`) -- all in the workspace
+static int fw_encode(const u8* src, const u64* srcOff, size_t nFrames, size_t nb, u32 bsLog, int codec, u8* ws, const FwLayout& L, hipStream_t s)
+{
+    u64* const first = (u64*)(ws + L.first); u32* const hashes = (u32*)(ws + L.hashes);
+    u64* const blkOff = (u64*)(ws + L.blkOff); u32* const blkFrame = (u32*)(ws + L.blkFrame);
+    size_t* const cres = (size_t*)(ws + L.cres); u64* const pos = (u64*)(ws + L.pos); u64* const partials = (u64*)(ws + L.partials);
+    u8* const slots = ws + L.slots;
+    hipLaunchKernelGGL(k_fw_counts, dim3(grid_for(nFrames)), dim3(FD_THREADS), 0, s, first, srcOff, nFrames, bsLog);
+    CKE(launch_exscan(first, nFrames, partials, s));
+    CKE(launch_xxh32(hashes, src, srcOff, nullptr, nFrames, 0, s));
+    if (nb) {
+        hipLaunchKernelGGL(k_fw_blocks, dim3(grid_for(nb + 1)), dim3(FD_THREADS), 0, s, blkOff, blkFrame, (const u64*)first, srcOff, nFrames, nb, bsLog);
+        CKE(hipGetLastError());
+        BlockView v; v.base = src; v.stride = 0; v.sizes = nullptr; v.uniform = 0; v.offsets = blkOff;
+        // every block of every content in one call of the one-shot coder (frame.hip:118-119: default table logs, alphabet 255, slot = capacity)
+        if (codec == 1) CKI(huf_compress_view(4, slots, L.slotStride, L.slotStride, cres, v, 255, FSEHIP_HUF_TABLELOG_DEFAULT, nb, ws + L.codec, L.codecBytes, s));
+        else CKI(fse_compress_view(slots, L.slotStride, L.slotStride, cres, v, 255, FSEHIP_FSE_DEFAULT_TABLELOG, nb, ws + L.codec, L.codecBytes, s));
+        hipLaunchKernelGGL(k_fw_lens, dim3(grid_for(nb)), dim3(FD_THREADS), 0, s, pos, (const size_t*)cres, (const u64*)blkOff, (const u32*)blkFrame, nb, bsLog);
+        CKE(launch_exscan(pos, nb, partials, s));
+    }
+    return (int)hipGetLastError();
+}
+// ... and behind the frames' verdicts: every block's header and record at its place
+static int fw_assemble(u8* dst, const u64* dstOff, const size_t* results, const u8* src, size_t nb, u32 bsLog, u8* ws, const FwLayout& L, hipStream_t s)
+{
+    if (nb) hipLaunchKernelGGL(k_fw_assemble, dim3((unsigned)nb), dim3(FD_THREADS), 0, s, dst, dstOff, results, src, (const u64*)(ws + L.blkOff), (const u32*)(ws + L.blkFrame),
+                               (const u64*)(ws + L.first), (const u64*)(ws + L.pos), (const size_t*)(ws + L.cres), (const u8*)(ws + L.slots), L.slotStride, bsLog);
+    return (int)hipGetLastError();
+}
+
 extern "C" int FSEHIP_frame_compress_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_src, const uint64_t* d_srcOffsets,
                                             size_t nFrames, size_t maxTotalBlocks, unsigned blockSizeId, int codec,
                                             void* d_workspace, size_t workspaceBytes, void* stream)
@@ -612,32 +683,55 @@ extern "C" int FSEHIP_frame_compress_dbatch(void* d_dst, const uint64_t* d_dstOf
     const FwLayout L = fw_layout(nFrames, maxTotalBlocks, blockSizeId, codec);
     if (workspaceBytes < L.total) return (int)hipErrorInvalidValue;
     u8* const ws = (u8*)d_workspace;
-    u64* const first = (u64*)(ws + L.first); u32* const hashes = (u32*)(ws + L.hashes);
-    u64* const blkOff = (u64*)(ws + L.blkOff); u32* const blkFrame = (u32*)(ws + L.blkFrame);
-    size_t* const cres = (size_t*)(ws + L.cres); u64* const pos = (u64*)(ws + L.pos); u64* const partials = (u64*)(ws + L.partials);
-    u8* const slots = ws + L.slots;
     const u64* const srcOff = (const u64*)d_srcOffsets; const u64* const dstOff = (const u64*)d_dstOffsets;
     const u32 bsLog = 10 + blockSizeId;
     const size_t nb = maxTotalBlocks;
+    CKI(fw_encode((const u8*)d_src, srcOff, nFrames, nb, bsLog, codec, ws, L, s));
+    hipLaunchKernelGGL(k_fw_verdict, dim3(grid_for(nFrames)), dim3(FD_THREADS), 0, s, (u8*)d_dst, dstOff, d_results, srcOff, (const u64*)(ws + L.first), (const u64*)(ws + L.pos),
+                       (const size_t*)(ws + L.cres), (const u32*)(ws + L.hashes), nFrames, nb, blockSizeId, codec);
+    return fw_assemble((u8*)d_dst, dstOff, (const size_t*)d_results, (const u8*)d_src, nb, bsLog, ws, L, s);
+}
 
-    hipLaunchKernelGGL(k_fw_counts, dim3(grid_for(nFrames)), dim3(FD_THREADS), 0, s, first, srcOff, nFrames, bsLog);
-    CKE(launch_exscan(first, nFrames, partials, s));
-    CKE(launch_xxh32(hashes, (const u8*)d_src, srcOff, nullptr, nFrames, 0, s));
-    if (nb) {
-        hipLaunchKernelGGL(k_fw_blocks, dim3(grid_for(nb + 1)), dim3(FD_THREADS), 0, s, blkOff, blkFrame, (const u64*)first, srcOff, nFrames, nb, bsLog);
-        CKE(hipGetLastError());
-        BlockView v; v.base = (const u8*)d_src; v.stride = 0; v.sizes = nullptr; v.uniform = 0; v.offsets = blkOff;
-        // every block of every content in one call of the one-shot coder (frame.hip:118-119: default table logs, alphabet 255, slot = capacity)
-        if (codec == 1) CKI(huf_compress_view(4, slots, L.slotStride, L.slotStride, cres, v, 255, FSEHIP_HUF_TABLELOG_DEFAULT, nb, ws + L.codec, L.codecBytes, s));
-        else CKI(fse_compress_view(slots, L.slotStride, L.slotStride, cres, v, 255, FSEHIP_FSE_DEFAULT_TABLELOG, nb, ws + L.codec, L.codecBytes, s));
-        hipLaunchKernelGGL(k_fw_lens, dim3(grid_for(nb)), dim3(FD_THREADS), 0, s, pos, (const size_t*)cres, (const u64*)blkOff, (const u32*)blkFrame, nb, bsLog);
-        CKE(launch_exscan(pos, nb, partials, s));
+extern "C" size_t FSEHIP_frame_packedBound(size_t totalSrcBytes, size_t nFrames, size_t totalBlocks, unsigned slotAlignLog)
+{
+    if (slotAlignLog > 12) return FSEHIP_ERROR(GENERIC);
+    return totalSrcBytes + 8 * nFrames + 5 * totalBlocks + nFrames * (((size_t)1 << slotAlignLog) - 1);
+}
+
+extern "C" size_t FSEHIP_frame_compress_packed_dbatch_workspaceSize(size_t nFrames, size_t maxTotalBlocks, unsigned blockSizeId, int codec)
+{
+    if (blockSizeId > MAX_BSID || (codec != 0 && codec != 1)) return FSEHIP_ERROR(GENERIC);
+    return fw_layout(nFrames, maxTotalBlocks, blockSizeId, codec, true).total;
+}
+
+extern "C" int FSEHIP_frame_compress_packed_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_dstOffsets, size_t* d_results, const void* d_src,
+                                                   const uint64_t* d_srcOffsets, size_t nFrames, size_t maxTotalBlocks, unsigned blockSizeId, int codec,
+                                                   unsigned slotAlignLog, void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (blockSizeId > MAX_BSID || (codec != 0 && codec != 1) || slotAlignLog > 12) return (int)hipErrorInvalidValue;
+    if ((uintptr_t)d_workspace & 255u) return (int)hipErrorInvalidValue;
+    if (maxTotalBlocks >= ((size_t)1 << 31) || nFrames >= ((size_t)1 << 31)) return (int)hipErrorInvalidValue;
+    const FwLayout L = fw_layout(nFrames, maxTotalBlocks, blockSizeId, codec, true);
+    if (workspaceBytes < L.total) return (int)hipErrorInvalidValue;
+    u8* const ws = (u8*)d_workspace;
+    const u64* const srcOff = (const u64*)d_srcOffsets; u64* const dstOff = (u64*)d_dstOffsets;
+    size_t* const fsize = (size_t*)(ws + L.fsize);
+    const u32 bsLog = 10 + blockSizeId;
+    const size_t nb = maxTotalBlocks;
+    if (nFrames) {
+        CKI(fw_encode((const u8*)d_src, srcOff, nFrames, nb, bsLog, codec, ws, L, s));
+        hipLaunchKernelGGL(k_fw_sizes, dim3(grid_for(nFrames)), dim3(FD_THREADS), 0, s, fsize, dstOff, (const u64*)(ws + L.first), (const u64*)(ws + L.pos),
+                           (const size_t*)(ws + L.cres), nFrames, nb, (u32)slotAlignLog);
     }
-    hipLaunchKernelGGL(k_fw_verdict, dim3(grid_for(nFrames)), dim3(FD_THREADS), 0, s, (u8*)d_dst, dstOff, d_results, srcOff, (const u64*)first, (const u64*)pos,
-                       (const size_t*)cres, (const u32*)hashes, nFrames, nb, blockSizeId, codec);
-    if (nb) hipLaunchKernelGGL(k_fw_assemble, dim3((unsigned)nb), dim3(FD_THREADS), 0, s, (u8*)d_dst, dstOff, (const size_t*)d_results, (const u8*)d_src,
-                               (const u64*)blkOff, (const u32*)blkFrame, (const u64*)first, (const u64*)pos, (const size_t*)cres, (const u8*)slots, L.slotStride, bsLog);
-    return (int)hipGetLastError();
+    CKE(launch_exscan(dstOff, nFrames, (u64*)(ws + L.partials), s));
+    hipLaunchKernelGGL(k_fr_clamp, dim3(grid_for(nFrames + 1)), dim3(FD_THREADS), 0, s, dstOff, nFrames + 1, (u64)dstCapacity);
+    CKE(hipGetLastError());
+    if (nFrames == 0) return 0;
+    hipLaunchKernelGGL(k_fw_place, dim3(grid_for(nFrames)), dim3(FD_THREADS), 0, s, (u8*)d_dst, (const u64*)dstOff, d_results, (const size_t*)fsize,
+                       (const u32*)(ws + L.hashes), nFrames, blockSizeId, codec);
+    if (!d_dst) return (int)hipGetLastError();               // the sizing query: offsets and results, no frame
+    return fw_assemble((u8*)d_dst, (const u64*)dstOff, (const size_t*)d_results, (const u8*)d_src, nb, bsLog, ws, L, s);
 }
 
 extern "C" size_t FSEHIP_frame_decompress_dbatch_workspaceSize(size_t nFrames, size_t maxTotalBlocks) { return fr_layout(nFrames, maxTotalBlocks).total; }

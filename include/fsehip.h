@@ -463,6 +463,27 @@ FSEHIP_API size_t FSEHIP_frame_decompress_batch(void* const* dsts, const size_t*
  *     Memory: reads the contents; writes exactly the bytes of every frame that succeeds -- nothing into the slot of a frame that fails,
  *     nothing behind a frame's last byte.
  *
+ *   FSEHIP_frame_packedBound   host arithmetic (works without a device): totalSrcBytes + 8 * nFrames + 5 * totalBlocks + nFrames *
+ *     ((1 << slotAlignLog) - 1), a dstCapacity of the packed writer at which no frame fails for lack of room (every frame at its
+ *     FSEHIP_frame_compressBound plus its padding).  slotAlignLog > 12: GENERIC.
+ *
+ *   FSEHIP_frame_compress_packed_dbatch   the writer above with the frames BACK TO BACK at their real sizes: d_dstOffsets is an OUTPUT
+ *     (nFrames + 1 entries).  size_i = what FSEHIP_frame_compress returns for content i at a capacity of FSEHIP_frame_compressBound, byte for
+ *     byte the same frame; where that is an error (a block coder's, passed on as it is; GENERIC for a frame whose blocks do not all lie
+ *     inside maxTotalBlocks) d_results[i] is that error and the frame takes 0 bytes.  With U[i] = sum over j < i of roundup(size_j,
+ *     1 << slotAlignLog):  d_dstOffsets[i] = min(U[i], dstCapacity) -- the clamping rule of FSEHIP_frame_plan_dbatch; a frame that does not
+ *     fit still counts with its size, so d_dstOffsets[nFrames] = min(packed total, dstCapacity).  Frame i is written at d_dst +
+ *     d_dstOffsets[i] and d_results[i] = size_i if its slot d_dstOffsets[i+1] - d_dstOffsets[i] holds size_i bytes; otherwise d_results[i] =
+ *     dstSize_tooSmall and no byte of it is written.  d_dst == NULL with dstCapacity = UINT64_MAX is the sizing query: offsets and results
+ *     are produced and nothing else is written -- the contents are still CODED (a frame's size is not known otherwise), so the query costs
+ *     what the call costs less the copy of the records.  nFrames == 0 writes d_dstOffsets[0] = 0; maxTotalBlocks == 0 is legal (empty
+ *     contents still give their 8-byte frames); slotAlignLog > 12: hipErrorInvalidValue, like the other bad arguments, and nothing written.
+ *     Memory: reads the contents; writes exactly the bytes of the frames that succeed -- not the padding between frames, nothing into the
+ *     slot of a frame that fails, nothing at or behind d_dst + dstCapacity.
+ *     The offsets are directly usable as d_frameOffsets of FSEHIP_frame_decompress_packed_dbatch (and of the other readers), for every
+ *     slotAlignLog: a reader's header walk stops at the frame's end mark, so the unwritten padding behind a frame is never interpreted.
+ *     Writer and reader thus chain on one stream, or in one graph, without a byte or a size leaving the device.
+ *
  *   FSEHIP_frame_decompress_dbatch   (FIO_decompressFilename, fileio.c:462-626, over many frames)
  *     frame i = d_frames[d_frameOffsets[i] .. d_frameOffsets[i+1]), regenerated at d_dst + d_dstOffsets[i], capacity d_dstOffsets[i+1] -
  *     d_dstOffsets[i].  Frames describe themselves: codecs and block-size ids may differ inside one call.  d_results[i] = what
@@ -523,6 +544,12 @@ FSEHIP_API size_t FSEHIP_frame_compress_dbatch_workspaceSize(size_t nFrames, siz
 FSEHIP_API int FSEHIP_frame_compress_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_src, const uint64_t* d_srcOffsets,
                                             size_t nFrames, size_t maxTotalBlocks, unsigned blockSizeId, int codec,
                                             void* d_workspace, size_t workspaceBytes, void* stream);
+FSEHIP_API size_t FSEHIP_frame_packedBound(size_t totalSrcBytes, size_t nFrames, size_t totalBlocks, unsigned slotAlignLog);
+FSEHIP_API size_t FSEHIP_frame_compress_packed_dbatch_workspaceSize(size_t nFrames, size_t maxTotalBlocks, unsigned blockSizeId, int codec);
+FSEHIP_API int FSEHIP_frame_compress_packed_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_dstOffsets, size_t* d_results,
+                                                   const void* d_src, const uint64_t* d_srcOffsets, size_t nFrames, size_t maxTotalBlocks,
+                                                   unsigned blockSizeId, int codec, unsigned slotAlignLog,
+                                                   void* d_workspace, size_t workspaceBytes, void* stream);
 FSEHIP_API size_t FSEHIP_frame_decompress_dbatch_workspaceSize(size_t nFrames, size_t maxTotalBlocks);
 FSEHIP_API int FSEHIP_frame_decompress_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_frames, const uint64_t* d_frameOffsets,
                                               size_t nFrames, size_t maxTotalBlocks, void* d_workspace, size_t workspaceBytes, void* stream);

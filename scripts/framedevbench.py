@@ -2,6 +2,8 @@
 next to the host-buffer batch calls (FSEHIP_frame_compress_batch / _decompress_batch, pinned host memory, 4 threads) on the same contents.
   (a) 1024 frames of 1 MiB   (b) one frame of 256 MiB   (c) the checksum kernel alone on both shapes      P14, block-size id 5, both codecs
   (d) 100k frames of 4 KB, device calls only
+The writer runs in both forms: fixed slots of FSEHIP_frame_compressBound each (offsets in) and packed (FSEHIP_frame_compress_packed_dbatch,
+offsets out) -- "extra_ms" is the packed call minus the fixed-slot call of the same run.
 On every shape the frames are also read as frames of UNKNOWN size: the plan alone (FSEHIP_frame_plan_dbatch: header walk, two scans, clamp)
 and the packed call (FSEHIP_frame_decompress_packed_dbatch) beside the known-offset call on the same frames -- "extra_ms" is the packed call
 minus the known-offset call of the same run.
@@ -60,7 +62,19 @@ def device_side(shape, n_frames, frame_bytes):
     for codec, name in ((0, "fse"), (1, "huf")):
         cws = hip.frame_dbatch_workspace(n_frames, nblk, BSID, codec)
         w = lambda: hip.frame_compress_dbatch(src, soff, BSID, codec, dst=frames, dst_offsets=foff, max_total_blocks=nblk, workspace=cws, results=cres)
-        report(shape, "device write", name, total, timed(w), frame_bytes=int(cres.sum().item()))
+        fixed = timed(w)
+        report(shape, "device write", name, total, fixed, frame_bytes=int(cres.sum().item()))
+        # the packed writer on the same contents: frames back to back, offsets from the device -- "extra_ms" = packed minus fixed-slot, same run
+        hip.lib.FSEHIP_frame_compress_packed_dbatch_workspaceSize.restype = C.c_size_t
+        kws = torch.empty(int(hip.lib.FSEHIP_frame_compress_packed_dbatch_workspaceSize(C.c_size_t(n_frames), C.c_size_t(nblk), C.c_uint(BSID), C.c_int(codec))),
+                          dtype=torch.uint8, device="cuda")
+        kframes = torch.empty(hip.frame_packed_bound(total, n_frames, nblk, 0), dtype=torch.uint8, device="cuda")
+        koff = torch.zeros(n_frames + 1, dtype=torch.int64, device="cuda"); kres = torch.zeros_like(cres)
+        k = lambda: hip.frame_compress_packed_dbatch(src, soff, BSID, codec, dst=kframes, max_total_blocks=nblk, dst_offsets=koff, workspace=kws, results=kres)
+        tight = timed(k)
+        report(shape, "device write, packed (offsets out)", name, total, tight, frame_bytes=int(koff[-1].item()), extra_ms=round(tight - fixed, 3))
+        assert torch.equal(kres, cres) and int(koff[-1].item()) == int(cres.sum().item())
+        del kws, kframes
         # the reader is handed the frames packed back to back, as a file or a message would hold them
         sz = cres.cpu().numpy()
         assert (sz > 0).all()
