@@ -1,14 +1,18 @@
-"""Lane-exact CPU model of k_huf_decode_par (csrc/huf_decode_par.hip), single-symbol tables, 4X and 1X.
+"""Lane-exact CPU model of k_huf_decode_par (csrc/huf_decode_par.hip), single- and double-symbol tables, 4X and 1X.
 
 What it copies from the kernel: the block checks that decide serial or parallel (the jump table, stream lengths, the end mark, HPAR_MIN_BITS per
 stream -- and, on the one-shot path, k_huf_dprep's rule on the shortest stream, huf_prep.hip), the cursor geometry (Cend, Cstart, T0), the
 pieces of PDW dwords, the warm-up formula, every lane's S_j / E_j and symbol count, the repair rounds up to the hand-over at HPAR_MAX_REPAIR,
 the spill of a lane with more than HPAR_KEEP iterations and the piece verdict.  What it reports per block: serial or parallel (and why),
 per stream and piece the rounds, bad links and spills, the HPAR_STATS record (rounds and bad links summed over the streams) and, for a
-parallel block, the bytes it regenerates.  The code table is the reference's HUF_readDTableX1 (u32 words, lib/huf_decompress.c:118-185).
+parallel block, the bytes it regenerates.  The code table is the reference's HUF_readDTableX1 (u32 words, lib/huf_decompress.c:118-185) or,
+with `accept_x2` (the HUF_decompress4X / 1X_usingDTable batches), its HUF_readDTableX2 (:460-640): `derive_x2` restates, cell for cell, how the
+X2 instantiation derives single-symbol cells from a double-symbol table and every rule by which it declines one (X2_CLAUSES).
 
 Both budgets of the product take every parallel block with the 4.5 KiB class (HPAR_ALL_SMALL, HPAR_USE_TINY 0: internal.h), so the piece
-size is that class's.  `mut` names a deliberately broken variant (MUTANTS) for tests/test_repair_corpus.py.
+size is that class's; a block with a double-symbol table is taken by the X2 launch, an instantiation of the large class (HPAR_DATA_LARGE:
+pieces of 2120 dwords).  `mut` names a deliberately broken variant (MUTANTS) for tests/test_repair_corpus.py and
+tests/test_huf_x2_par_model.py.
 """
 import numpy as np
 
@@ -19,6 +23,21 @@ KEEP = 40                   # HPAR_KEEP (iterations of four symbols)
 MIN_BITS = 4096             # HPAR_MIN_BITS
 DATA_SMALL = 4608           # HPAR_DATA_SMALL
 PDW = DATA_SMALL // 4 - 24  # dwords of a piece
+DATA_LARGE = 8192 + 384     # HPAR_DATA_LARGE: the X2 launch
+PDW_X2 = DATA_LARGE // 4 - 24
+
+# the rules a double-symbol table must keep to be decoded through derived single-symbol cells, in the order derive_x2 reports them
+X2_CLAUSES = {
+    "runs": "the cells that begin with one symbol form ONE run",
+    "pow2_aligned": "a run's length is a power of two and the run starts on a multiple of it",
+    "n_lt_ts": "a run is shorter than the table (n < ts: no code of zero bits)",
+    "len_1_or_2": "a cell's length field is 1 or 2",
+    "len1_bits": "a one-symbol cell consumes the bits of its symbol",
+    "second_present": "the second symbol of a two-symbol cell begins some cell",
+    "len2_bits": "a two-symbol cell consumes the bits of its two symbols together",
+    "nbtot_le_log": "a two-symbol cell consumes at most tableLog bits",
+    "second_follows": "the second symbol is the first symbol of what follows the first code",
+}
 
 MUTANTS = {
     "trust_S_after_round0": "a lane repaired in round 1 is trusted: links are not checked again",
@@ -29,7 +48,10 @@ MUTANTS = {
     "min_bits_le": "a stream of exactly HPAR_MIN_BITS bits goes to the serial decoder",
     "warm_unclamped": "the warm-up is not clamped to 48 .. 192 bits",
     "no_pieces": "a stream is never cut into pieces",
+    "x2_small_pieces": "a block with a double-symbol table is cut into the lean launch's pieces of 1128 dwords",
+    "x2_len_from_cell": "the derived single-symbol cell takes the double-symbol cell's nbBits, not the length of its first symbol's run",
 }
+MUTANTS.update({"x2_no_" + k: "double-symbol tables, rule dropped: " + v for k, v in X2_CLAUSES.items()})
 
 
 def hibit(v):
@@ -71,8 +93,46 @@ class Stream:
         return out
 
 
-def simulate_block(payload, dt, dst_size, streams=4, oneshot=False, max_table_log=12, decode=True, mut=None):
-    """payload: the block without its header (jump table + streams, or the one stream of 1X); dt: the reference's DTable (u32 words)"""
+def derive_x2(dt, mut=None):
+    """huf_decode_par.hip:347-421 on the reference's double-symbol DTable (u32 words, cell = s1 | s2 << 8 | nbBits << 16 | length << 24):
+    (accept, the first rule of X2_CLAUSES the table breaks or None, the single-symbol cells s1 | len(s1) << 8 in table order or None)"""
+    dt = np.asarray(dt, dtype=np.uint32)
+    dtLog = (int(dt[0]) >> 16) & 0xFF
+    ts = 1 << dtLog
+    c = dt[1:1 + ts].astype(np.int64)
+    s1, s2, nbTot, ln = c & 0xFF, (c >> 8) & 0xFF, (c >> 16) & 0xFF, c >> 24
+    drop = mut[6:] if mut and mut.startswith("x2_no_") else None
+    # runs at their boundaries: a count per first symbol, where its (last) run starts and where the run in front of a boundary ended
+    starts = np.nonzero(np.concatenate([[True], s1[1:] != s1[:-1]]))[0]
+    cnt = np.bincount(s1[starts], minlength=256)
+    lo, hi = np.zeros(256, np.int64), np.zeros(256, np.int64)
+    lo[s1[starts]] = starts                                             # (several runs of one symbol: the last one's, as stores in index order leave it)
+    hi[s1[starts]] = np.concatenate([starts[1:] - 1, [ts - 1]])
+    n = hi - lo + 1
+    nbs = np.full(256, 0xFF, np.int64)
+    present = cnt > 0
+    for name, broken in (("runs", present & (cnt != 1)),
+                         ("pow2_aligned", present & (((n & (n - 1)) != 0) | ((lo & (n - 1)) != 0))),
+                         ("n_lt_ts", present & (n >= ts))):
+        if name != drop and broken.any():
+            return False, name, None
+    for sy in np.nonzero(present)[0]:
+        nbs[sy] = dtLog - hibit(max(int(n[sy]), 1))
+    n1, n2 = nbs[s1], nbs[s2]
+    one, two = ln == 1, ln == 2
+    for name, broken in (("len_1_or_2", ~(one | two)), ("len1_bits", one & (nbTot != n1)), ("second_present", two & (n2 == 0xFF)),
+                         ("len2_bits", two & (nbTot != n1 + n2)), ("nbtot_le_log", two & (nbTot > dtLog))):
+        if name != drop and broken.any():
+            return False, name, None
+    j = (np.arange(ts, dtype=np.int64) << np.minimum(n1, 32)) & (ts - 1)    # what follows the first code, zero-extended
+    if drop != "second_follows" and (two & (s1[j] != s2)).any():
+        return False, "second_follows", None
+    return True, None, s1 | ((nbTot if mut == "x2_len_from_cell" else n1) << 8)
+
+
+def simulate_block(payload, dt, dst_size, streams=4, oneshot=False, max_table_log=12, decode=True, mut=None, accept_x2=False):
+    """payload: the block without its header (jump table + streams, or the one stream of 1X); dt: the reference's DTable (u32 words);
+    accept_x2: the call is HUF_decompress4X / 1X_usingDTable's batch, which takes double-symbol tables (never the one-shot path)"""
     payload = np.ascontiguousarray(payload, dtype=np.uint8)
     dt = np.asarray(dt, dtype=np.uint32)
     desc = int(dt[0])
@@ -91,7 +151,8 @@ def simulate_block(payload, dt, dst_size, streams=4, oneshot=False, max_table_lo
         if not (nS == 4 and cSize >= 10 and dst_size >= 64 and used < cSize and 8 * min(lens[:3] + [cSize - used]) >= MIN_BITS + 8):
             rec["reason"] = "prep"
             return rec
-    ok = tableType == 0 and 1 <= dtLog <= ldsLog and dtLog <= max_table_log and 10 <= cSize < (1 << 28) and 64 <= dst_size < (1 << 28)
+    x2 = tableType == 1 and accept_x2 and not oneshot
+    ok = (tableType == 0 or x2) and 1 <= dtLog <= ldsLog and dtLog <= max_table_log and 10 <= cSize < (1 << 28) and 64 <= dst_size < (1 << 28)
     if ok and nS == 4:
         used = 6 + sum(lens[:3])
         if used > cSize:
@@ -118,12 +179,22 @@ def simulate_block(payload, dt, dst_size, streams=4, oneshot=False, max_table_lo
     if not ok:
         rec["reason"] = "block"
         return rec
-    cells = dt[1:1 + (1 << dtLog) // 2].view(np.uint16)[:1 << dtLog].astype(np.int64)
-    nbc = cells >> 8
-    if ((nbc < 1) | (nbc > dtLog)).any():
-        rec["reason"] = "table"
-        return rec
+    if x2:
+        acc, rec["clause"], cells = derive_x2(dt, mut)
+        if not acc:
+            rec["reason"] = "table"
+            return rec
+        if ((cells >> 8) < 1).any():                                     # (only a mutant gets here: a code of zero bits pins every cursor)
+            rec.update(entered=True, reason="hang")
+            return rec
+    else:
+        cells = dt[1:1 + (1 << dtLog) // 2].view(np.uint16)[:1 << dtLog].astype(np.int64)
+        nbc = cells >> 8
+        if ((nbc < 1) | (nbc > dtLog)).any():
+            rec["reason"] = "table"
+            return rec
     rec["entered"] = True
+    pdw = PDW_X2 if x2 and mut != "x2_small_pieces" else PDW
     out = np.zeros(dst_size, np.uint8) if decode else None
     p = jump
     good = True
@@ -144,7 +215,7 @@ def simulate_block(payload, dt, dst_size, streams=4, oneshot=False, max_table_lo
         while good and Cstart < Cend:
             mTop = (Cstart - 1) >> 5
             rest = Sd - mTop
-            nPc = 1 if mut == "no_pieces" else (rest + PDW - 1) // PDW
+            nPc = 1 if mut == "no_pieces" else (rest + pdw - 1) // pdw
             nd = rest if nPc <= 1 else (rest + nPc - 1) // nPc
             lastPiece = mTop + nd == Sd
             C0 = Cstart

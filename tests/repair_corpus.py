@@ -445,7 +445,8 @@ def huf_device_batch(entries, torch, payloads=None):
 def device_stats(what, out_path):
     """child process (FSEHIP_LIB = an instrumented build): run the corpus through the caller-table batches and save the device's
     records -- `enc` (FSE_ENC_TIMING: rounds, nBad0, firstBad of every wave) or `huf1` / `huf4` (HPAR_STATS: repair rounds and bad links
-    of every block), with the results and the bytes"""
+    of every block), with the results and the bytes; `x2_1` / `x2_4`: the same record for the device entries of tests/huf_x2_par_corpus.py
+    through HUF_decompress1X / 4X_usingDTable's batch.  The record is a device global that nothing zeroes: ONE decoding call per process"""
     import ctypes
     import torch
     from finitestateentropy_amd.api import FseHip
@@ -466,9 +467,14 @@ def device_stats(what, out_path):
             save["g%d_dst" % gi] = dst.cpu().numpy()
     else:
         form = int(what[3:])
-        es = [e for e in huf_entries(orc) if e.form == form]
+        if what.startswith("x2_"):
+            import huf_x2_par_corpus as pc
+            es = [e for e in pc.build(orc.ref, orc) if e.form == form and not e.cpu_only]
+            fn = hip.huf_decompress1x_using_dtable_batch if form == 1 else hip.huf_decompress4x_using_dtable_batch
+        else:
+            es = [e for e in huf_entries(orc) if e.form == form]
+            fn = hip.huf_decompress1x1_using_dtable_batch if form == 1 else hip.huf_decompress4x1_using_dtable_batch
         c, cs, dt, ds = huf_device_batch(es, torch)
-        fn = hip.huf_decompress1x1_using_dtable_batch if form == 1 else hip.huf_decompress4x1_using_dtable_batch
         out, res = fn(c, cs, dt, ds)
         torch.cuda.synchronize()
         buf = np.zeros(4096 * 8, np.uint64)
