@@ -20,6 +20,8 @@
 // maxSV): the table is written straight to global memory, symbolTT entries coalesced, stateTable entries as scattered 2-byte stores inside the
 // block's 4 KiB (the L2 merges them) -- an LDS image would cost 6 KiB per build, i.e. occupancy.  Shared by k_fse_cprep (counters it has just
 // normalised) and k_fse_ctable_from_norm (the caller's counters: FSE_buildCTable as a call of its own).  Uses __syncthreads(): the workgroup is the wave.
+// MAXC: cells per lane the spread / rank core keeps in registers (fse_wave_build.h); the caller has checked 1 << tl <= 64 * MAXC.
+template <u32 MAXC>
 DEV void fse_wave_build_ctable(const WaveBuildLds& w, const int nn[4], u32 maxSV, u32 tl, u32* img, u32 lane)
 {
     u16* const cumAll = w.cumP;                                            // [256] first stateTable slot of every symbol (the core leaves cumP to its caller)
@@ -52,7 +54,7 @@ DEV void fse_wave_build_ctable(const WaveBuildLds& w, const int nn[4], u32 maxSV
         if (lane == 0) img[0] = tl | (maxSV << 16);
     }
     __syncthreads();
-    wave_spread_rank(w, maxSV, tl, lane, [&](u32 s) { return (u32)cumAll[s]; },
+    wave_spread_rank<MAXC>(w, maxSV, tl, lane, [&](u32 s) { return (u32)cumAll[s]; },
                      [&](u32 u, u32 s, u32 r, u32 first) { (void)s; stateTable[first + r] = (u16)(ts + u); });   // :125-133
 }
 
@@ -61,6 +63,9 @@ DEV void fse_wave_build_ctable(const WaveBuildLds& w, const int nn[4], u32 maxSV
 // header (wave_glue.h: every symbol handled independently, totals by wave reductions, bit offsets by scans), then
 // FSE_buildCTable_wksp (lib/fse_compress.c:66-169) with the wave-cooperative spread / rank of fse_wave_build.h.  The counters
 // never leave the wave's registers / LDS; the header is assembled in LDS and copied out once.
+// Two instantiations (launch_fse_cprep): MAXC = 32 cells per lane for a workspace of tableLog <= 11 (69 VGPRs: the LDS footprint decides how many
+// builds a CU runs), MAXC = 64 for tableLog 12 (113 VGPRs).
+template <u32 MAXC>
 __global__ __launch_bounds__(64) void k_fse_cprep(FseCPrepArgs a, u32 capTs)
 {
     extern __shared__ __attribute__((aligned(16))) u8 wbLds[];
@@ -76,13 +81,18 @@ __global__ __launch_bounds__(64) void k_fse_cprep(FseCPrepArgs a, u32 capTs)
     else if (top == n) result = 1;                                         // one symbol only: rle
     else if (top == 1 || top < (n >> 7)) result = 0;                       // every symbol once / too flat to pay off
     else go = true;
-    const WaveBuildLds w = wave_build_carve(wbLds, capTs);
+    const WaveBuildLds w = wave_build_carve(wbLds, capTs, true);
     u32* const hdrImg = w.cnt;                                             // header image; the rank matrix is idle until the build
     u32 maxSV = 0, tl = 0;
     int nn[4] = { 0, 0, 0, 0 };
     if (go) {
         maxSV = a.maxSVs[b];
         tl = wg_optimal_tablelog(a.tableLogReq, n, maxSV, 2);             // :649,658
+        // never more than tableLogReq <= maxTl, and the launcher picks MAXC by maxTl: a table this instantiation has no registers (and the
+        // launch no LDS) for cannot come up.  Uniform.
+        if ((1u << tl) > 64u * MAXC || (1u << tl) > capTs) { result = FERR(tableLog_tooLarge); go = false; }
+    }
+    if (go) {
         const uint4 cv = ((const uint4*)(a.counts + b * 256))[lane];       // symbols 4*lane .. 4*lane+3
         const u32 c[4] = { cv.x, cv.y, cv.z, cv.w };
         for (u32 i = lane; i < 136; i += 64) hdrImg[i] = 0;
@@ -115,7 +125,7 @@ __global__ __launch_bounds__(64) void k_fse_cprep(FseCPrepArgs a, u32 capTs)
     }
     m.tableLog = tl; m.maxSV = maxSV;
     if (lane == 0) a.meta[b] = m;
-    fse_wave_build_ctable(w, nn, maxSV, tl, a.ctables + b * a.ctStrideU32, lane);
+    fse_wave_build_ctable<MAXC>(w, nn, maxSV, tl, a.ctables + b * a.ctStrideU32, lane);
 }
 
 // Decompress side, two kernels:
@@ -125,29 +135,45 @@ __global__ __launch_bounds__(64) void k_fse_cprep(FseCPrepArgs a, u32 capTs)
 //   k_fse_dbuild : one wave per block -- FSE_buildDTable (lib/fse_decompress.c:71-126) with the wave-cooperative
 //                  spread / rank of fse_wave_build.h, emitting the decoder's compact cell formats (u16 cell, symbol in
 //                  a separate byte table; bit-reversed layout when maxLog <= 11, see fse_decode.hip) straight to global memory.
+// The wave first brings the head of its 64 headers into LDS (ncount_stage: every lane's loads in flight together, where the parser alone would
+// wait for memory once per field) and clears its 64 rows of counters -- one contiguous 32 KiB of a.norms -- with coalesced 16-byte stores; the
+// rows of blocks that are not parsed (raw / RLE records) are cleared with them, which nothing reads: k_fse_dbuild only looks at blocks on a list.
 __global__ __launch_bounds__(64) void k_fse_dparse(FseDPrepArgs a)
 {
-    const size_t b = (size_t)blockIdx.x * 64 + threadIdx.x;
+    __shared__ __attribute__((aligned(16))) u32 stage[NCS_WORDS];
+    const size_t b0 = (size_t)blockIdx.x * 64, b = b0 + threadIdx.x;
     const u32 lane = threadIdx.x;
+    const bool have = b < a.nBlocks;
+    const u8* const in = have ? view_ptr(a.csrc, b) : nullptr;
+    const size_t cSize = have ? view_size(a.csrc, b) : 0;
+    bool done = false;                                                     // a raw / RLE record of a packed batch: regenerated by k_rawrle_expand, result written there
+    if (have && a.rawRle) { const size_t orig = a.origSizes ? a.origSizes[b] : a.uniformOrig; done = cSize == orig || cSize == 1; }
+    const u32 staged = ncount_stage(stage, in, cSize, lane, have && !done);
+    {   uint4* const rows = (uint4*)(a.norms + b0 * 256);                  // (a.norms is 256-byte aligned, a row 512 bytes)
+        const u32 nRows = a.nBlocks - b0 < 64 ? (u32)(a.nBlocks - b0) : 64u;
+        for (u32 i = lane; i < nRows * 32u; i += 64) rows[i] = make_uint4(0, 0, 0, 0);
+    }
+    __syncthreads();                                                       // every lane's zeros are ordered before the counters another lane stores to the same row
     int cls = -1;                                                          // decoder class of my block (-1: none / finished here)
-    if (b < a.nBlocks) {
+    if (have) {
         FseMeta m; m.state = 0; m.hdrSize = 0; m.tableLog = 0; m.maxSV = 0; m.pace = 0; m.pace = 0;
-        const u8* const in = view_ptr(a.csrc, b);
-        const size_t cSize = view_size(a.csrc, b);
         size_t result = 0;
-        bool done = false;                                                 // a raw / RLE record of a packed batch: regenerated by k_rawrle_expand, result written there
-        if (a.rawRle) { const size_t orig = a.origSizes ? a.origSizes[b] : a.uniformOrig; done = cSize == orig || cSize == 1; }
         if (!done) do {
             u32 tl = 0, maxSV = 255;
             s16* const norm = a.norms + b * 256;
-            const size_t h = ncount_read<1>(norm, &maxSV, &tl, in, cSize);     // fse_decompress.c:264
+            const size_t h = ncount_read_staged(norm, &maxSV, &tl, stage + lane, staged, in, cSize);     // fse_decompress.c:264
             if (is_err(h)) { result = h; break; }
             if (tl > a.maxLog) { result = FERR(tableLog_tooLarge); break; }    // :266
             // class by the block's own tableLog (internal.h); a counter above half the table makes cells with nbBits == 0
             cls = FSE_DCLS_REV11;
             if (tl > FSE_DEC_FAST_MAXLOG) {
-                int top = 0;
-                for (u32 s = 0; s <= maxSV; ++s) top = norm[s] > top ? norm[s] : top;
+                int top = 0;                                               // (eight counters per load; the row is zero beyond maxSV)
+                for (u32 i = 0; i <= maxSV >> 3; ++i) {
+                    const uint4 v = ((const uint4*)norm)[i];
+                    const u32 q[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) { const int lo = (s16)(q[k] & 0xFFFFu), hi = (s16)(q[k] >> 16); top = lo > top ? lo : top; top = hi > top ? hi : top; }
+                }
                 cls = 2 * top > (1 << tl) ? FSE_DCLS_PLAIN : FSE_DCLS_REV12;
             }
             m.state = 1u | ((u32)cls << 2); m.hdrSize = (u32)h; m.tableLog = tl; m.maxSV = maxSV;
@@ -176,6 +202,8 @@ __global__ __launch_bounds__(64) void k_fse_dparse(FseDPrepArgs a)
 
 // Workgroup w builds the w-th block of the class lists [firstList, firstList + nLists) taken one after the other (the lists sit
 // `nBlocks` entries apart; their lengths are device-side, so the grid is sized for the worst case and the surplus exits).
+// MAXC = 32 for a launch whose tables have at most 2048 cells (ldsCapTs: the launch of the tableLog <= 11 class), 64 otherwise.
+template <u32 MAXC>
 __global__ __launch_bounds__(64) void k_fse_dbuild(FseDPrepArgs a, u32 capTs, int firstList, int nLists, u32 ldsCapTs)
 {
     extern __shared__ __attribute__((aligned(16))) u8 wbLds[];
@@ -209,14 +237,20 @@ __global__ __launch_bounds__(64) void k_fse_dbuild(FseDPrepArgs a, u32 capTs, in
     const u32 lane = threadIdx.x;
     const FseMeta m = a.meta[b];
     if (m.state == 0) return;                                              // uniform
-    const WaveBuildLds w = wave_build_carve(wbLds, ldsCapTs);
+    const u32 tl = m.tableLog, ts = 1u << tl;
+    // the class lists keep every block out of a launch with less LDS / fewer registers than its table needs (k_fse_dparse files by tableLog);
+    // should one get here all the same, it fails instead of writing past either.  Uniform.
+    if (ts > ldsCapTs || ts > 64u * MAXC) {
+        if (lane == 0) { a.meta[b].state = 0; a.results[b] = FERR(tableLog_tooLarge); }
+        return;
+    }
+    const WaveBuildLds w = wave_build_carve(wbLds, ldsCapTs, false);      // (no cumP: the decoding table has no use for it)
     *(uint2*)(w.nrm + 4 * lane) = *(const uint2*)(a.norms + b * 256 + 4 * lane);
     __syncthreads();
-    const u32 tl = m.tableLog, ts = 1u << tl;
     const bool rev = ((m.state >> 2) & 3u) != FSE_DCLS_PLAIN;              // uniform
     u16* const A = a.atab + b * capTs;
     u8* const S = a.symtab + b * capTs;
-    const bool fast = wave_spread_rank(w, m.maxSV, tl, lane, [&](u32 s) { return (u32)(int)w.nrm[s]; }, [&](u32 u, u32 s, u32 r, u32 nrm) {
+    const bool fast = wave_spread_rank<MAXC>(w, m.maxSV, tl, lane, [&](u32 s) { return (u32)(int)w.nrm[s]; }, [&](u32 u, u32 s, u32 r, u32 nrm) {
         const int n = (int)nrm;
         const u32 next = (n > 0 ? (u32)n : 1u) + r;                        // symbolNext[s]++, fse_decompress.c:117-122
         const u32 nb = tl - hibit32(next);
@@ -283,6 +317,7 @@ DEV size_t fse_norm_load_checked(int nn[4], const s16* nb, u32 maxSV, u32 tl, u3
     cells = wg_sum<64>(cells);
     return (wg_any<64>(bad, lane) || cells != (1u << tl)) ? FERR(GENERIC) : 0;
 }
+template <u32 MAXC>
 __global__ __launch_bounds__(64) void k_fse_ctable_from_norm(const s16* norms, size_t normStride, const u32* maxSVs, u32 tl, u32* ctables, size_t ctStrideU32,
                                                             size_t* results, u32 capTs)
 {
@@ -291,19 +326,42 @@ __global__ __launch_bounds__(64) void k_fse_ctable_from_norm(const s16* norms, s
     const u32 lane = threadIdx.x;
     const u32 maxSV = maxSVs[b];
     int nn[4] = { 0, 0, 0, 0 };
-    const size_t r = fse_norm_load_checked(nn, norms + b * normStride, maxSV, tl, FSE_MAX_TL, lane);
+    static_assert(MAXC == 32 || MAXC == 64, "64 * MAXC cells = a table of tableLog 11 or 12");
+    // (the launcher instantiates MAXC = 32 for tl <= 11 only, so the bound below is FSE_MAX_TL's whenever it can be reached)
+    const size_t r = fse_norm_load_checked(nn, norms + b * normStride, maxSV, tl, MAXC == 32 ? 11u : FSE_MAX_TL, lane);
     if (lane == 0) results[b] = r;
     if (is_err(r)) return;                                                 // uniform
-    fse_wave_build_ctable(wave_build_carve(wbLds, capTs), nn, maxSV, tl, ctables + b * ctStrideU32, lane);
+    fse_wave_build_ctable<MAXC>(wave_build_carve(wbLds, capTs, true), nn, maxSV, tl, ctables + b * ctStrideU32, lane);
 }
 hipError_t launch_fse_ctable_from_norm(const s16* norms, size_t normStride, const u32* maxSVs, u32 tl, u32* ctables, size_t ctStrideU32, size_t* results,
                                        size_t nBlocks, hipStream_t s)
 {
     if (nBlocks == 0) return hipSuccess;
     const u32 capTs = 1u << (tl >= 1 && tl <= FSE_MAX_TL ? tl : FSE_MAX_TL);
-    hipLaunchKernelGGL(k_fse_ctable_from_norm, dim3((unsigned)nBlocks), dim3(64), wave_build_lds_bytes(capTs), s, norms, normStride, maxSVs, tl, ctables, ctStrideU32,
-                       results, capTs);
+    if (wb_small(capTs))
+        hipLaunchKernelGGL(k_fse_ctable_from_norm<32>, dim3((unsigned)nBlocks), dim3(64), wave_build_lds_bytes(capTs, true), s, norms, normStride, maxSVs, tl, ctables,
+                           ctStrideU32, results, capTs);
+    else
+        hipLaunchKernelGGL(k_fse_ctable_from_norm<64>, dim3((unsigned)nBlocks), dim3(64), wave_build_lds_bytes(capTs, true), s, norms, normStride, maxSVs, tl, ctables,
+                           ctStrideU32, results, capTs);
     return hipGetLastError();
+}
+
+// The builds are latency-bound single-wave workgroups: their LDS footprint (sized by the largest table of the launch) and their registers (sized by
+// the cells a lane owns) decide how many run per CU, so the tableLog <= 11 class gets a launch of its own, of the 32-cell instantiation
+static void launch_fse_dbuild_lists(const FseDPrepArgs& a, u32 capTs, int firstList, int nLists, u32 ldsCapTs, hipStream_t s)
+{
+    if (wb_small(ldsCapTs))
+        hipLaunchKernelGGL(k_fse_dbuild<32>, dim3((unsigned)a.nBlocks), dim3(64), wave_build_lds_bytes(ldsCapTs, false), s, a, capTs, firstList, nLists, ldsCapTs);
+    else
+        hipLaunchKernelGGL(k_fse_dbuild<64>, dim3((unsigned)a.nBlocks), dim3(64), wave_build_lds_bytes(ldsCapTs, false), s, a, capTs, firstList, nLists, ldsCapTs);
+}
+static void launch_fse_dbuilds(const FseDPrepArgs& a, hipStream_t s)
+{
+    const u32 capTs = 1u << a.maxLog;
+    const u32 capA = a.maxLog < FSE_DEC_FAST_MAXLOG ? capTs : (1u << FSE_DEC_FAST_MAXLOG);
+    launch_fse_dbuild_lists(a, capTs, (int)FSE_DCLS_REV11 * FSE_DBINS, (int)FSE_DBINS, capA, s);
+    if (a.maxLog > FSE_DEC_FAST_MAXLOG) launch_fse_dbuild_lists(a, capTs, (int)FSE_DCLS_REV12 * FSE_DBINS, 2 * (int)FSE_DBINS, capTs, s);
 }
 
 // the counters -> what k_fse_dparse leaves behind for k_fse_dbuild (meta, counters in scratch, the block filed under its decoder class)
@@ -332,14 +390,10 @@ __global__ __launch_bounds__(64) void k_fse_dmeta_from_norm(FseDPrepArgs a, cons
 hipError_t launch_fse_dprep_from_norm(const FseDPrepArgs& a, const s16* norms, size_t normStride, const u32* maxSVs, u32 tl, hipStream_t s)
 {
     if (a.nBlocks == 0) return hipSuccess;
-    const u32 capTs = 1u << a.maxLog;
     hipError_t e = launch_zero_u32(a.counts, FSE_DCLS_COUNT + FSE_DCLS_KINDS, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_fse_dmeta_from_norm, dim3((unsigned)a.nBlocks), dim3(64), 0, s, a, norms, normStride, maxSVs, tl);
-    const u32 capA = a.maxLog < FSE_DEC_FAST_MAXLOG ? capTs : (1u << FSE_DEC_FAST_MAXLOG);
-    hipLaunchKernelGGL(k_fse_dbuild, dim3((unsigned)a.nBlocks), dim3(64), wave_build_lds_bytes(capA), s, a, capTs, (int)FSE_DCLS_REV11 * FSE_DBINS, (int)FSE_DBINS, capA);
-    if (a.maxLog > FSE_DEC_FAST_MAXLOG)
-        hipLaunchKernelGGL(k_fse_dbuild, dim3((unsigned)a.nBlocks), dim3(64), wave_build_lds_bytes(capTs), s, a, capTs, (int)FSE_DCLS_REV12 * FSE_DBINS, 2 * (int)FSE_DBINS, capTs);
+    launch_fse_dbuilds(a, s);
     return hipGetLastError();
 }
 
@@ -437,26 +491,21 @@ hipError_t launch_fse_cprep(const FseCPrepArgs& a, hipStream_t s)
 {
     if (a.nBlocks == 0) return hipSuccess;
     const u32 capTs = 1u << a.maxTl;
-    const size_t ldsBytes = wave_build_lds_bytes(capTs);
+    const size_t ldsBytes = wave_build_lds_bytes(capTs, true);
     probe_before(PK_FSE_CPREP, s);
-    hipLaunchKernelGGL(k_fse_cprep, dim3((unsigned)a.nBlocks), dim3(64), ldsBytes, s, a, capTs);
+    if (wb_small(capTs)) hipLaunchKernelGGL(k_fse_cprep<32>, dim3((unsigned)a.nBlocks), dim3(64), ldsBytes, s, a, capTs);
+    else hipLaunchKernelGGL(k_fse_cprep<64>, dim3((unsigned)a.nBlocks), dim3(64), ldsBytes, s, a, capTs);
     probe_after(PK_FSE_CPREP, s);
     return hipGetLastError();
 }
 hipError_t launch_fse_dprep(const FseDPrepArgs& a, hipStream_t s)
 {
     if (a.nBlocks == 0) return hipSuccess;
-    const u32 capTs = 1u << a.maxLog;
     hipError_t e = launch_zero_u32(a.counts, FSE_DCLS_COUNT + FSE_DCLS_KINDS, s);      // the lists' lengths and the classes' totals
     if (e != hipSuccess) return e;
     probe_before(PK_FSE_DPREP, s);
     hipLaunchKernelGGL(k_fse_dparse, dim3((unsigned)((a.nBlocks + 63) / 64)), dim3(64), 0, s, a);
-    // the builds are latency-bound single-wave workgroups: their LDS footprint (sized by the largest table of the launch)
-    // decides how many run per CU, so the tableLog <= 11 class gets a launch of its own
-    const u32 capA = a.maxLog < FSE_DEC_FAST_MAXLOG ? capTs : (1u << FSE_DEC_FAST_MAXLOG);
-    hipLaunchKernelGGL(k_fse_dbuild, dim3((unsigned)a.nBlocks), dim3(64), wave_build_lds_bytes(capA), s, a, capTs, (int)FSE_DCLS_REV11 * FSE_DBINS, (int)FSE_DBINS, capA);
-    if (a.maxLog > FSE_DEC_FAST_MAXLOG)
-        hipLaunchKernelGGL(k_fse_dbuild, dim3((unsigned)a.nBlocks), dim3(64), wave_build_lds_bytes(capTs), s, a, capTs, (int)FSE_DCLS_REV12 * FSE_DBINS, 2 * (int)FSE_DBINS, capTs);
+    launch_fse_dbuilds(a, s);
     probe_after(PK_FSE_DPREP, s);
     return hipGetLastError();
 }

@@ -9,9 +9,10 @@
 // Restated without the loop-carried dependencies:
 //   1. step is odd, so m -> (m * step) mod tableSize is a bijection and the serial walk visits m = 0, 1, 2, ... in
 //      order; the k-th *kept* visit (u <= highThreshold) gets the symbol whose cumulative count range contains k.  Every
-//      symbol marks the first k of its range with symbol+1; each lane takes a contiguous range of m, a wave prefix sum of
-//      the kept visits gives its first k, and the symbol of a visit is the running maximum of the marks up to its k
-//      (a wave prefix maximum carries it across lanes).
+//      symbol marks the first k of its range with itself (one byte; 0 = no mark: only the smallest symbol in use can be 0, its
+//      mark sits at k = 0, and a running maximum that starts at 0 names it just the same); each lane takes a contiguous range
+//      of m, a wave prefix sum of the kept visits gives its first k, and the symbol of a visit is the running maximum of the
+//      marks up to its k (a wave prefix maximum carries it across lanes).
 //   2. rank(u) = number of cells u' < u with the same symbol.  Lane l owns the contiguous cells [l*C, (l+1)*C);
 //      a byte matrix cnt[symbol][lane] counts the symbols per lane range (LDS atomic add with return = the rank inside
 //      the range), a per-symbol running sum over groups of 4 lanes gives the ranks of everything before the range.
@@ -42,36 +43,41 @@ __device__ unsigned long long g_wbTiming[4096 * 8];
 // never go to LDS: they stay in the lane's registers from the rank pass to the emit pass.
 struct WaveBuildLds {
     s16* nrm;                // [256] normalized counters, zero beyond maxSV (input)
-    u16* cumP;               // [257] (unused by the core; callers may use it)
+    u16* cumP;               // [257] (unused by the core; callers may use it -- only a carve `withCum` has it)
     u8*  symP;               // [256] symbols in use (counter != 0), ascending
     u8*  symTab;             // [wb_si(capTs)] symbol of every cell (output of the spread), index through wb_si(); shares its bytes with coarse
-    u16* marks;              // [wb_ci(capTs)] scratch of the spread, index through wb_ci(); shares its bytes with cnt
+    u8*  marks;              // [wb_si(capTs)] scratch of the spread, index through wb_si(); shares its bytes with cnt
     u32* cnt;                // [WB_WIN * 16] byte matrix cnt[symbol - window base][lane]
     u16* coarse;             // [WB_WIN * 16] per symbol of the window: cells before lane group j (4 lanes per group)
 };
-// marks[] / symTab[] are indexed through wb_ci() / wb_si(): every row of 32 cells is followed by 4 bytes of padding.  Lane l
+// marks[] / symTab[] are indexed through wb_si(): every row of 32 cells is followed by 4 bytes of padding.  Lane l
 // works on cells [l*C, (l+1)*C) (C = 32 at tableLog 11), so without the padding the 64 lanes of one LDS instruction
 // would sit 64 (or 32) bytes apart -- on 2 (4) of the 32 banks; with it they are 17 (9) dwords apart: conflict-free.
-__host__ __device__ inline u32 wb_ci(u32 u) { return u + ((u >> 5) << 1); }     // u16 array (marks)
-__host__ __device__ inline u32 wb_si(u32 u) { return u + ((u >> 5) << 2); }     // u8 array (symTab)
+__host__ __device__ inline u32 wb_si(u32 u) { return u + ((u >> 5) << 2); }
 // A/B aid: unused LDS per build, i.e. fewer waves per CU (how much do the builders live on residency?)
 #ifndef WB_EXTRA_LDS
 #define WB_EXTRA_LDS 0u
 #endif
-__host__ __device__ inline size_t wb_part_a(u32 capTs) { const size_t m = 2 * (size_t)wb_ci(capTs); return m > WB_WIN * 64 ? m : WB_WIN * 64; }   // cnt | marks
-__host__ __device__ inline size_t wb_part_b(u32 capTs) { const size_t t = wb_si(capTs); return t > WB_WIN * 32 ? t : WB_WIN * 32; }           // symTab | coarse
-// 7,944 bytes at tableLog 11 (20 builds per CU by LDS; the kernels' 113 VGPRs allow 16), 14,600 at tableLog 12
-__host__ __device__ inline size_t wave_build_lds_bytes(u32 capTs) { return wb_part_a(capTs) + wb_part_b(capTs) + 512 + 520 + 256 + WB_EXTRA_LDS; }
-DEV WaveBuildLds wave_build_carve(u8* base, u32 capTs)
+// (both variable-size parts are rounded up to 16 bytes, so that everything behind them stays aligned whatever capTs and WB_WIN are)
+__host__ __device__ inline size_t wb_up16(size_t n) { return (n + 15) & ~(size_t)15; }
+__host__ __device__ inline size_t wb_part_a(u32 capTs) { const size_t m = wb_si(capTs); return wb_up16(m > WB_WIN * 64 ? m : WB_WIN * 64); }   // cnt | marks
+__host__ __device__ inline size_t wb_part_b(u32 capTs) { const size_t t = wb_si(capTs); return wb_up16(t > WB_WIN * 32 ? t : WB_WIN * 32); }   // symTab | coarse
+// `withCum`: the carve has cumP (the CTable builders use it; k_fse_dbuild does not).  At tableLog 11: 7,168 bytes without, 7,696 with
+// (22 / 21 builds per CU by LDS; the 32-cell kernels' registers allow 24 and more), at tableLog 12: 9,984 / 10,512 (16 / 15; the
+// 64-cell kernels' registers allow 16)
+__host__ __device__ inline size_t wave_build_lds_bytes(u32 capTs, bool withCum) { return wb_part_a(capTs) + wb_part_b(capTs) + 512 + 256 + (withCum ? 528 : 0) + WB_EXTRA_LDS; }
+DEV WaveBuildLds wave_build_carve(u8* base, u32 capTs, bool withCum)
 {
     WaveBuildLds w;
-    w.cnt = (u32*)base; w.marks = (u16*)base; base += wb_part_a(capTs);   // 16-byte aligned parts first (both sizes are multiples of 16)
+    w.cnt = (u32*)base; w.marks = base; base += wb_part_a(capTs);         // 16-byte aligned parts first
     w.coarse = (u16*)base; w.symTab = base; base += wb_part_b(capTs);
     w.nrm = (s16*)base; base += 512;
-    w.cumP = (u16*)base; base += 520;
-    w.symP = base;
+    w.symP = base; base += 256;
+    w.cumP = withCum ? (u16*)base : nullptr;
     return w;
 }
+// cells per lane a builder instantiation keeps in registers: 32 where no table of the launch has more than 2048 cells, else 64
+__host__ __device__ inline bool wb_small(u32 capTs) { return capTs <= 2048u; }
 
 DEV u32 wb_bytesum(u32 v) { return __builtin_amdgcn_sad_u8(v, 0u, 0u); }
 DEV u32 wb_scan_excl(u32 v, u32 lane, u32* total)         // exclusive prefix sum over the 64 lanes
@@ -95,7 +101,9 @@ DEV void wb_opaque(u32& v) { asm volatile("" : "+v"(v)); }
 
 // All 64 lanes of one wave call this with uniform arguments; w.nrm holds the counters.  Uses __syncthreads(), so the
 // workgroup must be exactly this wave.  Returns the fastMode flag of FSE_buildDTable (no counter >= tableSize/2).
-template <class Payload, class Emit>
+// MAXC = the cells per lane the instantiation has registers for (the symbols and local ranks of a lane's cells, four to a register):
+// the CALLER guarantees 1 << tl <= 64 * MAXC (the kernels check it, uniformly, before they get here).
+template <u32 MAXC, class Payload, class Emit>
 DEV bool wave_spread_rank(const WaveBuildLds& w, u32 maxSV, u32 tl, u32 lane, Payload&& payload, Emit&& emit)
 {
 #ifdef FSE_WB_TIMING
@@ -106,7 +114,8 @@ DEV bool wave_spread_rank(const WaveBuildLds& w, u32 maxSV, u32 tl, u32 lane, Pa
     const u32 C = ts >= 64 ? ts >> 6 : 1;                                 // cells (and visits) per lane
     const bool act = lane * C < ts;
     const u32 m0 = lane * C;
-    u16* const marks = w.marks;                                           // [ts] scratch of the spread (cnt[] is not in use yet)
+    static_assert(MAXC % 8 == 0 && MAXC <= WB_MAXC, "cells per lane: whole groups of eight, at most the largest table's");
+    u8* const marks = w.marks;                                            // [ts] scratch of the spread (cnt[] is not in use yet)
     // ---- per symbol: lane l looks after symbols 4l .. 4l+3
     int n[4];
     {   const uint2 raw = *(const uint2*)(w.nrm + 4 * lane);
@@ -126,15 +135,15 @@ DEV bool wave_spread_rank(const WaveBuildLds& w, u32 maxSV, u32 tl, u32 lane, Pa
     const u32 nLow = (totals >> 13) & 0x1FFu, nAny = totals >> 22;
     const int high = (int)ts - 1 - (int)nLow;                             // highThreshold (-1: every cell is a low-probability one)
     // clear the spread marks
-    if (act) { if (C >= 2) for (u32 i = 0; i < C; i += 2) *(u32*)(marks + wb_ci(m0 + i)) = 0; else marks[wb_ci(m0)] = 0; }
+    if (act) { if (C >= 4) for (u32 i = 0; i < C; i += 4) *(u32*)(marks + wb_si(m0 + i)) = 0; else for (u32 i = 0; i < C; ++i) marks[wb_si(m0 + i)] = 0; }
     __syncthreads();
     WBT(1)
     // symbols in use (for the per-symbol pass below); low-probability symbols take the top cells; every symbol with a
-    // positive count marks the first of its kept visits with symbol+1
+    // positive count marks the first of its kept visits with itself
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         if (n[i] != 0) w.symP[anyBase++] = (u8)(4 * lane + i);
-        if (n[i] > 0) { marks[wb_ci(posBase)] = (u16)(4 * lane + i + 1); posBase += (u32)n[i]; }
+        if (n[i] > 0) { marks[wb_si(posBase)] = (u8)(4 * lane + i); posBase += (u32)n[i]; }
         else if (n[i] == -1) { w.symTab[wb_si(ts - 1 - lowBase)] = (u8)(4 * lane + i); ++lowBase; }
     }
     // ---- spread: lane l visits m in [l*C, (l+1)*C); the k-th kept visit belongs to the symbol of the last mark at or
@@ -150,7 +159,7 @@ DEV bool wave_spread_rank(const WaveBuildLds& w, u32 maxSV, u32 tl, u32 lane, Pa
     for (u32 i = 0; i < nv; i += 8) {
         u32 v[8];
 #pragma unroll
-        for (u32 j = 0; j < 8; ++j) { const u32 idx = k0 + i + j; v[j] = marks[wb_ci(idx < ts ? idx : ts - 1)]; }
+        for (u32 j = 0; j < 8; ++j) { const u32 idx = k0 + i + j; v[j] = marks[wb_si(idx < ts ? idx : ts - 1)]; }
 #pragma unroll
         for (u32 j = 0; j < 8; ++j) if (i + j < nv) localMax = v[j] > localMax ? v[j] : localMax;
     }
@@ -172,14 +181,14 @@ DEV bool wave_spread_rank(const WaveBuildLds& w, u32 maxSV, u32 tl, u32 lane, Pa
 #pragma unroll
             for (u32 j = 0; j < 8; ++j) {
                 uu[j] = u; keep[j] = (int)u <= high;
-                v[j] = marks[wb_ci(k < ts ? k : ts - 1)];
+                v[j] = marks[wb_si(k < ts ? k : ts - 1)];
                 k += keep[j]; u = (u + step) & mask;
             }
 #pragma unroll
-            for (u32 j = 0; j < 8; ++j) if (keep[j]) { run = v[j] > run ? v[j] : run; w.symTab[wb_si(uu[j])] = (u8)(run - 1u); }
+            for (u32 j = 0; j < 8; ++j) if (keep[j]) { run = v[j] > run ? v[j] : run; w.symTab[wb_si(uu[j])] = (u8)run; }
         }
         for (; i < C; ++i) {
-            if ((int)u <= high) { const u32 v = marks[wb_ci(k)]; ++k; run = v > run ? v : run; w.symTab[wb_si(u)] = (u8)(run - 1u); }
+            if ((int)u <= high) { const u32 v = marks[wb_si(k)]; ++k; run = v > run ? v : run; w.symTab[wb_si(u)] = (u8)run; }
             u = (u + step) & mask;
         }
     }
@@ -190,13 +199,13 @@ DEV bool wave_spread_rank(const WaveBuildLds& w, u32 maxSV, u32 tl, u32 lane, Pa
     //      my range, packed the same way (a rank is < C <= 64).  Cells go in groups of eight; C is 1, 2 or 4 (one partial group)
     //      or a multiple of 8.  The loops over the groups are unrolled so that the arrays stay in registers.
     const u32 nj = C < 8 ? C : 8;                                         // cells per group
-    u32 sym[WB_MAXC / 4], lr[WB_MAXC / 4];
+    u32 sym[MAXC / 4], lr[MAXC / 4];
 #pragma unroll
-    for (u32 q = 0; q < WB_MAXC / 4; ++q) { sym[q] = 0; lr[q] = 0; }
+    for (u32 q = 0; q < MAXC / 4; ++q) { sym[q] = 0; lr[q] = 0; }
     if (act) {
         if (C >= 8) {
 #pragma unroll
-            for (u32 g = 0; g < WB_MAXC / 8; ++g)
+            for (u32 g = 0; g < MAXC / 8; ++g)
                 if (8 * g < C) {
                     const u32* const syp = (const u32*)(w.symTab + wb_si(m0 + 8 * g));   // 8 cells of one row: two aligned dwords
                     sym[2 * g] = syp[0]; sym[2 * g + 1] = syp[1];
@@ -219,7 +228,7 @@ DEV bool wave_spread_rank(const WaveBuildLds& w, u32 maxSV, u32 tl, u32 lane, Pa
         // that the LDS round trips overlap.  A cell of a later window keeps the rank an earlier window gave it.
         if (act) {
 #pragma unroll
-            for (u32 g = 0; g < WB_MAXC / 8; ++g) {
+            for (u32 g = 0; g < MAXC / 8; ++g) {
                 if (8 * g >= C) break;                                    // uniform
                 wb_opaque(sym[2 * g]); wb_opaque(sym[2 * g + 1]);
                 u32 old[8]; bool in[8];
@@ -265,7 +274,7 @@ DEV bool wave_spread_rank(const WaveBuildLds& w, u32 maxSV, u32 tl, u32 lane, Pa
         // emit: everything a cell needs is gathered for eight cells before the first one is emitted
         if (act) {
 #pragma unroll
-            for (u32 g = 0; g < WB_MAXC / 8; ++g) {
+            for (u32 g = 0; g < MAXC / 8; ++g) {
                 if (8 * g >= C) break;                                    // uniform
                 wb_opaque(sym[2 * g]); wb_opaque(sym[2 * g + 1]);
                 u32 mg = m0 + 8 * g; wb_opaque(mg);
