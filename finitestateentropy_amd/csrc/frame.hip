@@ -434,7 +434,7 @@ void frame_worker(FrameJob* j, hipStream_t s)
 }
 
 // The helpers of the batched frame calls are PERSISTENT (round 5): a worker keeps its thread, its stream and -- the point -- its
-// thread_local scratch arena (capi.hip) from call to call.  Spawned per call, every worker paid a hipMalloc for its arena at its first
+// thread_local scratch arena (capi_host.hip) from call to call.  Spawned per call, every worker paid a hipMalloc for its arena at its first
 // frame and a hipFree at thread exit, and hipFree synchronises the device under the other workers' streams.
 // One batch call uses the pool at a time; a second caller arriving meanwhile runs on threads of its own (the former behaviour).  The pool
 // object is created on first use and never destroyed: its idle threads sit on a condition variable until the process ends -- no joins in

@@ -2,6 +2,22 @@
 #pragma once
 #include "dev_common.h"
 
+// host-side error transport of the calls that return a hipError_t as int
+#define CK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) return (int)e__; } while (0)
+static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+static inline BlockView mkview(const void* base, size_t stride, const size_t* sizes, size_t uniform)
+{
+    BlockView v; v.base = (const u8*)base; v.stride = stride; v.sizes = sizes; v.uniform = uniform; v.offsets = nullptr; return v;
+}
+static inline BlockView subview(const BlockView& v, size_t b0)      // blocks b0.. of a view
+{
+    BlockView r = v;
+    if (v.offsets) r.offsets = v.offsets + b0;
+    else { r.base = v.base + b0 * v.stride; r.sizes = v.sizes ? v.sizes + b0 : nullptr; }
+    return r;
+}
+
 // ---- a1: HIST_count ------------------------------------------------------------------------------
 struct HistArgs {
     unsigned* counts;            // nBlocks x 256
@@ -241,7 +257,7 @@ struct HufDPrepArgs {            // glue g6: HUF_readStats + HUF_readDTableX1 (+
 };
 hipError_t launch_huf_dprep(const HufDPrepArgs& a, hipStream_t s);
 hipError_t launch_huf_dprep_x2(const HufDPrepArgs& a, hipStream_t s);   // HUF_readDTableX2 (double-symbol cells): tableOnly, dtMaxLog as the descriptor has it
-// results[b] = meta[b].hdrSize for every block a prepare kernel left pending (state != 0): the table-building batch calls
+// results[b] = meta[b].hdrSize for every block a prepare kernel left pending (state != 0): the table-building batch calls (capi.hip)
 hipError_t launch_hdr_results(const void* meta, size_t metaStride, size_t* results, size_t nBlocks, hipStream_t s);
 // FSE_buildDTable over a batch: the decoder-format tables of k_fse_dbuild written out in the reference's layout (lib/fse.h:565-575)
 hipError_t launch_fse_export_dtables(const FseDPrepArgs& a, u32* dtables, size_t dtStrideU32, hipStream_t s);
@@ -302,12 +318,20 @@ hipError_t launch_u16_decode_lds(const U16DArgs& a, hipStream_t s);   // fse_u16
 // ---- workload generator -----------------------------------------------------------------------------
 hipError_t launch_probagen(u8* dst, size_t dstStride, size_t blockSize, size_t nBlocks, const u8* d_table, u32 firstSeed, u32 seedStep, hipStream_t s);
 
+// ---- packed batches (compact.hip) ----------------------------------------------------------------------
+hipError_t launch_compact(u8* packed, size_t packedCapacity, u64* offsets, const u8* slots, size_t slotStride, const size_t* results, const BlockView& src,
+                          size_t nBlocks, u64* partials, hipStream_t s);
+// rawRle: the bench loop's treatment of blocks the compressor declined (programs/bench.c:393-406) -- a record as long as the block is the
+// block itself, a record of one byte is that byte repeated -- applied by k_rawrle_expand; k_fse_dparse then leaves those alone
+hipError_t launch_rawrle_expand(u8* dst, size_t dstStride, size_t dstCapacity, size_t* results, const BlockView& csrc, const size_t* origSizes, size_t uniformOrig,
+                                size_t nBlocks, hipStream_t s);
+
 // ---- kernel timing probe (HIP events on the launch stream; used by bench.py for the live roofline figure) ----
 enum { PK_HIST = 0, PK_FSE_CPREP, PK_FSE_ENCODE, PK_FSE_DPREP, PK_FSE_DECODE, PK_HUF_CPREP, PK_HUF_ENCODE, PK_HUF_DPREP, PK_HUF_DECODE, PK_FSE_ENCODE_WAVE, PK_COUNT };
 void probe_before(int kernelId, hipStream_t s);
 void probe_after(int kernelId, hipStream_t s);
 
-// Scratch for the calls on HOST pointers (single-block calls, .fse frames): a per-thread, per-device arena of device memory that only
+// Scratch for the calls on HOST pointers (single-block calls, .fse frames; capi_host.hip): a per-thread, per-device arena of device memory that only
 // grows -- a call carves its buffers from it stack-wise instead of paying hipMalloc / hipFree (tens of microseconds each, and a
 // device-wide synchronisation in hipFree) four or five times.  A buffer that does not fit is allocated the old way and the arena grows
 // to the call's peak before the next call (up to FSEHIP_SCRATCH_MAX); the batched calls on device pointers never allocate at all.
@@ -327,7 +351,7 @@ private:
 struct DevProps { int cus; int ldsPerCU; bool ok; };
 const DevProps& dev_props();
 hipError_t ensure_dyn_lds(const void* kernel, int bytes);
-// the one-shot pipelines on views (capi.hip): the batch calls with the source blocks, or the compressed blocks and the destinations, anywhere in one
+// the one-shot pipelines on views (capi_batch.hip): the batch calls with the source blocks, or the compressed blocks and the destinations, anywhere in one
 // buffer -- what the device frame calls (frame_dev.hip) need.  Same workspaces as the batch calls of the same name.
 int fse_compress_view(void* d_dst, size_t dstStride, size_t dstCapacity, size_t* d_results, const BlockView& src, unsigned maxSymbolValue, unsigned tableLog,
                       size_t nBlocks, void* d_workspace, size_t workspaceBytes, hipStream_t s);
@@ -337,7 +361,13 @@ int fse_decompress_view(void* d_dst, const u64* d_dstOffsets, const size_t* d_ds
                         void* d_workspace, size_t workspaceBytes, hipStream_t s);
 int huf_decompress_view(void* d_dst, const u64* d_dstOffsets, const size_t* d_dstSizes, size_t* d_results, const BlockView& csrc, size_t nBlocks,
                         void* d_workspace, size_t workspaceBytes, hipStream_t s);
+// HUF_compress2 / HUF_compress1X over a batch (capi_batch.hip): the argument checks of the batch call, then huf_compress_view
+int huf_compress_batch_impl(int streams, void* d_dst, size_t dstStride, size_t dstCapacity, size_t* d_results,
+                            const void* d_src, size_t srcStride, const size_t* d_sizes, size_t uniformSize,
+                            unsigned maxSymbolValue, unsigned tableLog, size_t nBlocks, void* d_workspace, size_t workspaceBytes, void* stream);
+// per-block argument errors of the one-shot batch calls (capi.hip, k_batch_arg_error)
+int batch_arg_error(size_t* d_results, const size_t* d_sizes, size_t uniform, size_t dstCapacity, size_t nBlocks, size_t code, int mode, hipStream_t s);
 hipError_t launch_xxh32(u32* hashes, const u8* data, const u64* starts, const u64* lens, size_t nItems, u32 seed, hipStream_t s);   // frame_dev.hip; lens == nullptr: starts[i + 1] - starts[i]
-int release_thread_scratch(void);          // capi.hip: gives the calling thread's host-call arena back
+int release_thread_scratch(void);          // capi_host.hip: gives the calling thread's host-call arena back
 int frame_pool_release_scratch(void);       // frame.hip: the same for the idle helper threads of the batched frame calls (0, a hipError_t, or FSEHIP_SCRATCH_BUSY)
 int frame_pool_shutdown(void);              // frame.hip: ends and joins those threads

@@ -124,6 +124,7 @@ FSEHIP_API size_t FSEHIP_FSE_decompress_wksp(void* dst, size_t dstCapacity, cons
  * tableLog 0, 1 or 3 -> GENERIC (FSE_TABLESTEP(2) and (8) are even, lib/fse.h:683: the reference's spread never leaves cell 0 and the rest of its table is
  * whatever the memory held; 2, 4 and everything from FSE_MIN_TABLELOG up are exact); maxSymbolValue > 255 -> maxSymbolValue_tooLarge (byte alphabets; FSE_buildDTable says so itself, :83).  A failed
  * FSE_writeNCount / FSE_readNCount leaves its output untouched (the reference may have written part of it). */
+/* Precondition, as in the reference: srcSize > 1 and maxSymbolValue >= 1.  Outside it the call still returns (the highest bit of 0 counts as bit 0). */
 FSEHIP_API unsigned FSEHIP_FSE_optimalTableLog(unsigned maxTableLog, size_t srcSize, unsigned maxSymbolValue);
 FSEHIP_API size_t FSEHIP_FSE_normalizeCount(short* normalizedCounter, unsigned tableLog, const unsigned* count, size_t srcSize, unsigned maxSymbolValue);
 FSEHIP_API size_t FSEHIP_FSE_NCountWriteBound(unsigned maxSymbolValue, unsigned tableLog);

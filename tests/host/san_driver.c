@@ -3,7 +3,7 @@
  *
  * A plain C program (the Python tests cannot run under AddressSanitizer on this image: the sanitizer runtime's HSA interceptor does not
  * get along with the ROCm runtime bundled inside the torch wheel) that drives, from several host threads at once, what keeps state on the
- * host side of the library -- the per-thread scratch arenas of the calls on host pointers (capi.hip), the frame calls' thread pool,
+ * host side of the library -- the per-thread scratch arenas of the calls on host pointers (capi_host.hip), the frame calls' thread pool,
  * streams and rings (frame.hip), FSEHIP_releaseScratch, the _wksp entry points -- and compares every result with the compiled reference
  * (oracle/_ref/libfse_ref.so: the reference's own lib/ sources) byte for byte.  Built twice by scripts/sanitize.sh: against the product
  * library and against the -fsanitize=address,undefined build of the same sources (finitestateentropy_amd/csrc/variants/san).
