@@ -1087,6 +1087,272 @@ _frame_dev_methods()
 
 
 # ---------------------------------------------------------------------------------------------------------
+#  Byte planes of tensors (csrc/planes.hip; fsehip.h "byte planes of tensors"): tensors of 1-, 2-, 4- and 8-byte elements, one frame per plane
+# ---------------------------------------------------------------------------------------------------------
+class CompressedTensors:
+    """What compress_tensors returns: per group of tensors of one element size the packed frames (a CUDA uint8 tensor cut to their real total),
+    their offsets and results and the split's tensor results (CUDA int64 tensors), and per tensor its dtype, shape and device."""
+
+    def __init__(self, groups, dtypes, shapes, device, codec, block_size_id):
+        self.groups, self.dtypes, self.shapes, self.device, self.codec, self.block_size_id = groups, dtypes, shapes, device, codec, block_size_id
+
+    @property
+    def nbytes(self):
+        """bytes of all frames"""
+        return sum(int(g["frames"].numel()) for g in self.groups)
+
+
+def _planes_methods():
+    def _elem(elem_bytes):
+        if elem_bytes not in (1, 2, 4, 8):
+            raise TypeError("element size %r: planes are cut for elements of 1, 2, 4 or 8 bytes" % (elem_bytes,))
+        return int(elem_bytes)
+
+    def _align_log(align_log):
+        if not isinstance(align_log, numbers.Integral) or not 0 <= align_log <= 12:
+            raise ValueError("align_log %r: slots are aligned to 1 << 0 .. 1 << 12 bytes" % (align_log,))
+        return int(align_log)
+
+    def _i64(self, t, n, device, what):
+        if t is None:
+            return torch.zeros(max(n, 1), dtype=torch.int64, device=device)[:n]
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int64 or not t.is_contiguous() or t.numel() < n:
+            raise TypeError("%s must be a contiguous CUDA int64 tensor of at least %d entries" % (what, n))
+        return t
+
+    def _room(self, t, capacity, what):
+        """a caller's flat buffer and the capacity handed to the library for it"""
+        self._flat(t, what)
+        capacity = t.numel() if capacity is None else int(capacity)
+        if capacity > t.numel():
+            raise ValueError("capacity %d: %s holds %d bytes" % (capacity, what, t.numel()))
+        return capacity
+
+    def planes_block_bound(self, total_bytes, n_tensors, elem_bytes, block_size_id=5):
+        """a sufficient max_total_blocks for the planes of n_tensors tensors of total_bytes bytes in all.  Host arithmetic: needs no device."""
+        self.lib.FSEHIP_planes_blockBound.restype = SZ
+        r = int(self.lib.FSEHIP_planes_blockBound(SZ(int(total_bytes)), SZ(int(n_tensors)), C.c_uint(elem_bytes), C.c_uint(block_size_id)))
+        if r >= (1 << 62):
+            raise ValueError("planes_block_bound(%r, %r, %r, %r)" % (total_bytes, n_tensors, elem_bytes, block_size_id))
+        return r
+
+    def planes_split_dbatch(self, src, src_offsets, elem_bytes, capacity=None, planes=None, plane_offsets=None, results=None):
+        """-> (planes, plane_offsets, results): tensor i = src[src_offsets[i] : src_offsets[i+1]]; plane p of it (its bytes p, p + E, ..) =
+        planes[plane_offsets[i*E+p] : plane_offsets[i*E+p+1]]; results[i] = its size, or -1 (GENERIC) for a tensor that ends behind `capacity`
+        (default: src's size).  elem_bytes 1: no kernel over the data, `planes` is src itself unless one is given (it is not written).  With
+        src_offsets on the device and planes, plane_offsets and results given the call is launches only and can be captured into a graph."""
+        E = _elem(elem_bytes)
+        self._flat(src, "src")
+        soff, _ = self._offsets(src_offsets, src.device, False)
+        n = soff.numel() - 1
+        capacity = _room(self, src, capacity, "src")
+        g = None
+        if planes is None:
+            if E == 1:
+                planes = src
+            else:
+                planes, g = self._dst(1, src.numel(), src.device)
+                planes = planes[0]
+        elif _room(self, planes, None, "planes") < capacity:
+            raise ValueError("planes holds %d bytes, the capacity is %d" % (planes.numel(), capacity))
+        poff = _i64(self, plane_offsets, n * E + 1, src.device, "plane_offsets")
+        res = _i64(self, results, n, src.device, "results")
+        _check(self.lib.FSEHIP_planes_split_dbatch(VP(0) if E == 1 else _ptr(planes), _ptr(poff), _ptr(res), _ptr(src), _ptr(soff), SZ(n), C.c_uint(E),
+                                                   C.c_uint64(capacity), _stream()), "planes_split_dbatch")
+        if g is not None:
+            g.check("planes_split_dbatch")
+        return planes, poff, res
+
+    def planes_merge_dbatch(self, planes, plane_offsets, plane_sizes, dst_offsets, elem_bytes, dst=None, capacity=None, results=None):
+        """-> (dst, results): the inverse of planes_split_dbatch.  Tensor i is rebuilt at dst[dst_offsets[i]:], its slot up to dst_offsets[i+1];
+        plane_offsets / plane_sizes (n * E entries are read of each) are what frame_decompress_packed_dbatch returns as dst_offsets / results:
+        negative sizes are error codes and become the tensor's result.  results[i] = the tensor's size, or -1 (slot behind `capacity`, default
+        dst's size), a plane's error, -4 (sizes that are not the planes of one tensor), -2 (slot too small): such a tensor is not written."""
+        E = _elem(elem_bytes)
+        self._flat(planes, "planes")
+        doff, dhost = self._offsets(dst_offsets, planes.device, dst is None)
+        n = doff.numel() - 1
+        poff = _i64(self, plane_offsets, n * E, planes.device, "plane_offsets")
+        psz = _i64(self, plane_sizes, n * E, planes.device, "plane_sizes")
+        g = None
+        if dst is None:
+            capacity = int(dhost[-1]) if capacity is None else int(capacity)
+            dst, g = self._dst(1, capacity, planes.device)
+            dst = dst[0]
+        else:
+            capacity = _room(self, dst, capacity, "dst")
+        res = _i64(self, results, n, planes.device, "results")
+        _check(self.lib.FSEHIP_planes_merge_dbatch(_ptr(dst), _ptr(doff), _ptr(res), _ptr(planes), _ptr(poff), _ptr(psz), SZ(n), C.c_uint(E), C.c_uint64(capacity),
+                                                   _stream()), "planes_merge_dbatch")
+        if g is not None:
+            g.check("planes_merge_dbatch")
+        return dst, res
+
+    def tensor_compress_dbatch(self, src, src_offsets, elem_bytes, block_size_id=5, codec=0, capacity=None, dst=None, dst_capacity=None, max_total_blocks=None,
+                               align_log=0, frame_offsets=None, frame_results=None, tensor_results=None, planes=None, plane_offsets=None, workspace=None):
+        """-> (dst, frame_offsets, frame_results, tensor_results): planes_split_dbatch, then frame_compress_packed_dbatch over the planes --
+        frame i*E+p = dst[frame_offsets[i*E+p] : .. + frame_results[i*E+p]] is the .fse frame of plane p of tensor i.  `capacity` (default:
+        src's size) bounds the tensors, `dst_capacity` (default: dst's size; dst None: frame_packed_bound of the planes) the frames.  planes
+        (src.numel() bytes) and plane_offsets (n*E+1) are scratch; the workspace is the packed writer's for n*E frames.  With everything given
+        and src_offsets on the device the call is launches only and can be captured into a graph."""
+        E = _elem(elem_bytes)
+        align_log = _align_log(align_log)
+        self._flat(src, "src")
+        soff, shost = self._offsets(src_offsets, src.device, max_total_blocks is None or (dst is None and dst_capacity is None))
+        n = soff.numel() - 1
+        capacity = _room(self, src, capacity, "src")
+        if shost is not None:
+            blocks = self.planes_block_bound(int(shost[-1] - shost[0]), n, E, min(block_size_id, 6))
+        if max_total_blocks is None:
+            max_total_blocks = blocks
+        g = None
+        if dst is None:
+            if dst_capacity is None:
+                dst_capacity = self.frame_packed_bound(int(shost[-1] - shost[0]), n * E, blocks, align_log)
+            dst, g = self._dst(1, int(dst_capacity), src.device)
+            dst = dst[0]
+        else:
+            dst_capacity = _room(self, dst, dst_capacity, "dst")
+        if planes is None and E > 1:
+            planes = torch.empty(max(src.numel(), 1), dtype=torch.uint8, device=src.device)
+        elif planes is not None and _room(self, planes, None, "planes") < capacity:
+            raise ValueError("planes holds %d bytes, the capacity is %d" % (planes.numel(), capacity))
+        foff = _i64(self, frame_offsets, n * E + 1, src.device, "frame_offsets")
+        fres = _i64(self, frame_results, n * E, src.device, "frame_results")
+        tres = _i64(self, tensor_results, n, src.device, "tensor_results")
+        poff = _i64(self, plane_offsets, n * E + 1, src.device, "plane_offsets")
+        if workspace is None:
+            self.lib.FSEHIP_frame_compress_packed_dbatch_workspaceSize.restype = SZ
+            need = int(self.lib.FSEHIP_frame_compress_packed_dbatch_workspaceSize(SZ(n * E), SZ(max_total_blocks), C.c_uint(min(block_size_id, 6)),
+                                                                                  C.c_int(codec if codec in (0, 1) else 0)))
+            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=src.device)
+        _check(self.lib.FSEHIP_tensor_compress_dbatch(_ptr(dst), C.c_uint64(int(dst_capacity)), _ptr(foff), _ptr(fres), _ptr(tres), _ptr(src), _ptr(soff), SZ(n),
+                                                      C.c_uint(E), C.c_uint64(capacity), SZ(max_total_blocks), C.c_uint(block_size_id), C.c_int(codec),
+                                                      C.c_uint(align_log), _ptr(planes), _ptr(poff), _ptr(workspace), SZ(workspace.numel()), _stream()),
+               "tensor_compress_dbatch")
+        if g is not None:
+            g.check("tensor_compress_dbatch")
+        return dst, foff, fres, tres
+
+    def tensor_decompress_dbatch(self, frames, frame_offsets, dst_offsets, elem_bytes, dst=None, dst_capacity=None, max_total_blocks=None, planes=None,
+                                 planes_capacity=None, plane_offsets=None, plane_results=None, workspace=None, results=None):
+        """-> (dst, results): frame_decompress_packed_dbatch of the n*E frames into `planes`, then planes_merge_dbatch into the slots dst_offsets
+        (n + 1 entries, an input).  results[i] = the tensor's size, or the (negative) error of the first of its frames that fails, or the merge's
+        own; such a tensor's slot is not written.  planes (default: as many bytes as the slots hold), plane_offsets (n*E+1) and plane_results
+        (n*E) are scratch / outputs; the workspace is the packed reader's for n*E frames.  max_total_blocks None: the exact block count of the
+        frames, from a frame_plan_dbatch sizing query whose total is read back (planes_block_bound of the tensors is a promise that needs no
+        query).  With everything given the call is launches only."""
+        E = _elem(elem_bytes)
+        self._flat(frames, "frames")
+        foff, _ = self._offsets(frame_offsets, frames.device, False)
+        doff, dhost = self._offsets(dst_offsets, frames.device, dst is None or planes is None)
+        n = doff.numel() - 1
+        if foff.numel() != n * E + 1:
+            raise ValueError("frame_offsets: one entry per plane (%d) and one more" % (n * E))
+        if max_total_blocks is None:                      # the exact count, from a sizing query (as frame_decompress_packed_dbatch does)
+            _, bfirst = self.frame_plan_dbatch(frames, foff, None, 0)
+            max_total_blocks = int(bfirst[n * E].item())
+        g = None
+        if dst is None:
+            dst_capacity = int(dhost[-1]) if dst_capacity is None else int(dst_capacity)
+            dst, g = self._dst(1, dst_capacity, frames.device)
+            dst = dst[0]
+        else:
+            dst_capacity = _room(self, dst, dst_capacity, "dst")
+        if planes is None:
+            planes_capacity = int(dhost[-1]) if planes_capacity is None else int(planes_capacity)
+            planes = torch.empty(max(planes_capacity, 1), dtype=torch.uint8, device=frames.device)
+        else:
+            planes_capacity = _room(self, planes, planes_capacity, "planes")
+        poff = _i64(self, plane_offsets, n * E + 1, frames.device, "plane_offsets")
+        pres = _i64(self, plane_results, n * E, frames.device, "plane_results")
+        res = _i64(self, results, n, frames.device, "results")
+        if workspace is None:
+            self.lib.FSEHIP_frame_decompress_packed_dbatch_workspaceSize.restype = SZ
+            workspace = torch.empty(max(int(self.lib.FSEHIP_frame_decompress_packed_dbatch_workspaceSize(SZ(n * E), SZ(max_total_blocks))), 1),
+                                    dtype=torch.uint8, device=frames.device)
+        _check(self.lib.FSEHIP_tensor_decompress_dbatch(_ptr(dst), _ptr(doff), C.c_uint64(dst_capacity), _ptr(res), _ptr(frames), _ptr(foff), SZ(n), C.c_uint(E),
+                                                        SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity), _ptr(poff), _ptr(pres),
+                                                        _ptr(workspace), SZ(workspace.numel()), _stream()), "tensor_decompress_dbatch")
+        if g is not None:
+            g.check("tensor_decompress_dbatch")
+        return dst, res
+
+    # ---- the user-facing pair
+    def compress_tensors(self, tensors, codec=0, block_size_id=5):
+        """CUDA tensors of any shapes and of dtypes of 1, 2, 4 or 8 bytes per element (TypeError otherwise) -> a CompressedTensors: every tensor as
+        element-size .fse frames, one per byte plane.  Tensors are grouped by element_size(), one tensor_compress_dbatch per group; inputs that
+        are not contiguous are made contiguous.  Reads the frames' total and results back once per group.  While a group is coded the call holds
+        the concatenated inputs, a planes buffer of the same size and a frame buffer at frame_packed_bound -- about three to four times the
+        group's bytes beside the inputs; the object keeps only the frames at their real total."""
+        tensors = list(tensors)
+        if not tensors:
+            return CompressedTensors([], [], [], None, codec, block_size_id)
+        device = tensors[0].device
+        for t in tensors:
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
+                raise TypeError("compress_tensors takes CUDA tensors of one device")
+            _elem(t.element_size())
+        groups = []
+        for E in (1, 2, 4, 8):
+            idx = [i for i, t in enumerate(tensors) if t.element_size() == E]
+            if not idx:
+                continue
+            raw = [tensors[i].contiguous().reshape(-1).view(torch.uint8) for i in idx]
+            offs = np.concatenate([[0], np.cumsum([r.numel() for r in raw])]).astype(np.uint64)
+            src = torch.cat(raw) if int(offs[-1]) else torch.zeros(1, dtype=torch.uint8, device=device)[:0]
+            dst, foff, fres, tres = self.tensor_compress_dbatch(src, offs, E, block_size_id, codec)
+            got = torch.cat([foff[-1:], fres, tres]).cpu().tolist()
+            if min(got) < 0:
+                bad = [k for k, r in enumerate(got[1:1 + len(idx) * E]) if r < 0]
+                raise RuntimeError("compress_tensors: element size %d, frames %s failed (%s)" % (E, bad[:8], [got[1 + k] for k in bad[:8]]))
+            groups.append(dict(elem_bytes=E, index=idx, sizes=[int(x) for x in np.diff(offs)], frames=dst[:got[0]].clone(), frame_offsets=foff,
+                               frame_results=fres, tensor_results=tres))
+        return CompressedTensors(groups, [t.dtype for t in tensors], [tuple(t.shape) for t in tensors], device, codec, block_size_id)
+
+    def decompress_tensors(self, obj):
+        """-> the tensors compress_tensors was given, in their order: same dtype, shape and device, the same bytes.  Every tensor owns its memory
+        (a copy out of the group's destination buffer).  The block promise is planes_block_bound of the recorded sizes: no query, no read-back
+        before the results."""
+        out = [None] * len(obj.dtypes)
+        for g in obj.groups:
+            E, sizes = g["elem_bytes"], g["sizes"]
+            offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
+            blocks = self.planes_block_bound(sum(sizes), len(sizes), E, obj.block_size_id)
+            dst, res = self.tensor_decompress_dbatch(g["frames"], g["frame_offsets"], offs, E, max_total_blocks=blocks)
+            got = res.cpu().tolist()
+            if got != sizes:
+                raise RuntimeError("decompress_tensors: element size %d, results %s for tensors of %s bytes" % (E, got[:8], sizes[:8]))
+            for k, i in enumerate(g["index"]):
+                out[i] = dst[int(offs[k]):int(offs[k + 1])].clone().view(obj.dtypes[i]).reshape(obj.shapes[i])
+        return out
+
+    for f in (planes_block_bound, planes_split_dbatch, planes_merge_dbatch, tensor_compress_dbatch, tensor_decompress_dbatch, compress_tensors, decompress_tensors):
+        setattr(FseHip, f.__name__, f)
+
+
+_planes_methods()
+_DEFAULT = None
+
+
+def _default():
+    global _DEFAULT
+    if _DEFAULT is None:
+        _DEFAULT = FseHip()
+    return _DEFAULT
+
+
+def compress_tensors(tensors, codec=0, block_size_id=5):
+    """FseHip.compress_tensors on a library handle of the module's own"""
+    return _default().compress_tensors(tensors, codec, block_size_id)
+
+
+def decompress_tensors(obj):
+    """FseHip.decompress_tensors on a library handle of the module's own"""
+    return _default().decompress_tensors(obj)
+
+
+# ---------------------------------------------------------------------------------------------------------
 #  FSE for 16-bit symbols (lib/fseU16.h): sizes of the uncompressed side are in symbols
 # ---------------------------------------------------------------------------------------------------------
 FSEU16_MAX_SYMBOL_VALUE = 286

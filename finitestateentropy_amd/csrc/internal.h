@@ -326,6 +326,14 @@ hipError_t launch_compact(u8* packed, size_t packedCapacity, u64* offsets, const
 hipError_t launch_rawrle_expand(u8* dst, size_t dstStride, size_t dstCapacity, size_t* results, const BlockView& csrc, const size_t* origSizes, size_t uniformOrig,
                                 size_t nBlocks, hipStream_t s);
 
+// ---- byte planes of tensors (planes.hip) ------------------------------------------------------------------
+// PLANES_TILE: bytes of the flat axis per workgroup of the two data kernels (fsehip.h, "byte planes": the work mapping).  The launchers check
+// nothing: the C calls of planes.hip do.  launch_planes_split: the offsets and results kernel, then (E > 1) the data kernel.
+#define PLANES_TILE ((u64)32768)
+hipError_t launch_planes_split(u8* planes, u64* planeOff, size_t* tensorRes, const u8* src, const u64* srcOff, size_t nTensors, unsigned E, u64 capacity, hipStream_t s);
+hipError_t launch_planes_merge(u8* dst, const u64* dstOff, size_t* results, const u8* planes, const u64* planeOff, const size_t* planeSizes, size_t nTensors, unsigned E,
+                               u64 dstCapacity, hipStream_t s);
+
 // ---- kernel timing probe (HIP events on the launch stream; used by bench.py for the live roofline figure) ----
 enum { PK_HIST = 0, PK_FSE_CPREP, PK_FSE_ENCODE, PK_FSE_DPREP, PK_FSE_DECODE, PK_HUF_CPREP, PK_HUF_ENCODE, PK_HUF_DPREP, PK_HUF_DECODE, PK_FSE_ENCODE_WAVE, PK_COUNT };
 void probe_before(int kernelId, hipStream_t s);

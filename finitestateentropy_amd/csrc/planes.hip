@@ -1,0 +1,283 @@
+// planes.hip -- tensors of 2-, 4- and 8-byte elements as BYTE PLANES (fsehip.h, "byte planes of tensors"): plane p of a tensor holds byte p of
+// every element, the planes of a tensor lie back to back where the tensor lies, and every plane becomes one .fse frame (frame_dev.hip).  An
+// order-0 coder then sees the exponent bytes and the mantissa bytes of a bf16 tensor in histograms of their own.  Kernel launches only.
+//
+//   FSEHIP_planes_split_dbatch     : k_planes_offsets (per tensor: its plane offsets in closed form, its result) -> k_planes_split
+//   FSEHIP_planes_merge_dbatch     : k_planes_verdicts (per tensor: its result) -> k_planes_merge
+//   FSEHIP_tensor_compress_dbatch  : the split -> FSEHIP_frame_compress_packed_dbatch over the planes (the plane offsets are its source offsets)
+//   FSEHIP_tensor_decompress_dbatch: FSEHIP_frame_decompress_packed_dbatch into the planes buffer -> the merge over the offsets and results it leaves
+//
+// The two data kernels are bandwidth kernels (n bytes in, n bytes out) over ragged tensors, with no workspace and no scan: the flat byte axis
+// is cut into tiles of PLANES_TILE bytes, ceil(capacity / T) + nTensors workgroups are launched, and workgroup w looks up -- a binary search
+// over the offsets -- the largest i with floor(S[i] / T) + i <= w and takes tile t = w - i of tensor i.  That key is strictly increasing in i,
+// and the keys of the tiles a tensor touches, floor(S[i] / T) + i .. floor((S[i+1] - 1) / T) + i, end below the next tensor's key plus one:
+// every (tile, tensor) intersection has exactly one workgroup, however many small or empty tensors share a tile; a workgroup whose
+// intersection is empty returns.  An element belongs to the tile its first byte lies in.
+// Inside its intersection a workgroup gives every lane 16 consecutive elements at a time: E loads of 16 bytes, the byte shuffle (v_perm_b32:
+// log2(E) rounds of "even bytes / odd bytes" over the lane's 4 E dwords, one permute per dword and round), E stores of 16 bytes, one per
+// plane, consecutive lanes at consecutive addresses.  The chunks start where plane 0 (split) or the tensor (merge) reaches a 16-byte boundary;
+// the elements in front of the first chunk and behind the last one -- fewer than 32, the partial last element of a tensor whose size is no
+// multiple of E among them -- go bytewise.  Sources at any alignment (unaligned 16-byte loads, as k_hist and k_xxh32 take theirs).
+#include "internal.h"
+
+namespace {
+#define PL_THREADS 256
+#define PL_TILE_LOG 15
+static_assert(PLANES_TILE == ((u64)1 << PL_TILE_LOG), "tile size");
+inline unsigned grid_for(size_t n) { return (unsigned)((n + PL_THREADS - 1) / PL_THREADS); }
+
+// bytes 0..3 of the result picked from the eight bytes hi:lo by the selector's bytes (0..3: of lo, 4..7: of hi) -- v_perm_b32
+DEV u32 pl_perm(u32 hi, u32 lo, u32 sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
+// w: 16 elements of E bytes (4 E dwords) -> o[p]: byte p of each of them (4 dwords).  One round takes the even and the odd bytes of a dword pair
+// apart; the even half then holds planes 0, 2, .. interleaved E / 2 wide, the odd half planes 1, 3, ..
+template <int E> DEV void pl_deinterleave(const u32* w, u32 (*o)[4], int p0 = 0, int step = 1)
+{
+    if constexpr (E == 1) { for (int k = 0; k < 4; ++k) o[p0][k] = w[k]; }
+    else {
+        u32 ev[2 * E], od[2 * E];
+#pragma unroll
+        for (int j = 0; j < 2 * E; ++j) { ev[j] = pl_perm(w[2 * j + 1], w[2 * j], 0x06040200u); od[j] = pl_perm(w[2 * j + 1], w[2 * j], 0x07050301u); }
+        pl_deinterleave<E / 2>(ev, o, p0, 2 * step);
+        pl_deinterleave<E / 2>(od, o, p0 + step, 2 * step);
+    }
+}
+// ... and back: the planes' dwords zipped bytewise, round by round
+template <int E> DEV void pl_interleave(u32* w, const u32 (*o)[4], int p0 = 0, int step = 1)
+{
+    if constexpr (E == 1) { for (int k = 0; k < 4; ++k) w[k] = o[p0][k]; }
+    else {
+        u32 ev[2 * E], od[2 * E];
+        pl_interleave<E / 2>(ev, o, p0, 2 * step);
+        pl_interleave<E / 2>(od, o, p0 + step, 2 * step);
+#pragma unroll
+        for (int j = 0; j < 2 * E; ++j) { w[2 * j] = pl_perm(od[j], ev[j], 0x05010400u); w[2 * j + 1] = pl_perm(od[j], ev[j], 0x07030602u); }
+    }
+}
+
+// size of plane p of a tensor of n bytes, and where it starts inside the tensor (the sizes of the planes in front of it)
+DEV u64 pl_size(u64 n, u32 p, u32 E) { return n > p ? (n - p + E - 1) / E : 0; }
+DEV u64 pl_start(u64 n, u32 p, u32 E) { const u64 r = n % E; return (u64)p * (n / E) + (p < r ? p : r); }
+
+// the work mapping: the largest i < nT with floor(S[i] / T) + i <= w (false: there is none)
+DEV bool pl_find(const u64* S, size_t nT, u64 w, size_t& i)
+{
+    if (nT == 0 || (S[0] >> PL_TILE_LOG) > w) return false;
+    size_t lo = 0, hi = nT - 1;
+    while (lo < hi) { const size_t mid = lo + ((hi - lo + 1) >> 1); if ((S[mid] >> PL_TILE_LOG) + mid <= w) lo = mid; else hi = mid - 1; }
+    i = lo;
+    return true;
+}
+// A workgroup's share of a tensor of n bytes at flat position s0, tile [lo, lo + T): the elements [e0, e1) whose first byte lies in the tile
+// and inside the tensor, cut into a bytewise head [e0, eb), `nch` chunks of 16 WHOLE elements from eb on, and a bytewise tail [et, e1).
+// `first` = the address that the chunks are aligned by, as a number: element e0 lies `first` bytes behind a 16-byte boundary of it
+struct PlShare { u64 e0, eb, et, e1, nch; };
+template <int E> DEV PlShare pl_share(u64 s0, u64 n, u64 lo, u64 alignAddr, u32 alignStride)
+{
+    PlShare r;
+    const u64 hi = lo + PLANES_TILE;
+    const u64 a = lo > s0 ? lo - s0 : 0, b = (hi < s0 + n ? hi : s0 + n) - s0;
+    r.e0 = (a + E - 1) / E; r.e1 = (b + E - 1) / E;
+    // elements up to the 16-byte boundary of alignAddr + e * alignStride (alignStride 1: plane 0 of the split; E: the merge's tensor, where its start allows it)
+    u64 head = alignStride ? ((0 - (alignAddr + r.e0 * alignStride)) & 15u) / alignStride : 0;
+    if (head > r.e1 - r.e0) head = r.e1 - r.e0;
+    r.eb = r.e0 + head;
+    const u64 whole = n / E < r.e1 ? n / E : r.e1;                  // (the last element of the tensor may be partial)
+    r.nch = whole > r.eb ? (whole - r.eb) >> 4 : 0;
+    r.et = r.eb + 16 * r.nch;
+    return r;
+}
+
+// ---- split -------------------------------------------------------------------------------------------------------------------------------
+// per tensor (and one thread more for the last entry): its E plane offsets and its result.  Offsets are monotone, so the tensors behind the
+// capacity are a suffix: all their entries collapse onto the start of the first of them
+__global__ void k_planes_offsets(u64* P, size_t* res, const u64* S, size_t nT, u32 E, u64 capacity)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > nT) return;
+    size_t lo = 0, hi = nT;                                      // the smallest j with S[j + 1] > capacity, nT without one
+    while (lo < hi) { const size_t mid = lo + ((hi - lo) >> 1); if (S[mid + 1] > capacity) hi = mid; else lo = mid + 1; }
+    const size_t bad = lo;
+    if (i == nT) { P[nT * E] = S[bad]; return; }
+    if (i >= bad) {
+        const u64 at = S[bad];
+        for (u32 p = 0; p < E; ++p) P[i * E + p] = at;
+        res[i] = FERR(GENERIC);
+        return;
+    }
+    const u64 s0 = S[i], s1 = S[i + 1], n = s1 > s0 ? s1 - s0 : 0;
+    for (u32 p = 0; p < E; ++p) P[i * E + p] = s0 + pl_start(n, p, E);
+    res[i] = (size_t)n;
+}
+template <int E>
+__global__ __launch_bounds__(PL_THREADS) void k_planes_split(u8* planes, const u8* src, const u64* S, size_t nT, u64 capacity)
+{
+    const u64 w = blockIdx.x;
+    size_t i;
+    if (!pl_find(S, nT, w, i)) return;                            // (uniform, like every return below)
+    const u64 s0 = S[i], s1 = S[i + 1], lo = (w - i) << PL_TILE_LOG;
+    if (!(s0 < s1) || s1 > capacity || lo >= s1 || lo + PLANES_TILE <= s0) return;
+    const u64 n = s1 - s0;
+    const u32 tid = threadIdx.x;
+    const u8* const sb = src + s0;
+    u8* const pb = planes + s0;
+    const PlShare h = pl_share<E>(s0, n, lo, (u64)(uintptr_t)pb, 1);
+    for (u64 c = tid; c < h.nch; c += PL_THREADS) {
+        const u64 e = h.eb + 16 * c;
+        u32 wv[4 * E], o[E][4];
+#pragma unroll
+        for (int k = 0; k < E; ++k) __builtin_memcpy(&wv[4 * k], sb + e * E + 16 * k, 16);
+        pl_deinterleave<E>(wv, o);
+#pragma unroll
+        for (int p = 0; p < E; ++p) __builtin_memcpy(pb + pl_start(n, p, E) + e, o[p], 16);
+    }
+    // head and tail, a byte per thread: byte k of the tensor is byte k / E of plane k % E
+    const u64 nHead = (h.eb - h.e0) * E, nTail = (h.e1 - h.et) * E;
+    for (u64 j = tid; j < nHead + nTail; j += PL_THREADS) {
+        const u64 k = j < nHead ? h.e0 * E + j : h.et * E + (j - nHead);
+        if (k < n) pb[pl_start(n, (u32)(k % E), E) + k / E] = sb[k];
+    }
+}
+
+// ---- merge -------------------------------------------------------------------------------------------------------------------------------
+// the result of tensor i (fsehip.h: the five rules in their order)
+DEV size_t pm_verdict(const u64* D, const size_t* PS, size_t i, u32 E, u64 dstCapacity)
+{
+    const u64 d0 = D[i], d1 = D[i + 1];
+    if (d1 > dstCapacity) return FERR(GENERIC);
+    u64 n = 0;
+    for (u32 p = 0; p < E; ++p) { const size_t z = PS[i * E + p]; if (is_err(z)) return z; n += z; }
+    for (u32 p = 0; p < E; ++p) if ((u64)PS[i * E + p] != pl_size(n, p, E)) return FERR(corruption_detected);
+    if (n > (d1 > d0 ? d1 - d0 : 0)) return FERR(dstSize_tooSmall);
+    return (size_t)n;
+}
+__global__ void k_planes_verdicts(size_t* res, const u64* D, const size_t* PS, size_t nT, u32 E, u64 dstCapacity)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nT) res[i] = pm_verdict(D, PS, i, E, dstCapacity);
+}
+template <int E>
+__global__ __launch_bounds__(PL_THREADS) void k_planes_merge(u8* dst, const u64* D, const u8* planes, const u64* PO, const size_t* PS, size_t nT, u64 dstCapacity)
+{
+    const u64 w = blockIdx.x;
+    size_t i;
+    if (!pl_find(D, nT, w, i)) return;
+    const u64 d0 = D[i], d1 = D[i + 1], lo = (w - i) << PL_TILE_LOG;
+    if (!(d0 < d1) || lo >= d1 || lo + PLANES_TILE <= d0) return;
+    const size_t v = pm_verdict(D, PS, i, E, dstCapacity);
+    if (is_err(v) || lo >= d0 + (u64)v) return;                  // (a good tensor: d0 + n <= d1 <= dstCapacity)
+    const u64 n = v;
+    const u32 tid = threadIdx.x;
+    u8* const db = dst + d0;
+    const u8* pp[E];
+#pragma unroll
+    for (int p = 0; p < E; ++p) pp[p] = planes + PO[i * E + p];
+    const u64 addr = (u64)(uintptr_t)db;
+    const PlShare h = pl_share<E>(d0, n, lo, addr, (addr % E) ? 0 : E);       // a tensor that starts inside an element's width never reaches a boundary
+    for (u64 c = tid; c < h.nch; c += PL_THREADS) {
+        const u64 e = h.eb + 16 * c;
+        u32 wv[4 * E], o[E][4];
+#pragma unroll
+        for (int p = 0; p < E; ++p) __builtin_memcpy(o[p], pp[p] + e, 16);
+        pl_interleave<E>(wv, o);
+#pragma unroll
+        for (int k = 0; k < E; ++k) __builtin_memcpy(db + e * E + 16 * k, &wv[4 * k], 16);
+    }
+    const u64 nHead = (h.eb - h.e0) * E, nTail = (h.e1 - h.et) * E;
+    for (u64 j = tid; j < nHead + nTail; j += PL_THREADS) {
+        const u64 k = j < nHead ? h.e0 * E + j : h.et * E + (j - nHead);
+        if (k < n) db[k] = planes[PO[i * E + k % E] + k / E];
+    }
+}
+
+inline bool bad_elem(unsigned E) { return E != 1 && E != 2 && E != 4 && E != 8; }
+// ceil(capacity / T) + nTensors workgroups of PL_THREADS threads in one launch
+inline bool bad_grid(u64 capacity, size_t nTensors) { return capacity >= ((u64)1 << 46) || (capacity >> PL_TILE_LOG) + 1 + nTensors >= ((u64)1 << 24); }
+inline unsigned tile_grid(u64 capacity, size_t nTensors) { return (unsigned)(((capacity + PLANES_TILE - 1) >> PL_TILE_LOG) + nTensors); }
+}   // namespace
+
+hipError_t launch_planes_split(u8* planes, u64* planeOff, size_t* tensorRes, const u8* src, const u64* srcOff, size_t nTensors, unsigned E, u64 capacity, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_planes_offsets, dim3(grid_for(nTensors + 1)), dim3(PL_THREADS), 0, s, planeOff, tensorRes, srcOff, nTensors, (u32)E, capacity);
+    if (E == 1 || nTensors == 0 || capacity == 0) return hipGetLastError();
+    const dim3 g(tile_grid(capacity, nTensors)), b(PL_THREADS);
+    if (E == 2) hipLaunchKernelGGL(k_planes_split<2>, g, b, 0, s, planes, src, srcOff, nTensors, capacity);
+    else if (E == 4) hipLaunchKernelGGL(k_planes_split<4>, g, b, 0, s, planes, src, srcOff, nTensors, capacity);
+    else hipLaunchKernelGGL(k_planes_split<8>, g, b, 0, s, planes, src, srcOff, nTensors, capacity);
+    return hipGetLastError();
+}
+
+hipError_t launch_planes_merge(u8* dst, const u64* dstOff, size_t* results, const u8* planes, const u64* planeOff, const size_t* planeSizes, size_t nTensors, unsigned E,
+                               u64 dstCapacity, hipStream_t s)
+{
+    if (nTensors == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_planes_verdicts, dim3(grid_for(nTensors)), dim3(PL_THREADS), 0, s, results, dstOff, planeSizes, nTensors, (u32)E, dstCapacity);
+    if (dstCapacity == 0) return hipGetLastError();
+    const dim3 g(tile_grid(dstCapacity, nTensors)), b(PL_THREADS);
+    if (E == 1) hipLaunchKernelGGL(k_planes_merge<1>, g, b, 0, s, dst, dstOff, planes, planeOff, planeSizes, nTensors, dstCapacity);
+    else if (E == 2) hipLaunchKernelGGL(k_planes_merge<2>, g, b, 0, s, dst, dstOff, planes, planeOff, planeSizes, nTensors, dstCapacity);
+    else if (E == 4) hipLaunchKernelGGL(k_planes_merge<4>, g, b, 0, s, dst, dstOff, planes, planeOff, planeSizes, nTensors, dstCapacity);
+    else hipLaunchKernelGGL(k_planes_merge<8>, g, b, 0, s, dst, dstOff, planes, planeOff, planeSizes, nTensors, dstCapacity);
+    return hipGetLastError();
+}
+
+extern "C" size_t FSEHIP_planes_blockBound(size_t totalBytes, size_t nTensors, unsigned elemBytes, unsigned blockSizeId)
+{
+    if (blockSizeId > 6 || bad_elem(elemBytes)) return FSEHIP_ERROR(GENERIC);
+    const size_t bs = (size_t)1024 << blockSizeId;
+    return totalBytes / bs + (totalBytes % bs ? 1 : 0) + nTensors * elemBytes;
+}
+
+extern "C" int FSEHIP_planes_split_dbatch(void* d_planes, uint64_t* d_planeOffsets, size_t* d_tensorResults, const void* d_src, const uint64_t* d_srcOffsets,
+                                          size_t nTensors, unsigned elemBytes, uint64_t capacity, void* stream)
+{
+    if (bad_elem(elemBytes) || !d_planeOffsets || !d_tensorResults || !d_srcOffsets || (elemBytes > 1 && (!d_planes || !d_src))) return (int)hipErrorInvalidValue;
+    if (nTensors >= ((size_t)1 << 31) / elemBytes || bad_grid(capacity, nTensors)) return (int)hipErrorInvalidValue;
+    return (int)launch_planes_split((u8*)d_planes, (u64*)d_planeOffsets, d_tensorResults, (const u8*)d_src, (const u64*)d_srcOffsets, nTensors, elemBytes, capacity,
+                                    (hipStream_t)stream);
+}
+
+extern "C" int FSEHIP_planes_merge_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_planes, const uint64_t* d_planeOffsets,
+                                          const size_t* d_planeSizes, size_t nTensors, unsigned elemBytes, uint64_t dstCapacity, void* stream)
+{
+    if (bad_elem(elemBytes) || !d_dst || !d_dstOffsets || !d_results || !d_planes || !d_planeOffsets || !d_planeSizes) return (int)hipErrorInvalidValue;
+    if (nTensors >= ((size_t)1 << 31) / elemBytes || bad_grid(dstCapacity, nTensors)) return (int)hipErrorInvalidValue;
+    return (int)launch_planes_merge((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeSizes, nTensors, elemBytes,
+                                    dstCapacity, (hipStream_t)stream);
+}
+
+extern "C" int FSEHIP_tensor_compress_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
+                                             const void* d_src, const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes, uint64_t capacity,
+                                             size_t maxTotalBlocks, unsigned blockSizeId, int codec, unsigned slotAlignLog,
+                                             void* d_planes, uint64_t* d_planeOffsets, void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    // the argument checks of both steps, as they stand today, in front of the first launch (fsehip.h: what the guarantee covers)
+    if (bad_elem(elemBytes) || !d_frameOffsets || !d_frameResults || !d_tensorResults || !d_src || !d_srcOffsets || !d_planeOffsets || (elemBytes > 1 && !d_planes))
+        return (int)hipErrorInvalidValue;
+    if (nTensors >= ((size_t)1 << 31) / elemBytes || bad_grid(capacity, nTensors)) return (int)hipErrorInvalidValue;
+    if (blockSizeId > 6 || (codec != 0 && codec != 1) || slotAlignLog > 12 || ((uintptr_t)d_workspace & 255u) || maxTotalBlocks >= ((size_t)1 << 31)) return (int)hipErrorInvalidValue;
+    const size_t nFrames = nTensors * elemBytes;
+    if (workspaceBytes < FSEHIP_frame_compress_packed_dbatch_workspaceSize(nFrames, maxTotalBlocks, blockSizeId, codec)) return (int)hipErrorInvalidValue;
+    const hipError_t e = launch_planes_split((u8*)d_planes, (u64*)d_planeOffsets, d_tensorResults, (const u8*)d_src, (const u64*)d_srcOffsets, nTensors, elemBytes, capacity,
+                                             (hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
+    return FSEHIP_frame_compress_packed_dbatch(d_dst, dstCapacity, d_frameOffsets, d_frameResults, elemBytes == 1 ? d_src : d_planes, d_planeOffsets, nFrames, maxTotalBlocks,
+                                               blockSizeId, codec, slotAlignLog, d_workspace, workspaceBytes, stream);
+}
+
+extern "C" int FSEHIP_tensor_decompress_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, size_t* d_results,
+                                               const void* d_frames, const uint64_t* d_frameOffsets, size_t nTensors, unsigned elemBytes, size_t maxTotalBlocks,
+                                               void* d_planes, uint64_t planesCapacity, uint64_t* d_planeOffsets, size_t* d_planeResults,
+                                               void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    if (bad_elem(elemBytes) || !d_dst || !d_dstOffsets || !d_results || !d_frames || !d_frameOffsets || !d_planes || !d_planeOffsets || !d_planeResults)
+        return (int)hipErrorInvalidValue;
+    if (nTensors >= ((size_t)1 << 31) / elemBytes || bad_grid(dstCapacity, nTensors)) return (int)hipErrorInvalidValue;
+    if (((uintptr_t)d_workspace & 255u) || maxTotalBlocks >= ((size_t)1 << 31)) return (int)hipErrorInvalidValue;
+    const size_t nFrames = nTensors * elemBytes;
+    if (workspaceBytes < FSEHIP_frame_decompress_packed_dbatch_workspaceSize(nFrames, maxTotalBlocks)) return (int)hipErrorInvalidValue;
+    const int e = FSEHIP_frame_decompress_packed_dbatch(d_planes, (size_t)planesCapacity, d_planeOffsets, d_planeResults, d_frames, d_frameOffsets, nFrames, maxTotalBlocks, 0,
+                                                        d_workspace, workspaceBytes, stream);
+    if (e != 0) return e;
+    return (int)launch_planes_merge((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeResults, nTensors, elemBytes,
+                                    dstCapacity, (hipStream_t)stream);
+}

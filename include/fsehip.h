@@ -563,6 +563,76 @@ FSEHIP_API int FSEHIP_frame_decompress_packed_dbatch(void* d_dst, size_t dstCapa
                                                      const uint64_t* d_frameOffsets, size_t nFrames, size_t maxTotalBlocks, unsigned slotAlignLog,
                                                      void* d_workspace, size_t workspaceBytes, void* stream);
 
+/* ---- Byte planes of tensors (planes.hip): tensors of 2-, 4- and 8-byte elements through the frame calls above, ONE FRAME PER BYTE PLANE.
+ * An order-0 coder over the raw bytes of such a tensor sees the bytes of an element (sign and exponent, mantissa) mixed in one histogram;
+ * plane by plane each byte position gets a table of its own, and a plane that does not compress falls through the frame's raw-block path.
+ * No bitstream, header or frame byte differs: every frame these calls write is a frame of the container above, read by the reference's tool.
+ * Like the device frame calls: kernel launches on `stream` and nothing else, all pointers DEVICE pointers, no size leaves the device, the
+ * return value is a hipError_t.  hipErrorInvalidValue -- elemBytes not 1 / 2 / 4 / 8, a null array, 2^31 planes or more, a capacity whose
+ * launch (capacity / 32 KB + nTensors workgroups) reaches 2^24 workgroups -- is decided before any device call (it answers on a host without
+ * a device) and nothing is written.
+ *
+ *   The layout.  Tensor i is the byte range [S[i], S[i+1]) of a flat buffer, the tensors back to back (nTensors + 1 offsets, any sizes, any
+ *     alignments).  With E = elemBytes, PLANE p (p < E) of a tensor of n bytes holds its bytes at the tensor-relative positions k with
+ *     k mod E == p, in order -- on a little-endian host byte p of every element: size_p = ceil((n - p) / E) for n > p, else 0.  n need not be
+ *     a multiple of E: the bytes of the last, partial element go to the first n mod E planes; there is no error case for a size.  The planes
+ *     of tensor i lie back to back, in plane order, where the tensor lies: P[i * E + p] = S[i] + size_0 + .. + size_(p-1), and
+ *     P[nTensors * E] = S[nTensors].  The planes buffer has the size of the source, and P (nTensors * E + 1 entries) is directly the
+ *     d_srcOffsets of FSEHIP_frame_compress_packed_dbatch with nFrames = nTensors * E.
+ *
+ *   FSEHIP_planes_split_dbatch   d_src -> d_planes, P into d_planeOffsets, per tensor its size into d_tensorResults.  `capacity` is the byte size
+ *     of d_src and of d_planes: it sizes the launch, no offset is read back.  A tensor with S[i+1] > capacity is REFUSED: its result is GENERIC,
+ *     nothing of it is read or written, and every entry of d_planeOffsets from its first plane on equals its start S[i] -- offsets are
+ *     monotone, so every later tensor is refused too, and all those planes are empty contents to the frame writer.
+ *     Memory: reads the accepted tensors' bytes; writes exactly their plane bytes, nothing else of d_planes.  d_planes must not overlap d_src.
+ *     elemBytes == 1: offsets and results only, no kernel over the data -- plane 0 of a tensor is the tensor; d_planes may be NULL.
+ *
+ *   FSEHIP_planes_merge_dbatch   the inverse.  Tensor i is rebuilt at d_dst + d_dstOffsets[i], its slot d_dstOffsets[i+1] - d_dstOffsets[i]
+ *     (nTensors + 1 entries, an INPUT); its plane p is d_planeSizes[i * E + p] bytes at d_planes + d_planeOffsets[i * E + p] -- exactly what
+ *     FSEHIP_frame_decompress_packed_dbatch leaves in its d_dstOffsets and d_results (error codes pass through).  d_results[i], in this order:
+ *     GENERIC if the slot ends behind dstCapacity; the first error among its E plane sizes, in plane order; corruption_detected if the sizes
+ *     are not the size_p of n = their sum; dstSize_tooSmall if n exceeds the slot; otherwise n.
+ *     Memory: a tensor whose result is n gets exactly n bytes written, every other tensor none; reads the planes of the good tensors.
+ *
+ *   Both data kernels read n bytes and write n bytes, and need no workspace and no scan: the flat byte axis is cut into tiles of T = 32 KB,
+ *     ceil(capacity / T) + nTensors workgroups are launched, and workgroup w takes tile t = w - i of the tensor i that is the largest with
+ *     floor(S[i] / T) + i <= w (a binary search over the offsets) -- every (tile, tensor) intersection exactly once, however many small or
+ *     empty tensors a tile holds.  An element belongs to the tile its first byte lies in.
+ *
+ *   FSEHIP_planes_blockBound   host arithmetic (works without a device): ceil(totalBytes / blockSize) + nTensors * elemBytes, a sufficient
+ *     maxTotalBlocks for the planes of nTensors tensors of totalBytes bytes in all (every plane may end in a partial block).  blockSizeId > 6
+ *     or a bad elemBytes: GENERIC.
+ *
+ *   FSEHIP_tensor_compress_dbatch   FSEHIP_planes_split_dbatch, then FSEHIP_frame_compress_packed_dbatch over the planes: frame i * E + p is
+ *     byte for byte FSEHIP_frame_compress of plane p of tensor i.  d_frameOffsets (nTensors * E + 1 entries) and d_frameResults (nTensors * E)
+ *     are the packed writer's d_dstOffsets and d_results, with its rules for dstCapacity, maxTotalBlocks and slotAlignLog; d_tensorResults are
+ *     the split's.  A refused tensor yields E empty frames of eight bytes and GENERIC in its tensor result.  d_planes (capacity bytes) and
+ *     d_planeOffsets (nTensors * E + 1 entries) are scratch, left as the split leaves them.  With elemBytes == 1 the writer reads d_src itself
+ *     and d_planes may be NULL.  d_workspace is the PACKED WRITER'S OWN: size it with
+ *     FSEHIP_frame_compress_packed_dbatch_workspaceSize(nTensors * elemBytes, maxTotalBlocks, blockSizeId, codec).
+ *     A call refused for one of the argument errors listed here or at the packed writer (blockSizeId, codec, slotAlignLog, a misaligned or
+ *     too small workspace, 2^31 blocks) has written nothing; that covers those checks only -- for any other error the writer returns, the
+ *     split has already run (d_planes, d_planeOffsets and d_tensorResults are written).
+ *
+ *   FSEHIP_tensor_decompress_dbatch   FSEHIP_frame_decompress_packed_dbatch with slotAlignLog 0 into d_planes (planesCapacity bytes;
+ *     d_planeOffsets, nTensors * E + 1 entries, and d_planeResults, nTensors * E, are its outputs), then FSEHIP_planes_merge_dbatch into the
+ *     slots d_dstOffsets (an INPUT).  A tensor one of whose frames fails has that frame's error as its result and its slot is not written.
+ *     d_workspace is the packed reader's: FSEHIP_frame_decompress_packed_dbatch_workspaceSize(nTensors * elemBytes, maxTotalBlocks).
+ */
+FSEHIP_API size_t FSEHIP_planes_blockBound(size_t totalBytes, size_t nTensors, unsigned elemBytes, unsigned blockSizeId);
+FSEHIP_API int FSEHIP_planes_split_dbatch(void* d_planes, uint64_t* d_planeOffsets, size_t* d_tensorResults, const void* d_src, const uint64_t* d_srcOffsets,
+                                          size_t nTensors, unsigned elemBytes, uint64_t capacity, void* stream);
+FSEHIP_API int FSEHIP_planes_merge_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_planes, const uint64_t* d_planeOffsets,
+                                          const size_t* d_planeSizes, size_t nTensors, unsigned elemBytes, uint64_t dstCapacity, void* stream);
+FSEHIP_API int FSEHIP_tensor_compress_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
+                                             const void* d_src, const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes, uint64_t capacity,
+                                             size_t maxTotalBlocks, unsigned blockSizeId, int codec, unsigned slotAlignLog,
+                                             void* d_planes, uint64_t* d_planeOffsets, void* d_workspace, size_t workspaceBytes, void* stream);
+FSEHIP_API int FSEHIP_tensor_decompress_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, size_t* d_results,
+                                               const void* d_frames, const uint64_t* d_frameOffsets, size_t nTensors, unsigned elemBytes, size_t maxTotalBlocks,
+                                               void* d_planes, uint64_t planesCapacity, uint64_t* d_planeOffsets, size_t* d_planeResults,
+                                               void* d_workspace, size_t workspaceBytes, void* stream);
+
 /* ---- FSE for 16-bit symbols (lib/fseU16.h:62-80, lib/fseU16.c) -- SURVEY 8(f) rank 4.  Alphabets of up to
  * FSEHIP_FSEU16_MAX_SYMBOL_VALUE + 1 symbols, table logs up to 13 (default 12), ONE tANS state per stream: a different format from
  * the byte coder's.  Sizes of the uncompressed side are in SYMBOLS (as in the reference), strides in bytes.
