@@ -1091,10 +1091,13 @@ _frame_dev_methods()
 # ---------------------------------------------------------------------------------------------------------
 class CompressedTensors:
     """What compress_tensors returns: per group of tensors of one element size the packed frames (a CUDA uint8 tensor cut to their real total),
-    their offsets and results and the split's tensor results (CUDA int64 tensors), and per tensor its dtype, shape and device."""
+    their offsets and results and the split's tensor results (CUDA int64 tensors), and per tensor its dtype, shape and device.  `delta`: the
+    frames hold `tensor XOR base` (compress_tensors with base=...) and decompress_tensors needs the same base again; the frames themselves do
+    not say so."""
 
-    def __init__(self, groups, dtypes, shapes, device, codec, block_size_id):
+    def __init__(self, groups, dtypes, shapes, device, codec, block_size_id, delta=False):
         self.groups, self.dtypes, self.shapes, self.device, self.codec, self.block_size_id = groups, dtypes, shapes, device, codec, block_size_id
+        self.delta = bool(delta)
 
     @property
     def nbytes(self):
@@ -1136,19 +1139,41 @@ def _planes_methods():
             raise ValueError("planes_block_bound(%r, %r, %r, %r)" % (total_bytes, n_tensors, elem_bytes, block_size_id))
         return r
 
+    def _base(self, base, like, capacity, what):
+        """the base of an XOR call: a flat buffer on the device of `like` that holds at least the capacity of the buffer it is laid out as"""
+        self._flat(base, "base")
+        if base.device != like.device:
+            raise ValueError("base is on %s, %s on %s" % (base.device, what, like.device))
+        if base.numel() < capacity:
+            raise ValueError("base holds %d bytes, the capacity of %s is %d" % (base.numel(), what, capacity))
+        return base
+
     def planes_split_dbatch(self, src, src_offsets, elem_bytes, capacity=None, planes=None, plane_offsets=None, results=None):
         """-> (planes, plane_offsets, results): tensor i = src[src_offsets[i] : src_offsets[i+1]]; plane p of it (its bytes p, p + E, ..) =
         planes[plane_offsets[i*E+p] : plane_offsets[i*E+p+1]]; results[i] = its size, or -1 (GENERIC) for a tensor that ends behind `capacity`
         (default: src's size).  elem_bytes 1: no kernel over the data, `planes` is src itself unless one is given (it is not written).  With
         src_offsets on the device and planes, plane_offsets and results given the call is launches only and can be captured into a graph."""
+        return _split(self, src, None, src_offsets, elem_bytes, capacity, planes, plane_offsets, results)
+
+    def planes_split_xor_dbatch(self, src, base, src_offsets, elem_bytes, capacity=None, planes=None, plane_offsets=None, results=None):
+        """planes_split_dbatch of src XOR base, the XOR fused into the split: `base` is laid out as src is (the same offsets, at least `capacity`
+        bytes).  For every elem_bytes, 1 included, `planes` is a buffer of its own and is written; it overlaps neither src nor base."""
+        if base is None:
+            raise ValueError("planes_split_xor_dbatch needs a base")
+        return _split(self, src, base, src_offsets, elem_bytes, capacity, planes, plane_offsets, results)
+
+    def _split(self, src, base, src_offsets, elem_bytes, capacity, planes, plane_offsets, results):
         E = _elem(elem_bytes)
         self._flat(src, "src")
         soff, _ = self._offsets(src_offsets, src.device, False)
         n = soff.numel() - 1
         capacity = _room(self, src, capacity, "src")
+        what = "planes_split_dbatch" if base is None else "planes_split_xor_dbatch"
+        if base is not None:
+            _base(self, base, src, capacity, "src")
         g = None
         if planes is None:
-            if E == 1:
+            if E == 1 and base is None:
                 planes = src
             else:
                 planes, g = self._dst(1, src.numel(), src.device)
@@ -1157,10 +1182,14 @@ def _planes_methods():
             raise ValueError("planes holds %d bytes, the capacity is %d" % (planes.numel(), capacity))
         poff = _i64(self, plane_offsets, n * E + 1, src.device, "plane_offsets")
         res = _i64(self, results, n, src.device, "results")
-        _check(self.lib.FSEHIP_planes_split_dbatch(VP(0) if E == 1 else _ptr(planes), _ptr(poff), _ptr(res), _ptr(src), _ptr(soff), SZ(n), C.c_uint(E),
-                                                   C.c_uint64(capacity), _stream()), "planes_split_dbatch")
+        if base is None:
+            _check(self.lib.FSEHIP_planes_split_dbatch(VP(0) if E == 1 else _ptr(planes), _ptr(poff), _ptr(res), _ptr(src), _ptr(soff), SZ(n), C.c_uint(E),
+                                                       C.c_uint64(capacity), _stream()), what)
+        else:
+            _check(self.lib.FSEHIP_planes_split_xor_dbatch(_ptr(planes), _ptr(poff), _ptr(res), _ptr(src), _ptr(base), _ptr(soff), SZ(n), C.c_uint(E),
+                                                           C.c_uint64(capacity), _stream()), what)
         if g is not None:
-            g.check("planes_split_dbatch")
+            g.check(what)
         return planes, poff, res
 
     def planes_merge_dbatch(self, planes, plane_offsets, plane_sizes, dst_offsets, elem_bytes, dst=None, capacity=None, results=None):
@@ -1168,6 +1197,17 @@ def _planes_methods():
         plane_offsets / plane_sizes (n * E entries are read of each) are what frame_decompress_packed_dbatch returns as dst_offsets / results:
         negative sizes are error codes and become the tensor's result.  results[i] = the tensor's size, or -1 (slot behind `capacity`, default
         dst's size), a plane's error, -4 (sizes that are not the planes of one tensor), -2 (slot too small): such a tensor is not written."""
+        return _merge(self, planes, plane_offsets, plane_sizes, None, dst_offsets, elem_bytes, dst, capacity, results)
+
+    def planes_merge_xor_dbatch(self, planes, plane_offsets, plane_sizes, base, dst_offsets, elem_bytes, dst=None, capacity=None, results=None):
+        """planes_merge_dbatch, every rebuilt tensor XORed with `base`, which is laid out as dst is (dst_offsets, at least `capacity` bytes): the
+        inverse of planes_split_xor_dbatch.  dst may be `base` itself -- IN PLACE: base then holds the new tensors, and a tensor whose result is
+        an error keeps its old bytes.  Any other overlap of dst and base is an error of the caller's that is not checked."""
+        if base is None:
+            raise ValueError("planes_merge_xor_dbatch needs a base")
+        return _merge(self, planes, plane_offsets, plane_sizes, base, dst_offsets, elem_bytes, dst, capacity, results)
+
+    def _merge(self, planes, plane_offsets, plane_sizes, base, dst_offsets, elem_bytes, dst, capacity, results):
         E = _elem(elem_bytes)
         self._flat(planes, "planes")
         doff, dhost = self._offsets(dst_offsets, planes.device, dst is None)
@@ -1182,10 +1222,17 @@ def _planes_methods():
         else:
             capacity = _room(self, dst, capacity, "dst")
         res = _i64(self, results, n, planes.device, "results")
-        _check(self.lib.FSEHIP_planes_merge_dbatch(_ptr(dst), _ptr(doff), _ptr(res), _ptr(planes), _ptr(poff), _ptr(psz), SZ(n), C.c_uint(E), C.c_uint64(capacity),
-                                                   _stream()), "planes_merge_dbatch")
+        if base is None:
+            what = "planes_merge_dbatch"
+            _check(self.lib.FSEHIP_planes_merge_dbatch(_ptr(dst), _ptr(doff), _ptr(res), _ptr(planes), _ptr(poff), _ptr(psz), SZ(n), C.c_uint(E), C.c_uint64(capacity),
+                                                       _stream()), what)
+        else:
+            what = "planes_merge_xor_dbatch"
+            _base(self, base, planes, capacity, "dst")
+            _check(self.lib.FSEHIP_planes_merge_xor_dbatch(_ptr(dst), _ptr(doff), _ptr(res), _ptr(planes), _ptr(poff), _ptr(psz), _ptr(base), SZ(n), C.c_uint(E),
+                                                           C.c_uint64(capacity), _stream()), what)
         if g is not None:
-            g.check("planes_merge_dbatch")
+            g.check(what)
         return dst, res
 
     def tensor_compress_dbatch(self, src, src_offsets, elem_bytes, block_size_id=5, codec=0, capacity=None, dst=None, dst_capacity=None, max_total_blocks=None,
@@ -1195,12 +1242,30 @@ def _planes_methods():
         src's size) bounds the tensors, `dst_capacity` (default: dst's size; dst None: frame_packed_bound of the planes) the frames.  planes
         (src.numel() bytes) and plane_offsets (n*E+1) are scratch; the workspace is the packed writer's for n*E frames.  With everything given
         and src_offsets on the device the call is launches only and can be captured into a graph."""
+        return _compress(self, src, None, src_offsets, elem_bytes, block_size_id, codec, capacity, dst, dst_capacity, max_total_blocks, align_log, frame_offsets,
+                         frame_results, tensor_results, planes, plane_offsets, workspace)
+
+    def tensor_compress_delta_dbatch(self, src, base, src_offsets, elem_bytes, block_size_id=5, codec=0, capacity=None, dst=None, dst_capacity=None,
+                                     max_total_blocks=None, align_log=0, frame_offsets=None, frame_results=None, tensor_results=None, planes=None, plane_offsets=None,
+                                     workspace=None):
+        """tensor_compress_dbatch of src XOR base (planes_split_xor_dbatch, then the packed writer over the planes): frame i*E+p is the .fse frame
+        of plane p of tensor_i XOR base_i.  `base` is laid out as src is.  `planes` is scratch for every elem_bytes, 1 included."""
+        if base is None:
+            raise ValueError("tensor_compress_delta_dbatch needs a base")
+        return _compress(self, src, base, src_offsets, elem_bytes, block_size_id, codec, capacity, dst, dst_capacity, max_total_blocks, align_log, frame_offsets,
+                         frame_results, tensor_results, planes, plane_offsets, workspace)
+
+    def _compress(self, src, base, src_offsets, elem_bytes, block_size_id, codec, capacity, dst, dst_capacity, max_total_blocks, align_log, frame_offsets,
+                  frame_results, tensor_results, planes, plane_offsets, workspace):
         E = _elem(elem_bytes)
         align_log = _align_log(align_log)
         self._flat(src, "src")
         soff, shost = self._offsets(src_offsets, src.device, max_total_blocks is None or (dst is None and dst_capacity is None))
         n = soff.numel() - 1
         capacity = _room(self, src, capacity, "src")
+        what = "tensor_compress_dbatch" if base is None else "tensor_compress_delta_dbatch"
+        if base is not None:
+            _base(self, base, src, capacity, "src")
         if shost is not None:
             blocks = self.planes_block_bound(int(shost[-1] - shost[0]), n, E, min(block_size_id, 6))
         if max_total_blocks is None:
@@ -1213,7 +1278,7 @@ def _planes_methods():
             dst = dst[0]
         else:
             dst_capacity = _room(self, dst, dst_capacity, "dst")
-        if planes is None and E > 1:
+        if planes is None and (E > 1 or base is not None):
             planes = torch.empty(max(src.numel(), 1), dtype=torch.uint8, device=src.device)
         elif planes is not None and _room(self, planes, None, "planes") < capacity:
             raise ValueError("planes holds %d bytes, the capacity is %d" % (planes.numel(), capacity))
@@ -1226,12 +1291,15 @@ def _planes_methods():
             need = int(self.lib.FSEHIP_frame_compress_packed_dbatch_workspaceSize(SZ(n * E), SZ(max_total_blocks), C.c_uint(min(block_size_id, 6)),
                                                                                   C.c_int(codec if codec in (0, 1) else 0)))
             workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=src.device)
-        _check(self.lib.FSEHIP_tensor_compress_dbatch(_ptr(dst), C.c_uint64(int(dst_capacity)), _ptr(foff), _ptr(fres), _ptr(tres), _ptr(src), _ptr(soff), SZ(n),
-                                                      C.c_uint(E), C.c_uint64(capacity), SZ(max_total_blocks), C.c_uint(block_size_id), C.c_int(codec),
-                                                      C.c_uint(align_log), _ptr(planes), _ptr(poff), _ptr(workspace), SZ(workspace.numel()), _stream()),
-               "tensor_compress_dbatch")
+        tail = (SZ(n), C.c_uint(E), C.c_uint64(capacity), SZ(max_total_blocks), C.c_uint(block_size_id), C.c_int(codec), C.c_uint(align_log), _ptr(planes), _ptr(poff),
+                _ptr(workspace), SZ(workspace.numel()), _stream())
+        if base is None:
+            _check(self.lib.FSEHIP_tensor_compress_dbatch(_ptr(dst), C.c_uint64(int(dst_capacity)), _ptr(foff), _ptr(fres), _ptr(tres), _ptr(src), _ptr(soff), *tail), what)
+        else:
+            _check(self.lib.FSEHIP_tensor_compress_delta_dbatch(_ptr(dst), C.c_uint64(int(dst_capacity)), _ptr(foff), _ptr(fres), _ptr(tres), _ptr(src), _ptr(base),
+                                                                _ptr(soff), *tail), what)
         if g is not None:
-            g.check("tensor_compress_dbatch")
+            g.check(what)
         return dst, foff, fres, tres
 
     def tensor_decompress_dbatch(self, frames, frame_offsets, dst_offsets, elem_bytes, dst=None, dst_capacity=None, max_total_blocks=None, planes=None,
@@ -1242,6 +1310,21 @@ def _planes_methods():
         (n*E) are scratch / outputs; the workspace is the packed reader's for n*E frames.  max_total_blocks None: the exact block count of the
         frames, from a frame_plan_dbatch sizing query whose total is read back (planes_block_bound of the tensors is a promise that needs no
         query).  With everything given the call is launches only."""
+        return _decompress(self, frames, frame_offsets, None, dst_offsets, elem_bytes, dst, dst_capacity, max_total_blocks, planes, planes_capacity, plane_offsets,
+                           plane_results, workspace, results)
+
+    def tensor_decompress_delta_dbatch(self, frames, frame_offsets, base, dst_offsets, elem_bytes, dst=None, dst_capacity=None, max_total_blocks=None, planes=None,
+                                       planes_capacity=None, plane_offsets=None, plane_results=None, workspace=None, results=None):
+        """tensor_decompress_dbatch of frames that tensor_compress_delta_dbatch wrote: the packed reader into `planes`, then planes_merge_xor_dbatch
+        against `base`, which is laid out as dst is.  dst may be `base` itself (in place): a tensor whose result is an error keeps the base's
+        bytes."""
+        if base is None:
+            raise ValueError("tensor_decompress_delta_dbatch needs a base")
+        return _decompress(self, frames, frame_offsets, base, dst_offsets, elem_bytes, dst, dst_capacity, max_total_blocks, planes, planes_capacity, plane_offsets,
+                           plane_results, workspace, results)
+
+    def _decompress(self, frames, frame_offsets, base, dst_offsets, elem_bytes, dst, dst_capacity, max_total_blocks, planes, planes_capacity, plane_offsets,
+                    plane_results, workspace, results):
         E = _elem(elem_bytes)
         self._flat(frames, "frames")
         foff, _ = self._offsets(frame_offsets, frames.device, False)
@@ -1271,28 +1354,54 @@ def _planes_methods():
             self.lib.FSEHIP_frame_decompress_packed_dbatch_workspaceSize.restype = SZ
             workspace = torch.empty(max(int(self.lib.FSEHIP_frame_decompress_packed_dbatch_workspaceSize(SZ(n * E), SZ(max_total_blocks))), 1),
                                     dtype=torch.uint8, device=frames.device)
-        _check(self.lib.FSEHIP_tensor_decompress_dbatch(_ptr(dst), _ptr(doff), C.c_uint64(dst_capacity), _ptr(res), _ptr(frames), _ptr(foff), SZ(n), C.c_uint(E),
-                                                        SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity), _ptr(poff), _ptr(pres),
-                                                        _ptr(workspace), SZ(workspace.numel()), _stream()), "tensor_decompress_dbatch")
+        if base is None:
+            what = "tensor_decompress_dbatch"
+            _check(self.lib.FSEHIP_tensor_decompress_dbatch(_ptr(dst), _ptr(doff), C.c_uint64(dst_capacity), _ptr(res), _ptr(frames), _ptr(foff), SZ(n), C.c_uint(E),
+                                                            SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity), _ptr(poff), _ptr(pres),
+                                                            _ptr(workspace), SZ(workspace.numel()), _stream()), what)
+        else:
+            what = "tensor_decompress_delta_dbatch"
+            _base(self, base, frames, dst_capacity, "dst")
+            _check(self.lib.FSEHIP_tensor_decompress_delta_dbatch(_ptr(dst), _ptr(doff), C.c_uint64(dst_capacity), _ptr(base), _ptr(res), _ptr(frames), _ptr(foff), SZ(n),
+                                                                  C.c_uint(E), SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity), _ptr(poff), _ptr(pres),
+                                                                  _ptr(workspace), SZ(workspace.numel()), _stream()), what)
         if g is not None:
-            g.check("tensor_decompress_dbatch")
+            g.check(what)
         return dst, res
 
     # ---- the user-facing pair
-    def compress_tensors(self, tensors, codec=0, block_size_id=5):
+    def _bases(base, dtypes, shapes, device):
+        """the `base` of the pair: one CUDA tensor per tensor, of its dtype, shape and device -> their bytes, flat"""
+        base = list(base)
+        if len(base) != len(dtypes):
+            raise ValueError("base: %d tensors for %d" % (len(base), len(dtypes)))
+        for k, (b, dt, sh) in enumerate(zip(base, dtypes, shapes)):
+            if not isinstance(b, torch.Tensor) or not b.is_cuda or b.device != device or b.dtype != dt:
+                raise TypeError("base[%d]: a CUDA tensor of %s on %s is needed" % (k, dt, device))
+            if tuple(b.shape) != tuple(sh):
+                raise ValueError("base[%d]: shape %s, the tensor's is %s" % (k, tuple(b.shape), tuple(sh)))
+        return [b.contiguous().reshape(-1).view(torch.uint8) for b in base]
+
+    def compress_tensors(self, tensors, codec=0, block_size_id=5, base=None):
         """CUDA tensors of any shapes and of dtypes of 1, 2, 4 or 8 bytes per element (TypeError otherwise) -> a CompressedTensors: every tensor as
         element-size .fse frames, one per byte plane.  Tensors are grouped by element_size(), one tensor_compress_dbatch per group; inputs that
         are not contiguous are made contiguous.  Reads the frames' total and results back once per group.  While a group is coded the call holds
         the concatenated inputs, a planes buffer of the same size and a frame buffer at frame_packed_bound -- about three to four times the
-        group's bytes beside the inputs; the object keeps only the frames at their real total."""
+        group's bytes beside the inputs; the object keeps only the frames at their real total.
+        base: a sequence of CUDA tensors matching `tensors` one to one in dtype, shape and device (TypeError / ValueError otherwise, before any
+        launch) -- what the receiver already holds.  The frames then hold `tensor XOR base` (the object's `delta` is True), far fewer bytes where
+        most bytes did not change, and decompress_tensors needs the same base."""
         tensors = list(tensors)
         if not tensors:
-            return CompressedTensors([], [], [], None, codec, block_size_id)
+            if base is not None and len(list(base)):
+                raise ValueError("base: tensors for none")
+            return CompressedTensors([], [], [], None, codec, block_size_id, base is not None)
         device = tensors[0].device
         for t in tensors:
             if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
                 raise TypeError("compress_tensors takes CUDA tensors of one device")
             _elem(t.element_size())
+        braw = None if base is None else _bases(base, [t.dtype for t in tensors], [tuple(t.shape) for t in tensors], device)
         groups = []
         for E in (1, 2, 4, 8):
             idx = [i for i, t in enumerate(tensors) if t.element_size() == E]
@@ -1301,25 +1410,40 @@ def _planes_methods():
             raw = [tensors[i].contiguous().reshape(-1).view(torch.uint8) for i in idx]
             offs = np.concatenate([[0], np.cumsum([r.numel() for r in raw])]).astype(np.uint64)
             src = torch.cat(raw) if int(offs[-1]) else torch.zeros(1, dtype=torch.uint8, device=device)[:0]
-            dst, foff, fres, tres = self.tensor_compress_dbatch(src, offs, E, block_size_id, codec)
+            if braw is None:
+                dst, foff, fres, tres = self.tensor_compress_dbatch(src, offs, E, block_size_id, codec)
+            else:
+                bsrc = torch.cat([braw[i] for i in idx]) if int(offs[-1]) else src
+                dst, foff, fres, tres = self.tensor_compress_delta_dbatch(src, bsrc, offs, E, block_size_id, codec)
             got = torch.cat([foff[-1:], fres, tres]).cpu().tolist()
             if min(got) < 0:
                 bad = [k for k, r in enumerate(got[1:1 + len(idx) * E]) if r < 0]
                 raise RuntimeError("compress_tensors: element size %d, frames %s failed (%s)" % (E, bad[:8], [got[1 + k] for k in bad[:8]]))
             groups.append(dict(elem_bytes=E, index=idx, sizes=[int(x) for x in np.diff(offs)], frames=dst[:got[0]].clone(), frame_offsets=foff,
                                frame_results=fres, tensor_results=tres))
-        return CompressedTensors(groups, [t.dtype for t in tensors], [tuple(t.shape) for t in tensors], device, codec, block_size_id)
+        return CompressedTensors(groups, [t.dtype for t in tensors], [tuple(t.shape) for t in tensors], device, codec, block_size_id, braw is not None)
 
-    def decompress_tensors(self, obj):
+    def decompress_tensors(self, obj, base=None):
         """-> the tensors compress_tensors was given, in their order: same dtype, shape and device, the same bytes.  Every tensor owns its memory
         (a copy out of the group's destination buffer).  The block promise is planes_block_bound of the recorded sizes: no query, no read-back
-        before the results."""
+        before the results.
+        base: for an object with `delta` set, the tensors compress_tensors was given as base (checked for dtype, shape and device, not for
+        content: the frames do not say what they are a delta against).  ValueError for a delta object without a base and for a base with a plain
+        object.  The bases are not changed: a group is rebuilt in place over a copy of its bases."""
+        if getattr(obj, "delta", False) != (base is not None):
+            raise ValueError("decompress_tensors: the object holds deltas and needs its base" if base is None else
+                             "decompress_tensors: the object holds no deltas, a base does not belong to it")
+        braw = None if base is None else _bases(base, obj.dtypes, obj.shapes, obj.device)
         out = [None] * len(obj.dtypes)
         for g in obj.groups:
             E, sizes = g["elem_bytes"], g["sizes"]
             offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
             blocks = self.planes_block_bound(sum(sizes), len(sizes), E, obj.block_size_id)
-            dst, res = self.tensor_decompress_dbatch(g["frames"], g["frame_offsets"], offs, E, max_total_blocks=blocks)
+            if braw is None:
+                dst, res = self.tensor_decompress_dbatch(g["frames"], g["frame_offsets"], offs, E, max_total_blocks=blocks)
+            else:
+                dst = torch.cat([braw[i] for i in g["index"]]) if sum(sizes) else torch.zeros(1, dtype=torch.uint8, device=obj.device)[:0]
+                dst, res = self.tensor_decompress_delta_dbatch(g["frames"], g["frame_offsets"], dst, offs, E, dst=dst, max_total_blocks=blocks)
             got = res.cpu().tolist()
             if got != sizes:
                 raise RuntimeError("decompress_tensors: element size %d, results %s for tensors of %s bytes" % (E, got[:8], sizes[:8]))
@@ -1327,7 +1451,8 @@ def _planes_methods():
                 out[i] = dst[int(offs[k]):int(offs[k + 1])].clone().view(obj.dtypes[i]).reshape(obj.shapes[i])
         return out
 
-    for f in (planes_block_bound, planes_split_dbatch, planes_merge_dbatch, tensor_compress_dbatch, tensor_decompress_dbatch, compress_tensors, decompress_tensors):
+    for f in (planes_block_bound, planes_split_dbatch, planes_merge_dbatch, tensor_compress_dbatch, tensor_decompress_dbatch, compress_tensors, decompress_tensors,
+              planes_split_xor_dbatch, planes_merge_xor_dbatch, tensor_compress_delta_dbatch, tensor_decompress_delta_dbatch):
         setattr(FseHip, f.__name__, f)
 
 
@@ -1342,14 +1467,14 @@ def _default():
     return _DEFAULT
 
 
-def compress_tensors(tensors, codec=0, block_size_id=5):
+def compress_tensors(tensors, codec=0, block_size_id=5, base=None):
     """FseHip.compress_tensors on a library handle of the module's own"""
-    return _default().compress_tensors(tensors, codec, block_size_id)
+    return _default().compress_tensors(tensors, codec, block_size_id, base)
 
 
-def decompress_tensors(obj):
+def decompress_tensors(obj, base=None):
     """FseHip.decompress_tensors on a library handle of the module's own"""
-    return _default().decompress_tensors(obj)
+    return _default().decompress_tensors(obj, base)
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -329,7 +329,10 @@ hipError_t launch_rawrle_expand(u8* dst, size_t dstStride, size_t dstCapacity, s
 // ---- byte planes of tensors (planes.hip) ------------------------------------------------------------------
 // PLANES_TILE: bytes of the flat axis per workgroup of the two data kernels (fsehip.h, "byte planes": the work mapping).  The launchers check
 // nothing: the C calls of planes.hip do.  launch_planes_split: the offsets and results kernel, then (E > 1) the data kernel.
+// launch_planes_offsets / _verdicts: the per-tensor kernels alone, as planes_delta.hip (the XOR forms) puts them in front of its data kernels.
 #define PLANES_TILE ((u64)32768)
+void launch_planes_offsets(u64* planeOff, size_t* tensorRes, const u64* srcOff, size_t nTensors, unsigned E, u64 capacity, hipStream_t s);
+void launch_planes_verdicts(size_t* results, const u64* dstOff, const size_t* planeSizes, size_t nTensors, unsigned E, u64 dstCapacity, hipStream_t s);
 hipError_t launch_planes_split(u8* planes, u64* planeOff, size_t* tensorRes, const u8* src, const u64* srcOff, size_t nTensors, unsigned E, u64 capacity, hipStream_t s);
 hipError_t launch_planes_merge(u8* dst, const u64* dstOff, size_t* results, const u8* planes, const u64* planeOff, const size_t* planeSizes, size_t nTensors, unsigned E,
                                u64 dstCapacity, hipStream_t s);

@@ -6,6 +6,7 @@
 //   FSEHIP_planes_merge_dbatch     : k_planes_verdicts (per tensor: its result) -> k_planes_merge
 //   FSEHIP_tensor_compress_dbatch  : the split -> FSEHIP_frame_compress_packed_dbatch over the planes (the plane offsets are its source offsets)
 //   FSEHIP_tensor_decompress_dbatch: FSEHIP_frame_decompress_packed_dbatch into the planes buffer -> the merge over the offsets and results it leaves
+// (The device helpers all of them are made of are in planes_dev.h, shared with the XOR forms of planes_delta.hip.)
 //
 // The two data kernels are bandwidth kernels (n bytes in, n bytes out) over ragged tensors, with no workspace and no scan: the flat byte axis
 // is cut into tiles of PLANES_TILE bytes, ceil(capacity / T) + nTensors workgroups are launched, and workgroup w looks up -- a binary search
@@ -18,75 +19,9 @@
 // plane, consecutive lanes at consecutive addresses.  The chunks start where plane 0 (split) or the tensor (merge) reaches a 16-byte boundary;
 // the elements in front of the first chunk and behind the last one -- fewer than 32, the partial last element of a tensor whose size is no
 // multiple of E among them -- go bytewise.  Sources at any alignment (unaligned 16-byte loads, as k_hist and k_xxh32 take theirs).
-#include "internal.h"
+#include "planes_dev.h"
 
 namespace {
-#define PL_THREADS 256
-#define PL_TILE_LOG 15
-static_assert(PLANES_TILE == ((u64)1 << PL_TILE_LOG), "tile size");
-inline unsigned grid_for(size_t n) { return (unsigned)((n + PL_THREADS - 1) / PL_THREADS); }
-
-// bytes 0..3 of the result picked from the eight bytes hi:lo by the selector's bytes (0..3: of lo, 4..7: of hi) -- v_perm_b32
-DEV u32 pl_perm(u32 hi, u32 lo, u32 sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
-// w: 16 elements of E bytes (4 E dwords) -> o[p]: byte p of each of them (4 dwords).  One round takes the even and the odd bytes of a dword pair
-// apart; the even half then holds planes 0, 2, .. interleaved E / 2 wide, the odd half planes 1, 3, ..
-template <int E> DEV void pl_deinterleave(const u32* w, u32 (*o)[4], int p0 = 0, int step = 1)
-{
-    if constexpr (E == 1) { for (int k = 0; k < 4; ++k) o[p0][k] = w[k]; }
-    else {
-        u32 ev[2 * E], od[2 * E];
-#pragma unroll
-        for (int j = 0; j < 2 * E; ++j) { ev[j] = pl_perm(w[2 * j + 1], w[2 * j], 0x06040200u); od[j] = pl_perm(w[2 * j + 1], w[2 * j], 0x07050301u); }
-        pl_deinterleave<E / 2>(ev, o, p0, 2 * step);
-        pl_deinterleave<E / 2>(od, o, p0 + step, 2 * step);
-    }
-}
-// ... and back: the planes' dwords zipped bytewise, round by round
-template <int E> DEV void pl_interleave(u32* w, const u32 (*o)[4], int p0 = 0, int step = 1)
-{
-    if constexpr (E == 1) { for (int k = 0; k < 4; ++k) w[k] = o[p0][k]; }
-    else {
-        u32 ev[2 * E], od[2 * E];
-        pl_interleave<E / 2>(ev, o, p0, 2 * step);
-        pl_interleave<E / 2>(od, o, p0 + step, 2 * step);
-#pragma unroll
-        for (int j = 0; j < 2 * E; ++j) { w[2 * j] = pl_perm(od[j], ev[j], 0x05010400u); w[2 * j + 1] = pl_perm(od[j], ev[j], 0x07030602u); }
-    }
-}
-
-// size of plane p of a tensor of n bytes, and where it starts inside the tensor (the sizes of the planes in front of it)
-DEV u64 pl_size(u64 n, u32 p, u32 E) { return n > p ? (n - p + E - 1) / E : 0; }
-DEV u64 pl_start(u64 n, u32 p, u32 E) { const u64 r = n % E; return (u64)p * (n / E) + (p < r ? p : r); }
-
-// the work mapping: the largest i < nT with floor(S[i] / T) + i <= w (false: there is none)
-DEV bool pl_find(const u64* S, size_t nT, u64 w, size_t& i)
-{
-    if (nT == 0 || (S[0] >> PL_TILE_LOG) > w) return false;
-    size_t lo = 0, hi = nT - 1;
-    while (lo < hi) { const size_t mid = lo + ((hi - lo + 1) >> 1); if ((S[mid] >> PL_TILE_LOG) + mid <= w) lo = mid; else hi = mid - 1; }
-    i = lo;
-    return true;
-}
-// A workgroup's share of a tensor of n bytes at flat position s0, tile [lo, lo + T): the elements [e0, e1) whose first byte lies in the tile
-// and inside the tensor, cut into a bytewise head [e0, eb), `nch` chunks of 16 WHOLE elements from eb on, and a bytewise tail [et, e1).
-// `first` = the address that the chunks are aligned by, as a number: element e0 lies `first` bytes behind a 16-byte boundary of it
-struct PlShare { u64 e0, eb, et, e1, nch; };
-template <int E> DEV PlShare pl_share(u64 s0, u64 n, u64 lo, u64 alignAddr, u32 alignStride)
-{
-    PlShare r;
-    const u64 hi = lo + PLANES_TILE;
-    const u64 a = lo > s0 ? lo - s0 : 0, b = (hi < s0 + n ? hi : s0 + n) - s0;
-    r.e0 = (a + E - 1) / E; r.e1 = (b + E - 1) / E;
-    // elements up to the 16-byte boundary of alignAddr + e * alignStride (alignStride 1: plane 0 of the split; E: the merge's tensor, where its start allows it)
-    u64 head = alignStride ? ((0 - (alignAddr + r.e0 * alignStride)) & 15u) / alignStride : 0;
-    if (head > r.e1 - r.e0) head = r.e1 - r.e0;
-    r.eb = r.e0 + head;
-    const u64 whole = n / E < r.e1 ? n / E : r.e1;                  // (the last element of the tensor may be partial)
-    r.nch = whole > r.eb ? (whole - r.eb) >> 4 : 0;
-    r.et = r.eb + 16 * r.nch;
-    return r;
-}
-
 // ---- split -------------------------------------------------------------------------------------------------------------------------------
 // per tensor (and one thread more for the last entry): its E plane offsets and its result.  Offsets are monotone, so the tensors behind the
 // capacity are a suffix: all their entries collapse onto the start of the first of them
@@ -139,17 +74,6 @@ __global__ __launch_bounds__(PL_THREADS) void k_planes_split(u8* planes, const u
 }
 
 // ---- merge -------------------------------------------------------------------------------------------------------------------------------
-// the result of tensor i (fsehip.h: the five rules in their order)
-DEV size_t pm_verdict(const u64* D, const size_t* PS, size_t i, u32 E, u64 dstCapacity)
-{
-    const u64 d0 = D[i], d1 = D[i + 1];
-    if (d1 > dstCapacity) return FERR(GENERIC);
-    u64 n = 0;
-    for (u32 p = 0; p < E; ++p) { const size_t z = PS[i * E + p]; if (is_err(z)) return z; n += z; }
-    for (u32 p = 0; p < E; ++p) if ((u64)PS[i * E + p] != pl_size(n, p, E)) return FERR(corruption_detected);
-    if (n > (d1 > d0 ? d1 - d0 : 0)) return FERR(dstSize_tooSmall);
-    return (size_t)n;
-}
 __global__ void k_planes_verdicts(size_t* res, const u64* D, const size_t* PS, size_t nT, u32 E, u64 dstCapacity)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -189,15 +113,21 @@ __global__ __launch_bounds__(PL_THREADS) void k_planes_merge(u8* dst, const u64*
     }
 }
 
-inline bool bad_elem(unsigned E) { return E != 1 && E != 2 && E != 4 && E != 8; }
-// ceil(capacity / T) + nTensors workgroups of PL_THREADS threads in one launch
-inline bool bad_grid(u64 capacity, size_t nTensors) { return capacity >= ((u64)1 << 46) || (capacity >> PL_TILE_LOG) + 1 + nTensors >= ((u64)1 << 24); }
-inline unsigned tile_grid(u64 capacity, size_t nTensors) { return (unsigned)(((capacity + PLANES_TILE - 1) >> PL_TILE_LOG) + nTensors); }
 }   // namespace
+
+// the two per-tensor kernels on their own: the XOR forms (planes_delta.hip) launch them in front of data kernels of their own
+void launch_planes_offsets(u64* planeOff, size_t* tensorRes, const u64* srcOff, size_t nTensors, unsigned E, u64 capacity, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_planes_offsets, dim3(grid_for(nTensors + 1)), dim3(PL_THREADS), 0, s, planeOff, tensorRes, srcOff, nTensors, (u32)E, capacity);
+}
+void launch_planes_verdicts(size_t* results, const u64* dstOff, const size_t* planeSizes, size_t nTensors, unsigned E, u64 dstCapacity, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_planes_verdicts, dim3(grid_for(nTensors)), dim3(PL_THREADS), 0, s, results, dstOff, planeSizes, nTensors, (u32)E, dstCapacity);
+}
 
 hipError_t launch_planes_split(u8* planes, u64* planeOff, size_t* tensorRes, const u8* src, const u64* srcOff, size_t nTensors, unsigned E, u64 capacity, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_planes_offsets, dim3(grid_for(nTensors + 1)), dim3(PL_THREADS), 0, s, planeOff, tensorRes, srcOff, nTensors, (u32)E, capacity);
+    launch_planes_offsets(planeOff, tensorRes, srcOff, nTensors, E, capacity, s);
     if (E == 1 || nTensors == 0 || capacity == 0) return hipGetLastError();
     const dim3 g(tile_grid(capacity, nTensors)), b(PL_THREADS);
     if (E == 2) hipLaunchKernelGGL(k_planes_split<2>, g, b, 0, s, planes, src, srcOff, nTensors, capacity);
@@ -210,7 +140,7 @@ hipError_t launch_planes_merge(u8* dst, const u64* dstOff, size_t* results, cons
                                u64 dstCapacity, hipStream_t s)
 {
     if (nTensors == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_planes_verdicts, dim3(grid_for(nTensors)), dim3(PL_THREADS), 0, s, results, dstOff, planeSizes, nTensors, (u32)E, dstCapacity);
+    launch_planes_verdicts(results, dstOff, planeSizes, nTensors, E, dstCapacity, s);
     if (dstCapacity == 0) return hipGetLastError();
     const dim3 g(tile_grid(dstCapacity, nTensors)), b(PL_THREADS);
     if (E == 1) hipLaunchKernelGGL(k_planes_merge<1>, g, b, 0, s, dst, dstOff, planes, planeOff, planeSizes, nTensors, dstCapacity);

@@ -633,6 +633,45 @@ FSEHIP_API int FSEHIP_tensor_decompress_dbatch(void* d_dst, const uint64_t* d_ds
                                                void* d_planes, uint64_t planesCapacity, uint64_t* d_planeOffsets, size_t* d_planeResults,
                                                void* d_workspace, size_t workspaceBytes, void* stream);
 
+/* Tensor deltas (planes_delta.hip): the four calls above on `tensor XOR base`, the XOR fused into the two data kernels.  For a tensor the
+ * receiver already holds an earlier version of -- weights after a training step, checkpoint N + 1 next to checkpoint N, optimizer state --
+ * XOR against that version zeroes every byte that did not change; the sign / exponent plane becomes almost all zeros and the order-0 coders
+ * do the rest.  The frames are ordinary .fse frames (of the planes of `tensor XOR base`): nothing in them says that they hold a delta or
+ * against what, and pairing them with the right base is the caller's business.
+ * Semantics: those of the plain call on src XOR base, and the inverse.  Offsets, results, refusals, what is written and what is not, the
+ * work mapping, and every argument rejection (decided before any device call) are the plain call's, word for word.  In addition a null
+ * d_base is hipErrorInvalidValue, for every elemBytes; and so is a null d_planes with elemBytes == 1 in the split and the compress call: the
+ * XOR has to be written somewhere, so the `<1>` data kernel runs and the packed writer then reads d_planes, not d_src.
+ *
+ *   FSEHIP_planes_split_xor_dbatch   d_base has THE LAYOUT OF d_src: the same offsets d_srcOffsets, the same capacity.  Plane p of tensor i holds
+ *     the bytes k mod E == p of src_i XOR base_i.  A refused tensor is not read, and neither is its base.  d_planes overlaps neither d_src
+ *     nor d_base (d_src and d_base are only read and may be anything, each other included).
+ *   FSEHIP_planes_merge_xor_dbatch   d_base has THE LAYOUT OF d_dst: d_dstOffsets, dstCapacity.  A tensor whose result is n gets the n bytes
+ *     merge(planes) XOR base_i; a tensor whose result is an error is neither written nor is its base read.
+ *     IN PLACE: d_base == d_dst is allowed -- the resident tensors become the new ones where they lie.  Every byte of a tensor is read (as
+ *     base) and written by exactly one thread, the load in front of the store, so there is nothing to order between threads.  A tensor
+ *     whose result is an error leaves its slot untouched: in place, it keeps its old bytes.  ANY OTHER overlap of d_base and d_dst (a
+ *     shifted one, a partial one) is the caller's error; it is not checked and the result is undefined.  d_planes overlaps neither.
+ *   FSEHIP_tensor_compress_delta_dbatch    the XOR split, then FSEHIP_frame_compress_packed_dbatch over d_planes: frame i * E + p is byte for
+ *     byte FSEHIP_frame_compress of plane p of tensor_i XOR base_i.  An unchanged tensor costs a few bytes per plane (RLE blocks).
+ *   FSEHIP_tensor_decompress_delta_dbatch  FSEHIP_frame_decompress_packed_dbatch into d_planes, then the XOR merge against d_base; with
+ *     d_base == d_dst a tensor one of whose frames is damaged keeps the base's bytes.
+ *   Workspaces are the packed writer's / reader's, sized as for the plain calls: there is no *_workspaceSize of these.
+ * Out of scope: a base with offsets of its own (it lies where the tensors lie); arithmetic (subtract) deltas; any record in the frames that
+ * they hold a delta. */
+FSEHIP_API int FSEHIP_planes_split_xor_dbatch(void* d_planes, uint64_t* d_planeOffsets, size_t* d_tensorResults, const void* d_src, const void* d_base,
+                                              const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes, uint64_t capacity, void* stream);
+FSEHIP_API int FSEHIP_planes_merge_xor_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_planes, const uint64_t* d_planeOffsets,
+                                              const size_t* d_planeSizes, const void* d_base, size_t nTensors, unsigned elemBytes, uint64_t dstCapacity, void* stream);
+FSEHIP_API int FSEHIP_tensor_compress_delta_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
+                                                   const void* d_src, const void* d_base, const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes,
+                                                   uint64_t capacity, size_t maxTotalBlocks, unsigned blockSizeId, int codec, unsigned slotAlignLog,
+                                                   void* d_planes, uint64_t* d_planeOffsets, void* d_workspace, size_t workspaceBytes, void* stream);
+FSEHIP_API int FSEHIP_tensor_decompress_delta_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base, size_t* d_results,
+                                                     const void* d_frames, const uint64_t* d_frameOffsets, size_t nTensors, unsigned elemBytes, size_t maxTotalBlocks,
+                                                     void* d_planes, uint64_t planesCapacity, uint64_t* d_planeOffsets, size_t* d_planeResults,
+                                                     void* d_workspace, size_t workspaceBytes, void* stream);
+
 /* ---- FSE for 16-bit symbols (lib/fseU16.h:62-80, lib/fseU16.c) -- SURVEY 8(f) rank 4.  Alphabets of up to
  * FSEHIP_FSEU16_MAX_SYMBOL_VALUE + 1 symbols, table logs up to 13 (default 12), ONE tANS state per stream: a different format from
  * the byte coder's.  Sizes of the uncompressed side are in SYMBOLS (as in the reference), strides in bytes.
