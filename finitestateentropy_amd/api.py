@@ -21,6 +21,28 @@ ERROR_NAMES = {1: "GENERIC", 2: "dstSize_tooSmall", 3: "srcSize_wrong", 4: "corr
                6: "maxSymbolValue_tooLarge", 7: "maxSymbolValue_tooSmall", 8: "workSpace_tooSmall"}
 
 
+CODECS_GIVEN, CODECS_CHOOSE = 0, 1      # FSEHIP_CODECS_GIVEN / FSEHIP_CODECS_CHOOSE (include/fsehip.h)
+
+
+class AutoCodec:
+    """`codec` of compress_tensors: a codec per frame, chosen by size on the device -- Huff0 unless its frame is more than
+    tolerance_permille / 1000 larger than the FSE frame (FSEHIP_CODECS_CHOOSE, include/fsehip.h)."""
+
+    def __init__(self, tolerance_permille=0):
+        if not isinstance(tolerance_permille, numbers.Integral) or not 0 <= tolerance_permille <= 1000:
+            raise ValueError("tolerance_permille %r: 0 .. 1000" % (tolerance_permille,))
+        self.tolerance_permille = int(tolerance_permille)
+
+    def __repr__(self):
+        return "AutoCodec(%d)" % self.tolerance_permille
+
+    def __eq__(self, other):
+        return isinstance(other, AutoCodec) and other.tolerance_permille == self.tolerance_permille
+
+    def __hash__(self):
+        return hash(("AutoCodec", self.tolerance_permille))
+
+
 def fse_compress_bound(n):      # lib/fse.h:290-292
     return 512 + n + (n >> 7) + 4 + 8
 
@@ -1030,6 +1052,17 @@ def _frame_dev_methods():
             raise ValueError("frame_packed_bound(%r, %r, %r, %r)" % (total_src_bytes, n_frames, total_blocks, align_log))
         return r
 
+    def _check_packed_guard(g, doff, res, n, what):
+        """guard mode of the packed writers: nothing behind the capacity, and nothing between the frames -- the writer's contract is the frames'
+        bytes and nothing else, the padding included (include/fsehip.h)"""
+        g.check(what)
+        total = int(doff[n].item())
+        if total:
+            idx = torch.arange(total, device=doff.device)
+            slot = torch.searchsorted(doff[1:n + 1].contiguous(), idx, right=True).clamp(max=n - 1)
+            beyond = (idx - doff[slot]) >= res[slot].clamp(min=0)
+            assert bool((g.full[0, :total][beyond] == g.fill).all()), "%s wrote outside a frame's bytes" % what
+
     def frame_compress_packed_dbatch(self, src, src_offsets, block_size_id=5, codec=0, dst=None, capacity=None, max_total_blocks=None, align_log=0, dst_offsets=None,
                                      workspace=None, results=None):
         """-> (dst, dst_offsets, results): frame i = dst[dst_offsets[i] : dst_offsets[i] + results[i]], the frames back to back with every start
@@ -1067,19 +1100,75 @@ def _frame_dev_methods():
                                                             SZ(max_total_blocks), C.c_uint(block_size_id), C.c_int(codec), C.c_uint(align_log),
                                                             _ptr(workspace), SZ(workspace.numel()), _stream()), "frame_compress_packed_dbatch")
         if g is not None:
-            g.check("frame_compress_packed_dbatch")
-            # ... and between the frames: the writer's contract is the frames' bytes and nothing else, the padding included (include/fsehip.h)
-            total = int(doff[n].item())
-            if total:
-                idx = torch.arange(total, device=src.device)
-                slot = torch.searchsorted(doff[1:].contiguous(), idx, right=True).clamp(max=n - 1)
-                beyond = (idx - doff[slot]) >= res[slot].clamp(min=0)
-                assert bool((g.full[0, :total][beyond] == g.fill).all()), "frame_compress_packed_dbatch wrote outside a frame's bytes"
+            _check_packed_guard(g, doff, res, n, "frame_compress_packed_dbatch")
         return dst, doff, res
+
+    # ---- the packed writer with a codec per frame (fsehip.h, FSEHIP_frame_compress_packed_mixed_dbatch): given, or chosen by size
+    def frame_mixed_workspace_bound(self, n_frames, max_total_blocks, block_size_id=5, choose=True):
+        """the workspace of frame_compress_packed_mixed_dbatch (choose: the CHOOSE policy, else GIVEN).  Host arithmetic: needs no device."""
+        self.lib.FSEHIP_frame_mixedWorkspaceBound.restype = SZ
+        r = int(self.lib.FSEHIP_frame_mixedWorkspaceBound(SZ(int(n_frames)), SZ(int(max_total_blocks)), C.c_uint(block_size_id),
+                                                          C.c_int(CODECS_CHOOSE if choose else CODECS_GIVEN)))
+        if r >= (1 << 62):
+            raise ValueError("frame_mixed_workspace_bound(%r, %r, %r)" % (n_frames, max_total_blocks, block_size_id))
+        return r
+
+    def frame_compress_packed_mixed_dbatch(self, src, src_offsets, codecs=None, tolerance_permille=0, block_size_id=5, dst=None, capacity=None, max_total_blocks=None,
+                                           align_log=0, dst_offsets=None, workspace=None, results=None):
+        """-> (dst, dst_offsets, results, codecs): frame_compress_packed_dbatch with a codec per frame.  `codecs` given (a CUDA uint8 tensor of
+        n entries, 0 = FSE, 1 = Huff0): frame i is written with codecs[i] (any other value: -1 for that frame, which takes no room); the tensor
+        is returned as it is.  codecs None: every block goes through both coders and frame i becomes Huff0 unless its Huff0 frame is more than
+        tolerance_permille / 1000 larger than its FSE frame; the tensor returned is the choice.  A steady workload chooses once and hands the
+        codecs back in afterwards.  Everything else is frame_compress_packed_dbatch's."""
+        align_log = _align_log(align_log)
+        _flat(src, "src")
+        soff, shost = self._offsets(src_offsets, src.device, max_total_blocks is None or (dst is None and capacity is None))
+        n = soff.numel() - 1
+        choose = codecs is None
+        if choose:
+            if not isinstance(tolerance_permille, numbers.Integral) or not 0 <= tolerance_permille <= 1000:
+                raise ValueError("tolerance_permille %r: 0 .. 1000" % (tolerance_permille,))
+            cgu = _Guarded(1, n, self.guard, src.device) if self.guard > 0 else None
+            codecs = cgu.view[0] if cgu is not None else torch.empty(max(n, 1), dtype=torch.uint8, device=src.device)
+        else:
+            cgu = None
+            if not isinstance(codecs, torch.Tensor) or not codecs.is_cuda or codecs.dtype != torch.uint8 or not codecs.is_contiguous() or codecs.numel() != n:
+                raise TypeError("codecs must be a contiguous CUDA uint8 tensor of %d entries" % n)
+        if shost is not None:
+            blocks = sum(self.frame_block_count(int(x), block_size_id) for x in np.diff(shost)) if block_size_id <= 6 else 0
+        if max_total_blocks is None:
+            max_total_blocks = blocks
+        g = None
+        if dst is None:
+            if capacity is None:
+                capacity = self.frame_packed_bound(int(shost[-1] - shost[0]), n, blocks, align_log)
+            dst, g = self._dst(1, int(capacity), src.device)
+            dst = dst[0]
+        else:
+            _flat(dst, "dst")
+            capacity = dst.numel() if capacity is None else int(capacity)
+            if capacity > dst.numel():
+                raise ValueError("capacity %d: dst holds %d bytes" % (capacity, dst.numel()))
+        doff = torch.empty(n + 1, dtype=torch.int64, device=src.device) if dst_offsets is None else dst_offsets
+        res = torch.zeros(max(n, 1), dtype=torch.int64, device=src.device)[:n] if results is None else results
+        if workspace is None:
+            workspace = torch.empty(max(self.frame_mixed_workspace_bound(n, max_total_blocks, min(block_size_id, 6), choose), 1), dtype=torch.uint8, device=src.device)
+        _check(self.lib.FSEHIP_frame_compress_packed_mixed_dbatch(_ptr(dst), C.c_uint64(int(capacity)), _ptr(doff), _ptr(res), _ptr(src), _ptr(soff), SZ(n),
+                                                                  SZ(max_total_blocks), C.c_uint(block_size_id), _ptr(codecs if codecs.numel() else codecs.new_zeros(1)),
+                                                                  C.c_int(CODECS_CHOOSE if choose else CODECS_GIVEN), C.c_uint(int(tolerance_permille) if choose else 0),
+                                                                  C.c_uint(align_log), _ptr(workspace), SZ(workspace.numel()), _stream()),
+               "frame_compress_packed_mixed_dbatch")
+        if cgu is not None:
+            cgu.check("frame_compress_packed_mixed_dbatch (codecs)")
+            assert n == 0 or bool((cgu.view[0, :n] <= 1).all()), "frame_compress_packed_mixed_dbatch did not write every codec"
+        if g is not None:
+            _check_packed_guard(g, doff, res, n, "frame_compress_packed_mixed_dbatch")
+        return dst, doff, res, codecs[:n]
 
     FseHip._flat = staticmethod(_flat)
     for f in (_offsets, frame_block_count, frame_dbatch_plan, frame_dbatch_workspace, xxh32_batch, frame_compress_dbatch, frame_decompress_dbatch,
-              frame_inspect, frame_plan_dbatch, frame_decompress_packed_dbatch, frame_packed_bound, frame_compress_packed_dbatch):
+              frame_inspect, frame_plan_dbatch, frame_decompress_packed_dbatch, frame_packed_bound, frame_compress_packed_dbatch,
+              frame_mixed_workspace_bound, frame_compress_packed_mixed_dbatch):
         setattr(FseHip, f.__name__, f)
 
 
@@ -1255,17 +1344,38 @@ def _planes_methods():
         return _compress(self, src, base, src_offsets, elem_bytes, block_size_id, codec, capacity, dst, dst_capacity, max_total_blocks, align_log, frame_offsets,
                          frame_results, tensor_results, planes, plane_offsets, workspace)
 
+    def tensor_compress_mixed_dbatch(self, src, src_offsets, elem_bytes, base=None, codecs=None, tolerance_permille=0, block_size_id=5, capacity=None, dst=None,
+                                     dst_capacity=None, max_total_blocks=None, align_log=0, frame_offsets=None, frame_results=None, tensor_results=None, planes=None,
+                                     plane_offsets=None, workspace=None):
+        """-> (dst, frame_offsets, frame_results, tensor_results, codecs): tensor_compress_dbatch (base None) or tensor_compress_delta_dbatch with
+        a codec per plane, as frame_compress_packed_mixed_dbatch has it: `codecs` (a CUDA uint8 tensor of n*E entries, entry i*E+p for plane p of
+        tensor i) is given, or None -- then chosen by size at tolerance_permille and returned.  The workspace is the mixed writer's
+        (frame_mixed_workspace_bound for n*E frames)."""
+        return _compress(self, src, base, src_offsets, elem_bytes, block_size_id, None, capacity, dst, dst_capacity, max_total_blocks, align_log, frame_offsets,
+                         frame_results, tensor_results, planes, plane_offsets, workspace, mixed=(codecs, tolerance_permille))
+
     def _compress(self, src, base, src_offsets, elem_bytes, block_size_id, codec, capacity, dst, dst_capacity, max_total_blocks, align_log, frame_offsets,
-                  frame_results, tensor_results, planes, plane_offsets, workspace):
+                  frame_results, tensor_results, planes, plane_offsets, workspace, mixed=None):
         E = _elem(elem_bytes)
         align_log = _align_log(align_log)
         self._flat(src, "src")
         soff, shost = self._offsets(src_offsets, src.device, max_total_blocks is None or (dst is None and dst_capacity is None))
         n = soff.numel() - 1
         capacity = _room(self, src, capacity, "src")
-        what = "tensor_compress_dbatch" if base is None else "tensor_compress_delta_dbatch"
+        what = "tensor_compress_mixed_dbatch" if mixed is not None else "tensor_compress_dbatch" if base is None else "tensor_compress_delta_dbatch"
         if base is not None:
             _base(self, base, src, capacity, "src")
+        cgu = None
+        if mixed is not None:
+            codecs, tol = mixed
+            choose = codecs is None
+            if choose:
+                if not isinstance(tol, numbers.Integral) or not 0 <= tol <= 1000:
+                    raise ValueError("tolerance_permille %r: 0 .. 1000" % (tol,))
+                cgu = _Guarded(1, n * E, self.guard, src.device) if self.guard > 0 else None
+                codecs = cgu.view[0] if cgu is not None else torch.empty(max(n * E, 1), dtype=torch.uint8, device=src.device)
+            elif not isinstance(codecs, torch.Tensor) or not codecs.is_cuda or codecs.dtype != torch.uint8 or not codecs.is_contiguous() or codecs.numel() != n * E:
+                raise TypeError("codecs must be a contiguous CUDA uint8 tensor of %d entries" % (n * E))
         if shost is not None:
             blocks = self.planes_block_bound(int(shost[-1] - shost[0]), n, E, min(block_size_id, 6))
         if max_total_blocks is None:
@@ -1286,11 +1396,25 @@ def _planes_methods():
         fres = _i64(self, frame_results, n * E, src.device, "frame_results")
         tres = _i64(self, tensor_results, n, src.device, "tensor_results")
         poff = _i64(self, plane_offsets, n * E + 1, src.device, "plane_offsets")
-        if workspace is None:
+        if workspace is None and mixed is not None:
+            workspace = torch.empty(max(self.frame_mixed_workspace_bound(n * E, max_total_blocks, min(block_size_id, 6), choose), 1), dtype=torch.uint8, device=src.device)
+        elif workspace is None:
             self.lib.FSEHIP_frame_compress_packed_dbatch_workspaceSize.restype = SZ
             need = int(self.lib.FSEHIP_frame_compress_packed_dbatch_workspaceSize(SZ(n * E), SZ(max_total_blocks), C.c_uint(min(block_size_id, 6)),
                                                                                   C.c_int(codec if codec in (0, 1) else 0)))
             workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=src.device)
+        if mixed is not None:
+            _check(self.lib.FSEHIP_tensor_compress_mixed_dbatch(_ptr(dst), C.c_uint64(int(dst_capacity)), _ptr(foff), _ptr(fres), _ptr(tres), _ptr(src), _ptr(base),
+                                                                _ptr(soff), SZ(n), C.c_uint(E), C.c_uint64(capacity), SZ(max_total_blocks), C.c_uint(block_size_id),
+                                                                _ptr(codecs if codecs.numel() else codecs.new_zeros(1)),
+                                                                C.c_int(CODECS_CHOOSE if choose else CODECS_GIVEN), C.c_uint(int(tol) if choose else 0),
+                                                                C.c_uint(align_log), _ptr(planes), _ptr(poff), _ptr(workspace), SZ(workspace.numel()), _stream()), what)
+            if cgu is not None:
+                cgu.check(what + " (codecs)")
+                assert n == 0 or bool((cgu.view[0, :n * E] <= 1).all()), what + " did not write every codec"
+            if g is not None:
+                g.check(what)
+            return dst, foff, fres, tres, codecs[:n * E]
         tail = (SZ(n), C.c_uint(E), C.c_uint64(capacity), SZ(max_total_blocks), C.c_uint(block_size_id), C.c_int(codec), C.c_uint(align_log), _ptr(planes), _ptr(poff),
                 _ptr(workspace), SZ(workspace.numel()), _stream())
         if base is None:
@@ -1390,8 +1514,22 @@ def _planes_methods():
         group's bytes beside the inputs; the object keeps only the frames at their real total.
         base: a sequence of CUDA tensors matching `tensors` one to one in dtype, shape and device (TypeError / ValueError otherwise, before any
         launch) -- what the receiver already holds.  The frames then hold `tensor XOR base` (the object's `delta` is True), far fewer bytes where
-        most bytes did not change, and decompress_tensors needs the same base."""
+        most bytes did not change, and decompress_tensors needs the same base.
+        codec: 0 (FSE), 1 (Huff0), an AutoCodec -- every plane's frame gets the codec chosen for it by size (tensor_compress_mixed_dbatch; each
+        group dict gains "codecs", a CUDA uint8 tensor with entry i*E+p for plane p of the group's tensor i, and the object's `codec` is the
+        AutoCodec) -- or a CompressedTensors an AutoCodec call returned for tensors of the same dtypes and shapes (ValueError otherwise, before
+        any launch): its codecs are given again, nothing is tried twice."""
         tensors = list(tensors)
+        earlier = None
+        if isinstance(codec, CompressedTensors):            # the codecs an earlier AutoCodec call chose, given again
+            earlier, codec = codec, codec.codec
+            if any("codecs" not in g for g in earlier.groups):
+                raise ValueError("compress_tensors: the earlier object carries no codecs (it was not written with an AutoCodec)")
+            if len(earlier.dtypes) != len(tensors):
+                raise ValueError("compress_tensors: the earlier object holds %d tensors, %d were given" % (len(earlier.dtypes), len(tensors)))
+            for k, (t, dt, sh) in enumerate(zip(tensors, earlier.dtypes, earlier.shapes)):
+                if isinstance(t, torch.Tensor) and (t.dtype != dt or tuple(t.shape) != tuple(sh)):
+                    raise ValueError("compress_tensors: tensor %d is %s %s, the earlier object's was %s %s" % (k, t.dtype, tuple(t.shape), dt, tuple(sh)))
         if not tensors:
             if base is not None and len(list(base)):
                 raise ValueError("base: tensors for none")
@@ -1410,10 +1548,14 @@ def _planes_methods():
             raw = [tensors[i].contiguous().reshape(-1).view(torch.uint8) for i in idx]
             offs = np.concatenate([[0], np.cumsum([r.numel() for r in raw])]).astype(np.uint64)
             src = torch.cat(raw) if int(offs[-1]) else torch.zeros(1, dtype=torch.uint8, device=device)[:0]
-            if braw is None:
+            bsrc = None if braw is None else torch.cat([braw[i] for i in idx]) if int(offs[-1]) else src
+            codecs = None
+            if isinstance(codec, AutoCodec):
+                given = None if earlier is None else [g for g in earlier.groups if g["elem_bytes"] == E][0]["codecs"]
+                dst, foff, fres, tres, codecs = self.tensor_compress_mixed_dbatch(src, offs, E, bsrc, given, codec.tolerance_permille, block_size_id)
+            elif braw is None:
                 dst, foff, fres, tres = self.tensor_compress_dbatch(src, offs, E, block_size_id, codec)
             else:
-                bsrc = torch.cat([braw[i] for i in idx]) if int(offs[-1]) else src
                 dst, foff, fres, tres = self.tensor_compress_delta_dbatch(src, bsrc, offs, E, block_size_id, codec)
             got = torch.cat([foff[-1:], fres, tres]).cpu().tolist()
             if min(got) < 0:
@@ -1421,6 +1563,8 @@ def _planes_methods():
                 raise RuntimeError("compress_tensors: element size %d, frames %s failed (%s)" % (E, bad[:8], [got[1 + k] for k in bad[:8]]))
             groups.append(dict(elem_bytes=E, index=idx, sizes=[int(x) for x in np.diff(offs)], frames=dst[:got[0]].clone(), frame_offsets=foff,
                                frame_results=fres, tensor_results=tres))
+            if codecs is not None:
+                groups[-1]["codecs"] = codecs.clone()
         return CompressedTensors(groups, [t.dtype for t in tensors], [tuple(t.shape) for t in tensors], device, codec, block_size_id, braw is not None)
 
     def decompress_tensors(self, obj, base=None):
@@ -1452,7 +1596,7 @@ def _planes_methods():
         return out
 
     for f in (planes_block_bound, planes_split_dbatch, planes_merge_dbatch, tensor_compress_dbatch, tensor_decompress_dbatch, compress_tensors, decompress_tensors,
-              planes_split_xor_dbatch, planes_merge_xor_dbatch, tensor_compress_delta_dbatch, tensor_decompress_delta_dbatch):
+              planes_split_xor_dbatch, planes_merge_xor_dbatch, tensor_compress_delta_dbatch, tensor_decompress_delta_dbatch, tensor_compress_mixed_dbatch):
         setattr(FseHip, f.__name__, f)
 
 

@@ -12,6 +12,12 @@
 //                                   (per frame: its result without a capacity; the size rounded up to the slot alignment) -> scan of those
 //                                   -> k_fr_clamp: the destination offsets, an OUTPUT -> k_fw_place (per frame: does it fit its slot; magic,
 //                                   trailer) -> k_fw_assemble over the offsets just produced
+//   FSEHIP_frame_compress_packed_mixed_dbatch: the packed writer with a codec PER FRAME.  GIVEN: k_fm_route (per block, its size for its frame's
+//                                   coder and 0 for the other) -> both one-shot coders over (offset, size) views of the same blocks and slots
+//                                   -> k_fm_lens (per block: the owner's result, the record's length) -> scan -> k_fm_sizes.  CHOOSE: both coders
+//                                   over every block into slots of their own -> k_fw_lens and scan for each -> k_fm_choose (per frame: both
+//                                   sizes, the rule, the codec -- an OUTPUT).  Then, for both: scan, k_fr_clamp -> k_fm_place -> k_fm_assemble
+//                                   (magic and records by the frame's codec)
 //   FSEHIP_frame_decompress_dbatch: k_fr_count (header walk per frame) -> scan -> k_fr_clear + k_fr_fill (the block table) -> the one-shot
 //                                   FSE and Huff0 decoders over (offset, size) views of the compressed blocks, writing every block in
 //                                   place at the position its predecessors ANNOUNCE -> k_fr_expand (raw / RLE blocks) -> k_fr_settle (per
@@ -326,6 +332,103 @@ __global__ __launch_bounds__(FD_THREADS) void k_fw_assemble(u8* dst, const u64* 
     else if (bt == BT_COMPRESSED) fd_copy(out + hdr, slots + g * slotStride, r, tid, -1);
 }
 
+// ---- the mixed packed writer: a codec per frame (0 = FSE, 1 = Huff0), given by the caller or chosen by size ----
+// GIVEN, per block: its size in the size array of its frame's coder, 0 in the other's -- a block of size 0 is "not compressible" to both
+// coders after the histogram (k_fse_cprep, k_huf_cprep: result 0, nothing written to its slot), so both can share one slot array.  A
+// frame whose codec byte is neither has no coder: 0 in both.
+__global__ void k_fm_route(size_t* szF, size_t* szH, const u64* blkOff, const u32* blkFrame, const u8* codecs, size_t maxBlocks)
+{
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= maxBlocks) return;
+    const u32 f = blkFrame[g];
+    const size_t n = (size_t)(blkOff[g + 1] - blkOff[g]);
+    const u32 c = f == FD_NONE ? 2u : codecs[f];
+    szF[g] = c == 0 ? n : 0; szH[g] = c == 1 ? n : 0;
+}
+// GIVEN, behind the two coders: cres[g] (the FSE coder's) becomes the result of the block's owner, pos[g] the length of its record (k_fw_lens)
+__global__ void k_fm_lens(u64* pos, size_t* cres, const size_t* cresH, const u64* blkOff, const u32* blkFrame, const u8* codecs, size_t maxBlocks, u32 bsLog)
+{
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= maxBlocks) return;
+    u64 len = 0;
+    const u32 f = blkFrame[g];
+    if (f != FD_NONE) {
+        size_t r = cres[g];
+        if (codecs[f] == 1) { r = cresH[g]; cres[g] = r; }
+        if (!is_err(r)) {
+            const u64 n = blkOff[g + 1] - blkOff[g];
+            len = (n == ((u64)1 << bsLog) ? 1u : 3u) + (r == 0 ? n : r == 1 ? 1u : 2u + (u64)r);
+        }
+    }
+    pos[g] = len;
+}
+// GIVEN: k_fw_sizes, and GENERIC for a frame whose codec byte names no coder
+__global__ void k_fm_sizes(size_t* fsize, u64* slots, const u64* first, const u64* pos, const size_t* cres, const u8* codecs, size_t nFrames, size_t maxBlocks, u32 alignLog)
+{
+    const size_t f = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= nFrames) return;
+    const size_t r = codecs[f] > 1 ? FERR(GENERIC) : fw_result(first[f], first[f + 1], pos, cres, maxBlocks);
+    fsize[f] = r;
+    const u64 a = ((u64)1 << alignLog) - 1;
+    slots[f] = is_err(r) ? 0 : ((u64)r + a) & ~a;
+}
+// what one coder left of every block: record positions (scanned), results, slots
+struct FmSet { const u64* pos; const size_t* cres; const u8* slots; };
+// CHOOSE, per frame: F and H, the sizes of its FSE and its Huff0 frame (fw_result); Huff0 iff H * 1000 <= F * (1000 + tol); an error on
+// one side takes the other, on both sides codec 0 and F's error.  The codec is an OUTPUT; fsize and slots as k_fw_sizes leaves them.
+__global__ void k_fm_choose(u8* codecs, size_t* fsize, u64* slots, const u64* first, FmSet F, FmSet H, size_t nFrames, size_t maxBlocks, u32 tol, u32 alignLog)
+{
+    const size_t f = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= nFrames) return;
+    const size_t rF = fw_result(first[f], first[f + 1], F.pos, F.cres, maxBlocks), rH = fw_result(first[f], first[f + 1], H.pos, H.cres, maxBlocks);
+    bool huf;
+    if (is_err(rH)) huf = false;
+    else if (is_err(rF)) huf = true;
+    else huf = (u64)rH * 1000u <= (u64)rF * (u64)(1000u + tol);
+    const size_t r = huf ? rH : rF;
+    codecs[f] = huf ? 1 : 0;
+    fsize[f] = r;
+    const u64 a = ((u64)1 << alignLog) - 1;
+    slots[f] = is_err(r) ? 0 : ((u64)r + a) & ~a;
+}
+// k_fw_place with the magic of the frame's own codec
+__global__ void k_fm_place(u8* dst, const u64* dstOff, size_t* results, const size_t* fsize, const u32* hashes, const u8* codecs, size_t nFrames, u32 bsid)
+{
+    const size_t f = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= nFrames) return;
+    size_t r = fsize[f];
+    if (!is_err(r)) {
+        if (dstOff[f + 1] - dstOff[f] < (u64)r) r = FERR(dstSize_tooSmall);
+        else if (dst) fw_ends(dst + dstOff[f], r, hashes[f], bsid, (int)codecs[f]);
+    }
+    results[f] = r;
+}
+// k_fw_assemble with the block's record taken from the set of its frame's codec (GIVEN: both sets are the one there is)
+__global__ __launch_bounds__(FD_THREADS) void k_fm_assemble(u8* dst, const u64* dstOff, const size_t* results, const u8* src, const u64* blkOff, const u32* blkFrame,
+                                                            const u64* first, FmSet F, FmSet H, const u8* codecs, size_t slotStride, u32 bsLog)
+{
+    const size_t g = blockIdx.x;
+    const u32 f = blkFrame[g];
+    if (f == FD_NONE || is_err(results[f])) return;              // uniform
+    const FmSet S = codecs[f] == 1 ? H : F;
+    const u32 tid = threadIdx.x;
+    const u64 n = blkOff[g + 1] - blkOff[g];
+    const size_t r = S.cres[g];
+    const u32 bt = r == 0 ? BT_RAW : r == 1 ? BT_RLE : BT_COMPRESSED;
+    const bool full = n == ((u64)1 << bsLog);
+    u8* out = dst + dstOff[f] + 5 + (S.pos[g] - S.pos[first[f]]);
+    const u32 hdr = (full ? 1u : 3u) + (bt == BT_COMPRESSED ? 2u : 0u);
+    if (tid == 0) {
+        u32 o = 0;
+        if (full) out[o++] = (u8)((bt << 6) + 0x20);
+        else { out[o++] = (u8)(bt << 6); out[o++] = (u8)(n >> 8); out[o++] = (u8)n; }
+        if (bt == BT_COMPRESSED) { out[o++] = (u8)(r >> 8); out[o++] = (u8)r; }
+        else if (bt == BT_RLE) out[o] = src[blkOff[g]];
+    }
+    if (bt == BT_RAW) fd_copy(out + hdr, src + blkOff[g], (size_t)n, tid, -1);
+    else if (bt == BT_COMPRESSED) fd_copy(out + hdr, S.slots + g * slotStride, r, tid, -1);
+}
+
 struct FwLayout { size_t first, hashes, blkOff, blkFrame, cres, pos, partials, slots, codec, fsize, total, slotStride, codecBytes; };
 // packed: the packed writer's layout -- the fixed-slot one with the frames' results behind it
 FwLayout fw_layout(size_t nFrames, size_t maxBlocks, unsigned bsid, int codec, bool packed = false)
@@ -340,6 +443,24 @@ FwLayout fw_layout(size_t nFrames, size_t maxBlocks, unsigned bsid, int codec, b
     L.partials = carve(scan_partials(nFrames > maxBlocks ? nFrames : maxBlocks) * 8);
     L.slots = carve(maxBlocks * L.slotStride); L.codec = carve(L.codecBytes);
     L.fsize = packed ? carve((nFrames + 1) * 8) : 0;
+    L.total = p;
+    return L;
+}
+
+// The mixed writer's layout: the packed writer's with the larger of the two coder workspaces (the coders run one after the other, as the
+// reader's do), and behind it the Huff0 coder's results, then GIVEN: the two size arrays; CHOOSE: the Huff0 coder's record positions and slots.
+struct FmLayout { FwLayout w; size_t szF, szH, cres2, pos2, slots2, total; };
+FmLayout fm_layout(size_t nFrames, size_t maxBlocks, unsigned bsid, int policy)
+{
+    FmLayout L;
+    const FwLayout a = fw_layout(nFrames, maxBlocks, bsid, 0, true), b = fw_layout(nFrames, maxBlocks, bsid, 1, true);
+    L.w = a.codecBytes >= b.codecBytes ? a : b;
+    size_t p = L.w.total;
+    auto carve = [&](size_t bytes) { const size_t r = p; p += up256(bytes); return r; };
+    L.cres2 = carve(maxBlocks * 8);
+    L.szF = L.szH = L.pos2 = L.slots2 = 0;
+    if (policy == FSEHIP_CODECS_GIVEN) { L.szF = carve(maxBlocks * 8); L.szH = carve(maxBlocks * 8); }
+    else { L.pos2 = carve((maxBlocks + 1) * 8); L.slots2 = carve(maxBlocks * L.w.slotStride); }
     L.total = p;
     return L;
 }
@@ -640,26 +761,34 @@ extern "C" size_t FSEHIP_frame_compress_dbatch_workspaceSize(size_t nFrames, siz
     return fw_layout(nFrames, maxTotalBlocks, blockSizeId, codec).total;
 }
 
-// the writer up to the record positions: block counts and their scan (`first`), the trailers' hashes, every block of every content through the
-// one-shot coder into its workspace slot (`cres`), the records' lengths and their scan (`pos`) -- all in the workspace
+// the writer's first steps: block counts and their scan (`first`), the trailers' hashes, where every block starts and whose it is -- in the workspace
+static int fw_blocks(const u8* src, const u64* srcOff, size_t nFrames, size_t nb, u32 bsLog, u8* ws, const FwLayout& L, hipStream_t s)
+{
+    u64* const first = (u64*)(ws + L.first);
+    hipLaunchKernelGGL(k_fw_counts, dim3(grid_for(nFrames)), dim3(FD_THREADS), 0, s, first, srcOff, nFrames, bsLog);
+    CKE(launch_exscan(first, nFrames, (u64*)(ws + L.partials), s));
+    CKE(launch_xxh32((u32*)(ws + L.hashes), src, srcOff, nullptr, nFrames, 0, s));
+    if (nb) hipLaunchKernelGGL(k_fw_blocks, dim3(grid_for(nb + 1)), dim3(FD_THREADS), 0, s, (u64*)(ws + L.blkOff), (u32*)(ws + L.blkFrame), (const u64*)first, srcOff, nFrames, nb, bsLog);
+    return (int)hipGetLastError();
+}
+// every block of the view in one call of the one-shot coder (frame.hip:118-119: default table logs, alphabet 255, slot = capacity)
+static int fw_code(int codec, u8* slots, size_t* cres, const BlockView& v, size_t nb, u8* ws, const FwLayout& L, hipStream_t s)
+{
+    if (codec == 1) return huf_compress_view(4, slots, L.slotStride, L.slotStride, cres, v, 255, FSEHIP_HUF_TABLELOG_DEFAULT, nb, ws + L.codec, L.codecBytes, s);
+    return fse_compress_view(slots, L.slotStride, L.slotStride, cres, v, 255, FSEHIP_FSE_DEFAULT_TABLELOG, nb, ws + L.codec, L.codecBytes, s);
+}
+// the writer up to the record positions: fw_blocks, every block of every content through the one-shot coder into its workspace slot
+// (`cres`), the records' lengths and their scan (`pos`) -- all in the workspace
 static int fw_encode(const u8* src, const u64* srcOff, size_t nFrames, size_t nb, u32 bsLog, int codec, u8* ws, const FwLayout& L, hipStream_t s)
 {
-    u64* const first = (u64*)(ws + L.first); u32* const hashes = (u32*)(ws + L.hashes);
-    u64* const blkOff = (u64*)(ws + L.blkOff); u32* const blkFrame = (u32*)(ws + L.blkFrame);
-    size_t* const cres = (size_t*)(ws + L.cres); u64* const pos = (u64*)(ws + L.pos); u64* const partials = (u64*)(ws + L.partials);
-    u8* const slots = ws + L.slots;
-    hipLaunchKernelGGL(k_fw_counts, dim3(grid_for(nFrames)), dim3(FD_THREADS), 0, s, first, srcOff, nFrames, bsLog);
-    CKE(launch_exscan(first, nFrames, partials, s));
-    CKE(launch_xxh32(hashes, src, srcOff, nullptr, nFrames, 0, s));
+    u64* const blkOff = (u64*)(ws + L.blkOff);
+    size_t* const cres = (size_t*)(ws + L.cres); u64* const pos = (u64*)(ws + L.pos);
+    CKI(fw_blocks(src, srcOff, nFrames, nb, bsLog, ws, L, s));
     if (nb) {
-        hipLaunchKernelGGL(k_fw_blocks, dim3(grid_for(nb + 1)), dim3(FD_THREADS), 0, s, blkOff, blkFrame, (const u64*)first, srcOff, nFrames, nb, bsLog);
-        CKE(hipGetLastError());
         BlockView v; v.base = src; v.stride = 0; v.sizes = nullptr; v.uniform = 0; v.offsets = blkOff;
-        // every block of every content in one call of the one-shot coder (frame.hip:118-119: default table logs, alphabet 255, slot = capacity)
-        if (codec == 1) CKI(huf_compress_view(4, slots, L.slotStride, L.slotStride, cres, v, 255, FSEHIP_HUF_TABLELOG_DEFAULT, nb, ws + L.codec, L.codecBytes, s));
-        else CKI(fse_compress_view(slots, L.slotStride, L.slotStride, cres, v, 255, FSEHIP_FSE_DEFAULT_TABLELOG, nb, ws + L.codec, L.codecBytes, s));
-        hipLaunchKernelGGL(k_fw_lens, dim3(grid_for(nb)), dim3(FD_THREADS), 0, s, pos, (const size_t*)cres, (const u64*)blkOff, (const u32*)blkFrame, nb, bsLog);
-        CKE(launch_exscan(pos, nb, partials, s));
+        CKI(fw_code(codec, ws + L.slots, cres, v, nb, ws, L, s));
+        hipLaunchKernelGGL(k_fw_lens, dim3(grid_for(nb)), dim3(FD_THREADS), 0, s, pos, (const size_t*)cres, (const u64*)blkOff, (const u32*)(ws + L.blkFrame), nb, bsLog);
+        CKE(launch_exscan(pos, nb, (u64*)(ws + L.partials), s));
     }
     return (int)hipGetLastError();
 }
@@ -732,6 +861,75 @@ extern "C" int FSEHIP_frame_compress_packed_dbatch(void* d_dst, uint64_t dstCapa
                        (const u32*)(ws + L.hashes), nFrames, blockSizeId, codec);
     if (!d_dst) return (int)hipGetLastError();               // the sizing query: offsets and results, no frame
     return fw_assemble((u8*)d_dst, (const u64*)dstOff, (const size_t*)d_results, (const u8*)d_src, nb, bsLog, ws, L, s);
+}
+
+extern "C" size_t FSEHIP_frame_mixedWorkspaceBound(size_t nFrames, size_t maxTotalBlocks, unsigned blockSizeId, int policy)
+{
+    if (blockSizeId > MAX_BSID || (policy != FSEHIP_CODECS_GIVEN && policy != FSEHIP_CODECS_CHOOSE)) return FSEHIP_ERROR(GENERIC);
+    return fm_layout(nFrames, maxTotalBlocks, blockSizeId, policy).total;
+}
+
+extern "C" int FSEHIP_frame_compress_packed_mixed_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_dstOffsets, size_t* d_results, const void* d_src,
+                                                         const uint64_t* d_srcOffsets, size_t nFrames, size_t maxTotalBlocks, unsigned blockSizeId,
+                                                         uint8_t* d_codecs, int policy, unsigned tolerancePermille, unsigned slotAlignLog,
+                                                         void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    const bool choose = policy == FSEHIP_CODECS_CHOOSE;
+    if (blockSizeId > MAX_BSID || (!choose && policy != FSEHIP_CODECS_GIVEN) || slotAlignLog > 12 || !d_codecs) return (int)hipErrorInvalidValue;
+    if (choose && tolerancePermille > 1000) return (int)hipErrorInvalidValue;
+    if ((uintptr_t)d_workspace & 255u) return (int)hipErrorInvalidValue;
+    if (maxTotalBlocks >= ((size_t)1 << 31) || nFrames >= ((size_t)1 << 31)) return (int)hipErrorInvalidValue;
+    const FmLayout M = fm_layout(nFrames, maxTotalBlocks, blockSizeId, policy);
+    if (workspaceBytes < M.total) return (int)hipErrorInvalidValue;
+    const FwLayout& L = M.w;
+    u8* const ws = (u8*)d_workspace;
+    const u8* const src = (const u8*)d_src;
+    const u64* const srcOff = (const u64*)d_srcOffsets; u64* const dstOff = (u64*)d_dstOffsets;
+    const u64* const first = (const u64*)(ws + L.first); const u64* const blkOff = (const u64*)(ws + L.blkOff); const u32* const blkFrame = (const u32*)(ws + L.blkFrame);
+    size_t* const cres = (size_t*)(ws + L.cres); size_t* const cres2 = (size_t*)(ws + M.cres2);
+    u64* const pos = (u64*)(ws + L.pos); u64* const partials = (u64*)(ws + L.partials);
+    size_t* const fsize = (size_t*)(ws + L.fsize);
+    const u32 bsLog = 10 + blockSizeId;
+    const size_t nb = maxTotalBlocks;
+    FmSet F, H;
+    F.pos = pos; F.cres = cres; F.slots = ws + L.slots;
+    H = F;
+    if (choose) { H.pos = (const u64*)(ws + M.pos2); H.cres = cres2; H.slots = ws + M.slots2; }
+    if (nFrames) {
+        CKI(fw_blocks(src, srcOff, nFrames, nb, bsLog, ws, L, s));
+        BlockView v; v.base = src; v.stride = 0; v.sizes = nullptr; v.uniform = 0; v.offsets = blkOff;
+        if (nb && !choose) {
+            size_t* const szF = (size_t*)(ws + M.szF); size_t* const szH = (size_t*)(ws + M.szH);
+            hipLaunchKernelGGL(k_fm_route, dim3(grid_for(nb)), dim3(FD_THREADS), 0, s, szF, szH, blkOff, blkFrame, (const u8*)d_codecs, nb);
+            CKE(hipGetLastError());
+            v.sizes = szF; CKI(fw_code(0, ws + L.slots, cres, v, nb, ws, L, s));
+            v.sizes = szH; CKI(fw_code(1, ws + L.slots, cres2, v, nb, ws, L, s));
+            hipLaunchKernelGGL(k_fm_lens, dim3(grid_for(nb)), dim3(FD_THREADS), 0, s, pos, cres, (const size_t*)cres2, blkOff, blkFrame, (const u8*)d_codecs, nb, bsLog);
+            CKE(launch_exscan(pos, nb, partials, s));
+        } else if (nb) {
+            u64* const pos2 = (u64*)(ws + M.pos2);
+            CKI(fw_code(0, ws + L.slots, cres, v, nb, ws, L, s));
+            CKI(fw_code(1, ws + M.slots2, cres2, v, nb, ws, L, s));
+            hipLaunchKernelGGL(k_fw_lens, dim3(grid_for(nb)), dim3(FD_THREADS), 0, s, pos, (const size_t*)cres, blkOff, blkFrame, nb, bsLog);
+            CKE(launch_exscan(pos, nb, partials, s));
+            hipLaunchKernelGGL(k_fw_lens, dim3(grid_for(nb)), dim3(FD_THREADS), 0, s, pos2, (const size_t*)cres2, blkOff, blkFrame, nb, bsLog);
+            CKE(launch_exscan(pos2, nb, partials, s));
+        }
+        if (choose) hipLaunchKernelGGL(k_fm_choose, dim3(grid_for(nFrames)), dim3(FD_THREADS), 0, s, (u8*)d_codecs, fsize, dstOff, first, F, H, nFrames, nb,
+                                       (u32)tolerancePermille, (u32)slotAlignLog);
+        else hipLaunchKernelGGL(k_fm_sizes, dim3(grid_for(nFrames)), dim3(FD_THREADS), 0, s, fsize, dstOff, first, (const u64*)pos, (const size_t*)cres, (const u8*)d_codecs,
+                                nFrames, nb, (u32)slotAlignLog);
+    }
+    CKE(launch_exscan(dstOff, nFrames, partials, s));
+    hipLaunchKernelGGL(k_fr_clamp, dim3(grid_for(nFrames + 1)), dim3(FD_THREADS), 0, s, dstOff, nFrames + 1, (u64)dstCapacity);
+    CKE(hipGetLastError());
+    if (nFrames == 0) return 0;
+    hipLaunchKernelGGL(k_fm_place, dim3(grid_for(nFrames)), dim3(FD_THREADS), 0, s, (u8*)d_dst, (const u64*)dstOff, d_results, (const size_t*)fsize,
+                       (const u32*)(ws + L.hashes), (const u8*)d_codecs, nFrames, blockSizeId);
+    if (d_dst && nb) hipLaunchKernelGGL(k_fm_assemble, dim3((unsigned)nb), dim3(FD_THREADS), 0, s, (u8*)d_dst, (const u64*)dstOff, (const size_t*)d_results, src, blkOff, blkFrame,
+                                        first, F, H, (const u8*)d_codecs, L.slotStride, bsLog);
+    return (int)hipGetLastError();
 }
 
 extern "C" size_t FSEHIP_frame_decompress_dbatch_workspaceSize(size_t nFrames, size_t maxTotalBlocks) { return fr_layout(nFrames, maxTotalBlocks).total; }

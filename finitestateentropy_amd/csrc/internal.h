@@ -13,8 +13,8 @@ static inline BlockView mkview(const void* base, size_t stride, const size_t* si
 static inline BlockView subview(const BlockView& v, size_t b0)      // blocks b0.. of a view
 {
     BlockView r = v;
-    if (v.offsets) r.offsets = v.offsets + b0;
-    else { r.base = v.base + b0 * v.stride; r.sizes = v.sizes ? v.sizes + b0 : nullptr; }
+    if (v.offsets) r.offsets = v.offsets + b0; else r.base = v.base + b0 * v.stride;
+    r.sizes = v.sizes ? v.sizes + b0 : nullptr;                    // (with offsets too: the (offset, size) views of the device frame calls)
     return r;
 }
 

@@ -165,6 +165,33 @@ extern "C" int FSEHIP_tensor_compress_delta_dbatch(void* d_dst, uint64_t dstCapa
                                                slotAlignLog, d_workspace, workspaceBytes, stream);
 }
 
+// the plain (d_base == nullptr) or the XOR split, then the packed writer with a codec per plane; the argument checks of both steps in front
+// of the first launch
+extern "C" int FSEHIP_tensor_compress_mixed_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
+                                                   const void* d_src, const void* d_base, const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes,
+                                                   uint64_t capacity, size_t maxTotalBlocks, unsigned blockSizeId, uint8_t* d_codecs, int policy,
+                                                   unsigned tolerancePermille, unsigned slotAlignLog, void* d_planes, uint64_t* d_planeOffsets,
+                                                   void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    if (bad_elem(elemBytes) || !d_frameOffsets || !d_frameResults || !d_tensorResults || !d_src || !d_srcOffsets || !d_planeOffsets || !d_codecs ||
+        ((elemBytes > 1 || d_base) && !d_planes))
+        return (int)hipErrorInvalidValue;
+    if (nTensors >= ((size_t)1 << 31) / elemBytes || bad_grid(capacity, nTensors)) return (int)hipErrorInvalidValue;
+    if (blockSizeId > 6 || (policy != FSEHIP_CODECS_GIVEN && policy != FSEHIP_CODECS_CHOOSE) || (policy == FSEHIP_CODECS_CHOOSE && tolerancePermille > 1000) ||
+        slotAlignLog > 12 || ((uintptr_t)d_workspace & 255u) || maxTotalBlocks >= ((size_t)1 << 31))
+        return (int)hipErrorInvalidValue;
+    const size_t nFrames = nTensors * elemBytes;
+    if (workspaceBytes < FSEHIP_frame_mixedWorkspaceBound(nFrames, maxTotalBlocks, blockSizeId, policy)) return (int)hipErrorInvalidValue;
+    const hipError_t e = d_base ? launch_split_xor((u8*)d_planes, (u64*)d_planeOffsets, d_tensorResults, (const u8*)d_src, (const u8*)d_base, (const u64*)d_srcOffsets,
+                                                   nTensors, elemBytes, capacity, (hipStream_t)stream)
+                                : launch_planes_split((u8*)d_planes, (u64*)d_planeOffsets, d_tensorResults, (const u8*)d_src, (const u64*)d_srcOffsets, nTensors, elemBytes,
+                                                      capacity, (hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
+    return FSEHIP_frame_compress_packed_mixed_dbatch(d_dst, dstCapacity, d_frameOffsets, d_frameResults, !d_base && elemBytes == 1 ? d_src : d_planes, d_planeOffsets,
+                                                     nFrames, maxTotalBlocks, blockSizeId, d_codecs, policy, tolerancePermille, slotAlignLog, d_workspace, workspaceBytes,
+                                                     stream);
+}
+
 extern "C" int FSEHIP_tensor_decompress_delta_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base, size_t* d_results,
                                                      const void* d_frames, const uint64_t* d_frameOffsets, size_t nTensors, unsigned elemBytes, size_t maxTotalBlocks,
                                                      void* d_planes, uint64_t planesCapacity, uint64_t* d_planeOffsets, size_t* d_planeResults,

@@ -485,6 +485,28 @@ FSEHIP_API size_t FSEHIP_frame_decompress_batch(void* const* dsts, const size_t*
  *     slotAlignLog: a reader's header walk stops at the frame's end mark, so the unwritten padding behind a frame is never interpreted.
  *     Writer and reader thus chain on one stream, or in one graph, without a byte or a size leaving the device.
  *
+ *   FSEHIP_frame_compress_packed_mixed_dbatch   the packed writer with a codec PER FRAME (the magic is per frame, and the readers take FSE and
+ *     Huff0 frames mixed in one call).  d_codecs has nFrames bytes, 0 = FSE, 1 = Huff0.  Everything not named here is the packed writer's
+ *     contract: launches on `stream` only, capturable, no size leaves the device; dstCapacity, maxTotalBlocks, slotAlignLog, the sizing query
+ *     with d_dst == NULL, dstSize_tooSmall for a frame the capacity cuts short, nothing written outside the frames' bytes, argument errors
+ *     (also: a policy that is neither of the two, a null d_codecs) decided before any device call.
+ *     policy FSEHIP_CODECS_GIVEN: d_codecs is an INPUT.  Frame i is byte for byte FSEHIP_frame_compress(content i, blockSizeId, d_codecs[i]);
+ *     each block is coded by its frame's coder only.  A d_codecs[i] above 1 gives frame i the result GENERIC: it takes no room, nothing of it
+ *     is written, its neighbours are unaffected.  tolerancePermille is ignored.  With all codecs 0 (or all 1) d_dst, d_dstOffsets and d_results
+ *     are the packed writer's with codec 0 (or 1), bit for bit.
+ *     policy FSEHIP_CODECS_CHOOSE: d_codecs is an OUTPUT, written in full (nFrames bytes, no other) in the sizing query too.  Every block goes
+ *     through BOTH one-shot coders -- a trial, not an estimate: with F and H what FSEHIP_frame_compress returns for content i at
+ *     FSEHIP_frame_compressBound with codec 0 and 1, the frame is Huff0 iff H * 1000 <= F * (1000 + tolerancePermille) in 64-bit integers
+ *     ("Huff0 unless it costs more than the tolerance over FSE").  If exactly one of F and H is an error the other codec is taken; if both
+ *     are (a frame beyond the block promise), the codec is 0 and the result F's.  The choice does not depend on dstCapacity.  The frame
+ *     written is byte for byte the GIVEN frame of the chosen codec.  tolerancePermille > 1000: hipErrorInvalidValue.  A steady workload calls
+ *     CHOOSE once and GIVEN afterwards with the codecs it got back.
+ *   FSEHIP_frame_mixedWorkspaceBound   host arithmetic (works without a device): the workspace of the call above.  With P(c) =
+ *     FSEHIP_frame_compress_packed_dbatch_workspaceSize(nFrames, maxTotalBlocks, blockSizeId, c), R(x) = x rounded up to 256 and B =
+ *     maxTotalBlocks -- GIVEN: max(P(0), P(1)) + 3 * R(8 * B) (the coders share one coder workspace serially; two per-block size arrays, one
+ *     more per-block result array).  CHOOSE: max(P(0), P(1)) + R(8 * B) + R(8 * (B + 1)) + R(B * slot), slot = FSE_compressBound(block size)
+ *     rounded up to 16 (the second coder's results, record positions and slots) -- less than P(0) + P(1).  A bad blockSizeId or policy: GENERIC.
+ *
  *   FSEHIP_frame_decompress_dbatch   (FIO_decompressFilename, fileio.c:462-626, over many frames)
  *     frame i = d_frames[d_frameOffsets[i] .. d_frameOffsets[i+1]), regenerated at d_dst + d_dstOffsets[i], capacity d_dstOffsets[i+1] -
  *     d_dstOffsets[i].  Frames describe themselves: codecs and block-size ids may differ inside one call.  d_results[i] = what
@@ -551,6 +573,13 @@ FSEHIP_API int FSEHIP_frame_compress_packed_dbatch(void* d_dst, uint64_t dstCapa
                                                    const void* d_src, const uint64_t* d_srcOffsets, size_t nFrames, size_t maxTotalBlocks,
                                                    unsigned blockSizeId, int codec, unsigned slotAlignLog,
                                                    void* d_workspace, size_t workspaceBytes, void* stream);
+#define FSEHIP_CODECS_GIVEN  0   /* d_codecs is an INPUT: nFrames bytes, 0 = FSE, 1 = Huff0 */
+#define FSEHIP_CODECS_CHOOSE 1   /* d_codecs is an OUTPUT: the codec chosen per frame */
+FSEHIP_API size_t FSEHIP_frame_mixedWorkspaceBound(size_t nFrames, size_t maxTotalBlocks, unsigned blockSizeId, int policy);
+FSEHIP_API int FSEHIP_frame_compress_packed_mixed_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_dstOffsets, size_t* d_results,
+                                                         const void* d_src, const uint64_t* d_srcOffsets, size_t nFrames, size_t maxTotalBlocks,
+                                                         unsigned blockSizeId, uint8_t* d_codecs, int policy, unsigned tolerancePermille,
+                                                         unsigned slotAlignLog, void* d_workspace, size_t workspaceBytes, void* stream);
 FSEHIP_API size_t FSEHIP_frame_decompress_dbatch_workspaceSize(size_t nFrames, size_t maxTotalBlocks);
 FSEHIP_API int FSEHIP_frame_decompress_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_frames, const uint64_t* d_frameOffsets,
                                               size_t nFrames, size_t maxTotalBlocks, void* d_workspace, size_t workspaceBytes, void* stream);
@@ -657,6 +686,12 @@ FSEHIP_API int FSEHIP_tensor_decompress_dbatch(void* d_dst, const uint64_t* d_ds
  *   FSEHIP_tensor_decompress_delta_dbatch  FSEHIP_frame_decompress_packed_dbatch into d_planes, then the XOR merge against d_base; with
  *     d_base == d_dst a tensor one of whose frames is damaged keeps the base's bytes.
  *   Workspaces are the packed writer's / reader's, sized as for the plain calls: there is no *_workspaceSize of these.
+ *   FSEHIP_tensor_compress_mixed_dbatch    d_base == NULL: FSEHIP_planes_split_dbatch, otherwise FSEHIP_planes_split_xor_dbatch; then
+ *     FSEHIP_frame_compress_packed_mixed_dbatch over the nTensors * E planes.  d_codecs has nTensors * E entries, entry i * E + p belongs to
+ *     plane p of tensor i; policy and tolerancePermille are the mixed writer's.  All other rules are those of FSEHIP_tensor_compress_dbatch /
+ *     _delta_dbatch: refused tensors, elemBytes == 1 with a null d_planes in the plain form only, what has been written when a later check
+ *     refuses.  The workspace is the mixed writer's: FSEHIP_frame_mixedWorkspaceBound(nTensors * E, maxTotalBlocks, blockSizeId, policy).
+ *     Nothing changes on the reading side: FSEHIP_tensor_decompress_dbatch / _delta_dbatch read such frames as they read any.
  * Out of scope: a base with offsets of its own (it lies where the tensors lie); arithmetic (subtract) deltas; any record in the frames that
  * they hold a delta. */
 FSEHIP_API int FSEHIP_planes_split_xor_dbatch(void* d_planes, uint64_t* d_planeOffsets, size_t* d_tensorResults, const void* d_src, const void* d_base,
@@ -667,6 +702,11 @@ FSEHIP_API int FSEHIP_tensor_compress_delta_dbatch(void* d_dst, uint64_t dstCapa
                                                    const void* d_src, const void* d_base, const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes,
                                                    uint64_t capacity, size_t maxTotalBlocks, unsigned blockSizeId, int codec, unsigned slotAlignLog,
                                                    void* d_planes, uint64_t* d_planeOffsets, void* d_workspace, size_t workspaceBytes, void* stream);
+FSEHIP_API int FSEHIP_tensor_compress_mixed_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
+                                                   const void* d_src, const void* d_base, const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes,
+                                                   uint64_t capacity, size_t maxTotalBlocks, unsigned blockSizeId, uint8_t* d_codecs, int policy,
+                                                   unsigned tolerancePermille, unsigned slotAlignLog, void* d_planes, uint64_t* d_planeOffsets,
+                                                   void* d_workspace, size_t workspaceBytes, void* stream);
 FSEHIP_API int FSEHIP_tensor_decompress_delta_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base, size_t* d_results,
                                                      const void* d_frames, const uint64_t* d_frameOffsets, size_t nTensors, unsigned elemBytes, size_t maxTotalBlocks,
                                                      void* d_planes, uint64_t planesCapacity, uint64_t* d_planeOffsets, size_t* d_planeResults,
