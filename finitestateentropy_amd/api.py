@@ -1182,7 +1182,10 @@ class CompressedTensors:
     """What compress_tensors returns: per group of tensors of one element size the packed frames (a CUDA uint8 tensor cut to their real total),
     their offsets and results and the split's tensor results (CUDA int64 tensors), and per tensor its dtype, shape and device.  `delta`: the
     frames hold `tensor XOR base` (compress_tensors with base=...) and decompress_tensors needs the same base again; the frames themselves do
-    not say so."""
+    not say so.  `segment_log` (None, or the integer compress_tensors_segmented set): every plane is cut into segments of 1 << segment_log
+    bytes with a frame each; frame_offsets, frame_results and codecs are then per segment and every group carries `seg_first` (numpy uint64,
+    the first segment of every plane and the segment count)."""
+    segment_log = None
 
     def __init__(self, groups, dtypes, shapes, device, codec, block_size_id, delta=False):
         self.groups, self.dtypes, self.shapes, self.device, self.codec, self.block_size_id = groups, dtypes, shapes, device, codec, block_size_id
@@ -1493,6 +1496,217 @@ def _planes_methods():
             g.check(what)
         return dst, res
 
+    # ---- segmented planes (csrc/planes_seg.hip; fsehip.h "segmented planes"): one frame per segment of 1 << segment_log bytes of a plane
+    def _seg_log(segment_log, block_size_id=0):
+        if not isinstance(segment_log, numbers.Integral) or isinstance(segment_log, bool) or not 10 + block_size_id <= segment_log <= 30:
+            raise ValueError("segment_log %r: %d .. 30 (a segment is a whole number of blocks)" % (segment_log, 10 + block_size_id))
+        return int(segment_log)
+
+    def planes_segment_first(self, sizes, elem_bytes, segment_log):
+        """tensor sizes in bytes -> seg_first (numpy uint64, len(sizes) * E + 1 entries): the index of the first segment of every plane, the last
+        entry the number of segments.  A plane of s bytes has max(1, ceil(s / (1 << segment_log))) segments.  Host arithmetic with numpy: needs
+        no device.  ValueError for a bad elem_bytes or segment_log, and for 2^31 segments or more."""
+        E, L = _elem(elem_bytes), _seg_log(segment_log)
+        n = np.asarray(list(sizes), dtype=np.int64).reshape(-1, 1)
+        if n.size and int(n.min()) < 0:
+            raise ValueError("sizes: negative")
+        p = np.arange(E, dtype=np.int64).reshape(1, -1)
+        psize = np.where(n > p, (n - p + E - 1) // E, 0)
+        cnt = np.maximum(1, (psize + (1 << L) - 1) >> L).reshape(-1)
+        first = np.concatenate([[0], np.cumsum(cnt, dtype=np.int64)])
+        if int(first[-1]) >= 1 << 31:
+            raise ValueError("planes_segment_first: %d segments, fewer than 2^31 are allowed" % int(first[-1]))
+        return first.astype(np.uint64)
+
+    def _seg_first(self, seg_first, n_segments, device, n_planes):
+        sf, host = self._offsets(seg_first, device, n_segments is None)
+        if sf.numel() != n_planes + 1:
+            raise ValueError("seg_first: one entry per plane (%d) and one more" % n_planes)
+        return sf, int(host[-1]) if n_segments is None else int(n_segments)
+
+    def planes_segments_dbatch(self, plane_offsets, src_offsets, seg_first, elem_bytes, segment_log, n_segments=None, tensor_results=None, seg_offsets=None):
+        """-> (seg_offsets, tensor_results): plane_offsets as planes_split_dbatch leaves them -> the offset of every segment in the planes buffer
+        (n_segments + 1 entries: the src_offsets of the packed writers).  A tensor whose counts in seg_first are not those its size implies
+        gets -1 in tensor_results (given: updated in place; None: zeros elsewhere) and entries equal to its start.  seg_first on the device
+        needs n_segments, else it is read from the host copy."""
+        E, L = _elem(elem_bytes), _seg_log(segment_log)
+        poff = plane_offsets
+        if not isinstance(poff, torch.Tensor) or not poff.is_cuda or poff.dtype != torch.int64 or not poff.is_contiguous():
+            raise TypeError("plane_offsets must be a contiguous CUDA int64 tensor")
+        soff, _ = self._offsets(src_offsets, poff.device, False)
+        n = soff.numel() - 1
+        if poff.numel() < n * E + 1:
+            raise ValueError("plane_offsets: one entry per plane (%d) and one more" % (n * E))
+        sf, nseg = _seg_first(self, seg_first, n_segments, poff.device, n * E)
+        g = None
+        if seg_offsets is None:
+            seg_offsets, g = self._dst(1, nseg + 1, poff.device, dtype=torch.int64)
+            seg_offsets = seg_offsets[0]
+        so = _i64(self, seg_offsets, nseg + 1, poff.device, "seg_offsets")
+        tres = _i64(self, tensor_results, n, poff.device, "tensor_results")
+        _check(self.lib.FSEHIP_planes_segments_dbatch(_ptr(so), _ptr(tres), _ptr(poff), _ptr(soff), _ptr(sf), SZ(n), C.c_uint(E), SZ(nseg), C.c_uint(L), _stream()),
+               "planes_segments_dbatch")
+        if g is not None:
+            g.check("planes_segments_dbatch")
+        return so, tres
+
+    def planes_fold_segments_dbatch(self, seg_offsets, seg_results, seg_first, segment_log, n_segments=None, plane_offsets=None, plane_sizes=None):
+        """-> (plane_offsets, plane_sizes): what frame_decompress_packed_dbatch returns per segment (dst_offsets, results) -> per plane its
+        first segment's offset and its size, or -1 (no segment), the first error among its segments, -4 (segments that are not full, or do not
+        lie back to back): what planes_merge_dbatch takes."""
+        L = _seg_log(segment_log)
+        if not isinstance(seg_offsets, torch.Tensor) or not seg_offsets.is_cuda or seg_offsets.dtype != torch.int64 or not seg_offsets.is_contiguous():
+            raise TypeError("seg_offsets must be a contiguous CUDA int64 tensor")
+        dev = seg_offsets.device
+        sf, host = self._offsets(seg_first, dev, n_segments is None)
+        nseg = int(host[-1]) if n_segments is None else int(n_segments)
+        npl = sf.numel() - 1
+        if seg_offsets.numel() < nseg + 1:
+            raise ValueError("seg_offsets: one entry per segment (%d) and one more" % nseg)
+        sres = _i64(self, seg_results, nseg, dev, "seg_results")
+        g = []
+        if plane_offsets is None:
+            plane_offsets, x = self._dst(1, npl, dev, dtype=torch.int64)
+            plane_offsets = plane_offsets[0]
+            g.append(x)
+        if plane_sizes is None:
+            plane_sizes, x = self._dst(1, npl, dev, dtype=torch.int64)
+            plane_sizes = plane_sizes[0]
+            g.append(x)
+        po = _i64(self, plane_offsets, npl, dev, "plane_offsets")
+        ps = _i64(self, plane_sizes, npl, dev, "plane_sizes")
+        _check(self.lib.FSEHIP_planes_fold_segments_dbatch(_ptr(po), _ptr(ps), _ptr(seg_offsets), _ptr(sres), _ptr(sf), SZ(npl), SZ(nseg), C.c_uint(L), _stream()),
+               "planes_fold_segments_dbatch")
+        for x in g:
+            if x is not None:
+                x.check("planes_fold_segments_dbatch")
+        return po[:npl], ps[:npl]
+
+    def tensor_compress_seg_dbatch(self, src, src_offsets, elem_bytes, segment_log, seg_first=None, n_segments=None, base=None, codec=0, codecs=None,
+                                   block_size_id=5, capacity=None, dst=None, dst_capacity=None, max_total_blocks=None, align_log=0, frame_offsets=None,
+                                   frame_results=None, tensor_results=None, planes=None, plane_offsets=None, seg_offsets=None, workspace=None):
+        """-> (dst, frame_offsets, frame_results, tensor_results, codecs): the split (against `base` if one is given), planes_segments_dbatch,
+        then the packed writer over the segments -- frame q = dst[frame_offsets[q] : .. + frame_results[q]] is the .fse frame of segment
+        q - seg_first[j] of the plane j that holds it.  codec 0 / 1: the packed writer, codecs returned None.  codec an AutoCodec: a codec per
+        segment chosen by size and returned; `codecs` (CUDA uint8, one per segment): given.  seg_first None: planes_segment_first of the
+        sizes; on the device it needs n_segments.  planes, plane_offsets (n*E+1) and seg_offsets (n_segments+1) are scratch; the workspace is
+        the (mixed) writer's for n_segments frames.  With everything given and the offsets on the device the call is launches only."""
+        E = _elem(elem_bytes)
+        align_log = _align_log(align_log)
+        L = _seg_log(segment_log, min(block_size_id, 6))
+        self._flat(src, "src")
+        soff, shost = self._offsets(src_offsets, src.device, seg_first is None or max_total_blocks is None or (dst is None and dst_capacity is None))
+        n = soff.numel() - 1
+        capacity = _room(self, src, capacity, "src")
+        what = "tensor_compress_seg_dbatch"
+        if base is not None:
+            _base(self, base, src, capacity, "src")
+        if seg_first is None:
+            seg_first = planes_segment_first(self, np.diff(shost.astype(np.int64)).clip(min=0), E, L)
+        sf, nseg = _seg_first(self, seg_first, n_segments, src.device, n * E)
+        mixed = codecs is not None or isinstance(codec, AutoCodec)
+        choose = mixed and codecs is None
+        cgu = None
+        if choose:
+            cgu = _Guarded(1, nseg, self.guard, src.device) if self.guard > 0 else None
+            codecs = cgu.view[0] if cgu is not None else torch.empty(max(nseg, 1), dtype=torch.uint8, device=src.device)
+        elif mixed and (not isinstance(codecs, torch.Tensor) or not codecs.is_cuda or codecs.dtype != torch.uint8 or not codecs.is_contiguous() or codecs.numel() != nseg):
+            raise TypeError("codecs must be a contiguous CUDA uint8 tensor of %d entries" % nseg)
+        if shost is not None:
+            blocks = self.planes_block_bound(int(shost[-1] - shost[0]), n, E, min(block_size_id, 6))
+        if max_total_blocks is None:
+            max_total_blocks = blocks
+        g = None
+        if dst is None:
+            if dst_capacity is None:
+                dst_capacity = self.frame_packed_bound(int(shost[-1] - shost[0]), nseg, blocks, align_log)
+            dst, g = self._dst(1, int(dst_capacity), src.device)
+            dst = dst[0]
+        else:
+            dst_capacity = _room(self, dst, dst_capacity, "dst")
+        if planes is None and (E > 1 or base is not None):
+            planes = torch.empty(max(src.numel(), 1), dtype=torch.uint8, device=src.device)
+        elif planes is not None and _room(self, planes, None, "planes") < capacity:
+            raise ValueError("planes holds %d bytes, the capacity is %d" % (planes.numel(), capacity))
+        foff = _i64(self, frame_offsets, nseg + 1, src.device, "frame_offsets")
+        fres = _i64(self, frame_results, nseg, src.device, "frame_results")
+        tres = _i64(self, tensor_results, n, src.device, "tensor_results")
+        poff = _i64(self, plane_offsets, n * E + 1, src.device, "plane_offsets")
+        so = _i64(self, seg_offsets, nseg + 1, src.device, "seg_offsets")
+        if workspace is None and mixed:
+            workspace = torch.empty(max(self.frame_mixed_workspace_bound(nseg, max_total_blocks, min(block_size_id, 6), choose), 1), dtype=torch.uint8, device=src.device)
+        elif workspace is None:
+            self.lib.FSEHIP_frame_compress_packed_dbatch_workspaceSize.restype = SZ
+            need = int(self.lib.FSEHIP_frame_compress_packed_dbatch_workspaceSize(SZ(nseg), SZ(max_total_blocks), C.c_uint(min(block_size_id, 6)),
+                                                                                  C.c_int(codec if codec in (0, 1) else 0)))
+            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=src.device)
+        tol = codec.tolerance_permille if choose and isinstance(codec, AutoCodec) else 0
+        _check(self.lib.FSEHIP_tensor_compress_seg_dbatch(
+            _ptr(dst), C.c_uint64(int(dst_capacity)), _ptr(foff), _ptr(fres), _ptr(tres), _ptr(src), _ptr(base), _ptr(soff), SZ(n), C.c_uint(E), C.c_uint64(capacity),
+            _ptr(sf), SZ(nseg), C.c_uint(L), SZ(max_total_blocks), C.c_uint(block_size_id), C.c_int(0 if mixed else codec),
+            _ptr((codecs if codecs.numel() else codecs.new_zeros(1)) if mixed else None), C.c_int(CODECS_CHOOSE if choose else CODECS_GIVEN), C.c_uint(tol),
+            C.c_uint(align_log), _ptr(planes), _ptr(poff), _ptr(so), _ptr(workspace), SZ(workspace.numel()), _stream()), what)
+        if cgu is not None:
+            cgu.check(what + " (codecs)")
+            assert nseg == 0 or bool((cgu.view[0, :nseg] <= 1).all()), what + " did not write every codec"
+        if g is not None:
+            g.check(what)
+        return dst, foff, fres, tres, (codecs[:nseg] if mixed else None)
+
+    def tensor_decompress_seg_dbatch(self, frames, frame_offsets, dst_offsets, elem_bytes, segment_log, seg_first=None, n_segments=None, base=None, dst=None,
+                                     dst_capacity=None, max_total_blocks=None, planes=None, planes_capacity=None, seg_offsets=None, seg_results=None, plane_offsets=None,
+                                     plane_sizes=None, workspace=None, results=None):
+        """-> (dst, results): frame_decompress_packed_dbatch of the n_segments frames into `planes`, planes_fold_segments_dbatch, then the merge
+        (against `base` if one is given; dst may be `base` itself) into the slots dst_offsets.  results[i] = the tensor's size, or the error of
+        the first of its segments that fails, or the fold's or the merge's own; such a tensor's slot is not written.  seg_first None:
+        planes_segment_first of the slots' sizes.  seg_offsets (n_segments+1), seg_results (n_segments), plane_offsets and plane_sizes (n*E
+        each) are outputs / scratch; the workspace is the packed reader's for n_segments frames.  max_total_blocks None: the exact count from
+        a sizing query whose total is read back."""
+        E, L = _elem(elem_bytes), _seg_log(segment_log)
+        self._flat(frames, "frames")
+        foff, _ = self._offsets(frame_offsets, frames.device, False)
+        doff, dhost = self._offsets(dst_offsets, frames.device, dst is None or planes is None or seg_first is None)
+        n = doff.numel() - 1
+        if seg_first is None:
+            seg_first = planes_segment_first(self, np.diff(dhost.astype(np.int64)).clip(min=0), E, L)
+        sf, nseg = _seg_first(self, seg_first, n_segments, frames.device, n * E)
+        if foff.numel() != nseg + 1:
+            raise ValueError("frame_offsets: one entry per segment (%d) and one more" % nseg)
+        if max_total_blocks is None:
+            _, bfirst = self.frame_plan_dbatch(frames, foff, None, 0)
+            max_total_blocks = int(bfirst[nseg].item())
+        g = None
+        if dst is None:
+            dst_capacity = int(dhost[-1]) if dst_capacity is None else int(dst_capacity)
+            dst, g = self._dst(1, dst_capacity, frames.device)
+            dst = dst[0]
+        else:
+            dst_capacity = _room(self, dst, dst_capacity, "dst")
+        if planes is None:
+            planes_capacity = int(dhost[-1]) if planes_capacity is None else int(planes_capacity)
+            planes = torch.empty(max(planes_capacity, 1), dtype=torch.uint8, device=frames.device)
+        else:
+            planes_capacity = _room(self, planes, planes_capacity, "planes")
+        so = _i64(self, seg_offsets, nseg + 1, frames.device, "seg_offsets")
+        sres = _i64(self, seg_results, nseg, frames.device, "seg_results")
+        poff = _i64(self, plane_offsets, n * E, frames.device, "plane_offsets")
+        psz = _i64(self, plane_sizes, n * E, frames.device, "plane_sizes")
+        res = _i64(self, results, n, frames.device, "results")
+        if workspace is None:
+            self.lib.FSEHIP_frame_decompress_packed_dbatch_workspaceSize.restype = SZ
+            workspace = torch.empty(max(int(self.lib.FSEHIP_frame_decompress_packed_dbatch_workspaceSize(SZ(nseg), SZ(max_total_blocks))), 1),
+                                    dtype=torch.uint8, device=frames.device)
+        what = "tensor_decompress_seg_dbatch"
+        if base is not None:
+            _base(self, base, frames, dst_capacity, "dst")
+        _check(self.lib.FSEHIP_tensor_decompress_seg_dbatch(
+            _ptr(dst), _ptr(doff), C.c_uint64(dst_capacity), _ptr(base), _ptr(res), _ptr(frames), _ptr(foff), SZ(n), C.c_uint(E), _ptr(sf), SZ(nseg), C.c_uint(L),
+            SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity), _ptr(so), _ptr(sres), _ptr(poff), _ptr(psz), _ptr(workspace), SZ(workspace.numel()),
+            _stream()), what)
+        if g is not None:
+            g.check(what)
+        return dst, res
+
     # ---- the user-facing pair
     def _bases(base, dtypes, shapes, device):
         """the `base` of the pair: one CUDA tensor per tensor, of its dtype, shape and device -> their bytes, flat"""
@@ -1518,13 +1732,38 @@ def _planes_methods():
         codec: 0 (FSE), 1 (Huff0), an AutoCodec -- every plane's frame gets the codec chosen for it by size (tensor_compress_mixed_dbatch; each
         group dict gains "codecs", a CUDA uint8 tensor with entry i*E+p for plane p of the group's tensor i, and the object's `codec` is the
         AutoCodec) -- or a CompressedTensors an AutoCodec call returned for tensors of the same dtypes and shapes (ValueError otherwise, before
-        any launch): its codecs are given again, nothing is tried twice."""
+        any launch): its codecs are given again, nothing is tried twice.  An object compress_tensors_segmented wrote is refused here
+        (ValueError): its codecs are per segment.  For tensors above a few MiB use compress_tensors_segmented."""
+        return _compress_tensors(self, tensors, codec, block_size_id, base, None)
+
+    def compress_tensors_segmented(self, tensors, segment_log=18, codec=0, block_size_id=5, base=None):
+        """compress_tensors with every plane cut into segments of 1 << segment_log bytes (10 + block_size_id .. 30, ValueError otherwise), one
+        frame each (tensor_compress_seg_dbatch): the CompressedTensors has `segment_log` set, each group gains "seg_first", and frame_offsets,
+        frame_results and codecs are per segment; decompress_tensors reads all of it from the object.  The frames hold the same blocks, eight
+        bytes more per additional frame.  Why: a frame ends in one checksum over its whole content, a serial chain of about 1.5 GB/s per
+        frame whatever else the device does, so a plane of hundreds of MiB as a single frame takes hundreds of milliseconds each way (one
+        bf16 tensor of 1 GiB: 330 ms to write, 385 ms to read), while its segments run at the rate of as many small tensors (2.4 and 2.8 ms).
+        Of 18, 20 and 22, 18 was the fastest on every shape measured, 20 within a quarter of it, 22 at half.  codec,
+        block_size_id and base are compress_tensors'; an AutoCodec object given back as `codec` must have been written with the same
+        segment_log (ValueError otherwise, before any launch)."""
+        return _compress_tensors(self, tensors, codec, block_size_id, base,
+                                 _seg_log(segment_log, block_size_id if isinstance(block_size_id, numbers.Integral) and 0 <= block_size_id <= 6 else 0))
+
+    def _segmented(obj, segment_log):
+        if segment_log is not None:
+            obj.segment_log = int(segment_log)
+        return obj
+
+    def _compress_tensors(self, tensors, codec, block_size_id, base, segment_log):
         tensors = list(tensors)
         earlier = None
         if isinstance(codec, CompressedTensors):            # the codecs an earlier AutoCodec call chose, given again
             earlier, codec = codec, codec.codec
             if any("codecs" not in g for g in earlier.groups):
                 raise ValueError("compress_tensors: the earlier object carries no codecs (it was not written with an AutoCodec)")
+            if getattr(earlier, "segment_log", None) != segment_log:
+                raise ValueError("compress_tensors: the earlier object was written with segment_log %r, this call has %r"
+                                 % (getattr(earlier, "segment_log", None), segment_log))
             if len(earlier.dtypes) != len(tensors):
                 raise ValueError("compress_tensors: the earlier object holds %d tensors, %d were given" % (len(earlier.dtypes), len(tensors)))
             for k, (t, dt, sh) in enumerate(zip(tensors, earlier.dtypes, earlier.shapes)):
@@ -1533,7 +1772,7 @@ def _planes_methods():
         if not tensors:
             if base is not None and len(list(base)):
                 raise ValueError("base: tensors for none")
-            return CompressedTensors([], [], [], None, codec, block_size_id, base is not None)
+            return _segmented(CompressedTensors([], [], [], None, codec, block_size_id, base is not None), segment_log)
         device = tensors[0].device
         for t in tensors:
             if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
@@ -1549,8 +1788,13 @@ def _planes_methods():
             offs = np.concatenate([[0], np.cumsum([r.numel() for r in raw])]).astype(np.uint64)
             src = torch.cat(raw) if int(offs[-1]) else torch.zeros(1, dtype=torch.uint8, device=device)[:0]
             bsrc = None if braw is None else torch.cat([braw[i] for i in idx]) if int(offs[-1]) else src
-            codecs = None
-            if isinstance(codec, AutoCodec):
+            codecs = sfirst = None
+            if segment_log is not None:
+                given = None if earlier is None else [g for g in earlier.groups if g["elem_bytes"] == E][0]["codecs"]
+                sfirst = self.planes_segment_first(np.diff(offs.astype(np.int64)), E, segment_log)
+                dst, foff, fres, tres, codecs = self.tensor_compress_seg_dbatch(src, offs, E, segment_log, sfirst, base=bsrc, codec=codec, codecs=given,
+                                                                                block_size_id=block_size_id)
+            elif isinstance(codec, AutoCodec):
                 given = None if earlier is None else [g for g in earlier.groups if g["elem_bytes"] == E][0]["codecs"]
                 dst, foff, fres, tres, codecs = self.tensor_compress_mixed_dbatch(src, offs, E, bsrc, given, codec.tolerance_permille, block_size_id)
             elif braw is None:
@@ -1559,13 +1803,16 @@ def _planes_methods():
                 dst, foff, fres, tres = self.tensor_compress_delta_dbatch(src, bsrc, offs, E, block_size_id, codec)
             got = torch.cat([foff[-1:], fres, tres]).cpu().tolist()
             if min(got) < 0:
-                bad = [k for k, r in enumerate(got[1:1 + len(idx) * E]) if r < 0]
+                bad = [k for k, r in enumerate(got[1:1 + fres.numel()]) if r < 0]
                 raise RuntimeError("compress_tensors: element size %d, frames %s failed (%s)" % (E, bad[:8], [got[1 + k] for k in bad[:8]]))
             groups.append(dict(elem_bytes=E, index=idx, sizes=[int(x) for x in np.diff(offs)], frames=dst[:got[0]].clone(), frame_offsets=foff,
                                frame_results=fres, tensor_results=tres))
             if codecs is not None:
                 groups[-1]["codecs"] = codecs.clone()
-        return CompressedTensors(groups, [t.dtype for t in tensors], [tuple(t.shape) for t in tensors], device, codec, block_size_id, braw is not None)
+            if sfirst is not None:
+                groups[-1]["seg_first"] = sfirst
+        return _segmented(CompressedTensors(groups, [t.dtype for t in tensors], [tuple(t.shape) for t in tensors], device, codec, block_size_id, braw is not None),
+                          segment_log)
 
     def decompress_tensors(self, obj, base=None):
         """-> the tensors compress_tensors was given, in their order: same dtype, shape and device, the same bytes.  Every tensor owns its memory
@@ -1583,7 +1830,12 @@ def _planes_methods():
             E, sizes = g["elem_bytes"], g["sizes"]
             offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
             blocks = self.planes_block_bound(sum(sizes), len(sizes), E, obj.block_size_id)
-            if braw is None:
+            seg_log = getattr(obj, "segment_log", None)
+            if seg_log is not None:
+                dst = None if braw is None else torch.cat([braw[i] for i in g["index"]]) if sum(sizes) else torch.zeros(1, dtype=torch.uint8, device=obj.device)[:0]
+                dst, res = self.tensor_decompress_seg_dbatch(g["frames"], g["frame_offsets"], offs, E, seg_log, g["seg_first"], base=dst, dst=dst,
+                                                             max_total_blocks=blocks)
+            elif braw is None:
                 dst, res = self.tensor_decompress_dbatch(g["frames"], g["frame_offsets"], offs, E, max_total_blocks=blocks)
             else:
                 dst = torch.cat([braw[i] for i in g["index"]]) if sum(sizes) else torch.zeros(1, dtype=torch.uint8, device=obj.device)[:0]
@@ -1596,7 +1848,8 @@ def _planes_methods():
         return out
 
     for f in (planes_block_bound, planes_split_dbatch, planes_merge_dbatch, tensor_compress_dbatch, tensor_decompress_dbatch, compress_tensors, decompress_tensors,
-              planes_split_xor_dbatch, planes_merge_xor_dbatch, tensor_compress_delta_dbatch, tensor_decompress_delta_dbatch, tensor_compress_mixed_dbatch):
+              planes_split_xor_dbatch, planes_merge_xor_dbatch, tensor_compress_delta_dbatch, tensor_decompress_delta_dbatch, tensor_compress_mixed_dbatch,
+              planes_segment_first, planes_segments_dbatch, planes_fold_segments_dbatch, tensor_compress_seg_dbatch, tensor_decompress_seg_dbatch, compress_tensors_segmented):
         setattr(FseHip, f.__name__, f)
 
 
@@ -1614,6 +1867,11 @@ def _default():
 def compress_tensors(tensors, codec=0, block_size_id=5, base=None):
     """FseHip.compress_tensors on a library handle of the module's own"""
     return _default().compress_tensors(tensors, codec, block_size_id, base)
+
+
+def compress_tensors_segmented(tensors, segment_log=18, codec=0, block_size_id=5, base=None):
+    """FseHip.compress_tensors_segmented on a library handle of the module's own"""
+    return _default().compress_tensors_segmented(tensors, segment_log, codec, block_size_id, base)
 
 
 def decompress_tensors(obj, base=None):

@@ -99,6 +99,7 @@ __global__ __launch_bounds__(PL_THREADS) void k_planes_merge_xor(u8* dst, const 
         if (k < n) db[k] = planes[PO[i * E + k % E] + k / E] ^ bb[k];
     }
 }
+}   // namespace
 
 hipError_t launch_split_xor(u8* planes, u64* planeOff, size_t* tensorRes, const u8* src, const u8* base, const u64* srcOff, size_t nTensors, unsigned E, u64 capacity,
                             hipStream_t s)
@@ -126,7 +127,6 @@ hipError_t launch_merge_xor(u8* dst, const u64* dstOff, size_t* results, const u
     else hipLaunchKernelGGL(k_planes_merge_xor<8>, g, b, 0, s, dst, dstOff, planes, planeOff, planeSizes, base, nTensors, dstCapacity);
     return hipGetLastError();
 }
-}   // namespace
 
 extern "C" int FSEHIP_planes_split_xor_dbatch(void* d_planes, uint64_t* d_planeOffsets, size_t* d_tensorResults, const void* d_src, const void* d_base,
                                               const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes, uint64_t capacity, void* stream)

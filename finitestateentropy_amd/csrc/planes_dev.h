@@ -83,7 +83,20 @@ DEV size_t pm_verdict(const u64* D, const size_t* PS, size_t i, u32 E, u64 dstCa
     return (size_t)n;
 }
 
+// ---- segmented planes (planes_seg.hip; fsehip.h, "segmented planes") ----
+// segments of a plane of `size` bytes at seg = 1 << segLog: every plane has at least one
+__host__ __device__ inline u64 ps_count(u64 size, u32 segLog) { const u64 c = (size + (((u64)1 << segLog) - 1)) >> segLog; return c ? c : 1; }
+// tensor i is accepted iff each of its E planes has in segFirst the count its size in S implies
+DEV bool ps_tensor_ok(const u64* S, const u64* SF, size_t i, u32 E, u32 segLog)
+{
+    const u64 s0 = S[i], s1 = S[i + 1], n = s1 > s0 ? s1 - s0 : 0;
+    bool ok = true;
+    for (u32 p = 0; p < E; ++p) ok = ok && SF[i * E + p + 1] - SF[i * E + p] == ps_count(pl_size(n, p, E), segLog);
+    return ok;
+}
+
 inline bool bad_elem(unsigned E) { return E != 1 && E != 2 && E != 4 && E != 8; }
+inline bool bad_seg(unsigned segLog, unsigned blockSizeId) { return segLog < 10 + blockSizeId || segLog > 30; }
 // ceil(capacity / T) + nTensors workgroups of PL_THREADS threads in one launch
 inline bool bad_grid(u64 capacity, size_t nTensors) { return capacity >= ((u64)1 << 46) || (capacity >> PL_TILE_LOG) + 1 + nTensors >= ((u64)1 << 24); }
 inline unsigned tile_grid(u64 capacity, size_t nTensors) { return (unsigned)(((capacity + PLANES_TILE - 1) >> PL_TILE_LOG) + nTensors); }

@@ -712,6 +712,76 @@ FSEHIP_API int FSEHIP_tensor_decompress_delta_dbatch(void* d_dst, const uint64_t
                                                      void* d_planes, uint64_t planesCapacity, uint64_t* d_planeOffsets, size_t* d_planeResults,
                                                      void* d_workspace, size_t workspaceBytes, void* stream);
 
+/* Segmented planes (planes_seg.hip): the tensor calls above with ONE FRAME PER SEGMENT OF A PLANE.  A frame ends in one XXH32 over its whole
+ * content -- a serial chain, about 1.5 GB/s per frame -- and the reader walks a frame's headers and settles its blocks frame by frame: a plane
+ * of hundreds of MiB as one frame takes hundreds of milliseconds however idle the device is.  The frame writer codes every block independently
+ * of its position, so a plane cut at multiples of the block size gives the same blocks, byte for byte, in several ordinary frames: eight
+ * bytes (5 of header, 3 of end mark) per additional frame, and no chain longer than a segment.  Nothing in a frame says that it is a segment;
+ * which frames make up a plane is `segFirst`, which the caller keeps beside the tensor offsets.
+ * Like the calls above: launches on `stream` only, capturable, no size leaves the device, argument errors (also: a segLog outside its range,
+ * 2^31 segments or more) are hipErrorInvalidValue, decided before any device call.  No *_workspaceSize of their own: the workspaces are the
+ * packed writer's, the mixed writer's and the packed reader's with nFrames = nSegments.
+ *
+ *   The layout.  seg = 1 << segLog with 10 + blockSizeId <= segLog <= 30 (calls that take no blockSizeId: 10 <= segLog <= 30), so that a
+ *     segment is a whole number of blocks.  Plane j = i * E + p of size_j bytes has cnt_j = max(1, ceil(size_j / seg)) segments, segment k
+ *     its bytes [k * seg, min((k + 1) * seg, size_j)); an empty plane has one empty segment, every plane keeps at least one frame.
+ *     segFirst[j] = the sum of cnt over the planes before j: nTensors * E + 1 entries, segFirst[0] = 0, segFirst[nTensors * E] = nSegments.
+ *     cnt is a function of the tensor offsets S alone -- a tensor refused for capacity still counts the segments its size in S implies, all
+ *     of them empty -- so the count never depends on what the device decides.  Frame q of a call is segment q - segFirst[j] of the plane j
+ *     that holds it: tensor order, plane order, segment order.  Full segments are whole blocks and only the last segment of a plane may end
+ *     in a partial one, so FSEHIP_planes_blockBound as it stands is still a sufficient maxTotalBlocks.
+ *
+ *   FSEHIP_planes_segmentFirst   host arithmetic (works without a device): fills h_segFirst (nTensors * E + 1 entries; NULL: count only) from the
+ *     tensor offsets (nTensors + 1) and returns nSegments; GENERIC for a bad elemBytes or segLog or when the count reaches 2^31.  Tensor shapes
+ *     are static: the caller uploads segFirst once, next to the offsets.
+ *
+ *   FSEHIP_planes_segments_dbatch   d_planeOffsets as the split leaves them + d_srcOffsets + d_segFirst -> d_segOffsets (nSegments + 1 entries,
+ *     directly the d_srcOffsets of the packed writers with nFrames = nSegments): entry q = min(P[j] + k * seg, P[j + 1]) for segment k of plane
+ *     j, the last entry P[nTensors * E].  One thread per entry, a binary search over segFirst for its plane.  Validation is local: tensor i is
+ *     accepted iff segFirst[j + 1] - segFirst[j] == cnt_j for each of its E planes; otherwise d_tensorResults[i] becomes GENERIC and all its
+ *     entries equal its start P[i * E] -- its segments are empty contents, frames of eight bytes, EXCEPT the last one, which the shared offset
+ *     array ends at the next tensor's start: that frame holds the refused tensor's bytes of d_planes as one content (or GENERIC beyond the
+ *     block promise) and is, like the others, to be discarded.  A tensor the split refused keeps its collapsed entries (P does it), and the
+ *     results of accepted tensors are not touched.  A segFirst that is not non-decreasing from 0 to nSegments is the caller's error as a
+ *     non-monotone offset array is: the outputs are then unspecified, but segFirst's values are never used as indices -- nothing outside the
+ *     given arrays is touched.
+ *
+ *   FSEHIP_planes_fold_segments_dbatch   the packed reader's per-segment d_dstOffsets (nSegments + 1) and d_results (nSegments) + d_segFirst ->
+ *     per plane d_planeOffsets[j] = its first segment's offset and d_planeSizes[j] (nPlanes entries each), exactly what
+ *     FSEHIP_planes_merge_dbatch takes.  d_planeSizes[j], in this order: GENERIC for a plane without a segment; the first error among its
+ *     segments' results, in segment order; corruption_detected unless every segment but the last holds exactly seg bytes and the last 1 .. seg
+ *     (0 only as the plane's only segment); corruption_detected unless off[q + 1] == off[q] + res[q] inside the plane -- the decoded segments
+ *     lie back to back, which the reader's slot alignment 0 gives whenever announced and decoded sizes agree; otherwise the sum.  One wave per
+ *     plane, its lanes striding over the segments; segment ranges are clamped to nSegments.
+ *
+ *   FSEHIP_tensor_compress_seg_dbatch   the split (d_base == NULL) or the XOR split, the segments kernel, then the packed writer with `codec`
+ *     (d_codecs == NULL) or the mixed writer with d_codecs (nSegments entries, one per segment, given or chosen), policy and
+ *     tolerancePermille.  Frame q is byte for byte FSEHIP_frame_compress of its segment.  d_frameOffsets (nSegments + 1) and d_frameResults
+ *     (nSegments) are the writer's; d_planes, d_planeOffsets (nTensors * E + 1) and d_segOffsets (nSegments + 1) are scratch the caller
+ *     supplies.  With elemBytes == 1 a null d_planes is allowed without a base only.  The workspace is the writer's for nSegments frames.
+ *     The argument checks of all steps run before the first launch; for any later error the earlier steps have run.
+ *
+ *   FSEHIP_tensor_decompress_seg_dbatch   FSEHIP_frame_decompress_packed_dbatch with slotAlignLog 0 into d_planes (d_segOffsets, nSegments + 1,
+ *     and d_segResults, nSegments, are its outputs), the fold (d_planeOffsets and d_planeSizes, nTensors * E each, its outputs), then the merge
+ *     (d_base == NULL) or the XOR merge, in place with d_base == d_dst included.  d_segFirst is an INPUT: what the sender used, or
+ *     FSEHIP_planes_segmentFirst of the tensor sizes.  A tensor any of whose segments fails gets that error and its slot is not written (in
+ *     place: it keeps its old bytes); frames read with another segLog than they were written with give corruption_detected. */
+FSEHIP_API size_t FSEHIP_planes_segmentFirst(uint64_t* h_segFirst, const uint64_t* h_offsets, size_t nTensors, unsigned elemBytes, unsigned segLog);
+FSEHIP_API int FSEHIP_planes_segments_dbatch(uint64_t* d_segOffsets, size_t* d_tensorResults, const uint64_t* d_planeOffsets, const uint64_t* d_srcOffsets,
+                                             const uint64_t* d_segFirst, size_t nTensors, unsigned elemBytes, size_t nSegments, unsigned segLog, void* stream);
+FSEHIP_API int FSEHIP_planes_fold_segments_dbatch(uint64_t* d_planeOffsets, size_t* d_planeSizes, const uint64_t* d_segOffsets, const size_t* d_segResults,
+                                                  const uint64_t* d_segFirst, size_t nPlanes, size_t nSegments, unsigned segLog, void* stream);
+FSEHIP_API int FSEHIP_tensor_compress_seg_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
+                                                 const void* d_src, const void* d_base, const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes,
+                                                 uint64_t capacity, const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, size_t maxTotalBlocks,
+                                                 unsigned blockSizeId, int codec, uint8_t* d_codecs, int policy, unsigned tolerancePermille, unsigned slotAlignLog,
+                                                 void* d_planes, uint64_t* d_planeOffsets, uint64_t* d_segOffsets, void* d_workspace, size_t workspaceBytes, void* stream);
+FSEHIP_API int FSEHIP_tensor_decompress_seg_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base, size_t* d_results,
+                                                   const void* d_frames, const uint64_t* d_frameOffsets, size_t nTensors, unsigned elemBytes,
+                                                   const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, size_t maxTotalBlocks,
+                                                   void* d_planes, uint64_t planesCapacity, uint64_t* d_segOffsets, size_t* d_segResults,
+                                                   uint64_t* d_planeOffsets, size_t* d_planeSizes, void* d_workspace, size_t workspaceBytes, void* stream);
+
 /* ---- FSE for 16-bit symbols (lib/fseU16.h:62-80, lib/fseU16.c) -- SURVEY 8(f) rank 4.  Alphabets of up to
  * FSEHIP_FSEU16_MAX_SYMBOL_VALUE + 1 symbols, table logs up to 13 (default 12), ONE tANS state per stream: a different format from
  * the byte coder's.  Sizes of the uncompressed side are in SYMBOLS (as in the reference), strides in bytes.
