@@ -1707,6 +1707,200 @@ def _planes_methods():
             g.check(what)
         return dst, res
 
+    # ---- windows of segmented tensors (csrc/planes_win.hip; fsehip.h "windows of segmented tensors"): elements [a, b) of every tensor, decoding
+    # only the segments that hold them
+    def _window_array(windows, n):
+        """(a, b) per tensor as python ints -> numpy int64 of shape (n, 2)"""
+        w = np.asarray([(int(a), int(b)) for a, b in windows], dtype=np.int64).reshape(-1, 2)
+        if w.shape[0] != n:
+            raise ValueError("windows: %d for %d tensors" % (w.shape[0], n))
+        return w
+
+    def planes_window_first(self, sizes, windows, elem_bytes, segment_log, block_size_id=5):
+        """tensor sizes in bytes and one window (a, b) per tensor, in elements -> (sel_first, max_blocks): sel_first (numpy uint64,
+        len(sizes) * E + 1 entries) is the index of the first selected segment frame of every plane, its last entry the number of selected
+        frames; max_blocks the exact number of blocks in them, the packed reader's block promise.  Every plane of a tensor contributes the
+        segments a >> segment_log .. (b - 1) >> segment_log, none for a == b.  Host arithmetic with numpy: needs no device.  ValueError for a
+        bad elem_bytes, block_size_id or segment_log, a window that is not 0 <= a <= b <= size // E, and for 2^31 frames or blocks or more."""
+        E = _elem(elem_bytes)
+        if not isinstance(block_size_id, numbers.Integral) or not 0 <= block_size_id <= 6:
+            raise ValueError("block_size_id %r: 0 .. 6" % (block_size_id,))
+        L = _seg_log(segment_log, block_size_id)
+        n = np.asarray(list(sizes), dtype=np.int64).reshape(-1)
+        w = _window_array(windows, n.size)
+        a, b = w[:, 0], w[:, 1]
+        if n.size and (int(n.min()) < 0 or bool(((a < 0) | (a > b) | (b > n // E)).any())):
+            raise ValueError("planes_window_first: a window is (a, b) in elements with 0 <= a <= b <= size // %d" % E)
+        k0 = a >> L
+        cnt = np.where(a < b, ((b - 1) >> L) - k0 + 1, 0)
+        first = np.concatenate([[0], np.cumsum(np.repeat(cnt, E), dtype=np.int64)])
+        p = np.arange(E, dtype=np.int64).reshape(1, -1)
+        nn = n.reshape(-1, 1)
+        psize = np.where(nn > p, (nn - p + E - 1) // E, 0)
+        last = np.minimum(1 << L, psize - ((k0 + cnt - 1).reshape(-1, 1) << L))            # bytes of the last selected segment of every plane
+        bl = 10 + int(block_size_id)
+        per_plane = (cnt.reshape(-1, 1) - 1) * (1 << (L - bl)) + ((last + (1 << bl) - 1) >> bl)
+        blocks = int(np.where(cnt.reshape(-1, 1) > 0, per_plane, 0).sum())
+        if int(first[-1]) >= 1 << 31 or blocks >= 1 << 31:
+            raise ValueError("planes_window_first: %d frames of %d blocks, fewer than 2^31 are allowed" % (int(first[-1]), blocks))
+        return first.astype(np.uint64), blocks
+
+    def _windows(self, windows, device, n):
+        """windows on the device as the library takes them: 2 * n int64 (a CUDA int64 tensor of that many entries is taken as it is)"""
+        if isinstance(windows, torch.Tensor) and windows.is_cuda:
+            if windows.dtype != torch.int64 or not windows.is_contiguous() or windows.numel() != 2 * n:
+                raise TypeError("windows must be a contiguous CUDA int64 tensor of %d entries" % (2 * n))
+            return windows, None
+        w = _window_array(windows.tolist() if isinstance(windows, (torch.Tensor, np.ndarray)) else windows, n)
+        return torch.from_numpy(np.ascontiguousarray(w.reshape(-1))).to(device), w
+
+    def _sel_first(self, sel_first, n_selected, device, n_planes):
+        wf, host = self._offsets(sel_first, device, n_selected is None)
+        if wf.numel() != n_planes + 1:
+            raise ValueError("sel_first: one entry per plane (%d) and one more" % n_planes)
+        return wf, int(host[-1]) if n_selected is None else int(n_selected)
+
+    def planes_select_window_dbatch(self, frame_offsets, src_offsets, windows, seg_first, sel_first, elem_bytes, segment_log, n_segments=None, n_selected=None,
+                                    sel_frame_offsets=None):
+        """-> sel_frame_offsets (n_selected + 1 entries): the frame_offsets of the packed reader for the selected segment frames alone -- entry r is
+        where selected frame r starts in the frames buffer, extent r runs to the next selected frame (unselected frames included: a reader
+        stops at the end mark), the last entry is the end of the last selected frame.  frame_offsets are ALL frames' (n_segments + 1),
+        src_offsets the sender's tensor layout, windows one (a, b) in elements per tensor, seg_first / sel_first what planes_segment_first /
+        planes_window_first give.  A tensor with a bad window or wrong counts gets empty extents.  seg_first / sel_first on the device need
+        n_segments / n_selected."""
+        E, L = _elem(elem_bytes), _seg_log(segment_log)
+        foff = frame_offsets
+        if not isinstance(foff, torch.Tensor) or not foff.is_cuda or foff.dtype != torch.int64 or not foff.is_contiguous():
+            raise TypeError("frame_offsets must be a contiguous CUDA int64 tensor")
+        soff, _ = self._offsets(src_offsets, foff.device, False)
+        n = soff.numel() - 1
+        sf, nseg = _seg_first(self, seg_first, n_segments, foff.device, n * E)
+        wf, nsel = _sel_first(self, sel_first, n_selected, foff.device, n * E)
+        if foff.numel() < nseg + 1:
+            raise ValueError("frame_offsets: one entry per segment (%d) and one more" % nseg)
+        win, _ = _windows(self, windows, foff.device, n)
+        g = None
+        if sel_frame_offsets is None:
+            sel_frame_offsets, g = self._dst(1, nsel + 1, foff.device, dtype=torch.int64)
+            sel_frame_offsets = sel_frame_offsets[0]
+        so = _i64(self, sel_frame_offsets, nsel + 1, foff.device, "sel_frame_offsets")
+        _check(self.lib.FSEHIP_planes_select_window_dbatch(_ptr(so), _ptr(foff), _ptr(soff), _ptr(win if n else win.new_zeros(1)), _ptr(sf), _ptr(wf), SZ(n), C.c_uint(E),
+                                                           SZ(nseg), SZ(nsel), C.c_uint(L), _stream()), "planes_select_window_dbatch")
+        if g is not None:
+            g.check("planes_select_window_dbatch")
+        return so[:nsel + 1]
+
+    def planes_fold_window_dbatch(self, sel_offsets, sel_results, src_offsets, windows, seg_first, sel_first, elem_bytes, segment_log, n_selected=None,
+                                  plane_offsets=None, plane_sizes=None):
+        """-> (plane_offsets, plane_sizes), n * E entries each, as planes_merge_dbatch takes them: what frame_decompress_packed_dbatch returns for
+        the selected extents (dst_offsets, results) -> per plane where the window's first byte lies and b - a, or -1 (a tensor with a bad
+        window or wrong counts), 0 (an empty window), the first error among its selected segments, -4 (a segment that did not regenerate exactly
+        its bytes, or segments that do not lie back to back); the offset is 0 unless the size is b - a > 0."""
+        E, L = _elem(elem_bytes), _seg_log(segment_log)
+        if not isinstance(sel_offsets, torch.Tensor) or not sel_offsets.is_cuda or sel_offsets.dtype != torch.int64 or not sel_offsets.is_contiguous():
+            raise TypeError("sel_offsets must be a contiguous CUDA int64 tensor")
+        dev = sel_offsets.device
+        soff, _ = self._offsets(src_offsets, dev, False)
+        n = soff.numel() - 1
+        npl = n * E
+        sf, _ = self._offsets(seg_first, dev, False)
+        if sf.numel() != npl + 1:
+            raise ValueError("seg_first: one entry per plane (%d) and one more" % npl)
+        wf, nsel = _sel_first(self, sel_first, n_selected, dev, npl)
+        if sel_offsets.numel() < nsel + 1:
+            raise ValueError("sel_offsets: one entry per selected frame (%d) and one more" % nsel)
+        sres = _i64(self, sel_results, nsel, dev, "sel_results")
+        win, _ = _windows(self, windows, dev, n)
+        g = []
+        if plane_offsets is None:
+            plane_offsets, x = self._dst(1, npl, dev, dtype=torch.int64)
+            plane_offsets = plane_offsets[0]
+            g.append(x)
+        if plane_sizes is None:
+            plane_sizes, x = self._dst(1, npl, dev, dtype=torch.int64)
+            plane_sizes = plane_sizes[0]
+            g.append(x)
+        po = _i64(self, plane_offsets, npl, dev, "plane_offsets")
+        ps = _i64(self, plane_sizes, npl, dev, "plane_sizes")
+        _check(self.lib.FSEHIP_planes_fold_window_dbatch(_ptr(po), _ptr(ps), _ptr(sel_offsets), _ptr(sres if nsel else sres.new_zeros(1)), _ptr(soff),
+                                                         _ptr(win if n else win.new_zeros(1)), _ptr(sf), _ptr(wf), SZ(n), C.c_uint(E), SZ(nsel), C.c_uint(L), _stream()),
+               "planes_fold_window_dbatch")
+        for x in g:
+            if x is not None:
+                x.check("planes_fold_window_dbatch")
+        return po[:npl], ps[:npl]
+
+    def tensor_decompress_window_dbatch(self, frames, frame_offsets, src_offsets, windows, dst_offsets, elem_bytes, segment_log, seg_first=None, n_segments=None,
+                                        sel_first=None, n_selected=None, base=None, dst=None, dst_capacity=None, max_total_blocks=None, block_size_id=5, planes=None,
+                                        planes_capacity=None, sel_frame_offsets=None, sel_offsets=None, sel_results=None, plane_offsets=None, plane_sizes=None,
+                                        workspace=None, results=None):
+        """-> (dst, results): elements [a, b) of every tensor of a segmented batch -- planes_select_window_dbatch, frame_decompress_packed_dbatch over
+        the n_selected extents into `planes`, planes_fold_window_dbatch, then the merge (against `base` if one is given, which holds the same
+        windows in dst's layout; dst may be `base` itself) into the slots dst_offsets: slot i receives the E * (b - a) bytes
+        tensor_i[a * E : b * E], results[i] is that size or an error, and such a tensor's slot is not written.  src_offsets is the SENDER'S
+        layout (the sizes the tensors were compressed with), frame_offsets all n_segments frames'.  seg_first None: planes_segment_first of
+        those sizes.  sel_first or max_total_blocks None: planes_window_first of the sizes and windows with `block_size_id` (both then need
+        src_offsets and windows on the host).  planes: n_selected << segment_log bytes are always enough (the default).  sel_frame_offsets,
+        sel_offsets (n_selected + 1), sel_results (n_selected), plane_offsets and plane_sizes (n * E) are outputs / scratch; the workspace is
+        the packed reader's for n_selected frames.  With everything given and on the device the call is launches only."""
+        E, L = _elem(elem_bytes), _seg_log(segment_log)
+        self._flat(frames, "frames")
+        foff, _ = self._offsets(frame_offsets, frames.device, False)
+        need_first = sel_first is None or max_total_blocks is None
+        soff, shost = self._offsets(src_offsets, frames.device, seg_first is None or need_first)
+        doff, dhost = self._offsets(dst_offsets, frames.device, dst is None)
+        n = soff.numel() - 1
+        if doff.numel() != n + 1:
+            raise ValueError("dst_offsets: one entry per tensor (%d) and one more" % n)
+        win, whost = _windows(self, windows, frames.device, n)
+        if seg_first is None:
+            seg_first = planes_segment_first(self, np.diff(shost.astype(np.int64)).clip(min=0), E, L)
+        sf, nseg = _seg_first(self, seg_first, n_segments, frames.device, n * E)
+        if foff.numel() != nseg + 1:
+            raise ValueError("frame_offsets: one entry per segment (%d) and one more" % nseg)
+        if need_first:
+            if whost is None:
+                raise ValueError("tensor_decompress_window_dbatch: windows on the device need sel_first, n_selected and max_total_blocks")
+            first, blocks = planes_window_first(self, np.diff(shost.astype(np.int64)).clip(min=0), whost, E, L, block_size_id)
+            sel_first = first if sel_first is None else sel_first
+            max_total_blocks = blocks if max_total_blocks is None else max_total_blocks
+        wf, nsel = _sel_first(self, sel_first, n_selected, frames.device, n * E)
+        g = None
+        if dst is None:
+            dst_capacity = int(dhost[-1]) if dst_capacity is None else int(dst_capacity)
+            dst, g = self._dst(1, dst_capacity, frames.device)
+            dst = dst[0]
+        else:
+            dst_capacity = _room(self, dst, dst_capacity, "dst")
+        if planes is None:
+            planes_capacity = nsel << L if planes_capacity is None else int(planes_capacity)
+            planes = torch.empty(max(planes_capacity, 1), dtype=torch.uint8, device=frames.device)
+        else:
+            planes_capacity = _room(self, planes, planes_capacity, "planes")
+        sfo = _i64(self, sel_frame_offsets, nsel + 1, frames.device, "sel_frame_offsets")
+        so = _i64(self, sel_offsets, nsel + 1, frames.device, "sel_offsets")
+        sres = _i64(self, sel_results, nsel, frames.device, "sel_results")
+        poff = _i64(self, plane_offsets, n * E, frames.device, "plane_offsets")
+        psz = _i64(self, plane_sizes, n * E, frames.device, "plane_sizes")
+        res = _i64(self, results, n, frames.device, "results")
+        if workspace is None:
+            self.lib.FSEHIP_frame_decompress_packed_dbatch_workspaceSize.restype = SZ
+            workspace = torch.empty(max(int(self.lib.FSEHIP_frame_decompress_packed_dbatch_workspaceSize(SZ(nsel), SZ(max_total_blocks))), 1),
+                                    dtype=torch.uint8, device=frames.device)
+        what = "tensor_decompress_window_dbatch"
+        if base is not None:
+            _base(self, base, frames, dst_capacity, "dst")
+
+        def some(t):                                             # (an array of no entries still needs an address)
+            return t if t.numel() else t.new_zeros(1)
+        _check(self.lib.FSEHIP_tensor_decompress_window_dbatch(
+            _ptr(some(dst)), _ptr(doff), C.c_uint64(dst_capacity), _ptr(base), _ptr(some(res)), _ptr(some(frames)), _ptr(foff), _ptr(soff), _ptr(some(win)), SZ(n),
+            C.c_uint(E), _ptr(sf), SZ(nseg), C.c_uint(L), _ptr(wf), SZ(nsel), SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity), _ptr(sfo), _ptr(so),
+            _ptr(some(sres)), _ptr(some(poff)), _ptr(some(psz)), _ptr(workspace), SZ(workspace.numel()), _stream()), what)
+        if g is not None:
+            g.check(what)
+        return dst, res
+
     # ---- the user-facing pair
     def _bases(base, dtypes, shapes, device):
         """the `base` of the pair: one CUDA tensor per tensor, of its dtype, shape and device -> their bytes, flat"""
@@ -1847,6 +2041,60 @@ def _planes_methods():
                 out[i] = dst[int(offs[k]):int(offs[k + 1])].clone().view(obj.dtypes[i]).reshape(obj.shapes[i])
         return out
 
+    def decompress_tensor_windows(self, obj, windows, base=None):
+        """-> per tensor of `obj` (a CompressedTensors of compress_tensors_segmented) the elements [start, stop) of the FLATTENED tensor as a 1-D
+        tensor of the recorded dtype that owns its memory: a row shard, a slice, a row range.  `windows` has one entry per tensor: None (the
+        tensor is skipped and None is returned in its place) or (start, stop) with 0 <= start <= stop <= numel.  Only the segment frames that
+        hold a window are decoded (tensor_decompress_window_dbatch): time and scratch follow the windows, not the tensors.
+        base: for an object with `delta` set, the WHOLE base tensors as decompress_tensors takes them; the call slices them and does not change
+        them.  ValueError for an object without segment_log, a window that is not one, a wrong number of windows, and a base / delta
+        mismatch as in decompress_tensors -- all before any launch."""
+        seg_log = getattr(obj, "segment_log", None)
+        if seg_log is None:
+            raise ValueError("decompress_tensor_windows: the object is not segmented (compress_tensors_segmented writes those)")
+        if getattr(obj, "delta", False) != (base is not None):
+            raise ValueError("decompress_tensor_windows: the object holds deltas and needs its base" if base is None else
+                             "decompress_tensor_windows: the object holds no deltas, a base does not belong to it")
+        windows = list(windows)
+        if len(windows) != len(obj.dtypes):
+            raise ValueError("decompress_tensor_windows: %d windows for %d tensors" % (len(windows), len(obj.dtypes)))
+        wins = []
+        for k, (w, sh) in enumerate(zip(windows, obj.shapes)):
+            if w is None:
+                wins.append(None)
+                continue
+            numel = int(np.prod(sh, dtype=np.int64))
+            if (not isinstance(w, (tuple, list)) or len(w) != 2 or any(not isinstance(x, numbers.Integral) or isinstance(x, bool) for x in w)
+                    or not 0 <= w[0] <= w[1] <= numel):
+                raise ValueError("decompress_tensor_windows: window %d is %r, (start, stop) with 0 <= start <= stop <= %d is needed" % (k, w, numel))
+            wins.append((int(w[0]), int(w[1])))
+        braw = None if base is None else _bases(base, obj.dtypes, obj.shapes, obj.device)
+        out = [None] * len(obj.dtypes)
+        for g in obj.groups:
+            E, sizes = g["elem_bytes"], g["sizes"]
+            gw = [wins[i] or (0, 0) for i in g["index"]]
+            if not any(b > a for a, b in gw):
+                for k, i in enumerate(g["index"]):
+                    if wins[i] is not None:
+                        out[i] = torch.empty(0, dtype=obj.dtypes[i], device=obj.device)
+                continue
+            soff = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
+            doff = np.concatenate([[0], np.cumsum([E * (b - a) for a, b in gw])]).astype(np.uint64)
+            dst = None
+            if braw is not None:
+                dst = torch.cat([braw[i][E * a:E * b] for i, (a, b) in zip(g["index"], gw)])             # a copy: rebuilt in place, the bases stay
+            dst, res = self.tensor_decompress_window_dbatch(g["frames"], g["frame_offsets"], soff, gw, doff, E, seg_log, g["seg_first"], base=dst, dst=dst,
+                                                            block_size_id=obj.block_size_id)
+            got, want = res.cpu().tolist(), [E * (b - a) for a, b in gw]
+            if got != want:
+                raise RuntimeError("decompress_tensor_windows: element size %d, results %s for windows of %s bytes" % (E, got[:8], want[:8]))
+            for k, i in enumerate(g["index"]):
+                if wins[i] is not None:
+                    out[i] = dst[int(doff[k]):int(doff[k + 1])].clone().view(obj.dtypes[i])
+        return out
+
+    for f in (planes_window_first, planes_select_window_dbatch, planes_fold_window_dbatch, tensor_decompress_window_dbatch, decompress_tensor_windows):
+        setattr(FseHip, f.__name__, f)
     for f in (planes_block_bound, planes_split_dbatch, planes_merge_dbatch, tensor_compress_dbatch, tensor_decompress_dbatch, compress_tensors, decompress_tensors,
               planes_split_xor_dbatch, planes_merge_xor_dbatch, tensor_compress_delta_dbatch, tensor_decompress_delta_dbatch, tensor_compress_mixed_dbatch,
               planes_segment_first, planes_segments_dbatch, planes_fold_segments_dbatch, tensor_compress_seg_dbatch, tensor_decompress_seg_dbatch, compress_tensors_segmented):
@@ -1877,6 +2125,11 @@ def compress_tensors_segmented(tensors, segment_log=18, codec=0, block_size_id=5
 def decompress_tensors(obj, base=None):
     """FseHip.decompress_tensors on a library handle of the module's own"""
     return _default().decompress_tensors(obj, base)
+
+
+def decompress_tensor_windows(obj, windows, base=None):
+    """FseHip.decompress_tensor_windows on a library handle of the module's own"""
+    return _default().decompress_tensor_windows(obj, windows, base)
 
 
 # ---------------------------------------------------------------------------------------------------------

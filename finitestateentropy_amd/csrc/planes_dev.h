@@ -95,6 +95,24 @@ DEV bool ps_tensor_ok(const u64* S, const u64* SF, size_t i, u32 E, u32 segLog)
     return ok;
 }
 
+// ---- windows of segmented tensors (planes_win.hip; fsehip.h, "windows of segmented tensors") ----
+// the window [a, b) of tensor i in elements, the segments k0 .. k0 + cnt - 1 of each of its planes that hold it (cnt 0: an empty window), and
+// whether the tensor is accepted: a valid window, cnt in selFirst for each of its planes, ending at or below nSel, and ps_tensor_ok.  For an
+// accepted tensor WF[i * E + p] + cnt <= nSel for every plane p, and segment k0 + cnt - 1 exists in every plane
+struct PwWin { u64 a, b, k0, cnt; bool ok; };
+DEV PwWin pw_window(const u64* S, const u64* W, const u64* SF, const u64* WF, size_t i, u32 E, u32 segLog, size_t nSel)
+{
+    const u64 s0 = S[i], s1 = S[i + 1], n = s1 > s0 ? s1 - s0 : 0;
+    PwWin w;
+    w.a = W[2 * i]; w.b = W[2 * i + 1];
+    w.ok = w.a <= w.b && w.b <= n / E;
+    w.k0 = w.a >> segLog;
+    w.cnt = w.ok && w.a < w.b ? ((w.b - 1) >> segLog) - w.k0 + 1 : 0;
+    for (u32 p = 0; p < E; ++p) w.ok = w.ok && WF[i * E + p + 1] - WF[i * E + p] == w.cnt;
+    w.ok = w.ok && WF[i * E] <= WF[(i + 1) * E] && WF[(i + 1) * E] <= nSel && ps_tensor_ok(S, SF, i, E, segLog);
+    return w;
+}
+
 inline bool bad_elem(unsigned E) { return E != 1 && E != 2 && E != 4 && E != 8; }
 inline bool bad_seg(unsigned segLog, unsigned blockSizeId) { return segLog < 10 + blockSizeId || segLog > 30; }
 // ceil(capacity / T) + nTensors workgroups of PL_THREADS threads in one launch

@@ -782,6 +782,78 @@ FSEHIP_API int FSEHIP_tensor_decompress_seg_dbatch(void* d_dst, const uint64_t* 
                                                    void* d_planes, uint64_t planesCapacity, uint64_t* d_segOffsets, size_t* d_segResults,
                                                    uint64_t* d_planeOffsets, size_t* d_planeSizes, void* d_workspace, size_t workspaceBytes, void* stream);
 
+/* Windows of segmented tensors (planes_win.hip): an ELEMENT RANGE of every tensor of a segmented batch, decoding only the segments that hold it.
+ * The segmented layout above leaves a large tensor as a row of independently decodable frames of seg = 1 << segLog plane bytes, and segFirst
+ * says which frame holds which part; a tensor-parallel rank that wants its row shard, a loader that wants a slice, an embedding update that
+ * patches a row range need 1 / share of them.  No frame byte changes and neither does a reader: every frame reader stops its header walk at
+ * the end mark and looks at no byte behind it (what the padding between packed frames already relies on), so the selected frames are handed
+ * to FSEHIP_frame_decompress_packed_dbatch as a batch of EXTENTS -- extent r runs from the start of selected frame r to the start of the next
+ * selected frame, whole unselected frames included, and reads as the frame at its start.  The merge does not change either: for a window of
+ * whole elements [a, b) every plane contributes the same plane-relative byte range [a, b); with the selected segments k0 .. k1 of a plane
+ * decoded back to back at X, plane byte e lies at X + (e - k0 * seg), so the window is the merge of a tensor of b - a elements whose plane p
+ * starts at X_p + (a - k0 * seg).
+ * Like the calls above: launches on `stream` only, capturable, no size leaves the device, argument errors (also: 2^31 selected frames or
+ * more, more selected frames than segments) are hipErrorInvalidValue, decided before any device call.  No *_workspaceSize of their own: the
+ * workspace is the packed reader's, FSEHIP_frame_decompress_packed_dbatch_workspaceSize(nSelected, maxTotalBlocks).
+ *
+ *   Definitions.  S = d_srcOffsets (nTensors + 1 entries) is the SENDER'S tensor layout: tensor i has n_i = S[i+1] - S[i] bytes, its plane p
+ *     sz = size_p(n_i) bytes, and segFirst is what the frames were written with.  `windows` holds 2 * nTensors uint64_t: (a_i, b_i) in
+ *     ELEMENTS of tensor i, valid iff a_i <= b_i <= floor(n_i / E) -- the partial last element of a tensor whose size is no multiple of E is
+ *     not addressable; reading everything remains FSEHIP_tensor_decompress_seg_dbatch's job.  The selected segments of EVERY plane of
+ *     tensor i: none if a == b, otherwise k0 = a >> segLog .. k1 = (b - 1) >> segLog, cnt = k1 - k0 + 1 (a valid window ends inside every
+ *     plane, so all E planes have these segments).  selFirst (nTensors * E + 1 entries) is the running sum of cnt in tensor, plane order,
+ *     selFirst[nTensors * E] = nSelected: like segFirst a function of shapes and windows alone, computed on the host and uploaded, so that
+ *     no launch size depends on the device.
+ *     Tensor i is ACCEPTED iff its window is valid, each of its E planes has the count cnt in selFirst, its entries of selFirst end at or
+ *     below nSelected (selFirst[i * E] <= selFirst[(i + 1) * E] <= nSelected), and each of its planes has in segFirst the count its size
+ *     implies (the rule of FSEHIP_planes_segments_dbatch).  Both kernels decide this locally, from the same arrays.  Values of segFirst,
+ *     selFirst and windows are never used as indices unclamped: whatever they hold, nothing outside the given arrays is touched.
+ *
+ *   FSEHIP_planes_windowFirst   host arithmetic (works without a device): fills h_selFirst (nTensors * E + 1 entries; NULL: count only) and
+ *     *h_maxBlocks (may be NULL) and returns nSelected.  *h_maxBlocks is the EXACT block count of the selected segments, the sum of
+ *     ceil(min(seg, sz - k * seg) / blockSize): the reader's block promise, which also sizes its workspace.  GENERIC for a bad elemBytes,
+ *     blockSizeId > 6, a segLog outside 10 + blockSizeId .. 30, a window that is not valid, or when either count reaches 2^31.
+ *
+ *   FSEHIP_planes_select_window_dbatch   the full d_frameOffsets F (nSegments + 1) + S + windows + segFirst + selFirst -> d_selFrameOffsets
+ *     (nSelected + 1 entries, directly the d_frameOffsets of the packed reader with nFrames = nSelected).  One thread per entry r, a binary
+ *     search over selFirst for its plane j; entry r = F[q] with q = segFirst[j] + k0 + (r - selFirst[j]).  The last entry is F[q + 1] of the
+ *     last selected frame, and F[0] when nothing is selected.  All entries of a refused tensor, the last entry included where it is the
+ *     last tensor with entries, are F[min(segFirst[(i + 1) * E], nSegments)]: its extents are empty (srcSize_wrong to the reader) except
+ *     possibly the last, which runs to the next tensor's first selected frame and is, like the others, to be discarded.  With monotone
+ *     inputs the array is non-decreasing and extent r holds selected frame r at its start.
+ *
+ *   FSEHIP_planes_fold_window_dbatch   the packed reader's per-extent d_dstOffsets (d_selOffsets, nSelected + 1) and d_results (d_selResults,
+ *     nSelected) + S + windows + segFirst + selFirst -> per plane d_planeOffsets[j] and d_planeSizes[j] (nTensors * E entries each) as the
+ *     merge takes them.  d_planeSizes[j], in this order: GENERIC if the tensor is refused; 0 for an empty window; the first error among its
+ *     selected segments' results, in segment order; corruption_detected unless segment k0 + t regenerated EXACTLY min(seg, sz - (k0 + t) * seg)
+ *     bytes (the plane's size is known here: stricter than the fold of the full read); corruption_detected unless off[r + 1] == off[r] + res[r]
+ *     between the plane's selected segments; otherwise b - a, and d_planeOffsets[j] = off[selFirst[j]] + (a - k0 * seg).  In every other
+ *     case d_planeOffsets[j] = 0.  One wave per plane, its lanes striding over the plane's selected segments.
+ *
+ *   FSEHIP_tensor_decompress_window_dbatch   the selection (d_selFrameOffsets its output), FSEHIP_frame_decompress_packed_dbatch over the
+ *     nSelected extents with slot alignment 0 into d_planes (d_selOffsets, nSelected + 1, and d_selResults, nSelected, are its outputs), the
+ *     fold (d_planeOffsets and d_planeSizes, nTensors * E each), then the merge (d_base == NULL) or the XOR merge into the caller's slots
+ *     d_dstOffsets (nTensors + 1 entries, an INPUT).  The slot of tensor i receives the E * (b - a) bytes tensor_i[a * E .. b * E);
+ *     d_results are the merge's, its five rules unchanged (n = E * (b - a)).  d_base has THE LAYOUT OF d_dst: it holds the same window of
+ *     the base.  IN PLACE (d_base == d_dst) is allowed: with d_dstOffsets[i] = T[i] + a_i * E over a resident buffer whose tensor i starts
+ *     at T[i], rows [a, b) of every resident tensor are patched where they lie; nothing outside the window is written, and a tensor with
+ *     an error keeps its old bytes.  planesCapacity >= nSelected << segLog is always sufficient.  maxTotalBlocks: what
+ *     FSEHIP_planes_windowFirst gives, or any upper bound.  The argument checks of all steps run before the first launch. */
+FSEHIP_API size_t FSEHIP_planes_windowFirst(uint64_t* h_selFirst, size_t* h_maxBlocks, const uint64_t* h_offsets, const uint64_t* h_windows, size_t nTensors,
+                                            unsigned elemBytes, unsigned segLog, unsigned blockSizeId);
+FSEHIP_API int FSEHIP_planes_select_window_dbatch(uint64_t* d_selFrameOffsets, const uint64_t* d_frameOffsets, const uint64_t* d_srcOffsets, const uint64_t* d_windows,
+                                                  const uint64_t* d_segFirst, const uint64_t* d_selFirst, size_t nTensors, unsigned elemBytes, size_t nSegments,
+                                                  size_t nSelected, unsigned segLog, void* stream);
+FSEHIP_API int FSEHIP_planes_fold_window_dbatch(uint64_t* d_planeOffsets, size_t* d_planeSizes, const uint64_t* d_selOffsets, const size_t* d_selResults,
+                                                const uint64_t* d_srcOffsets, const uint64_t* d_windows, const uint64_t* d_segFirst, const uint64_t* d_selFirst,
+                                                size_t nTensors, unsigned elemBytes, size_t nSelected, unsigned segLog, void* stream);
+FSEHIP_API int FSEHIP_tensor_decompress_window_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base, size_t* d_results,
+                                                      const void* d_frames, const uint64_t* d_frameOffsets, const uint64_t* d_srcOffsets, const uint64_t* d_windows,
+                                                      size_t nTensors, unsigned elemBytes, const uint64_t* d_segFirst, size_t nSegments, unsigned segLog,
+                                                      const uint64_t* d_selFirst, size_t nSelected, size_t maxTotalBlocks, void* d_planes, uint64_t planesCapacity,
+                                                      uint64_t* d_selFrameOffsets, uint64_t* d_selOffsets, size_t* d_selResults, uint64_t* d_planeOffsets,
+                                                      size_t* d_planeSizes, void* d_workspace, size_t workspaceBytes, void* stream);
+
 /* ---- FSE for 16-bit symbols (lib/fseU16.h:62-80, lib/fseU16.c) -- SURVEY 8(f) rank 4.  Alphabets of up to
  * FSEHIP_FSEU16_MAX_SYMBOL_VALUE + 1 symbols, table logs up to 13 (default 12), ONE tANS state per stream: a different format from
  * the byte coder's.  Sizes of the uncompressed side are in SYMBOLS (as in the reference), strides in bytes.
