@@ -1232,13 +1232,85 @@ def _planes_methods():
         return r
 
     def _base(self, base, like, capacity, what):
-        """the base of an XOR call: a flat buffer on the device of `like` that holds at least the capacity of the buffer it is laid out as"""
+        """the base of an XOR call (None: a plain call, nothing to check): a flat buffer on the device of `like` that holds at least the
+        capacity of the buffer it is laid out as"""
+        if base is None:
+            return None
         self._flat(base, "base")
         if base.device != like.device:
             raise ValueError("base is on %s, %s on %s" % (base.device, what, like.device))
         if base.numel() < capacity:
             raise ValueError("base holds %d bytes, the capacity of %s is %d" % (base.numel(), what, capacity))
         return base
+
+    # ---- what the compress wrappers set up alike ...
+    def _codecs(self, codecs, n_frames, device):
+        """-> (codecs, guard): the codecs argument of a mixed writer for n_frames frames -- given, or None: an array for the library to fill"""
+        if codecs is None:
+            g = _Guarded(1, n_frames, self.guard, device) if self.guard > 0 else None
+            return (g.view[0] if g is not None else torch.empty(max(n_frames, 1), dtype=torch.uint8, device=device)), g
+        if not isinstance(codecs, torch.Tensor) or not codecs.is_cuda or codecs.dtype != torch.uint8 or not codecs.is_contiguous() or codecs.numel() != n_frames:
+            raise TypeError("codecs must be a contiguous CUDA uint8 tensor of %d entries" % n_frames)
+        return codecs, None
+
+    def _check_codecs(g, n_frames, what):
+        if g is not None:
+            g.check(what + " (codecs)")
+            assert n_frames == 0 or bool((g.view[0, :n_frames] <= 1).all()), what + " did not write every codec"
+
+    def _frames_room(self, shost, n, E, n_frames, block_size_id, max_total_blocks, dst, dst_capacity, align_log, device):
+        """-> (max_total_blocks, dst, dst_capacity, guard): the block bound of the planes and the room for n_frames frames of them"""
+        if shost is not None:
+            blocks = self.planes_block_bound(int(shost[-1] - shost[0]), n, E, min(block_size_id, 6))
+        if max_total_blocks is None:
+            max_total_blocks = blocks
+        if dst is not None:
+            return max_total_blocks, dst, _room(self, dst, dst_capacity, "dst"), None
+        if dst_capacity is None:
+            dst_capacity = self.frame_packed_bound(int(shost[-1] - shost[0]), n_frames, blocks, align_log)
+        dst, g = self._dst(1, int(dst_capacity), device)
+        return max_total_blocks, dst[0], dst_capacity, g
+
+    def _split_room(self, planes, src, capacity, needed):
+        """the planes buffer of a split: the caller's, which must hold `capacity` bytes, or (where the split writes one) as large as src"""
+        if planes is None and needed:
+            return torch.empty(max(src.numel(), 1), dtype=torch.uint8, device=src.device)
+        if planes is not None and _room(self, planes, None, "planes") < capacity:
+            raise ValueError("planes holds %d bytes, the capacity is %d" % (planes.numel(), capacity))
+        return planes
+
+    def _writer_workspace(self, workspace, n_frames, max_total_blocks, block_size_id, codec, mixed, choose, device):
+        if workspace is not None:
+            return workspace
+        if mixed:
+            need = self.frame_mixed_workspace_bound(n_frames, max_total_blocks, min(block_size_id, 6), choose)
+        else:
+            self.lib.FSEHIP_frame_compress_packed_dbatch_workspaceSize.restype = SZ
+            need = int(self.lib.FSEHIP_frame_compress_packed_dbatch_workspaceSize(SZ(n_frames), SZ(max_total_blocks), C.c_uint(min(block_size_id, 6)),
+                                                                                  C.c_int(codec if codec in (0, 1) else 0)))
+        return torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+
+    # ---- ... and the merge and decompress wrappers
+    def _dst_room(self, dst, capacity, dhost, device):
+        """-> (dst, capacity, guard): the caller's destination, or one of `capacity` (default: the end of the last slot) bytes"""
+        if dst is not None:
+            return dst, _room(self, dst, capacity, "dst"), None
+        capacity = int(dhost[-1]) if capacity is None else int(capacity)
+        dst, g = self._dst(1, capacity, device)
+        return dst[0], capacity, g
+
+    def _planes_room(self, planes, planes_capacity, default, device):
+        """-> (planes, planes_capacity): the caller's scratch for the decoded planes, or one of planes_capacity (default: `default`) bytes"""
+        if planes is not None:
+            return planes, _room(self, planes, planes_capacity, "planes")
+        planes_capacity = default if planes_capacity is None else int(planes_capacity)
+        return torch.empty(max(planes_capacity, 1), dtype=torch.uint8, device=device), planes_capacity
+
+    def _reader_workspace(self, workspace, n_frames, max_total_blocks, device):
+        if workspace is not None:
+            return workspace
+        self.lib.FSEHIP_frame_decompress_packed_dbatch_workspaceSize.restype = SZ
+        return torch.empty(max(int(self.lib.FSEHIP_frame_decompress_packed_dbatch_workspaceSize(SZ(n_frames), SZ(max_total_blocks))), 1), dtype=torch.uint8, device=device)
 
     def planes_split_dbatch(self, src, src_offsets, elem_bytes, capacity=None, planes=None, plane_offsets=None, results=None):
         """-> (planes, plane_offsets, results): tensor i = src[src_offsets[i] : src_offsets[i+1]]; plane p of it (its bytes p, p + E, ..) =
@@ -1261,8 +1333,7 @@ def _planes_methods():
         n = soff.numel() - 1
         capacity = _room(self, src, capacity, "src")
         what = "planes_split_dbatch" if base is None else "planes_split_xor_dbatch"
-        if base is not None:
-            _base(self, base, src, capacity, "src")
+        _base(self, base, src, capacity, "src")
         g = None
         if planes is None:
             if E == 1 and base is None:
@@ -1306,13 +1377,7 @@ def _planes_methods():
         n = doff.numel() - 1
         poff = _i64(self, plane_offsets, n * E, planes.device, "plane_offsets")
         psz = _i64(self, plane_sizes, n * E, planes.device, "plane_sizes")
-        g = None
-        if dst is None:
-            capacity = int(dhost[-1]) if capacity is None else int(capacity)
-            dst, g = self._dst(1, capacity, planes.device)
-            dst = dst[0]
-        else:
-            capacity = _room(self, dst, capacity, "dst")
+        dst, capacity, g = _dst_room(self, dst, capacity, dhost, planes.device)
         res = _i64(self, results, n, planes.device, "results")
         if base is None:
             what = "planes_merge_dbatch"
@@ -1366,55 +1431,28 @@ def _planes_methods():
         n = soff.numel() - 1
         capacity = _room(self, src, capacity, "src")
         what = "tensor_compress_mixed_dbatch" if mixed is not None else "tensor_compress_dbatch" if base is None else "tensor_compress_delta_dbatch"
-        if base is not None:
-            _base(self, base, src, capacity, "src")
-        cgu = None
+        _base(self, base, src, capacity, "src")
+        choose = False
         if mixed is not None:
             codecs, tol = mixed
             choose = codecs is None
-            if choose:
-                if not isinstance(tol, numbers.Integral) or not 0 <= tol <= 1000:
-                    raise ValueError("tolerance_permille %r: 0 .. 1000" % (tol,))
-                cgu = _Guarded(1, n * E, self.guard, src.device) if self.guard > 0 else None
-                codecs = cgu.view[0] if cgu is not None else torch.empty(max(n * E, 1), dtype=torch.uint8, device=src.device)
-            elif not isinstance(codecs, torch.Tensor) or not codecs.is_cuda or codecs.dtype != torch.uint8 or not codecs.is_contiguous() or codecs.numel() != n * E:
-                raise TypeError("codecs must be a contiguous CUDA uint8 tensor of %d entries" % (n * E))
-        if shost is not None:
-            blocks = self.planes_block_bound(int(shost[-1] - shost[0]), n, E, min(block_size_id, 6))
-        if max_total_blocks is None:
-            max_total_blocks = blocks
-        g = None
-        if dst is None:
-            if dst_capacity is None:
-                dst_capacity = self.frame_packed_bound(int(shost[-1] - shost[0]), n * E, blocks, align_log)
-            dst, g = self._dst(1, int(dst_capacity), src.device)
-            dst = dst[0]
-        else:
-            dst_capacity = _room(self, dst, dst_capacity, "dst")
-        if planes is None and (E > 1 or base is not None):
-            planes = torch.empty(max(src.numel(), 1), dtype=torch.uint8, device=src.device)
-        elif planes is not None and _room(self, planes, None, "planes") < capacity:
-            raise ValueError("planes holds %d bytes, the capacity is %d" % (planes.numel(), capacity))
+            if choose and (not isinstance(tol, numbers.Integral) or not 0 <= tol <= 1000):
+                raise ValueError("tolerance_permille %r: 0 .. 1000" % (tol,))
+            codecs, cgu = _codecs(self, codecs, n * E, src.device)
+        max_total_blocks, dst, dst_capacity, g = _frames_room(self, shost, n, E, n * E, block_size_id, max_total_blocks, dst, dst_capacity, align_log, src.device)
+        planes = _split_room(self, planes, src, capacity, E > 1 or base is not None)
         foff = _i64(self, frame_offsets, n * E + 1, src.device, "frame_offsets")
         fres = _i64(self, frame_results, n * E, src.device, "frame_results")
         tres = _i64(self, tensor_results, n, src.device, "tensor_results")
         poff = _i64(self, plane_offsets, n * E + 1, src.device, "plane_offsets")
-        if workspace is None and mixed is not None:
-            workspace = torch.empty(max(self.frame_mixed_workspace_bound(n * E, max_total_blocks, min(block_size_id, 6), choose), 1), dtype=torch.uint8, device=src.device)
-        elif workspace is None:
-            self.lib.FSEHIP_frame_compress_packed_dbatch_workspaceSize.restype = SZ
-            need = int(self.lib.FSEHIP_frame_compress_packed_dbatch_workspaceSize(SZ(n * E), SZ(max_total_blocks), C.c_uint(min(block_size_id, 6)),
-                                                                                  C.c_int(codec if codec in (0, 1) else 0)))
-            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=src.device)
+        workspace = _writer_workspace(self, workspace, n * E, max_total_blocks, block_size_id, codec, mixed is not None, choose, src.device)
         if mixed is not None:
             _check(self.lib.FSEHIP_tensor_compress_mixed_dbatch(_ptr(dst), C.c_uint64(int(dst_capacity)), _ptr(foff), _ptr(fres), _ptr(tres), _ptr(src), _ptr(base),
                                                                 _ptr(soff), SZ(n), C.c_uint(E), C.c_uint64(capacity), SZ(max_total_blocks), C.c_uint(block_size_id),
                                                                 _ptr(codecs if codecs.numel() else codecs.new_zeros(1)),
                                                                 C.c_int(CODECS_CHOOSE if choose else CODECS_GIVEN), C.c_uint(int(tol) if choose else 0),
                                                                 C.c_uint(align_log), _ptr(planes), _ptr(poff), _ptr(workspace), SZ(workspace.numel()), _stream()), what)
-            if cgu is not None:
-                cgu.check(what + " (codecs)")
-                assert n == 0 or bool((cgu.view[0, :n * E] <= 1).all()), what + " did not write every codec"
+            _check_codecs(cgu, n * E, what)
             if g is not None:
                 g.check(what)
             return dst, foff, fres, tres, codecs[:n * E]
@@ -1462,25 +1500,12 @@ def _planes_methods():
         if max_total_blocks is None:                      # the exact count, from a sizing query (as frame_decompress_packed_dbatch does)
             _, bfirst = self.frame_plan_dbatch(frames, foff, None, 0)
             max_total_blocks = int(bfirst[n * E].item())
-        g = None
-        if dst is None:
-            dst_capacity = int(dhost[-1]) if dst_capacity is None else int(dst_capacity)
-            dst, g = self._dst(1, dst_capacity, frames.device)
-            dst = dst[0]
-        else:
-            dst_capacity = _room(self, dst, dst_capacity, "dst")
-        if planes is None:
-            planes_capacity = int(dhost[-1]) if planes_capacity is None else int(planes_capacity)
-            planes = torch.empty(max(planes_capacity, 1), dtype=torch.uint8, device=frames.device)
-        else:
-            planes_capacity = _room(self, planes, planes_capacity, "planes")
+        dst, dst_capacity, g = _dst_room(self, dst, dst_capacity, dhost, frames.device)
+        planes, planes_capacity = _planes_room(self, planes, planes_capacity, None if planes is not None else int(dhost[-1]), frames.device)
         poff = _i64(self, plane_offsets, n * E + 1, frames.device, "plane_offsets")
         pres = _i64(self, plane_results, n * E, frames.device, "plane_results")
         res = _i64(self, results, n, frames.device, "results")
-        if workspace is None:
-            self.lib.FSEHIP_frame_decompress_packed_dbatch_workspaceSize.restype = SZ
-            workspace = torch.empty(max(int(self.lib.FSEHIP_frame_decompress_packed_dbatch_workspaceSize(SZ(n * E), SZ(max_total_blocks))), 1),
-                                    dtype=torch.uint8, device=frames.device)
+        workspace = _reader_workspace(self, workspace, n * E, max_total_blocks, frames.device)
         if base is None:
             what = "tensor_decompress_dbatch"
             _check(self.lib.FSEHIP_tensor_decompress_dbatch(_ptr(dst), _ptr(doff), C.c_uint64(dst_capacity), _ptr(res), _ptr(frames), _ptr(foff), SZ(n), C.c_uint(E),
@@ -1599,56 +1624,28 @@ def _planes_methods():
         n = soff.numel() - 1
         capacity = _room(self, src, capacity, "src")
         what = "tensor_compress_seg_dbatch"
-        if base is not None:
-            _base(self, base, src, capacity, "src")
+        _base(self, base, src, capacity, "src")
         if seg_first is None:
             seg_first = planes_segment_first(self, np.diff(shost.astype(np.int64)).clip(min=0), E, L)
         sf, nseg = _seg_first(self, seg_first, n_segments, src.device, n * E)
         mixed = codecs is not None or isinstance(codec, AutoCodec)
         choose = mixed and codecs is None
-        cgu = None
-        if choose:
-            cgu = _Guarded(1, nseg, self.guard, src.device) if self.guard > 0 else None
-            codecs = cgu.view[0] if cgu is not None else torch.empty(max(nseg, 1), dtype=torch.uint8, device=src.device)
-        elif mixed and (not isinstance(codecs, torch.Tensor) or not codecs.is_cuda or codecs.dtype != torch.uint8 or not codecs.is_contiguous() or codecs.numel() != nseg):
-            raise TypeError("codecs must be a contiguous CUDA uint8 tensor of %d entries" % nseg)
-        if shost is not None:
-            blocks = self.planes_block_bound(int(shost[-1] - shost[0]), n, E, min(block_size_id, 6))
-        if max_total_blocks is None:
-            max_total_blocks = blocks
-        g = None
-        if dst is None:
-            if dst_capacity is None:
-                dst_capacity = self.frame_packed_bound(int(shost[-1] - shost[0]), nseg, blocks, align_log)
-            dst, g = self._dst(1, int(dst_capacity), src.device)
-            dst = dst[0]
-        else:
-            dst_capacity = _room(self, dst, dst_capacity, "dst")
-        if planes is None and (E > 1 or base is not None):
-            planes = torch.empty(max(src.numel(), 1), dtype=torch.uint8, device=src.device)
-        elif planes is not None and _room(self, planes, None, "planes") < capacity:
-            raise ValueError("planes holds %d bytes, the capacity is %d" % (planes.numel(), capacity))
+        codecs, cgu = _codecs(self, codecs, nseg, src.device) if mixed else (None, None)
+        max_total_blocks, dst, dst_capacity, g = _frames_room(self, shost, n, E, nseg, block_size_id, max_total_blocks, dst, dst_capacity, align_log, src.device)
+        planes = _split_room(self, planes, src, capacity, E > 1 or base is not None)
         foff = _i64(self, frame_offsets, nseg + 1, src.device, "frame_offsets")
         fres = _i64(self, frame_results, nseg, src.device, "frame_results")
         tres = _i64(self, tensor_results, n, src.device, "tensor_results")
         poff = _i64(self, plane_offsets, n * E + 1, src.device, "plane_offsets")
         so = _i64(self, seg_offsets, nseg + 1, src.device, "seg_offsets")
-        if workspace is None and mixed:
-            workspace = torch.empty(max(self.frame_mixed_workspace_bound(nseg, max_total_blocks, min(block_size_id, 6), choose), 1), dtype=torch.uint8, device=src.device)
-        elif workspace is None:
-            self.lib.FSEHIP_frame_compress_packed_dbatch_workspaceSize.restype = SZ
-            need = int(self.lib.FSEHIP_frame_compress_packed_dbatch_workspaceSize(SZ(nseg), SZ(max_total_blocks), C.c_uint(min(block_size_id, 6)),
-                                                                                  C.c_int(codec if codec in (0, 1) else 0)))
-            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=src.device)
+        workspace = _writer_workspace(self, workspace, nseg, max_total_blocks, block_size_id, codec, mixed, choose, src.device)
         tol = codec.tolerance_permille if choose and isinstance(codec, AutoCodec) else 0
         _check(self.lib.FSEHIP_tensor_compress_seg_dbatch(
             _ptr(dst), C.c_uint64(int(dst_capacity)), _ptr(foff), _ptr(fres), _ptr(tres), _ptr(src), _ptr(base), _ptr(soff), SZ(n), C.c_uint(E), C.c_uint64(capacity),
             _ptr(sf), SZ(nseg), C.c_uint(L), SZ(max_total_blocks), C.c_uint(block_size_id), C.c_int(0 if mixed else codec),
             _ptr((codecs if codecs.numel() else codecs.new_zeros(1)) if mixed else None), C.c_int(CODECS_CHOOSE if choose else CODECS_GIVEN), C.c_uint(tol),
             C.c_uint(align_log), _ptr(planes), _ptr(poff), _ptr(so), _ptr(workspace), SZ(workspace.numel()), _stream()), what)
-        if cgu is not None:
-            cgu.check(what + " (codecs)")
-            assert nseg == 0 or bool((cgu.view[0, :nseg] <= 1).all()), what + " did not write every codec"
+        _check_codecs(cgu, nseg, what)
         if g is not None:
             g.check(what)
         return dst, foff, fres, tres, (codecs[:nseg] if mixed else None)
@@ -1675,30 +1672,16 @@ def _planes_methods():
         if max_total_blocks is None:
             _, bfirst = self.frame_plan_dbatch(frames, foff, None, 0)
             max_total_blocks = int(bfirst[nseg].item())
-        g = None
-        if dst is None:
-            dst_capacity = int(dhost[-1]) if dst_capacity is None else int(dst_capacity)
-            dst, g = self._dst(1, dst_capacity, frames.device)
-            dst = dst[0]
-        else:
-            dst_capacity = _room(self, dst, dst_capacity, "dst")
-        if planes is None:
-            planes_capacity = int(dhost[-1]) if planes_capacity is None else int(planes_capacity)
-            planes = torch.empty(max(planes_capacity, 1), dtype=torch.uint8, device=frames.device)
-        else:
-            planes_capacity = _room(self, planes, planes_capacity, "planes")
+        dst, dst_capacity, g = _dst_room(self, dst, dst_capacity, dhost, frames.device)
+        planes, planes_capacity = _planes_room(self, planes, planes_capacity, None if planes is not None else int(dhost[-1]), frames.device)
         so = _i64(self, seg_offsets, nseg + 1, frames.device, "seg_offsets")
         sres = _i64(self, seg_results, nseg, frames.device, "seg_results")
         poff = _i64(self, plane_offsets, n * E, frames.device, "plane_offsets")
         psz = _i64(self, plane_sizes, n * E, frames.device, "plane_sizes")
         res = _i64(self, results, n, frames.device, "results")
-        if workspace is None:
-            self.lib.FSEHIP_frame_decompress_packed_dbatch_workspaceSize.restype = SZ
-            workspace = torch.empty(max(int(self.lib.FSEHIP_frame_decompress_packed_dbatch_workspaceSize(SZ(nseg), SZ(max_total_blocks))), 1),
-                                    dtype=torch.uint8, device=frames.device)
+        workspace = _reader_workspace(self, workspace, nseg, max_total_blocks, frames.device)
         what = "tensor_decompress_seg_dbatch"
-        if base is not None:
-            _base(self, base, frames, dst_capacity, "dst")
+        _base(self, base, frames, dst_capacity, "dst")
         _check(self.lib.FSEHIP_tensor_decompress_seg_dbatch(
             _ptr(dst), _ptr(doff), C.c_uint64(dst_capacity), _ptr(base), _ptr(res), _ptr(frames), _ptr(foff), SZ(n), C.c_uint(E), _ptr(sf), SZ(nseg), C.c_uint(L),
             SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity), _ptr(so), _ptr(sres), _ptr(poff), _ptr(psz), _ptr(workspace), SZ(workspace.numel()),
@@ -1865,31 +1848,17 @@ def _planes_methods():
             sel_first = first if sel_first is None else sel_first
             max_total_blocks = blocks if max_total_blocks is None else max_total_blocks
         wf, nsel = _sel_first(self, sel_first, n_selected, frames.device, n * E)
-        g = None
-        if dst is None:
-            dst_capacity = int(dhost[-1]) if dst_capacity is None else int(dst_capacity)
-            dst, g = self._dst(1, dst_capacity, frames.device)
-            dst = dst[0]
-        else:
-            dst_capacity = _room(self, dst, dst_capacity, "dst")
-        if planes is None:
-            planes_capacity = nsel << L if planes_capacity is None else int(planes_capacity)
-            planes = torch.empty(max(planes_capacity, 1), dtype=torch.uint8, device=frames.device)
-        else:
-            planes_capacity = _room(self, planes, planes_capacity, "planes")
+        dst, dst_capacity, g = _dst_room(self, dst, dst_capacity, dhost, frames.device)
+        planes, planes_capacity = _planes_room(self, planes, planes_capacity, nsel << L, frames.device)
         sfo = _i64(self, sel_frame_offsets, nsel + 1, frames.device, "sel_frame_offsets")
         so = _i64(self, sel_offsets, nsel + 1, frames.device, "sel_offsets")
         sres = _i64(self, sel_results, nsel, frames.device, "sel_results")
         poff = _i64(self, plane_offsets, n * E, frames.device, "plane_offsets")
         psz = _i64(self, plane_sizes, n * E, frames.device, "plane_sizes")
         res = _i64(self, results, n, frames.device, "results")
-        if workspace is None:
-            self.lib.FSEHIP_frame_decompress_packed_dbatch_workspaceSize.restype = SZ
-            workspace = torch.empty(max(int(self.lib.FSEHIP_frame_decompress_packed_dbatch_workspaceSize(SZ(nsel), SZ(max_total_blocks))), 1),
-                                    dtype=torch.uint8, device=frames.device)
+        workspace = _reader_workspace(self, workspace, nsel, max_total_blocks, frames.device)
         what = "tensor_decompress_window_dbatch"
-        if base is not None:
-            _base(self, base, frames, dst_capacity, "dst")
+        _base(self, base, frames, dst_capacity, "dst")
 
         def some(t):                                             # (an array of no entries still needs an address)
             return t if t.numel() else t.new_zeros(1)

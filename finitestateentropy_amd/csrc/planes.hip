@@ -6,7 +6,18 @@
 //   FSEHIP_planes_merge_dbatch     : k_planes_verdicts (per tensor: its result) -> k_planes_merge
 //   FSEHIP_tensor_compress_dbatch  : the split -> FSEHIP_frame_compress_packed_dbatch over the planes (the plane offsets are its source offsets)
 //   FSEHIP_tensor_decompress_dbatch: FSEHIP_frame_decompress_packed_dbatch into the planes buffer -> the merge over the offsets and results it leaves
-// (The device helpers all of them are made of are in planes_dev.h, shared with the XOR forms of planes_delta.hip.)
+// (The device helpers all of them are made of are in planes_dev.h, shared with planes_seg.hip and planes_win.hip.)
+//
+// TENSOR DELTAS (fsehip.h, "tensor deltas"): the same calls on `tensor XOR base`, the XOR fused into the two data kernels.  The receiver of a
+// tensor often holds an earlier version of it (weights after a step, the checkpoint before this one); XOR against that version zeroes every
+// byte that did not change, the sign / exponent plane becomes almost all zeros, and the order-0 coders do the rest.  No bitstream, header or
+// frame byte differs: the frames are ordinary .fse frames of the planes of `tensor XOR base`.
+//
+//   FSEHIP_planes_split_xor_dbatch       : the split with a base, for every element size (E == 1 too: the XOR has to be written somewhere)
+//   FSEHIP_planes_merge_xor_dbatch       : the merge with a base, which may be the destination itself
+//   FSEHIP_tensor_compress_delta_dbatch  : the XOR split -> the packed writer over the planes
+//   FSEHIP_tensor_compress_mixed_dbatch  : the plain or the XOR split -> the packed writer with a codec per plane
+//   FSEHIP_tensor_decompress_delta_dbatch: the packed reader into the planes buffer -> the XOR merge
 //
 // The two data kernels are bandwidth kernels (n bytes in, n bytes out) over ragged tensors, with no workspace and no scan: the flat byte axis
 // is cut into tiles of PLANES_TILE bytes, ceil(capacity / T) + nTensors workgroups are launched, and workgroup w looks up -- a binary search
@@ -19,6 +30,10 @@
 // plane, consecutive lanes at consecutive addresses.  The chunks start where plane 0 (split) or the tensor (merge) reaches a 16-byte boundary;
 // the elements in front of the first chunk and behind the last one -- fewer than 32, the partial last element of a tensor whose size is no
 // multiple of E among them -- go bytewise.  Sources at any alignment (unaligned 16-byte loads, as k_hist and k_xxh32 take theirs).
+// The XOR forms (X) are the same kernels with one more read stream: per chunk E more loads of 16 bytes from the base, which lies where the
+// source (split) or the destination (merge) lies, each XORed into its words as it arrives.  XOR acts bit by bit, so it commutes with the byte
+// shuffle: the split XORs in front of it, the merge behind it.  3 n bytes of traffic where the plain kernels have 2 n; the plain kernels
+// never read `base`.
 #include "planes_dev.h"
 
 namespace {
@@ -43,8 +58,9 @@ __global__ void k_planes_offsets(u64* P, size_t* res, const u64* S, size_t nT, u
     for (u32 p = 0; p < E; ++p) P[i * E + p] = s0 + pl_start(n, p, E);
     res[i] = (size_t)n;
 }
-template <int E>
-__global__ __launch_bounds__(PL_THREADS) void k_planes_split(u8* planes, const u8* src, const u64* S, size_t nT, u64 capacity)
+// X: the planes of src XOR base, the base laid out as src is
+template <int E, bool X>
+__global__ __launch_bounds__(PL_THREADS) void k_planes_split(u8* planes, const u8* src, const u8* base, const u64* S, size_t nT, u64 capacity)
 {
     const u64 w = blockIdx.x;
     size_t i;
@@ -54,6 +70,7 @@ __global__ __launch_bounds__(PL_THREADS) void k_planes_split(u8* planes, const u
     const u64 n = s1 - s0;
     const u32 tid = threadIdx.x;
     const u8* const sb = src + s0;
+    const u8* const bb = X ? base + s0 : nullptr;
     u8* const pb = planes + s0;
     const PlShare h = pl_share<E>(s0, n, lo, (u64)(uintptr_t)pb, 1);
     for (u64 c = tid; c < h.nch; c += PL_THREADS) {
@@ -61,6 +78,10 @@ __global__ __launch_bounds__(PL_THREADS) void k_planes_split(u8* planes, const u
         u32 wv[4 * E], o[E][4];
 #pragma unroll
         for (int k = 0; k < E; ++k) __builtin_memcpy(&wv[4 * k], sb + e * E + 16 * k, 16);
+        if constexpr (X) {
+#pragma unroll
+            for (int k = 0; k < E; ++k) pl_xor16(&wv[4 * k], bb + e * E + 16 * k);
+        }
         pl_deinterleave<E>(wv, o);
 #pragma unroll
         for (int p = 0; p < E; ++p) __builtin_memcpy(pb + pl_start(n, p, E) + e, o[p], 16);
@@ -69,7 +90,11 @@ __global__ __launch_bounds__(PL_THREADS) void k_planes_split(u8* planes, const u
     const u64 nHead = (h.eb - h.e0) * E, nTail = (h.e1 - h.et) * E;
     for (u64 j = tid; j < nHead + nTail; j += PL_THREADS) {
         const u64 k = j < nHead ? h.e0 * E + j : h.et * E + (j - nHead);
-        if (k < n) pb[pl_start(n, (u32)(k % E), E) + k / E] = sb[k];
+        if (k < n) {
+            u8 v = sb[k];
+            if constexpr (X) v ^= bb[k];
+            pb[pl_start(n, (u32)(k % E), E) + k / E] = v;
+        }
     }
 }
 
@@ -79,8 +104,16 @@ __global__ void k_planes_verdicts(size_t* res, const u64* D, const size_t* PS, s
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < nT) res[i] = pm_verdict(D, PS, i, E, dstCapacity);
 }
-template <int E>
-__global__ __launch_bounds__(PL_THREADS) void k_planes_merge(u8* dst, const u64* D, const u8* planes, const u64* PO, const size_t* PS, size_t nT, u64 dstCapacity)
+// X: every rebuilt tensor XOR base, the base laid out as dst is.
+// IN PLACE: `base` may be exactly `dst` (the resident tensors are updated where they lie).  Chunks, head and tail partition the elements of a
+// workgroup's share, the shares partition the tensor (planes_dev.h: pl_share, the work mapping), and a tensor's bytes belong to no other
+// tensor: every byte of dst is read (as base) and written by exactly ONE thread, and no thread reads a base byte that another one writes.
+// Within a thread the base loads of a chunk -- all E of them -- precede its stores in program order, and neither pointer is __restrict__,
+// so the compiler keeps that order: a store never lands in front of the load of the same bytes.  Any other overlap of base and dst is the
+// caller's error and is not checked.  A refused or failed tensor returns in front of every load and store: in place its base stays as it is.
+template <int E, bool X>
+__global__ __launch_bounds__(PL_THREADS) void k_planes_merge(u8* dst, const u64* D, const u8* planes, const u64* PO, const size_t* PS, const u8* base, size_t nT,
+                                                             u64 dstCapacity)
 {
     const u64 w = blockIdx.x;
     size_t i;
@@ -92,6 +125,7 @@ __global__ __launch_bounds__(PL_THREADS) void k_planes_merge(u8* dst, const u64*
     const u64 n = v;
     const u32 tid = threadIdx.x;
     u8* const db = dst + d0;
+    const u8* const bb = X ? base + d0 : nullptr;
     const u8* pp[E];
 #pragma unroll
     for (int p = 0; p < E; ++p) pp[p] = planes + PO[i * E + p];
@@ -103,51 +137,94 @@ __global__ __launch_bounds__(PL_THREADS) void k_planes_merge(u8* dst, const u64*
 #pragma unroll
         for (int p = 0; p < E; ++p) __builtin_memcpy(o[p], pp[p] + e, 16);
         pl_interleave<E>(wv, o);
+        if constexpr (X) {
+#pragma unroll
+            for (int k = 0; k < E; ++k) pl_xor16(&wv[4 * k], bb + e * E + 16 * k);          // (in place: these loads, then the stores below)
+        }
 #pragma unroll
         for (int k = 0; k < E; ++k) __builtin_memcpy(db + e * E + 16 * k, &wv[4 * k], 16);
     }
     const u64 nHead = (h.eb - h.e0) * E, nTail = (h.e1 - h.et) * E;
     for (u64 j = tid; j < nHead + nTail; j += PL_THREADS) {
         const u64 k = j < nHead ? h.e0 * E + j : h.et * E + (j - nHead);
-        if (k < n) db[k] = planes[PO[i * E + k % E] + k / E];
+        if (k < n) {
+            u8 v8 = planes[PO[i * E + k % E] + k / E];
+            if constexpr (X) v8 ^= bb[k];                         // (in place: this load, then the store)
+            db[k] = v8;
+        }
     }
 }
-
 }   // namespace
 
-// the two per-tensor kernels on their own: the XOR forms (planes_delta.hip) launch them in front of data kernels of their own
-void launch_planes_offsets(u64* planeOff, size_t* tensorRes, const u64* srcOff, size_t nTensors, unsigned E, u64 capacity, hipStream_t s)
+// base null: the plain kernels, and no data kernel at all for E == 1 (the planes of such a tensor are the tensor).  The offsets kernel runs
+// even for no tensors: it writes the last entry
+hipError_t launch_planes_split(u8* planes, u64* planeOff, size_t* tensorRes, const u8* src, const u8* base, const u64* srcOff, size_t nTensors, unsigned E, u64 capacity,
+                               hipStream_t s)
 {
     hipLaunchKernelGGL(k_planes_offsets, dim3(grid_for(nTensors + 1)), dim3(PL_THREADS), 0, s, planeOff, tensorRes, srcOff, nTensors, (u32)E, capacity);
-}
-void launch_planes_verdicts(size_t* results, const u64* dstOff, const size_t* planeSizes, size_t nTensors, unsigned E, u64 dstCapacity, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_planes_verdicts, dim3(grid_for(nTensors)), dim3(PL_THREADS), 0, s, results, dstOff, planeSizes, nTensors, (u32)E, dstCapacity);
-}
-
-hipError_t launch_planes_split(u8* planes, u64* planeOff, size_t* tensorRes, const u8* src, const u64* srcOff, size_t nTensors, unsigned E, u64 capacity, hipStream_t s)
-{
-    launch_planes_offsets(planeOff, tensorRes, srcOff, nTensors, E, capacity, s);
-    if (E == 1 || nTensors == 0 || capacity == 0) return hipGetLastError();
+    if ((E == 1 && !base) || nTensors == 0 || capacity == 0) return hipGetLastError();
     const dim3 g(tile_grid(capacity, nTensors)), b(PL_THREADS);
-    if (E == 2) hipLaunchKernelGGL(k_planes_split<2>, g, b, 0, s, planes, src, srcOff, nTensors, capacity);
-    else if (E == 4) hipLaunchKernelGGL(k_planes_split<4>, g, b, 0, s, planes, src, srcOff, nTensors, capacity);
-    else hipLaunchKernelGGL(k_planes_split<8>, g, b, 0, s, planes, src, srcOff, nTensors, capacity);
+    pl_for_elem(E, [&](auto eb) {
+        constexpr int EB = decltype(eb)::value;
+        if (base) hipLaunchKernelGGL((k_planes_split<EB, true>), g, b, 0, s, planes, src, base, srcOff, nTensors, capacity);
+        else hipLaunchKernelGGL((k_planes_split<EB, false>), g, b, 0, s, planes, src, base, srcOff, nTensors, capacity);
+    });
     return hipGetLastError();
 }
 
-hipError_t launch_planes_merge(u8* dst, const u64* dstOff, size_t* results, const u8* planes, const u64* planeOff, const size_t* planeSizes, size_t nTensors, unsigned E,
-                               u64 dstCapacity, hipStream_t s)
+// base null: the plain merge.  The tail of every decompress composite, over whatever plane offsets and sizes the steps in front of it left
+hipError_t launch_planes_merge(u8* dst, const u64* dstOff, size_t* results, const u8* planes, const u64* planeOff, const size_t* planeSizes, const u8* base,
+                               size_t nTensors, unsigned E, u64 dstCapacity, hipStream_t s)
 {
     if (nTensors == 0) return hipSuccess;
-    launch_planes_verdicts(results, dstOff, planeSizes, nTensors, E, dstCapacity, s);
+    hipLaunchKernelGGL(k_planes_verdicts, dim3(grid_for(nTensors)), dim3(PL_THREADS), 0, s, results, dstOff, planeSizes, nTensors, (u32)E, dstCapacity);
     if (dstCapacity == 0) return hipGetLastError();
     const dim3 g(tile_grid(dstCapacity, nTensors)), b(PL_THREADS);
-    if (E == 1) hipLaunchKernelGGL(k_planes_merge<1>, g, b, 0, s, dst, dstOff, planes, planeOff, planeSizes, nTensors, dstCapacity);
-    else if (E == 2) hipLaunchKernelGGL(k_planes_merge<2>, g, b, 0, s, dst, dstOff, planes, planeOff, planeSizes, nTensors, dstCapacity);
-    else if (E == 4) hipLaunchKernelGGL(k_planes_merge<4>, g, b, 0, s, dst, dstOff, planes, planeOff, planeSizes, nTensors, dstCapacity);
-    else hipLaunchKernelGGL(k_planes_merge<8>, g, b, 0, s, dst, dstOff, planes, planeOff, planeSizes, nTensors, dstCapacity);
+    pl_for_elem(E, [&](auto eb) {
+        constexpr int EB = decltype(eb)::value;
+        if (base) hipLaunchKernelGGL((k_planes_merge<EB, true>), g, b, 0, s, dst, dstOff, planes, planeOff, planeSizes, base, nTensors, dstCapacity);
+        else hipLaunchKernelGGL((k_planes_merge<EB, false>), g, b, 0, s, dst, dstOff, planes, planeOff, planeSizes, base, nTensors, dstCapacity);
+    });
     return hipGetLastError();
+}
+
+// The one compress path of the four composites, each of which has checked its own pointers: the remaining argument checks of all steps in
+// front of the first launch (fsehip.h: what the guarantee covers), the split (d_base given: the XOR split), the segments kernel where
+// d_segFirst is given, then the packed writer -- a codec per frame where w.d_codecs is given -- over the planes or their segments, read
+// from d_src itself where the split moved nothing
+int planes_compress(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults, const void* d_src, const void* d_base,
+                    const uint64_t* d_srcOffsets, size_t nTensors, unsigned E, uint64_t capacity, const uint64_t* d_segFirst, size_t nSegments, unsigned segLog,
+                    void* d_planes, uint64_t* d_planeOffsets, uint64_t* d_segOffsets, const PlWriter& w, void* stream)
+{
+    if (d_segFirst ? bad_seg(segLog, w.blockSizeId) || bad_counts(nTensors, E, nSegments) : bad_tensors(nTensors, E)) return (int)hipErrorInvalidValue;
+    const size_t nFrames = d_segFirst ? nSegments : nTensors * E;
+    if (bad_grid(capacity, nTensors) || bad_writer(w, nFrames)) return (int)hipErrorInvalidValue;
+    const hipStream_t s = (hipStream_t)stream;
+    hipError_t e = launch_planes_split((u8*)d_planes, (u64*)d_planeOffsets, d_tensorResults, (const u8*)d_src, (const u8*)d_base, (const u64*)d_srcOffsets, nTensors, E,
+                                       capacity, s);
+    if (e == hipSuccess && d_segFirst)
+        e = launch_segments((u64*)d_segOffsets, d_tensorResults, (const u64*)d_planeOffsets, (const u64*)d_srcOffsets, (const u64*)d_segFirst, nTensors, E, nSegments, segLog, s);
+    if (e != hipSuccess) return (int)e;
+    const void* const from = !d_base && E == 1 ? d_src : d_planes;
+    const uint64_t* const fromOff = d_segFirst ? d_segOffsets : d_planeOffsets;
+    if (w.d_codecs)
+        return FSEHIP_frame_compress_packed_mixed_dbatch(d_dst, dstCapacity, d_frameOffsets, d_frameResults, from, fromOff, nFrames, w.maxTotalBlocks, w.blockSizeId,
+                                                         w.d_codecs, w.policy, w.tolerancePermille, w.slotAlignLog, w.d_workspace, w.workspaceBytes, stream);
+    return FSEHIP_frame_compress_packed_dbatch(d_dst, dstCapacity, d_frameOffsets, d_frameResults, from, fromOff, nFrames, w.maxTotalBlocks, w.blockSizeId, w.codec,
+                                               w.slotAlignLog, w.d_workspace, w.workspaceBytes, stream);
+}
+
+// FSEHIP_tensor_decompress_dbatch and _delta_dbatch behind their pointer checks: they differ in the base alone
+static int planes_decompress(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base, size_t* d_results, const void* d_frames,
+                             const uint64_t* d_frameOffsets, size_t nTensors, unsigned E, size_t maxTotalBlocks, void* d_planes, uint64_t planesCapacity,
+                             uint64_t* d_planeOffsets, size_t* d_planeResults, void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    if (bad_tensors(nTensors, E) || bad_grid(dstCapacity, nTensors) || bad_reader(d_workspace, workspaceBytes, nTensors * E, maxTotalBlocks)) return (int)hipErrorInvalidValue;
+    const int e = FSEHIP_frame_decompress_packed_dbatch(d_planes, (size_t)planesCapacity, d_planeOffsets, d_planeResults, d_frames, d_frameOffsets, nTensors * E, maxTotalBlocks,
+                                                        0, d_workspace, workspaceBytes, stream);
+    if (e != 0) return e;
+    return (int)launch_planes_merge((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeResults, (const u8*)d_base,
+                                    nTensors, E, dstCapacity, (hipStream_t)stream);
 }
 
 extern "C" size_t FSEHIP_planes_blockBound(size_t totalBytes, size_t nTensors, unsigned elemBytes, unsigned blockSizeId)
@@ -161,18 +238,34 @@ extern "C" int FSEHIP_planes_split_dbatch(void* d_planes, uint64_t* d_planeOffse
                                           size_t nTensors, unsigned elemBytes, uint64_t capacity, void* stream)
 {
     if (bad_elem(elemBytes) || !d_planeOffsets || !d_tensorResults || !d_srcOffsets || (elemBytes > 1 && (!d_planes || !d_src))) return (int)hipErrorInvalidValue;
-    if (nTensors >= ((size_t)1 << 31) / elemBytes || bad_grid(capacity, nTensors)) return (int)hipErrorInvalidValue;
-    return (int)launch_planes_split((u8*)d_planes, (u64*)d_planeOffsets, d_tensorResults, (const u8*)d_src, (const u64*)d_srcOffsets, nTensors, elemBytes, capacity,
+    if (bad_tensors(nTensors, elemBytes) || bad_grid(capacity, nTensors)) return (int)hipErrorInvalidValue;
+    return (int)launch_planes_split((u8*)d_planes, (u64*)d_planeOffsets, d_tensorResults, (const u8*)d_src, nullptr, (const u64*)d_srcOffsets, nTensors, elemBytes, capacity,
                                     (hipStream_t)stream);
+}
+extern "C" int FSEHIP_planes_split_xor_dbatch(void* d_planes, uint64_t* d_planeOffsets, size_t* d_tensorResults, const void* d_src, const void* d_base,
+                                              const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes, uint64_t capacity, void* stream)
+{
+    if (bad_elem(elemBytes) || !d_planes || !d_planeOffsets || !d_tensorResults || !d_src || !d_base || !d_srcOffsets) return (int)hipErrorInvalidValue;
+    if (bad_tensors(nTensors, elemBytes) || bad_grid(capacity, nTensors)) return (int)hipErrorInvalidValue;
+    return (int)launch_planes_split((u8*)d_planes, (u64*)d_planeOffsets, d_tensorResults, (const u8*)d_src, (const u8*)d_base, (const u64*)d_srcOffsets, nTensors, elemBytes,
+                                    capacity, (hipStream_t)stream);
 }
 
 extern "C" int FSEHIP_planes_merge_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_planes, const uint64_t* d_planeOffsets,
                                           const size_t* d_planeSizes, size_t nTensors, unsigned elemBytes, uint64_t dstCapacity, void* stream)
 {
     if (bad_elem(elemBytes) || !d_dst || !d_dstOffsets || !d_results || !d_planes || !d_planeOffsets || !d_planeSizes) return (int)hipErrorInvalidValue;
-    if (nTensors >= ((size_t)1 << 31) / elemBytes || bad_grid(dstCapacity, nTensors)) return (int)hipErrorInvalidValue;
-    return (int)launch_planes_merge((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeSizes, nTensors, elemBytes,
-                                    dstCapacity, (hipStream_t)stream);
+    if (bad_tensors(nTensors, elemBytes) || bad_grid(dstCapacity, nTensors)) return (int)hipErrorInvalidValue;
+    return (int)launch_planes_merge((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeSizes, nullptr, nTensors,
+                                    elemBytes, dstCapacity, (hipStream_t)stream);
+}
+extern "C" int FSEHIP_planes_merge_xor_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_planes, const uint64_t* d_planeOffsets,
+                                              const size_t* d_planeSizes, const void* d_base, size_t nTensors, unsigned elemBytes, uint64_t dstCapacity, void* stream)
+{
+    if (bad_elem(elemBytes) || !d_dst || !d_dstOffsets || !d_results || !d_planes || !d_planeOffsets || !d_planeSizes || !d_base) return (int)hipErrorInvalidValue;
+    if (bad_tensors(nTensors, elemBytes) || bad_grid(dstCapacity, nTensors)) return (int)hipErrorInvalidValue;
+    return (int)launch_planes_merge((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeSizes, (const u8*)d_base,
+                                    nTensors, elemBytes, dstCapacity, (hipStream_t)stream);
 }
 
 extern "C" int FSEHIP_tensor_compress_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
@@ -180,18 +273,34 @@ extern "C" int FSEHIP_tensor_compress_dbatch(void* d_dst, uint64_t dstCapacity, 
                                              size_t maxTotalBlocks, unsigned blockSizeId, int codec, unsigned slotAlignLog,
                                              void* d_planes, uint64_t* d_planeOffsets, void* d_workspace, size_t workspaceBytes, void* stream)
 {
-    // the argument checks of both steps, as they stand today, in front of the first launch (fsehip.h: what the guarantee covers)
     if (bad_elem(elemBytes) || !d_frameOffsets || !d_frameResults || !d_tensorResults || !d_src || !d_srcOffsets || !d_planeOffsets || (elemBytes > 1 && !d_planes))
         return (int)hipErrorInvalidValue;
-    if (nTensors >= ((size_t)1 << 31) / elemBytes || bad_grid(capacity, nTensors)) return (int)hipErrorInvalidValue;
-    if (blockSizeId > 6 || (codec != 0 && codec != 1) || slotAlignLog > 12 || ((uintptr_t)d_workspace & 255u) || maxTotalBlocks >= ((size_t)1 << 31)) return (int)hipErrorInvalidValue;
-    const size_t nFrames = nTensors * elemBytes;
-    if (workspaceBytes < FSEHIP_frame_compress_packed_dbatch_workspaceSize(nFrames, maxTotalBlocks, blockSizeId, codec)) return (int)hipErrorInvalidValue;
-    const hipError_t e = launch_planes_split((u8*)d_planes, (u64*)d_planeOffsets, d_tensorResults, (const u8*)d_src, (const u64*)d_srcOffsets, nTensors, elemBytes, capacity,
-                                             (hipStream_t)stream);
-    if (e != hipSuccess) return (int)e;
-    return FSEHIP_frame_compress_packed_dbatch(d_dst, dstCapacity, d_frameOffsets, d_frameResults, elemBytes == 1 ? d_src : d_planes, d_planeOffsets, nFrames, maxTotalBlocks,
-                                               blockSizeId, codec, slotAlignLog, d_workspace, workspaceBytes, stream);
+    return planes_compress(d_dst, dstCapacity, d_frameOffsets, d_frameResults, d_tensorResults, d_src, nullptr, d_srcOffsets, nTensors, elemBytes, capacity, nullptr, 0, 0,
+                           d_planes, d_planeOffsets, nullptr, PlWriter{ maxTotalBlocks, blockSizeId, codec, nullptr, 0, 0, slotAlignLog, d_workspace, workspaceBytes }, stream);
+}
+extern "C" int FSEHIP_tensor_compress_delta_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
+                                                   const void* d_src, const void* d_base, const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes,
+                                                   uint64_t capacity, size_t maxTotalBlocks, unsigned blockSizeId, int codec, unsigned slotAlignLog,
+                                                   void* d_planes, uint64_t* d_planeOffsets, void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    if (bad_elem(elemBytes) || !d_frameOffsets || !d_frameResults || !d_tensorResults || !d_src || !d_base || !d_srcOffsets || !d_planeOffsets || !d_planes)
+        return (int)hipErrorInvalidValue;
+    return planes_compress(d_dst, dstCapacity, d_frameOffsets, d_frameResults, d_tensorResults, d_src, d_base, d_srcOffsets, nTensors, elemBytes, capacity, nullptr, 0, 0,
+                           d_planes, d_planeOffsets, nullptr, PlWriter{ maxTotalBlocks, blockSizeId, codec, nullptr, 0, 0, slotAlignLog, d_workspace, workspaceBytes }, stream);
+}
+// the plain (d_base == nullptr) or the XOR split, then the packed writer with a codec per plane
+extern "C" int FSEHIP_tensor_compress_mixed_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
+                                                   const void* d_src, const void* d_base, const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes,
+                                                   uint64_t capacity, size_t maxTotalBlocks, unsigned blockSizeId, uint8_t* d_codecs, int policy,
+                                                   unsigned tolerancePermille, unsigned slotAlignLog, void* d_planes, uint64_t* d_planeOffsets,
+                                                   void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    if (bad_elem(elemBytes) || !d_frameOffsets || !d_frameResults || !d_tensorResults || !d_src || !d_srcOffsets || !d_planeOffsets || !d_codecs ||
+        ((elemBytes > 1 || d_base) && !d_planes))
+        return (int)hipErrorInvalidValue;
+    return planes_compress(d_dst, dstCapacity, d_frameOffsets, d_frameResults, d_tensorResults, d_src, d_base, d_srcOffsets, nTensors, elemBytes, capacity, nullptr, 0, 0,
+                           d_planes, d_planeOffsets, nullptr,
+                           PlWriter{ maxTotalBlocks, blockSizeId, 0, d_codecs, policy, tolerancePermille, slotAlignLog, d_workspace, workspaceBytes }, stream);
 }
 
 extern "C" int FSEHIP_tensor_decompress_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, size_t* d_results,
@@ -201,13 +310,16 @@ extern "C" int FSEHIP_tensor_decompress_dbatch(void* d_dst, const uint64_t* d_ds
 {
     if (bad_elem(elemBytes) || !d_dst || !d_dstOffsets || !d_results || !d_frames || !d_frameOffsets || !d_planes || !d_planeOffsets || !d_planeResults)
         return (int)hipErrorInvalidValue;
-    if (nTensors >= ((size_t)1 << 31) / elemBytes || bad_grid(dstCapacity, nTensors)) return (int)hipErrorInvalidValue;
-    if (((uintptr_t)d_workspace & 255u) || maxTotalBlocks >= ((size_t)1 << 31)) return (int)hipErrorInvalidValue;
-    const size_t nFrames = nTensors * elemBytes;
-    if (workspaceBytes < FSEHIP_frame_decompress_packed_dbatch_workspaceSize(nFrames, maxTotalBlocks)) return (int)hipErrorInvalidValue;
-    const int e = FSEHIP_frame_decompress_packed_dbatch(d_planes, (size_t)planesCapacity, d_planeOffsets, d_planeResults, d_frames, d_frameOffsets, nFrames, maxTotalBlocks, 0,
-                                                        d_workspace, workspaceBytes, stream);
-    if (e != 0) return e;
-    return (int)launch_planes_merge((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeResults, nTensors, elemBytes,
-                                    dstCapacity, (hipStream_t)stream);
+    return planes_decompress(d_dst, d_dstOffsets, dstCapacity, nullptr, d_results, d_frames, d_frameOffsets, nTensors, elemBytes, maxTotalBlocks, d_planes, planesCapacity,
+                             d_planeOffsets, d_planeResults, d_workspace, workspaceBytes, stream);
+}
+extern "C" int FSEHIP_tensor_decompress_delta_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base, size_t* d_results,
+                                                     const void* d_frames, const uint64_t* d_frameOffsets, size_t nTensors, unsigned elemBytes, size_t maxTotalBlocks,
+                                                     void* d_planes, uint64_t planesCapacity, uint64_t* d_planeOffsets, size_t* d_planeResults,
+                                                     void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    if (bad_elem(elemBytes) || !d_dst || !d_dstOffsets || !d_base || !d_results || !d_frames || !d_frameOffsets || !d_planes || !d_planeOffsets || !d_planeResults)
+        return (int)hipErrorInvalidValue;
+    return planes_decompress(d_dst, d_dstOffsets, dstCapacity, d_base, d_results, d_frames, d_frameOffsets, nTensors, elemBytes, maxTotalBlocks, d_planes, planesCapacity,
+                             d_planeOffsets, d_planeResults, d_workspace, workspaceBytes, stream);
 }

@@ -1,11 +1,14 @@
-// planes_dev.h -- what the data kernels of planes.hip (byte planes of tensors) and planes_delta.hip (their XOR forms) share: the byte shuffle, the
-// plane arithmetic, the work mapping, a workgroup's share of a tensor, the merge's verdict and the launch limits.  Device helpers are inlined
-// into the kernels of the file that includes this; nothing here is a kernel.
+// planes_dev.h -- what the plane files (planes.hip: byte planes of tensors and their XOR forms; planes_seg.hip; planes_win.hip) share: the byte
+// shuffle, the plane arithmetic, the search behind every work mapping, a workgroup's share of a tensor, the merge's verdict, the fold of a
+// plane's segment results, the dispatch over the element size and the argument checks of the C calls.  Device helpers are inlined into the
+// kernels of the file that includes this; nothing here is a kernel.
 #pragma once
 #include "internal.h"
+#include <type_traits>
 
 namespace {
 #define PL_THREADS 256
+#define HDEV __host__ __device__ __forceinline__
 #define PL_TILE_LOG 15
 static_assert(PLANES_TILE == ((u64)1 << PL_TILE_LOG), "tile size");
 inline unsigned grid_for(size_t n) { return (unsigned)((n + PL_THREADS - 1) / PL_THREADS); }
@@ -38,17 +41,32 @@ template <int E> DEV void pl_interleave(u32* w, const u32 (*o)[4], int p0 = 0, i
     }
 }
 
-// size of plane p of a tensor of n bytes, and where it starts inside the tensor (the sizes of the planes in front of it)
-DEV u64 pl_size(u64 n, u32 p, u32 E) { return n > p ? (n - p + E - 1) / E : 0; }
-DEV u64 pl_start(u64 n, u32 p, u32 E) { const u64 r = n % E; return (u64)p * (n / E) + (p < r ? p : r); }
+// w ^= the 16 bytes at `from` (the base stream of the XOR forms; any alignment)
+DEV void pl_xor16(u32* w, const u8* from)
+{
+    u32 t[4];
+    __builtin_memcpy(t, from, 16);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) w[k] ^= t[k];
+}
 
+// size of plane p of a tensor of n bytes, and where it starts inside the tensor (the sizes of the planes in front of it)
+HDEV u64 pl_size(u64 n, u32 p, u32 E) { return n > p ? (n - p + E - 1) / E : 0; }
+HDEV u64 pl_start(u64 n, u32 p, u32 E) { const u64 r = n % E; return (u64)p * (n / E) + (p < r ? p : r); }
+
+// the largest j < n with key(j) <= q, for n >= 1 and a key that does not decrease; 0 where there is none.  The result is an index below n
+// whatever the keys hold: a caller that reads its keys from an array it does not trust indexes with the result, never with a key
+template <class Key> DEV size_t pl_last_le(size_t n, u64 q, Key key)
+{
+    size_t lo = 0, hi = n - 1;
+    while (lo < hi) { const size_t mid = lo + ((hi - lo + 1) >> 1); if (key(mid) <= q) lo = mid; else hi = mid - 1; }
+    return lo;
+}
 // the work mapping: the largest i < nT with floor(S[i] / T) + i <= w (false: there is none)
 DEV bool pl_find(const u64* S, size_t nT, u64 w, size_t& i)
 {
     if (nT == 0 || (S[0] >> PL_TILE_LOG) > w) return false;
-    size_t lo = 0, hi = nT - 1;
-    while (lo < hi) { const size_t mid = lo + ((hi - lo + 1) >> 1); if ((S[mid] >> PL_TILE_LOG) + mid <= w) lo = mid; else hi = mid - 1; }
-    i = lo;
+    i = pl_last_le(nT, w, [S](size_t j) { return (S[j] >> PL_TILE_LOG) + j; });
     return true;
 }
 // A workgroup's share of a tensor of n bytes at flat position s0, tile [lo, lo + T): the elements [e0, e1) whose first byte lies in the tile
@@ -94,11 +112,35 @@ DEV bool ps_tensor_ok(const u64* S, const u64* SF, size_t i, u32 E, u32 segLog)
     for (u32 p = 0; p < E; ++p) ok = ok && SF[i * E + p + 1] - SF[i * E + p] == ps_count(pl_size(n, p, E), segLog);
     return ok;
 }
+// What the two folds (k_planes_fold, k_planes_fold_window) share: one wave over the results res[0 .. cnt) of a plane's segments, which were
+// written at off[0 .. cnt).  firstErr = the smallest index that holds an error (none: 0xFFFFFFFF); bad = a good segment whose size the
+// caller's rule sizeOk(k, r) refuses, or that does not end where the next one starts; sum = the bytes of the good ones.  Every check is per
+// segment, the reductions stand behind the loop, where all lanes are active again: all lanes return the same
+struct PsFold { u32 firstErr, bad; u64 sum; };
+template <class Rule> DEV PsFold ps_fold(const u64* off, const size_t* res, u64 cnt, u32 lane, Rule sizeOk)
+{
+    PsFold f = { 0xFFFFFFFFu, 0, 0 };
+    for (u64 k = lane; k < cnt; k += WAVE) {
+        const size_t r = res[k];
+        if (is_err(r)) { if ((u32)k < f.firstErr) f.firstErr = (u32)k; continue; }
+        if (!sizeOk(k, (u64)r)) f.bad = 1;
+        if (k + 1 < cnt && off[k + 1] != off[k] + r) f.bad = 1;                        // ... and they lie back to back
+        f.sum += r;
+    }
+    f.firstErr = group_reduce<64, ScanMin>(f.firstErr, lane);
+    f.bad = group_reduce<64, ScanMax>(f.bad, lane);
+    f.sum = group_last64<64>(group_scan_incl_add64<64>(f.sum, lane), lane);
+    return f;
+}
 
 // ---- windows of segmented tensors (planes_win.hip; fsehip.h, "windows of segmented tensors") ----
 // the window [a, b) of tensor i in elements, the segments k0 .. k0 + cnt - 1 of each of its planes that hold it (cnt 0: an empty window), and
 // whether the tensor is accepted: a valid window, cnt in selFirst for each of its planes, ending at or below nSel, and ps_tensor_ok.  For an
 // accepted tensor WF[i * E + p] + cnt <= nSel for every plane p, and segment k0 + cnt - 1 exists in every plane
+// (the segments k0 .. k0 + cnt - 1 of a plane that hold the elements [a, b) of a valid window, cnt 0 for an empty or a refused one: pw_range,
+// the host's arithmetic too)
+struct PwRange { u64 k0, cnt; };
+HDEV PwRange pw_range(u64 a, u64 b, bool valid, u32 segLog) { const u64 k0 = a >> segLog; return { k0, valid && a < b ? ((b - 1) >> segLog) - k0 + 1 : 0 }; }
 struct PwWin { u64 a, b, k0, cnt; bool ok; };
 DEV PwWin pw_window(const u64* S, const u64* W, const u64* SF, const u64* WF, size_t i, u32 E, u32 segLog, size_t nSel)
 {
@@ -106,11 +148,21 @@ DEV PwWin pw_window(const u64* S, const u64* W, const u64* SF, const u64* WF, si
     PwWin w;
     w.a = W[2 * i]; w.b = W[2 * i + 1];
     w.ok = w.a <= w.b && w.b <= n / E;
-    w.k0 = w.a >> segLog;
-    w.cnt = w.ok && w.a < w.b ? ((w.b - 1) >> segLog) - w.k0 + 1 : 0;
+    const PwRange r = pw_range(w.a, w.b, w.ok, segLog);
+    w.k0 = r.k0; w.cnt = r.cnt;
     for (u32 p = 0; p < E; ++p) w.ok = w.ok && WF[i * E + p + 1] - WF[i * E + p] == w.cnt;
     w.ok = w.ok && WF[i * E] <= WF[(i + 1) * E] && WF[(i + 1) * E] <= nSel && ps_tensor_ok(S, SF, i, E, segLog);
     return w;
+}
+
+// ---- the launches and the argument checks of the C calls ----
+// the one dispatch over the element size: f(std::integral_constant<int, E>) for the E that bad_elem lets through
+template <class F> inline void pl_for_elem(unsigned E, F f)
+{
+    if (E == 1) f(std::integral_constant<int, 1>());
+    else if (E == 2) f(std::integral_constant<int, 2>());
+    else if (E == 4) f(std::integral_constant<int, 4>());
+    else f(std::integral_constant<int, 8>());
 }
 
 inline bool bad_elem(unsigned E) { return E != 1 && E != 2 && E != 4 && E != 8; }
@@ -118,4 +170,21 @@ inline bool bad_seg(unsigned segLog, unsigned blockSizeId) { return segLog < 10 
 // ceil(capacity / T) + nTensors workgroups of PL_THREADS threads in one launch
 inline bool bad_grid(u64 capacity, size_t nTensors) { return capacity >= ((u64)1 << 46) || (capacity >> PL_TILE_LOG) + 1 + nTensors >= ((u64)1 << 24); }
 inline unsigned tile_grid(u64 capacity, size_t nTensors) { return (unsigned)(((capacity + PLANES_TILE - 1) >> PL_TILE_LOG) + nTensors); }
+// fewer than 2^31 planes, and fewer than 2^31 segment (or selected) frames
+inline bool bad_tensors(size_t nTensors, unsigned E) { return nTensors >= ((size_t)1 << 31) / E; }
+inline bool bad_counts(size_t nTensors, unsigned E, size_t nFrames) { return bad_tensors(nTensors, E) || nFrames >= ((size_t)1 << 31); }
+// what a composite hands on to the packed writer (one codec, or a codec per frame where w.d_codecs is given) and to the packed reader, for
+// nFrames frames: the checks those calls make themselves, here in front of the composite's first launch
+inline bool bad_writer(const PlWriter& w, size_t nFrames)
+{
+    if (w.blockSizeId > 6 || w.slotAlignLog > 12 || ((uintptr_t)w.d_workspace & 255u) || w.maxTotalBlocks >= ((size_t)1 << 31)) return true;
+    if (!w.d_codecs)
+        return (w.codec != 0 && w.codec != 1) || w.workspaceBytes < FSEHIP_frame_compress_packed_dbatch_workspaceSize(nFrames, w.maxTotalBlocks, w.blockSizeId, w.codec);
+    if ((w.policy != FSEHIP_CODECS_GIVEN && w.policy != FSEHIP_CODECS_CHOOSE) || (w.policy == FSEHIP_CODECS_CHOOSE && w.tolerancePermille > 1000)) return true;
+    return w.workspaceBytes < FSEHIP_frame_mixedWorkspaceBound(nFrames, w.maxTotalBlocks, w.blockSizeId, w.policy);
+}
+inline bool bad_reader(const void* d_workspace, size_t workspaceBytes, size_t nFrames, size_t maxTotalBlocks)
+{
+    return ((uintptr_t)d_workspace & 255u) || maxTotalBlocks >= ((size_t)1 << 31) || workspaceBytes < FSEHIP_frame_decompress_packed_dbatch_workspaceSize(nFrames, maxTotalBlocks);
+}
 }   // namespace

@@ -9,11 +9,11 @@
 //   FSEHIP_planes_fold_segments_dbatch   : k_planes_fold -- per plane (one wave) the offset and the verdict of its segments' results
 //   FSEHIP_tensor_compress_seg_dbatch    : the (XOR) split -> the segments kernel -> the packed (mixed) writer over the segments
 //   FSEHIP_tensor_decompress_seg_dbatch  : the packed reader into the planes buffer -> the fold -> the (XOR) merge
-// The data kernels of planes.hip / planes_delta.hip run unchanged in front of and behind these.
+// The data kernels of planes.hip run unchanged in front of and behind these.
 #include "planes_dev.h"
 
 namespace {
-// One thread per segment entry q <= nSeg: the plane j that holds it is the largest j < nP with SF[j] <= q (a binary search, the pattern of
+// One thread per segment entry q <= nSeg: the plane j that holds it is the largest j < nP with SF[j] <= q (pl_last_le, the search of
 // pl_find), its entry min(P[j] + (q - SF[j]) * seg, P[j + 1]); the entries of a tensor whose counts in SF are not those its size implies are
 // all its start P[i * E].  The last entry is P[nP].  Threads i < nT also write tensor i's GENERIC.  SF's values are never used as indices and
 // every index is clamped: whatever SF holds, nothing outside the arrays is touched.
@@ -24,16 +24,14 @@ __global__ void k_planes_segments(u64* SO, size_t* tres, const u64* P, const u64
     if (q < nT && !ps_tensor_ok(S, SF, q, E, segLog)) tres[q] = FERR(GENERIC);
     if (q > nSeg) return;
     if (q == nSeg || nP == 0) { SO[q] = P[nP]; return; }
-    size_t lo = 0, hi = nP - 1;
-    while (lo < hi) { const size_t mid = lo + ((hi - lo + 1) >> 1); if (SF[mid] <= q) lo = mid; else hi = mid - 1; }
-    const size_t j = lo, i = j / E;
+    const size_t j = pl_last_le(nP, q, [SF](size_t m) { return SF[m]; }), i = j / E;
     if (!ps_tensor_ok(S, SF, i, E, segLog)) { SO[q] = P[i * E]; return; }
     const u64 f = SF[j], k = q >= f ? q - f : 0, at = P[j] + (k << segLog), end = P[j + 1];
     SO[q] = at < end ? at : end;
 }
 
-// One wave per plane, its lanes striding over the plane's segments; the verdict in the order of fsehip.h.  Every check is per segment, the
-// sum and the first error (the smallest segment index that holds one) are wave reductions behind the loop, where all lanes are active again.
+// One wave per plane, its lanes striding over the plane's segments (ps_fold); the verdict in the order of fsehip.h.  The size rule: every
+// segment but the last is full, the last holds 1 .. seg bytes (0 where it is the only one).
 __global__ __launch_bounds__(PL_THREADS) void k_planes_fold(u64* PO, size_t* PS, const u64* off, const size_t* res, const u64* SF, size_t nP, size_t nSeg, u32 segLog)
 {
     const size_t j = (size_t)blockIdx.x * (PL_THREADS / WAVE) + (threadIdx.x / WAVE);
@@ -43,31 +41,12 @@ __global__ __launch_bounds__(PL_THREADS) void k_planes_fold(u64* PO, size_t* PS,
     if (q1 > nSeg) q1 = nSeg;
     if (q0 > q1) q0 = q1;
     const u64 cnt = q1 - q0, seg = (u64)1 << segLog;
-    u32 firstErr = 0xFFFFFFFFu, bad = 0;
-    u64 sum = 0;
-    for (u64 k = lane; k < cnt; k += WAVE) {
-        const size_t r = res[q0 + k];
-        if (is_err(r)) { if ((u32)k < firstErr) firstErr = (u32)k; continue; }
-        const bool last = k + 1 == cnt;
-        if (last ? (r > seg || (r == 0 && cnt != 1)) : r != seg) bad = 1;            // every segment but the last is full, the last holds 1 .. seg bytes
-        if (!last && off[q0 + k + 1] != off[q0 + k] + r) bad = 1;                      // ... and they lie back to back
-        sum += r;
-    }
-    firstErr = group_reduce<64, ScanMin>(firstErr, lane);
-    bad = group_reduce<64, ScanMax>(bad, lane);
-    sum = group_last64<64>(group_scan_incl_add64<64>(sum, lane), lane);
+    const PsFold f = ps_fold(off + q0, res + q0, cnt, lane, [=](u64 k, u64 r) { return k + 1 == cnt ? r <= seg && (r != 0 || cnt == 1) : r == seg; });
     if (lane) return;
     PO[j] = off[q0];
-    PS[j] = cnt == 0 ? FERR(GENERIC) : firstErr != 0xFFFFFFFFu ? res[q0 + firstErr] : bad ? FERR(corruption_detected) : (size_t)sum;
+    PS[j] = cnt == 0 ? FERR(GENERIC) : f.firstErr != 0xFFFFFFFFu ? res[q0 + f.firstErr] : f.bad ? FERR(corruption_detected) : (size_t)f.sum;
 }
 
-hipError_t launch_segments(u64* segOff, size_t* tensorRes, const u64* planeOff, const u64* srcOff, const u64* segFirst, size_t nTensors, unsigned E, size_t nSeg,
-                           unsigned segLog, hipStream_t s)
-{
-    const size_t n = nSeg + 1 > nTensors ? nSeg + 1 : nTensors;
-    hipLaunchKernelGGL(k_planes_segments, dim3(grid_for(n)), dim3(PL_THREADS), 0, s, segOff, tensorRes, planeOff, srcOff, segFirst, nTensors, (u32)E, nSeg, (u32)segLog);
-    return hipGetLastError();
-}
 hipError_t launch_fold(u64* planeOff, size_t* planeSizes, const u64* segOff, const size_t* segRes, const u64* segFirst, size_t nPlanes, size_t nSeg, unsigned segLog,
                        hipStream_t s)
 {
@@ -77,19 +56,26 @@ hipError_t launch_fold(u64* planeOff, size_t* planeSizes, const u64* segOff, con
                        nPlanes, nSeg, (u32)segLog);
     return hipGetLastError();
 }
-inline bool bad_counts(size_t nTensors, unsigned E, size_t nSeg) { return nTensors >= ((size_t)1 << 31) / E || nSeg >= ((size_t)1 << 31); }
 }   // namespace
+
+hipError_t launch_segments(u64* segOff, size_t* tensorRes, const u64* planeOff, const u64* srcOff, const u64* segFirst, size_t nTensors, unsigned E, size_t nSeg,
+                           unsigned segLog, hipStream_t s)
+{
+    const size_t n = nSeg + 1 > nTensors ? nSeg + 1 : nTensors;
+    hipLaunchKernelGGL(k_planes_segments, dim3(grid_for(n)), dim3(PL_THREADS), 0, s, segOff, tensorRes, planeOff, srcOff, segFirst, nTensors, (u32)E, nSeg, (u32)segLog);
+    return hipGetLastError();
+}
 
 extern "C" size_t FSEHIP_planes_segmentFirst(uint64_t* h_segFirst, const uint64_t* h_offsets, size_t nTensors, unsigned elemBytes, unsigned segLog)
 {
     if (bad_elem(elemBytes) || bad_seg(segLog, 0) || (nTensors && !h_offsets)) return FSEHIP_ERROR(GENERIC);
-    const u64 E = elemBytes;
+    const u32 E = elemBytes;
     u64 total = 0;
     if (h_segFirst) h_segFirst[0] = 0;
     for (size_t i = 0; i < nTensors; ++i) {
         const u64 s0 = h_offsets[i], s1 = h_offsets[i + 1], n = s1 > s0 ? s1 - s0 : 0;
-        for (u64 p = 0; p < E; ++p) {
-            total += ps_count(n > p ? (n - p + E - 1) / E : 0, segLog);
+        for (u32 p = 0; p < E; ++p) {
+            total += ps_count(pl_size(n, p, E), segLog);
             if (total >= ((u64)1 << 31)) return FSEHIP_ERROR(GENERIC);
             if (h_segFirst) h_segFirst[i * E + p + 1] = total;
         }
@@ -115,7 +101,6 @@ extern "C" int FSEHIP_planes_fold_segments_dbatch(uint64_t* d_planeOffsets, size
                             (hipStream_t)stream);
 }
 
-// the argument checks of all three steps in front of the first launch, as FSEHIP_tensor_compress_dbatch / _mixed_dbatch have them
 extern "C" int FSEHIP_tensor_compress_seg_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
                                                  const void* d_src, const void* d_base, const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes,
                                                  uint64_t capacity, const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, size_t maxTotalBlocks,
@@ -125,30 +110,12 @@ extern "C" int FSEHIP_tensor_compress_seg_dbatch(void* d_dst, uint64_t dstCapaci
     if (bad_elem(elemBytes) || !d_frameOffsets || !d_frameResults || !d_tensorResults || !d_src || !d_srcOffsets || !d_segFirst || !d_planeOffsets || !d_segOffsets ||
         ((elemBytes > 1 || d_base) && !d_planes))
         return (int)hipErrorInvalidValue;
-    if (blockSizeId > 6 || bad_seg(segLog, blockSizeId) || bad_counts(nTensors, elemBytes, nSegments) || bad_grid(capacity, nTensors)) return (int)hipErrorInvalidValue;
-    if (slotAlignLog > 12 || ((uintptr_t)d_workspace & 255u) || maxTotalBlocks >= ((size_t)1 << 31)) return (int)hipErrorInvalidValue;
-    if (d_codecs ? (policy != FSEHIP_CODECS_GIVEN && policy != FSEHIP_CODECS_CHOOSE) || (policy == FSEHIP_CODECS_CHOOSE && tolerancePermille > 1000)
-                 : (codec != 0 && codec != 1))
-        return (int)hipErrorInvalidValue;
-    if (workspaceBytes < (d_codecs ? FSEHIP_frame_mixedWorkspaceBound(nSegments, maxTotalBlocks, blockSizeId, policy)
-                                   : FSEHIP_frame_compress_packed_dbatch_workspaceSize(nSegments, maxTotalBlocks, blockSizeId, codec)))
-        return (int)hipErrorInvalidValue;
-    const hipStream_t s = (hipStream_t)stream;
-    hipError_t e = d_base ? launch_split_xor((u8*)d_planes, (u64*)d_planeOffsets, d_tensorResults, (const u8*)d_src, (const u8*)d_base, (const u64*)d_srcOffsets, nTensors,
-                                             elemBytes, capacity, s)
-                          : launch_planes_split((u8*)d_planes, (u64*)d_planeOffsets, d_tensorResults, (const u8*)d_src, (const u64*)d_srcOffsets, nTensors, elemBytes, capacity, s);
-    if (e == hipSuccess)
-        e = launch_segments((u64*)d_segOffsets, d_tensorResults, (const u64*)d_planeOffsets, (const u64*)d_srcOffsets, (const u64*)d_segFirst, nTensors, elemBytes, nSegments,
-                            segLog, s);
-    if (e != hipSuccess) return (int)e;
-    const void* const from = !d_base && elemBytes == 1 ? d_src : d_planes;
-    if (d_codecs)
-        return FSEHIP_frame_compress_packed_mixed_dbatch(d_dst, dstCapacity, d_frameOffsets, d_frameResults, from, d_segOffsets, nSegments, maxTotalBlocks, blockSizeId,
-                                                         d_codecs, policy, tolerancePermille, slotAlignLog, d_workspace, workspaceBytes, stream);
-    return FSEHIP_frame_compress_packed_dbatch(d_dst, dstCapacity, d_frameOffsets, d_frameResults, from, d_segOffsets, nSegments, maxTotalBlocks, blockSizeId, codec,
-                                               slotAlignLog, d_workspace, workspaceBytes, stream);
+    return planes_compress(d_dst, dstCapacity, d_frameOffsets, d_frameResults, d_tensorResults, d_src, d_base, d_srcOffsets, nTensors, elemBytes, capacity, d_segFirst,
+                           nSegments, segLog, d_planes, d_planeOffsets, d_segOffsets,
+                           PlWriter{ maxTotalBlocks, blockSizeId, codec, d_codecs, policy, tolerancePermille, slotAlignLog, d_workspace, workspaceBytes }, stream);
 }
 
+// the argument checks of all three steps in front of the first launch
 extern "C" int FSEHIP_tensor_decompress_seg_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base, size_t* d_results,
                                                    const void* d_frames, const uint64_t* d_frameOffsets, size_t nTensors, unsigned elemBytes,
                                                    const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, size_t maxTotalBlocks,
@@ -158,9 +125,8 @@ extern "C" int FSEHIP_tensor_decompress_seg_dbatch(void* d_dst, const uint64_t* 
     if (bad_elem(elemBytes) || !d_dst || !d_dstOffsets || !d_results || !d_frames || !d_frameOffsets || !d_segFirst || !d_planes || !d_segOffsets || !d_segResults ||
         !d_planeOffsets || !d_planeSizes)
         return (int)hipErrorInvalidValue;
-    if (bad_seg(segLog, 0) || bad_counts(nTensors, elemBytes, nSegments) || bad_grid(dstCapacity, nTensors)) return (int)hipErrorInvalidValue;
-    if (((uintptr_t)d_workspace & 255u) || maxTotalBlocks >= ((size_t)1 << 31)) return (int)hipErrorInvalidValue;
-    if (workspaceBytes < FSEHIP_frame_decompress_packed_dbatch_workspaceSize(nSegments, maxTotalBlocks)) return (int)hipErrorInvalidValue;
+    if (bad_seg(segLog, 0) || bad_counts(nTensors, elemBytes, nSegments) || bad_grid(dstCapacity, nTensors) || bad_reader(d_workspace, workspaceBytes, nSegments, maxTotalBlocks))
+        return (int)hipErrorInvalidValue;
     const int r = FSEHIP_frame_decompress_packed_dbatch(d_planes, (size_t)planesCapacity, d_segOffsets, d_segResults, d_frames, d_frameOffsets, nSegments, maxTotalBlocks, 0,
                                                         d_workspace, workspaceBytes, stream);
     if (r != 0) return r;
@@ -168,9 +134,6 @@ extern "C" int FSEHIP_tensor_decompress_seg_dbatch(void* d_dst, const uint64_t* 
     const hipError_t e = launch_fold((u64*)d_planeOffsets, d_planeSizes, (const u64*)d_segOffsets, d_segResults, (const u64*)d_segFirst, nTensors * elemBytes, nSegments,
                                      segLog, s);
     if (e != hipSuccess) return (int)e;
-    if (d_base)
-        return (int)launch_merge_xor((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeSizes, (const u8*)d_base,
-                                     nTensors, elemBytes, dstCapacity, s);
-    return (int)launch_planes_merge((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeSizes, nTensors, elemBytes,
-                                    dstCapacity, s);
+    return (int)launch_planes_merge((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeSizes, (const u8*)d_base,
+                                    nTensors, elemBytes, dstCapacity, s);
 }

@@ -1,7 +1,7 @@
 // planes_win.hip -- WINDOWS OF SEGMENTED TENSORS (fsehip.h, "windows of segmented tensors"): an element range [a, b) of every tensor of a
 // segmented batch, decoding only the segment frames that hold it.  No frame byte and no reader changes: a frame reader stops at the end mark,
 // so the selected frames go to the packed reader as extents that run to the next selected frame, whole unselected frames included; and for a
-// window of whole elements every plane contributes the same plane-relative range, so the (XOR) merge of planes.hip / planes_delta.hip runs
+// window of whole elements every plane contributes the same plane-relative range, so the (XOR) merge of planes.hip runs
 // unchanged over plane offsets moved to the window's first byte.  Kernel launches only.
 //
 //   FSEHIP_planes_windowFirst              : host arithmetic, the first selected frame of every plane and the exact block count of the selection
@@ -22,9 +22,7 @@ __global__ void k_planes_select(u64* SO, const u64* F, const u64* S, const u64* 
     if (r > nSel) return;
     if (nSel == 0 || nP == 0) { SO[r] = F[0]; return; }
     const size_t at = r < nSel ? r : nSel - 1;
-    size_t lo = 0, hi = nP - 1;
-    while (lo < hi) { const size_t mid = lo + ((hi - lo + 1) >> 1); if (WF[mid] <= at) lo = mid; else hi = mid - 1; }
-    const size_t j = lo, i = j / E;
+    const size_t j = pl_last_le(nP, at, [WF](size_t m) { return WF[m]; }), i = j / E;
     const PwWin w = pw_window(S, W, SF, WF, i, E, segLog, nSel);
     u64 q;
     if (!w.ok) q = SF[(i + 1) * E];
@@ -37,8 +35,9 @@ __global__ void k_planes_select(u64* SO, const u64* F, const u64* S, const u64* 
     SO[r] = F[q < nSeg ? q : nSeg];
 }
 
-// One wave per plane, its lanes striding over the plane's selected segments; the verdict in the order of fsehip.h, the reductions those of
-// k_planes_fold.  Whether the tensor is accepted and its window empty is the same for all lanes; behind that, q0 + cnt <= nSel.
+// One wave per plane, its lanes striding over the plane's selected segments (ps_fold, as k_planes_fold); the verdict in the order of
+// fsehip.h.  The size rule: a selected segment regenerates exactly its bytes of the plane.  Whether the tensor is accepted and its window
+// empty is the same for all lanes; behind that, q0 + cnt <= nSel.
 __global__ __launch_bounds__(PL_THREADS) void k_planes_fold_window(u64* PO, size_t* PS, const u64* off, const size_t* res, const u64* S, const u64* W, const u64* SF,
                                                                    const u64* WF, size_t nT, u32 E, size_t nSel, u32 segLog)
 {
@@ -53,20 +52,14 @@ __global__ __launch_bounds__(PL_THREADS) void k_planes_fold_window(u64* PO, size
     }
     const u64 s0 = S[i], s1 = S[i + 1], sz = pl_size(s1 > s0 ? s1 - s0 : 0, (u32)(j % E), E), seg = (u64)1 << segLog;
     const u64 q0 = WF[j];
-    u32 firstErr = 0xFFFFFFFFu, bad = 0;
-    for (u64 t = lane; t < w.cnt; t += WAVE) {
-        const size_t r = res[q0 + t];
-        if (is_err(r)) { if ((u32)t < firstErr) firstErr = (u32)t; continue; }
-        const u64 at = (w.k0 + t) << segLog, want = sz - at < seg ? sz - at : seg;      // (an accepted tensor: at < b <= sz)
-        if (r != want) bad = 1;
-        if (t + 1 < w.cnt && off[q0 + t + 1] != off[q0 + t] + r) bad = 1;               // ... and they lie back to back
-    }
-    firstErr = group_reduce<64, ScanMin>(firstErr, lane);
-    bad = group_reduce<64, ScanMax>(bad, lane);
+    const PsFold f = ps_fold(off + q0, res + q0, w.cnt, lane, [=](u64 t, u64 r) {
+        const u64 at = (w.k0 + t) << segLog;                      // (an accepted tensor: at < b <= sz)
+        return r == (sz - at < seg ? sz - at : seg);
+    });
     if (lane) return;
-    const bool good = firstErr == 0xFFFFFFFFu && !bad;
+    const bool good = f.firstErr == 0xFFFFFFFFu && !f.bad;
     PO[j] = good ? off[q0] + (w.a - (w.k0 << segLog)) : 0;
-    PS[j] = firstErr != 0xFFFFFFFFu ? res[q0 + firstErr] : bad ? FERR(corruption_detected) : (size_t)(w.b - w.a);
+    PS[j] = f.firstErr != 0xFFFFFFFFu ? res[q0 + f.firstErr] : f.bad ? FERR(corruption_detected) : (size_t)(w.b - w.a);
 }
 
 hipError_t launch_select(u64* selFrameOff, const u64* frameOff, const u64* srcOff, const u64* windows, const u64* segFirst, const u64* selFirst, size_t nTensors, unsigned E,
@@ -85,26 +78,26 @@ hipError_t launch_fold_window(u64* planeOff, size_t* planeSizes, const u64* selO
                        windows, segFirst, selFirst, nTensors, (u32)E, nSel, (u32)segLog);
     return hipGetLastError();
 }
-inline bool bad_counts(size_t nTensors, unsigned E, size_t nSel) { return nTensors >= ((size_t)1 << 31) / E || nSel >= ((size_t)1 << 31); }
 }   // namespace
 
 extern "C" size_t FSEHIP_planes_windowFirst(uint64_t* h_selFirst, size_t* h_maxBlocks, const uint64_t* h_offsets, const uint64_t* h_windows, size_t nTensors,
                                             unsigned elemBytes, unsigned segLog, unsigned blockSizeId)
 {
     if (bad_elem(elemBytes) || blockSizeId > 6 || bad_seg(segLog, blockSizeId) || (nTensors && (!h_offsets || !h_windows))) return FSEHIP_ERROR(GENERIC);
-    const u64 E = elemBytes, seg = (u64)1 << segLog, bsLog = 10 + blockSizeId, bs = (u64)1 << bsLog;
+    const u32 E = elemBytes;
+    const u64 seg = (u64)1 << segLog, bsLog = 10 + blockSizeId, bs = (u64)1 << bsLog;
     u64 total = 0, blocks = 0;
     if (h_selFirst) h_selFirst[0] = 0;
     for (size_t i = 0; i < nTensors; ++i) {
         const u64 s0 = h_offsets[i], s1 = h_offsets[i + 1], n = s1 > s0 ? s1 - s0 : 0, a = h_windows[2 * i], b = h_windows[2 * i + 1];
         if (a > b || b > n / E) return FSEHIP_ERROR(GENERIC);
-        const u64 k0 = a >> segLog, cnt = a < b ? ((b - 1) >> segLog) - k0 + 1 : 0;
-        for (u64 p = 0; p < E; ++p) {
-            if (cnt) {                                           // all selected segments but the last are full; the last one ends where the plane or the segment does
-                const u64 sz = n > p ? (n - p + E - 1) / E : 0, last = sz - ((k0 + cnt - 1) << segLog);
-                blocks += (cnt - 1) * (seg >> bsLog) + ((last < seg ? last : seg) + bs - 1) / bs;
+        const PwRange r = pw_range(a, b, true, segLog);
+        for (u32 p = 0; p < E; ++p) {
+            if (r.cnt) {                                         // all selected segments but the last are full; the last one ends where the plane or the segment does
+                const u64 last = pl_size(n, p, E) - ((r.k0 + r.cnt - 1) << segLog);
+                blocks += (r.cnt - 1) * (seg >> bsLog) + ((last < seg ? last : seg) + bs - 1) / bs;
             }
-            total += cnt;
+            total += r.cnt;
             if (total >= ((u64)1 << 31) || blocks >= ((u64)1 << 31)) return FSEHIP_ERROR(GENERIC);
             if (h_selFirst) h_selFirst[i * E + p + 1] = total;
         }
@@ -136,7 +129,7 @@ extern "C" int FSEHIP_planes_fold_window_dbatch(uint64_t* d_planeOffsets, size_t
                                    (const u64*)d_segFirst, (const u64*)d_selFirst, nTensors, elemBytes, nSelected, segLog, (hipStream_t)stream);
 }
 
-// the argument checks of all four steps in front of the first launch, as FSEHIP_tensor_decompress_seg_dbatch has them
+// the argument checks of all four steps in front of the first launch
 extern "C" int FSEHIP_tensor_decompress_window_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base, size_t* d_results,
                                                       const void* d_frames, const uint64_t* d_frameOffsets, const uint64_t* d_srcOffsets, const uint64_t* d_windows,
                                                       size_t nTensors, unsigned elemBytes, const uint64_t* d_segFirst, size_t nSegments, unsigned segLog,
@@ -149,8 +142,7 @@ extern "C" int FSEHIP_tensor_decompress_window_dbatch(void* d_dst, const uint64_
         return (int)hipErrorInvalidValue;
     if (bad_seg(segLog, 0) || bad_counts(nTensors, elemBytes, nSelected) || nSegments >= ((size_t)1 << 31) || nSelected > nSegments || bad_grid(dstCapacity, nTensors))
         return (int)hipErrorInvalidValue;
-    if (((uintptr_t)d_workspace & 255u) || maxTotalBlocks >= ((size_t)1 << 31)) return (int)hipErrorInvalidValue;
-    if (workspaceBytes < FSEHIP_frame_decompress_packed_dbatch_workspaceSize(nSelected, maxTotalBlocks)) return (int)hipErrorInvalidValue;
+    if (bad_reader(d_workspace, workspaceBytes, nSelected, maxTotalBlocks)) return (int)hipErrorInvalidValue;
     const hipStream_t s = (hipStream_t)stream;
     hipError_t e = launch_select((u64*)d_selFrameOffsets, (const u64*)d_frameOffsets, (const u64*)d_srcOffsets, (const u64*)d_windows, (const u64*)d_segFirst,
                                  (const u64*)d_selFirst, nTensors, elemBytes, nSegments, nSelected, segLog, s);
@@ -161,9 +153,6 @@ extern "C" int FSEHIP_tensor_decompress_window_dbatch(void* d_dst, const uint64_
     e = launch_fold_window((u64*)d_planeOffsets, d_planeSizes, (const u64*)d_selOffsets, d_selResults, (const u64*)d_srcOffsets, (const u64*)d_windows,
                            (const u64*)d_segFirst, (const u64*)d_selFirst, nTensors, elemBytes, nSelected, segLog, s);
     if (e != hipSuccess) return (int)e;
-    if (d_base)
-        return (int)launch_merge_xor((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeSizes, (const u8*)d_base,
-                                     nTensors, elemBytes, dstCapacity, s);
-    return (int)launch_planes_merge((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeSizes, nTensors, elemBytes,
-                                    dstCapacity, s);
+    return (int)launch_planes_merge((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeSizes, (const u8*)d_base,
+                                    nTensors, elemBytes, dstCapacity, s);
 }

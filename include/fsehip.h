@@ -662,7 +662,7 @@ FSEHIP_API int FSEHIP_tensor_decompress_dbatch(void* d_dst, const uint64_t* d_ds
                                                void* d_planes, uint64_t planesCapacity, uint64_t* d_planeOffsets, size_t* d_planeResults,
                                                void* d_workspace, size_t workspaceBytes, void* stream);
 
-/* Tensor deltas (planes_delta.hip): the four calls above on `tensor XOR base`, the XOR fused into the two data kernels.  For a tensor the
+/* Tensor deltas (planes.hip): the four calls above on `tensor XOR base`, the XOR fused into the two data kernels.  For a tensor the
  * receiver already holds an earlier version of -- weights after a training step, checkpoint N + 1 next to checkpoint N, optimizer state --
  * XOR against that version zeroes every byte that did not change; the sign / exponent plane becomes almost all zeros and the order-0 coders
  * do the rest.  The frames are ordinary .fse frames (of the planes of `tensor XOR base`): nothing in them says that they hold a delta or

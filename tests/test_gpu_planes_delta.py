@@ -192,6 +192,54 @@ def test_merge_xor_refusals(hip, E, in_place):
                     assert (got[0][D[j]:D[j] + want[j]] == tensors[j]).all() and (tensors[j] != base_buf[D[j]:D[j] + want[j]]).any(), (i, j)
 
 
+@pytest.mark.parametrize("E", pc.ELEMS)
+def test_a_zero_base_is_the_plain_call(hip, E):
+    """The plain and the XOR kernels are one template: against an all-zero base the XOR split writes what the plain split writes (planes,
+    plane offsets, results) and the XOR merge what the plain merge writes (destination, results), into a separate destination and in place.
+    The ragged batch of the corpus, every buffer off 16-byte alignment by an amount of its own."""
+    tensors = _pairs(E)[0]
+    n, S, shift = len(tensors), pc.offsets(tensors), SHIFTS[1]
+    total = int(S[-1])
+    assert 0 in [len(t) for t in tensors] and len(tensors[0]) == 1 and shift[0] % 16 == 1
+    zeros = [np.zeros(len(t), np.uint8) for t in tensors]
+    xored = run_split(hip, tensors, zeros, E, shift=shift)
+    src, planes = _filled(total, shift[0], pc.cat(tensors)), _filled(total, shift[2])
+    poff = torch.full((n * E + 2,), -7, dtype=torch.int64, device="cuda")
+    res = torch.full((n + 1,), -7, dtype=torch.int64, device="cuda")
+    hip.planes_split_dbatch(src[:total], S, E, planes=planes, plane_offsets=poff, results=res)
+    torch.cuda.synchronize()
+    assert xored[1] == poff.cpu().tolist()[:n * E + 1] and xored[2] == res.cpu().tolist()[:n] == [len(t) for t in tensors]
+    plain = planes.cpu().numpy()
+    if E == 1:                                                 # (the plain split of bytes writes nothing: its planes are the source)
+        assert (plain == FILL).all()
+        plain[:total] = pc.cat(tensors)
+    assert (xored[0] == plain).all(), np.nonzero(xored[0] != plain)[0][:8]
+
+    slots = [len(t) + (i % 3) for i, t in enumerate(tensors)]  # slots with some room to spare, and one a byte short
+    slots[9] = len(tensors[9]) - 1
+    D = [0]
+    for s in slots:
+        D.append(D[-1] + s)
+    buf, _, P, _ = pc.split_model(tensors, E)
+    psizes = [pc.plane_size(len(t), p, E) for t in tensors for p in range(E)]
+    zero_base = np.zeros(D[n], np.uint8)
+    pbuf, dst = _filled(len(buf), shift[0], buf), _filled(D[n], shift[2])
+    res = torch.full((n + 1,), -7, dtype=torch.int64, device="cuda")
+    hip.planes_merge_dbatch(pbuf[:len(buf)], _i64(P[:-1]), _i64(psizes), np.asarray(D, np.uint64), E, dst=dst, capacity=D[n], results=res)
+    torch.cuda.synchronize()
+    plain, pres = dst.cpu().numpy(), res.cpu().tolist()[:n]
+    assert pres == [len(t) if i != 9 else TOO_SMALL for i, t in enumerate(tensors)]
+    apart = run_merge(hip, E, buf, P[:-1], psizes, D, zero_base, shift=shift)
+    assert apart[1] == pres and (apart[0] == plain).all(), np.nonzero(apart[0] != plain)[0][:8]
+    inpl = run_merge(hip, E, buf, P[:-1], psizes, D, zero_base, shift=shift, in_place=True)
+    written = np.zeros(len(plain), bool)                       # (what neither merge writes stays as it was: FILL there, the zero base here)
+    for i, t in enumerate(tensors):
+        if i != 9:
+            written[D[i]:D[i] + len(t)] = True
+    assert inpl[1] == pres and (inpl[0][written] == plain[written]).all() and (plain[~written] == FILL).all()
+    assert (inpl[0][:D[n]][~written[:D[n]]] == 0).all() and (inpl[0][D[n]:] == FILL).all()
+
+
 # ---------------------------------------------------------------------------------------------------------------- 10, 11
 def _delta_corpus(oracle, E, codec):
     """(tensors, bases, the oracle's frames of every plane of t ^ b): an unchanged tensor, random against random, the bf16 weight update of
