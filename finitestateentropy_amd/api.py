@@ -1870,6 +1870,324 @@ def _planes_methods():
             g.check(what)
         return dst, res
 
+    # ---- patching segmented tensors (csrc/planes_patch.hip; fsehip.h "patching segmented tensors"): the segments that hold a window of every
+    # tensor coded anew, the other frames kept
+    def _some(t):                                                # (an array of no entries still needs an address)
+        return t if t is None or t.numel() else t.new_zeros(1)
+
+    def planes_stage_offsets(self, sizes, windows, elem_bytes, segment_log):
+        """tensor sizes in bytes and one window (a, b) per tensor, in elements -> stage_offsets (numpy uint64, len(sizes) + 1 entries): the
+        running sum of the bytes of every tensor that its selected segments cover, [k0 * seg * E, min((k0 + cnt) * seg * E, size)) -- where
+        planes_split_window_dbatch stages them.  Host arithmetic with numpy: needs no device.  ValueError as planes_window_first."""
+        E, L = _elem(elem_bytes), _seg_log(segment_log)
+        n = np.asarray(list(sizes), dtype=np.int64).reshape(-1)
+        w = _window_array(windows, n.size)
+        a, b = w[:, 0], w[:, 1]
+        if n.size and (int(n.min()) < 0 or bool(((a < 0) | (a > b) | (b > n // E)).any())):
+            raise ValueError("planes_stage_offsets: a window is (a, b) in elements with 0 <= a <= b <= size // %d" % E)
+        k0 = a >> L
+        cnt = np.where(a < b, ((b - 1) >> L) - k0 + 1, 0)
+        at = (k0 << L) * E
+        m = np.where(cnt > 0, np.minimum(n - at, (cnt << L) * E), 0)
+        return np.concatenate([[0], np.cumsum(m, dtype=np.int64)]).astype(np.uint64)
+
+    def planes_split_window_dbatch(self, src, src_offsets, windows, elem_bytes, segment_log, stage_offsets=None, base=None, capacity=None, stage=None,
+                                   stage_capacity=None, plane_offsets=None, results=None):
+        """-> (stage, plane_offsets, results): per tensor the planes of the bytes its selected segments cover (planes_stage_offsets), staged back to
+        back at stage_offsets -- plane p of staged tensor i = stage[plane_offsets[i*E+p] : plane_offsets[i*E+p+1]] is segments k0 .. k1 of plane
+        p of the tensor (of tensor XOR base where a base is given).  results[i] = the staged bytes, or -1 for a tensor with a bad window, one
+        that ends behind `capacity`, or a pair of stage offsets that does not hold exactly those bytes below stage_capacity.  stage_offsets
+        None: planes_stage_offsets (src_offsets and windows then on the host); on the device they need stage or stage_capacity."""
+        E, L = _elem(elem_bytes), _seg_log(segment_log)
+        soff, shost = self._offsets(src_offsets, src.device, stage_offsets is None)
+        n = soff.numel() - 1
+        capacity = _room(self, src, capacity, "src")
+        _base(self, base, src, capacity, "src")
+        win, whost = _windows(self, windows, src.device, n)
+        if stage_offsets is None:
+            if whost is None:
+                raise ValueError("planes_split_window_dbatch: windows on the device need stage_offsets")
+            stage_offsets = planes_stage_offsets(self, np.diff(shost.astype(np.int64)).clip(min=0), whost, E, L)
+        toff, thost = self._offsets(stage_offsets, src.device, stage is None and stage_capacity is None)
+        if toff.numel() != n + 1:
+            raise ValueError("stage_offsets: one entry per tensor (%d) and one more" % n)
+        g = None
+        if stage is None:
+            stage_capacity = int(thost[-1]) if stage_capacity is None else int(stage_capacity)
+            stage, g = self._dst(1, stage_capacity, src.device)
+            stage = stage[0]
+        else:
+            stage_capacity = _room(self, stage, stage_capacity, "stage")
+        poff = _i64(self, plane_offsets, n * E + 1, src.device, "plane_offsets")
+        res = _i64(self, results, n, src.device, "results")
+        what = "planes_split_window_dbatch"
+        _check(self.lib.FSEHIP_planes_split_window_dbatch(_ptr(stage), _ptr(poff), _ptr(_some(res)), _ptr(_some(src)), _ptr(base), _ptr(soff), _ptr(_some(win)),
+                                                          _ptr(toff), SZ(n), C.c_uint(E), C.c_uint(L), C.c_uint64(capacity), C.c_uint64(stage_capacity), _stream()), what)
+        if g is not None:
+            g.check(what)
+        return stage, poff, res
+
+    def planes_splice_scratch_bound(self, n_tensors, elem_bytes, n_segments):
+        """bytes of scratch planes_splice_dbatch and tensor_patch_window_dbatch need.  Host arithmetic: needs no device."""
+        self.lib.FSEHIP_planes_spliceScratchBound.restype = SZ
+        r = int(self.lib.FSEHIP_planes_spliceScratchBound(SZ(int(n_tensors)), C.c_uint(_elem(elem_bytes)), SZ(int(n_segments))))
+        if r >= (1 << 62):
+            raise ValueError("planes_splice_scratch_bound(%r, %r, %r)" % (n_tensors, elem_bytes, n_segments))
+        return r
+
+    def _u8(t, n, device, what):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device or t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() < n:
+            raise TypeError("%s must be a contiguous CUDA uint8 tensor of at least %d entries" % (what, n))
+        return t
+
+    def _splice_out(self, out, out_capacity, default, codecs, out_codecs, nseg, device):
+        """-> (out, out_capacity, out_codecs, guards): the caller's output, or one of out_capacity (default: `default`) bytes; the output codecs
+        where the object has some"""
+        g = []
+        if out is None:
+            out_capacity = default if out_capacity is None else int(out_capacity)
+            out, x = self._dst(1, out_capacity, device)
+            out = out[0]
+            g.append(x)
+        else:
+            out_capacity = _room(self, out, out_capacity, "out")
+        if codecs is not None and out_codecs is None:
+            out_codecs, x = self._dst(1, nseg, device)
+            out_codecs = out_codecs[0]
+            g.append(x)
+        elif out_codecs is not None:
+            if codecs is None:
+                raise ValueError("out_codecs: the object has no codecs")
+            _u8(out_codecs, nseg, device, "out_codecs")
+        return out, out_capacity, out_codecs, [x for x in g if x is not None]
+
+    def planes_splice_dbatch(self, frames, frame_offsets, frame_results, new_frames, new_offsets, new_results, src_offsets, windows, seg_first, sel_first,
+                             elem_bytes, segment_log, n_segments=None, n_selected=None, codecs=None, new_codecs=None, stage_results=None, frames_capacity=None,
+                             new_capacity=None, out=None, out_capacity=None, out_offsets=None, out_results=None, out_codecs=None, tensor_results=None, scratch=None):
+        """-> (out, out_offsets, out_results, tensor_results, out_codecs): a new packed object from the frames of an old one (frames,
+        frame_offsets n_segments + 1, frame_results, codecs or None) and the new frames of the selected segments (new_frames, new_offsets
+        n_selected + 1, new_results, new_codecs iff codecs).  Frame q of the output is new frame sel_first[j] + k - k0 where q is selected
+        segment k of plane j, the old frame q otherwise; out_offsets[q + 1] - out_offsets[q] is the new frame's slot or the old extent, and
+        only a frame's real bytes are copied.  tensor_results[i] = the tensor's size, or an error: the tensor then keeps ALL its old frames --
+        a bad window or wrong counts (-1), an error in stage_results, an old frame that does not lie inside frames_capacity or does not hold
+        its result (-4), a new frame with an error (that error).  If the object does not fit out_capacity nothing is written and every
+        tensor gets -3; out_offsets are whole even then.  out must not overlap frames or new_frames."""
+        E, L = _elem(elem_bytes), _seg_log(segment_log)
+        self._flat(frames, "frames")
+        dev = frames.device
+        foff, _ = self._offsets(frame_offsets, dev, False)
+        soff, _ = self._offsets(src_offsets, dev, False)
+        n = soff.numel() - 1
+        sf, nseg = _seg_first(self, seg_first, n_segments, dev, n * E)
+        wf, nsel = _sel_first(self, sel_first, n_selected, dev, n * E)
+        if foff.numel() < nseg + 1:
+            raise ValueError("frame_offsets: one entry per segment (%d) and one more" % nseg)
+        fres = _i64(self, frame_results, nseg, dev, "frame_results")
+        if frame_results is None:
+            raise TypeError("frame_results: the results of the object's frames are needed")
+        frames_capacity = _room(self, frames, frames_capacity, "frames")
+        win, _ = _windows(self, windows, dev, n)
+        if nsel:
+            new_capacity = _room(self, new_frames, new_capacity, "new_frames")
+            noff, _ = self._offsets(new_offsets, dev, False)
+            if noff.numel() < nsel + 1:
+                raise ValueError("new_offsets: one entry per selected frame (%d) and one more" % nsel)
+            nres = _i64(self, new_results, nsel, dev, "new_results")
+        else:
+            new_capacity, noff, nres = 0, None, None
+        if codecs is not None:
+            _u8(codecs, nseg, dev, "codecs")
+            if nsel:
+                _u8(new_codecs, nsel, dev, "new_codecs")
+        elif new_codecs is not None:
+            raise ValueError("new_codecs: the object has no codecs")
+        if stage_results is not None:
+            _i64(self, stage_results, n, dev, "stage_results")
+        out, out_capacity, out_codecs, guards = _splice_out(self, out, out_capacity, frames_capacity + new_capacity, codecs, out_codecs, nseg, dev)
+        ooff = _i64(self, out_offsets, nseg + 1, dev, "out_offsets")
+        ores = _i64(self, out_results, nseg, dev, "out_results")
+        tres = _i64(self, tensor_results, n, dev, "tensor_results")
+        if scratch is None:
+            scratch = torch.empty(planes_splice_scratch_bound(self, n, E, nseg), dtype=torch.uint8, device=dev)
+        what = "planes_splice_dbatch"
+        _check(self.lib.FSEHIP_planes_splice_dbatch(
+            _ptr(out), C.c_uint64(out_capacity), _ptr(ooff), _ptr(_some(ores)), _ptr(_some(out_codecs)), _ptr(_some(tres)), _ptr(_some(frames)),
+            C.c_uint64(frames_capacity), _ptr(foff), _ptr(_some(fres)), _ptr(_some(codecs)), _ptr(new_frames if nsel else None), C.c_uint64(new_capacity), _ptr(noff),
+            _ptr(nres), _ptr(new_codecs if nsel else None), _ptr(_some(stage_results)), _ptr(soff), _ptr(_some(win)), SZ(n), C.c_uint(E), _ptr(sf), SZ(nseg), C.c_uint(L),
+            _ptr(wf), SZ(nsel), _ptr(scratch), SZ(scratch.numel()), _stream()), what)
+        for x in guards:
+            x.check(what)
+        return out, ooff, ores, tres, (out_codecs[:nseg] if out_codecs is not None else None)
+
+    def tensor_patch_window_dbatch(self, frames, frame_offsets, frame_results, src, src_offsets, windows, elem_bytes, segment_log, seg_first=None, n_segments=None,
+                                   sel_first=None, n_selected=None, stage_offsets=None, base=None, codec=0, codecs=None, new_codecs=None, block_size_id=5,
+                                   capacity=None, frames_capacity=None, max_total_blocks=None, align_log=0, out=None, out_capacity=None, out_offsets=None,
+                                   out_results=None, out_codecs=None, tensor_results=None, stage=None, stage_capacity=None, stage_plane_offsets=None,
+                                   stage_seg_offsets=None, stage_results=None, new_frames=None, new_capacity=None, new_offsets=None, new_results=None, scratch=None,
+                                   workspace=None):
+        """-> (out, out_offsets, out_results, tensor_results, out_codecs): the object (frames, frame_offsets, frame_results, codecs) of
+        tensor_compress_seg_dbatch brought up to date with `src`, the WHOLE current tensors in the layout src_offsets they were compressed in,
+        which changed inside one window (a, b) of elements each.  The segments a >> segment_log .. (b - 1) >> segment_log of every plane are
+        coded anew from src (XOR base), all other frames are the old ones byte for byte: planes_split_window_dbatch, planes_segments_dbatch
+        over the stage, the packed writer, planes_splice_dbatch.  WHOLE SEGMENTS are replaced: inside a selected segment the bytes of src win
+        outside the window too, elsewhere the old ones stay, so src must equal the object's content outside the windows (not checked).  For
+        tensors that differ inside the windows only, the result is tensor_compress_seg_dbatch of src, byte for byte.
+        codecs None: `codec` 0 / 1 for every new frame.  codecs the object's (one per segment): `codec` an AutoCodec -- the new frames' codecs
+        are chosen by size -- or new_codecs given (one per selected frame).  align_log: what the object was written with.  tensor_results
+        and capacity as planes_splice_dbatch; out_capacity None: frames_capacity + frame_packed_bound of the staged bytes.  sel_first,
+        stage_offsets or max_total_blocks None: planes_window_first / planes_stage_offsets (src_offsets and windows then on the host).  The
+        stage, its offsets and results, the new frames, the scratch and the writer's workspace for n_selected frames are scratch; with
+        everything given and on the device the call is launches only."""
+        E = _elem(elem_bytes)
+        align_log = _align_log(align_log)
+        L = _seg_log(segment_log, min(block_size_id, 6))
+        self._flat(frames, "frames")
+        self._flat(src, "src")
+        dev = frames.device
+        if src.device != dev:
+            raise ValueError("src is on %s, the frames on %s" % (src.device, dev))
+        what = "tensor_patch_window_dbatch"
+        foff, _ = self._offsets(frame_offsets, dev, False)
+        need_first = sel_first is None or max_total_blocks is None or stage_offsets is None
+        soff, shost = self._offsets(src_offsets, dev, seg_first is None or need_first)
+        n = soff.numel() - 1
+        capacity = _room(self, src, capacity, "src")
+        _base(self, base, src, capacity, "src")
+        frames_capacity = _room(self, frames, frames_capacity, "frames")
+        win, whost = _windows(self, windows, dev, n)
+        if seg_first is None:
+            seg_first = planes_segment_first(self, np.diff(shost.astype(np.int64)).clip(min=0), E, L)
+        sf, nseg = _seg_first(self, seg_first, n_segments, dev, n * E)
+        if foff.numel() < nseg + 1:
+            raise ValueError("frame_offsets: one entry per segment (%d) and one more" % nseg)
+        if frame_results is None:
+            raise TypeError("frame_results: the results of the object's frames are needed")
+        fres = _i64(self, frame_results, nseg, dev, "frame_results")
+        if need_first:
+            if whost is None:
+                raise ValueError(what + ": windows on the device need sel_first, n_selected, stage_offsets and max_total_blocks")
+            sizes = np.diff(shost.astype(np.int64)).clip(min=0)
+            first, blocks = planes_window_first(self, sizes, whost, E, L, min(block_size_id, 6))
+            sel_first = first if sel_first is None else sel_first
+            max_total_blocks = blocks if max_total_blocks is None else max_total_blocks
+            stage_offsets = planes_stage_offsets(self, sizes, whost, E, L) if stage_offsets is None else stage_offsets
+        wf, nsel = _sel_first(self, sel_first, n_selected, dev, n * E)
+        toff, thost = self._offsets(stage_offsets, dev, stage is None and stage_capacity is None)
+        if toff.numel() != n + 1:
+            raise ValueError("stage_offsets: one entry per tensor (%d) and one more" % n)
+        if stage is None:
+            stage_capacity = int(thost[-1]) if stage_capacity is None else int(stage_capacity)
+            stage = torch.empty(max(stage_capacity, 1), dtype=torch.uint8, device=dev)
+        else:
+            stage_capacity = _room(self, stage, stage_capacity, "stage")
+        mixed = codecs is not None
+        choose = mixed and new_codecs is None
+        if mixed:
+            _u8(codecs, nseg, dev, "codecs")
+            if choose and not isinstance(codec, AutoCodec):
+                raise ValueError(what + ": an object with codecs needs an AutoCodec as `codec`, or new_codecs")
+        elif new_codecs is not None or codec not in (0, 1):
+            raise ValueError(what + ": an object without codecs takes codec 0 or 1 and no new_codecs")
+        new_codecs, cgu = _codecs(self, new_codecs, nsel, dev) if mixed else (None, None)
+        if new_frames is None:
+            new_capacity = self.frame_packed_bound(stage_capacity, nsel, max_total_blocks, align_log) if new_capacity is None else int(new_capacity)
+            new_frames = torch.empty(max(new_capacity, 1), dtype=torch.uint8, device=dev)
+        else:
+            new_capacity = _room(self, new_frames, new_capacity, "new_frames")
+        out, out_capacity, out_codecs, guards = _splice_out(self, out, out_capacity, frames_capacity + new_capacity, codecs, out_codecs, nseg, dev)
+        ooff = _i64(self, out_offsets, nseg + 1, dev, "out_offsets")
+        ores = _i64(self, out_results, nseg, dev, "out_results")
+        tres = _i64(self, tensor_results, n, dev, "tensor_results")
+        spo = _i64(self, stage_plane_offsets, n * E + 1, dev, "stage_plane_offsets")
+        sso = _i64(self, stage_seg_offsets, nsel + 1, dev, "stage_seg_offsets")
+        sres = _i64(self, stage_results, n, dev, "stage_results")
+        noff = _i64(self, new_offsets, nsel + 1, dev, "new_offsets")
+        nres = _i64(self, new_results, nsel, dev, "new_results")
+        if scratch is None:
+            scratch = torch.empty(planes_splice_scratch_bound(self, n, E, nseg), dtype=torch.uint8, device=dev)
+        workspace = _writer_workspace(self, workspace, nsel, max_total_blocks, block_size_id, codec, mixed, choose, dev)
+        tol = codec.tolerance_permille if choose else 0
+        _check(self.lib.FSEHIP_tensor_patch_window_dbatch(
+            _ptr(out), C.c_uint64(out_capacity), _ptr(ooff), _ptr(_some(ores)), _ptr(_some(out_codecs)), _ptr(_some(tres)), _ptr(_some(frames)),
+            C.c_uint64(frames_capacity), _ptr(foff), _ptr(_some(fres)), _ptr(_some(codecs)), _ptr(_some(src)), _ptr(base), _ptr(soff), C.c_uint64(capacity),
+            _ptr(_some(win)), SZ(n), C.c_uint(E), _ptr(sf), SZ(nseg), C.c_uint(L), _ptr(wf), SZ(nsel), _ptr(toff), C.c_uint64(stage_capacity), SZ(max_total_blocks),
+            C.c_uint(block_size_id), C.c_int(0 if mixed else codec), _ptr(_some(new_codecs)), C.c_int(CODECS_CHOOSE if choose else CODECS_GIVEN), C.c_uint(tol),
+            C.c_uint(align_log), _ptr(stage), _ptr(spo), _ptr(sso), _ptr(_some(sres)), _ptr(new_frames), C.c_uint64(new_capacity), _ptr(noff), _ptr(_some(nres)),
+            _ptr(scratch), SZ(scratch.numel()), _ptr(workspace), SZ(workspace.numel()), _stream()), what)
+        _check_codecs(cgu, nsel, what)
+        for x in guards:
+            x.check(what)
+        return out, ooff, ores, tres, (out_codecs[:nseg] if out_codecs is not None else None)
+
+    def patch_tensor_windows(self, obj, tensors, windows, base=None):
+        """-> a NEW CompressedTensors: `obj` (of compress_tensors_segmented) brought up to date with `tensors`, the WHOLE current CUDA tensors --
+        one per tensor of the object, of its dtype, shape and device -- which changed inside the elements [start, stop) of the flattened tensor
+        that `windows` names: one entry per tensor, None (nothing changed) or (start, stop) with 0 <= start <= stop <= numel.  Only the segment
+        frames that hold a window are coded again (tensor_patch_window_dbatch); every other frame is copied as it is.  The patch works on
+        WHOLE SEGMENTS of 1 << segment_log bytes per plane: inside a segment that holds part of a window all bytes come from `tensors`,
+        elsewhere the old ones stay -- so `tensors` must equal the object's content outside the windows, which is not checked.  Where they do,
+        the result is what compress_tensors_segmented(tensors) gives, byte for byte.  `obj` is not changed.  The new object has the same
+        segment_log, block_size_id, delta, codec and seg_first; an object written with an AutoCodec has the codecs of the new frames chosen
+        anew.  base: for an object with `delta` set, the whole base tensors as compress_tensors takes them.  ValueError / TypeError before any
+        launch: an object that is not segmented, a wrong number of tensors or windows, a tensor of another dtype, shape or device, a window
+        that is not one, a base / delta mismatch."""
+        seg_log = getattr(obj, "segment_log", None)
+        if seg_log is None:
+            raise ValueError("patch_tensor_windows: the object is not segmented (compress_tensors_segmented writes those)")
+        if getattr(obj, "delta", False) != (base is not None):
+            raise ValueError("patch_tensor_windows: the object holds deltas and needs its base" if base is None else
+                             "patch_tensor_windows: the object holds no deltas, a base does not belong to it")
+        tensors, windows = list(tensors), list(windows)
+        if len(tensors) != len(obj.dtypes) or len(windows) != len(obj.dtypes):
+            raise ValueError("patch_tensor_windows: %d tensors and %d windows for %d tensors" % (len(tensors), len(windows), len(obj.dtypes)))
+        for k, (t, dt, sh) in enumerate(zip(tensors, obj.dtypes, obj.shapes)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != obj.device or t.dtype != dt:
+                raise TypeError("patch_tensor_windows: tensor %d: a CUDA tensor of %s on %s is needed" % (k, dt, obj.device))
+            if tuple(t.shape) != tuple(sh):
+                raise ValueError("patch_tensor_windows: tensor %d has shape %s, the object's has %s" % (k, tuple(t.shape), tuple(sh)))
+        wins = []
+        for k, (w, sh) in enumerate(zip(windows, obj.shapes)):
+            numel = int(np.prod(sh, dtype=np.int64))
+            if w is not None and (not isinstance(w, (tuple, list)) or len(w) != 2 or any(not isinstance(x, numbers.Integral) or isinstance(x, bool) for x in w)
+                                  or not 0 <= w[0] <= w[1] <= numel):
+                raise ValueError("patch_tensor_windows: window %d is %r, None or (start, stop) with 0 <= start <= stop <= %d is needed" % (k, w, numel))
+            wins.append((0, 0) if w is None else (int(w[0]), int(w[1])))
+        braw = None if base is None else _bases(base, obj.dtypes, obj.shapes, obj.device)
+        auto = isinstance(obj.codec, AutoCodec)
+        groups = []
+        for g in obj.groups:
+            E, sizes, idx = g["elem_bytes"], g["sizes"], g["index"]
+            gw = [wins[i] for i in idx]
+            new = dict(g)
+            if any(b > a for a, b in gw):
+                raw = [tensors[i].contiguous().reshape(-1).view(torch.uint8) for i in idx]
+                offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
+                src = torch.cat(raw)
+                bsrc = None if braw is None else torch.cat([braw[i] for i in idx])
+                first, blocks = self.planes_window_first(sizes, gw, E, seg_log, obj.block_size_id)
+                toff = self.planes_stage_offsets(sizes, gw, E, seg_log)
+                cap = int(g["frames"].numel()) + self.frame_packed_bound(int(toff[-1]), int(first[-1]), blocks, 0)
+                out, ooff, ores, tres, ocod = self.tensor_patch_window_dbatch(
+                    g["frames"], g["frame_offsets"], g["frame_results"], src, offs, gw, E, seg_log, g["seg_first"], sel_first=first, stage_offsets=toff, base=bsrc,
+                    codec=obj.codec if auto or "codecs" not in g else 0, codecs=g.get("codecs"), block_size_id=obj.block_size_id, max_total_blocks=blocks,
+                    out_capacity=cap)
+                got = torch.cat([ooff[-1:], tres]).cpu().tolist()
+                if got[1:] != sizes or got[0] > cap:
+                    raise RuntimeError("patch_tensor_windows: element size %d, results %s for tensors of %s bytes" % (E, got[1:9], sizes[:8]))
+                new.update(frames=out[:got[0]].clone(), frame_offsets=ooff, frame_results=ores, tensor_results=tres)
+                if ocod is not None:
+                    new["codecs"] = ocod.clone()
+            else:
+                new.update(frames=g["frames"].clone(), frame_offsets=g["frame_offsets"].clone(), frame_results=g["frame_results"].clone(),
+                           tensor_results=g["tensor_results"].clone())
+                if "codecs" in g:
+                    new["codecs"] = g["codecs"].clone()
+            groups.append(new)
+        return _segmented(CompressedTensors(groups, list(obj.dtypes), list(obj.shapes), obj.device, obj.codec, obj.block_size_id, obj.delta), seg_log)
+
+    for f in (planes_stage_offsets, planes_split_window_dbatch, planes_splice_scratch_bound, planes_splice_dbatch, tensor_patch_window_dbatch, patch_tensor_windows):
+        setattr(FseHip, f.__name__, f)
+
     # ---- the user-facing pair
     def _bases(base, dtypes, shapes, device):
         """the `base` of the pair: one CUDA tensor per tensor, of its dtype, shape and device -> their bytes, flat"""
@@ -2099,6 +2417,11 @@ def decompress_tensors(obj, base=None):
 def decompress_tensor_windows(obj, windows, base=None):
     """FseHip.decompress_tensor_windows on a library handle of the module's own"""
     return _default().decompress_tensor_windows(obj, windows, base)
+
+
+def patch_tensor_windows(obj, tensors, windows, base=None):
+    """FseHip.patch_tensor_windows on a library handle of the module's own"""
+    return _default().patch_tensor_windows(obj, tensors, windows, base)
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -187,6 +187,9 @@ __global__ __launch_bounds__(FD_THREADS) void k_scan_apply(u64* a, size_t n, con
     if (blockIdx.x == 0 && tid == 0) a[n] = partials[nGroups];
 }
 inline size_t scan_partials(size_t n) { return (n + FD_PER_WG - 1) / FD_PER_WG + 2; }           // u64 words of scratch
+}   // namespace
+// (declared in internal.h: planes_patch.hip scans its frame extents with it)
+size_t exscan_partials(size_t n) { return scan_partials(n); }
 hipError_t launch_exscan(u64* a, size_t n, u64* partials, hipStream_t s)
 {
     const u32 nGroups = (u32)((n + FD_PER_WG - 1) / FD_PER_WG);
@@ -196,6 +199,7 @@ hipError_t launch_exscan(u64* a, size_t n, u64* partials, hipStream_t s)
     hipLaunchKernelGGL(k_scan_apply, dim3(nGroups), dim3(FD_THREADS), 0, s, a, n, (const u64*)partials, nGroups);
     return hipGetLastError();
 }
+namespace {
 
 // `len` bytes from s to d, any alignments, by the FD_THREADS threads of a workgroup: up to the next 16-byte boundary of d bytewise, 16-byte
 // pieces (unaligned loads, aligned stores), the rest bytewise.  fill >= 0: that byte repeated instead.

@@ -325,6 +325,10 @@ hipError_t launch_compact(u8* packed, size_t packedCapacity, u64* offsets, const
 // block itself, a record of one byte is that byte repeated -- applied by k_rawrle_expand; k_fse_dparse then leaves those alone
 hipError_t launch_rawrle_expand(u8* dst, size_t dstStride, size_t dstCapacity, size_t* results, const BlockView& csrc, const size_t* origSizes, size_t uniformOrig,
                                 size_t nBlocks, hipStream_t s);
+// the exclusive scan of frame_dev.hip, in place: a[0 .. n) -> their running sums from 0, a[n] = the total; `partials` holds
+// exscan_partials(n) u64 words of scratch
+hipError_t launch_exscan(u64* a, size_t n, u64* partials, hipStream_t s);
+size_t exscan_partials(size_t n);
 
 // ---- byte planes of tensors (planes.hip) ------------------------------------------------------------------
 // PLANES_TILE: bytes of the flat axis per workgroup of the two data kernels (fsehip.h, "byte planes": the work mapping).  The launchers check

@@ -1,4 +1,4 @@
-// planes_dev.h -- what the plane files (planes.hip: byte planes of tensors and their XOR forms; planes_seg.hip; planes_win.hip) share: the byte
+// planes_dev.h -- what the plane files (planes.hip: byte planes of tensors and their XOR forms; planes_seg.hip; planes_win.hip; planes_patch.hip) share: the byte
 // shuffle, the plane arithmetic, the search behind every work mapping, a workgroup's share of a tensor, the merge's verdict, the fold of a
 // plane's segment results, the dispatch over the element size and the argument checks of the C calls.  Device helpers are inlined into the
 // kernels of the file that includes this; nothing here is a kernel.
@@ -153,6 +153,23 @@ DEV PwWin pw_window(const u64* S, const u64* W, const u64* SF, const u64* WF, si
     for (u32 p = 0; p < E; ++p) w.ok = w.ok && WF[i * E + p + 1] - WF[i * E + p] == w.cnt;
     w.ok = w.ok && WF[i * E] <= WF[(i + 1) * E] && WF[(i + 1) * E] <= nSel && ps_tensor_ok(S, SF, i, E, segLog);
     return w;
+}
+
+// ---- patching segmented tensors (planes_patch.hip; fsehip.h, "patching segmented tensors") ----
+// the bytes [at, at + m) of a tensor of n bytes that its selected segments k0 .. k0 + cnt - 1 cover: at is a multiple of E, so the planes of
+// this sub-tensor are those segments of the tensor's planes (the host's arithmetic too)
+struct PpSub { u64 at, m; };
+HDEV PpSub pp_sub(u64 n, u64 k0, u64 cnt, u32 E, u32 segLog)
+{
+    const u64 at = (k0 << segLog) * E, full = (cnt << segLog) * E;
+    return { at, cnt && at < n ? (n - at < full ? n - at : full) : 0 };
+}
+// frame q of a packed batch lies inside its buffer and holds its result: 0 <= F[q] <= F[q + 1] <= capacity, R[q] <= F[q + 1] - F[q]
+DEV bool pp_extent_ok(const u64* F, const size_t* R, size_t q, u64 capacity)
+{
+    const u64 f0 = F[q], f1 = F[q + 1];
+    const size_t r = R[q];
+    return f0 <= f1 && f1 <= capacity && !is_err(r) && (u64)r <= f1 - f0;
 }
 
 // ---- the launches and the argument checks of the C calls ----

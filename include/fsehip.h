@@ -854,6 +854,84 @@ FSEHIP_API int FSEHIP_tensor_decompress_window_dbatch(void* d_dst, const uint64_
                                                       uint64_t* d_selFrameOffsets, uint64_t* d_selOffsets, size_t* d_selResults, uint64_t* d_planeOffsets,
                                                       size_t* d_planeSizes, void* d_workspace, size_t workspaceBytes, void* stream);
 
+/* Patching segmented tensors (planes_patch.hip): the WRITE side of the windows above.  The tensors of a segmented batch changed inside an
+ * element window each; the frames of the selected segments -- those FSEHIP_planes_windowFirst picks for the windows, k0 .. k1 of every plane,
+ * selFirst and nSelected as above -- are coded anew from the whole current tensors and a NEW packed object is built from the old frames and
+ * the new ones.  No frame byte, no reader and no writer changes: the frame writer codes a block whatever its position and a segment is a
+ * frame of its own.  Like the calls above: launches on `stream` only, capturable, no size leaves the device, argument errors are
+ * hipErrorInvalidValue, decided before any device call.  No *_workspaceSize of their own: the workspace is the packed (mixed) writer's for
+ * nSelected frames; the splice's scratch is FSEHIP_planes_spliceScratchBound bytes, 256-byte aligned.
+ *
+ *   Granularity.  The patch works on WHOLE SEGMENTS: of a selected segment ALL bytes come from d_src (XOR d_base, laid out as d_src, for an
+ *     object of deltas), those outside [a, b) included.  The caller's contract is that the tensors equal the object's content outside the
+ *     windows; it is not checked.  Otherwise: inside selected segments the new bytes win, everywhere else the old ones stay.
+ *   The identity.  For tensors `old` and `new` that differ inside the windows only, the patch of FSEHIP_tensor_compress_seg_dbatch(old) with
+ *     `new` IS FSEHIP_tensor_compress_seg_dbatch(new): offsets, results, codecs and every frame byte, for one codec, given and chosen codecs.
+ *
+ *   Layout of the output (out of place: d_out must not overlap d_frames, the new frames or the stage).  F = d_frameOffsets, R = d_frameResults
+ *     of the object, F', R' = d_outOffsets (nSegments + 1), d_outResults (nSegments).  F'[0] = 0, F'[q + 1] = F'[q] + extent_q; extent_q is
+ *     the old extent F[q + 1] - F[q] of a kept frame and the new frame's slot (the writer's, at the slotAlignLog given: pass what the object
+ *     was written with) of a selected one.  Of every frame only its real bytes R'[q] are copied: padding inside an extent and every byte
+ *     behind F'[nSegments] are left as they are.  R'[q] and d_outCodecs[q] are the kept frame's old ones or the writer's.
+ *   Capacity.  If F'[nSegments] > outCapacity nothing is written to d_out and every tensor's result is dstSize_tooSmall; F' is still whole.
+ *
+ *   A tensor is patched WHOLE OR NOT AT ALL.  Tensor i keeps ALL its old frames, d_tensorResults[i] gets the error, and no other tensor is
+ *     affected, by these rules in their order:
+ *       1. GENERIC (the split's own result where it refused): its window is not valid (a > b or b > floor(n / E)), its slot of d_srcOffsets
+ *          ends behind `capacity`, or its pair of stage offsets does not hold its sub-tensor below stageCapacity;
+ *       2. GENERIC: its counts in segFirst or selFirst are not those its size and its window imply (the acceptance rule of the windows
+ *          above), or a plane's range of segFirst does not lie inside nSegments;
+ *       3. corruption_detected: one of its old frames q -- selected or not -- is not 0 <= F[q] <= F[q + 1] <= framesCapacity with
+ *          R[q] <= F[q + 1] - F[q].  Such a frame of the refused tensor cannot be kept: it gets GENERIC in R', and no room where the extent
+ *          itself is not one; its other frames are kept;
+ *       4. the writer's error for one of its new frames, the first in plane and segment order (corruption_detected for a new frame that does
+ *          not lie inside newCapacity as rule 3 asks of the old ones).
+ *     Otherwise d_tensorResults[i] = n_i, its size in bytes.  A window (a, a) selects nothing: the tensor keeps its frames and gets n_i.
+ *     Values of segFirst, selFirst, windows and both frame offset arrays are clamped or checked before they index anything.
+ *
+ *   FSEHIP_planes_split_window_dbatch   stages, per tensor, the planes of its sub-tensor: the bytes [k0 * seg * E, min((k0 + cnt) * seg * E, n))
+ *     of it, which start at a multiple of E, so that by size_p and the plane starts of "byte planes" plane p of the sub-tensor is exactly
+ *     segments k0 .. k1 of plane p of the tensor, a partial last element included.  T = d_stageOffsets (nTensors + 1) is the running sum of the
+ *     sub-tensor sizes, like selFirst a function of shapes and windows alone; sub-tensor i is staged at d_stage + T[i] .. T[i + 1], and
+ *     d_stagePlaneOffsets (nTensors * E + 1) and d_stageResults (the staged bytes, or GENERIC by rule 1) are what the split of "byte planes"
+ *     writes, over T.  The entries of a refused tensor are all min(T[i], stageCapacity).  d_base != NULL: the planes of src XOR base.  The
+ *     data path is the split's, the source displaced per tensor; elemBytes == 1 without a base stages by copy.
+ *   Segment offsets.  A staged sub-tensor has exactly cnt segments per plane, so FSEHIP_planes_segments_dbatch runs unchanged with
+ *     d_stagePlaneOffsets, T as d_srcOffsets and selFirst as d_segFirst: its d_segOffsets (nSelected + 1) are the writers' d_srcOffsets.  (It
+ *     reports GENERIC for a tensor with an empty window, whose planes it expects one empty segment of: give it a results array of its own.)
+ *   FSEHIP_planes_splice_dbatch   old object (d_frames, framesCapacity, F, R, d_codecs or NULL) + new frames (d_newFrames, newCapacity,
+ *     d_newOffsets nSelected + 1, d_newResults, d_newCodecs -- given iff d_codecs is) -> the output above.  d_stageResults (nTensors, may be
+ *     NULL) are the split's: an error there refuses the tensor.  One wave per plane settles rules 1 to 4, one thread per frame its extent,
+ *     source, result and codec, an exclusive scan the offsets, and a gather with one workgroup per (32 KiB tile of d_out, frame) intersection
+ *     copies: bytewise up to a 16-byte boundary of d_out, 16-byte pieces, a bytewise rest.  nSelected == 0 copies the object.
+ *   FSEHIP_tensor_patch_window_dbatch   the window split, the segments kernel, FSEHIP_frame_compress_packed_dbatch with `codec`
+ *     (d_newCodecs == NULL) or FSEHIP_frame_compress_packed_mixed_dbatch with d_newCodecs (nSelected entries, given or chosen) into
+ *     d_newFrames, then the splice.  d_src, d_base, d_srcOffsets and `capacity` are as for FSEHIP_tensor_compress_seg_dbatch; d_stage
+ *     (stageCapacity >= T[nTensors] bytes), d_stagePlaneOffsets, d_stageSegOffsets (nSelected + 1), d_stageResults, d_newFrames
+ *     (FSEHIP_frame_packedBound of the staged bytes is sufficient), d_newOffsets and d_newResults are scratch the caller supplies.
+ *     maxTotalBlocks: what FSEHIP_planes_windowFirst gives, or an upper bound; the new frames of a promise that is short fail (rule 4).  The
+ *     argument checks of all steps run before the first launch. */
+FSEHIP_API int FSEHIP_planes_split_window_dbatch(void* d_stage, uint64_t* d_stagePlaneOffsets, size_t* d_stageResults, const void* d_src, const void* d_base,
+                                                 const uint64_t* d_srcOffsets, const uint64_t* d_windows, const uint64_t* d_stageOffsets, size_t nTensors,
+                                                 unsigned elemBytes, unsigned segLog, uint64_t capacity, uint64_t stageCapacity, void* stream);
+FSEHIP_API size_t FSEHIP_planes_spliceScratchBound(size_t nTensors, unsigned elemBytes, size_t nSegments);
+FSEHIP_API int FSEHIP_planes_splice_dbatch(void* d_out, uint64_t outCapacity, uint64_t* d_outOffsets, size_t* d_outResults, uint8_t* d_outCodecs, size_t* d_tensorResults,
+                                           const void* d_frames, uint64_t framesCapacity, const uint64_t* d_frameOffsets, const size_t* d_frameResults,
+                                           const uint8_t* d_codecs, const void* d_newFrames, uint64_t newCapacity, const uint64_t* d_newOffsets,
+                                           const size_t* d_newResults, const uint8_t* d_newCodecs, const size_t* d_stageResults, const uint64_t* d_srcOffsets,
+                                           const uint64_t* d_windows, size_t nTensors, unsigned elemBytes, const uint64_t* d_segFirst, size_t nSegments, unsigned segLog,
+                                           const uint64_t* d_selFirst, size_t nSelected, void* d_scratch, size_t scratchBytes, void* stream);
+FSEHIP_API int FSEHIP_tensor_patch_window_dbatch(void* d_out, uint64_t outCapacity, uint64_t* d_outOffsets, size_t* d_outResults, uint8_t* d_outCodecs,
+                                                 size_t* d_tensorResults, const void* d_frames, uint64_t framesCapacity, const uint64_t* d_frameOffsets,
+                                                 const size_t* d_frameResults, const uint8_t* d_codecs, const void* d_src, const void* d_base,
+                                                 const uint64_t* d_srcOffsets, uint64_t capacity, const uint64_t* d_windows, size_t nTensors, unsigned elemBytes,
+                                                 const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, const uint64_t* d_selFirst, size_t nSelected,
+                                                 const uint64_t* d_stageOffsets, uint64_t stageCapacity, size_t maxTotalBlocks, unsigned blockSizeId, int codec,
+                                                 uint8_t* d_newCodecs, int policy, unsigned tolerancePermille, unsigned slotAlignLog, void* d_stage,
+                                                 uint64_t* d_stagePlaneOffsets, uint64_t* d_stageSegOffsets, size_t* d_stageResults, void* d_newFrames,
+                                                 uint64_t newCapacity, uint64_t* d_newOffsets, size_t* d_newResults, void* d_scratch, size_t scratchBytes,
+                                                 void* d_workspace, size_t workspaceBytes, void* stream);
+
 /* ---- FSE for 16-bit symbols (lib/fseU16.h:62-80, lib/fseU16.c) -- SURVEY 8(f) rank 4.  Alphabets of up to
  * FSEHIP_FSEU16_MAX_SYMBOL_VALUE + 1 symbols, table logs up to 13 (default 12), ONE tANS state per stream: a different format from
  * the byte coder's.  Sizes of the uncompressed side are in SYMBOLS (as in the reference), strides in bytes.
