@@ -43,6 +43,30 @@ class AutoCodec:
         return hash(("AutoCodec", self.tolerance_permille))
 
 
+DELTA_OPS = {"xor": 0, "sub": 1}        # FSEHIP_DELTA_XOR / FSEHIP_DELTA_SUB (include/fsehip.h)
+
+
+class DeltaBase:
+    """`base` of compress_tensors with the delta's operation beside it: "sub" -- the elements' bit patterns subtracted as integers and
+    zigzag-folded (FSEHIP_DELTA_SUB, include/fsehip.h "arithmetic tensor deltas"), 11 to 19 % fewer frame bytes than XOR on weight updates
+    -- or "xor", which is what a plain sequence as `base` means.  The object written carries the op as `delta_op`; the reading calls take
+    the op from the object and the base as a plain sequence, or as a DeltaBase of the same op."""
+
+    def __init__(self, tensors, op="sub"):
+        if not isinstance(op, str) or op not in DELTA_OPS:
+            raise ValueError("DeltaBase: op %r, \"sub\" or \"xor\" is needed" % (op,))
+        self.tensors, self.op = list(tensors), op
+
+    def __len__(self):
+        return len(self.tensors)
+
+    def __iter__(self):
+        return iter(self.tensors)
+
+    def __repr__(self):
+        return "DeltaBase(%d tensors, op=%r)" % (len(self.tensors), self.op)
+
+
 def fse_compress_bound(n):      # lib/fse.h:290-292
     return 512 + n + (n >> 7) + 4 + 8
 
@@ -1184,8 +1208,11 @@ class CompressedTensors:
     frames hold `tensor XOR base` (compress_tensors with base=...) and decompress_tensors needs the same base again; the frames themselves do
     not say so.  `segment_log` (None, or the integer compress_tensors_segmented set): every plane is cut into segments of 1 << segment_log
     bytes with a frame each; frame_offsets, frame_results and codecs are then per segment and every group carries `seg_first` (numpy uint64,
-    the first segment of every plane and the segment count)."""
+    the first segment of every plane and the segment count).  `delta_op` ("xor", or "sub" where compress_tensors was given a
+    DeltaBase(..., "sub")): what the frames of an object with `delta` set hold -- `tensor XOR base` or zigzag(tensor - base); the reading
+    calls take it from here."""
     segment_log = None
+    delta_op = "xor"
 
     def __init__(self, groups, dtypes, shapes, device, codec, block_size_id, delta=False):
         self.groups, self.dtypes, self.shapes, self.device, self.codec, self.block_size_id = groups, dtypes, shapes, device, codec, block_size_id
@@ -1242,6 +1269,20 @@ def _planes_methods():
         if base.numel() < capacity:
             raise ValueError("base holds %d bytes, the capacity of %s is %d" % (base.numel(), what, capacity))
         return base
+
+    def _delta_op(delta_op):
+        """the `delta_op` of a call that takes a base: 0 / "xor" or 1 / "sub" (FSEHIP_DELTA_XOR / FSEHIP_DELTA_SUB) -> 0 or 1"""
+        if isinstance(delta_op, str) and delta_op in DELTA_OPS:
+            return DELTA_OPS[delta_op]
+        if isinstance(delta_op, numbers.Integral) and not isinstance(delta_op, bool) and delta_op in (0, 1):
+            return int(delta_op)
+        raise ValueError("delta_op %r: 0 (\"xor\") or 1 (\"sub\")" % (delta_op,))
+
+    def _call_base(self, name, op, at, *args):
+        """the C call `name`, whose d_base is args[at]: itself for XOR, else its *_op_dbatch sibling with deltaOp behind d_base"""
+        if not op:
+            return getattr(self.lib, name)(*args)
+        return getattr(self.lib, name.replace("_xor_", "_").replace("_dbatch", "_op_dbatch"))(*args[:at + 1], C.c_uint(op), *args[at + 1:])
 
     # ---- what the compress wrappers set up alike ...
     def _codecs(self, codecs, n_frames, device):
@@ -1319,14 +1360,15 @@ def _planes_methods():
         src_offsets on the device and planes, plane_offsets and results given the call is launches only and can be captured into a graph."""
         return _split(self, src, None, src_offsets, elem_bytes, capacity, planes, plane_offsets, results)
 
-    def planes_split_xor_dbatch(self, src, base, src_offsets, elem_bytes, capacity=None, planes=None, plane_offsets=None, results=None):
+    def planes_split_xor_dbatch(self, src, base, src_offsets, elem_bytes, capacity=None, planes=None, plane_offsets=None, results=None, delta_op=0):
         """planes_split_dbatch of src XOR base, the XOR fused into the split: `base` is laid out as src is (the same offsets, at least `capacity`
-        bytes).  For every elem_bytes, 1 included, `planes` is a buffer of its own and is written; it overlaps neither src nor base."""
+        bytes).  For every elem_bytes, 1 included, `planes` is a buffer of its own and is written; it overlaps neither src nor base.
+        delta_op 1 ("sub"): the planes of zigzag(src - base) instead (FSEHIP_planes_split_op_dbatch)."""
         if base is None:
             raise ValueError("planes_split_xor_dbatch needs a base")
-        return _split(self, src, base, src_offsets, elem_bytes, capacity, planes, plane_offsets, results)
+        return _split(self, src, base, src_offsets, elem_bytes, capacity, planes, plane_offsets, results, _delta_op(delta_op))
 
-    def _split(self, src, base, src_offsets, elem_bytes, capacity, planes, plane_offsets, results):
+    def _split(self, src, base, src_offsets, elem_bytes, capacity, planes, plane_offsets, results, op=0):
         E = _elem(elem_bytes)
         self._flat(src, "src")
         soff, _ = self._offsets(src_offsets, src.device, False)
@@ -1349,8 +1391,8 @@ def _planes_methods():
             _check(self.lib.FSEHIP_planes_split_dbatch(VP(0) if E == 1 else _ptr(planes), _ptr(poff), _ptr(res), _ptr(src), _ptr(soff), SZ(n), C.c_uint(E),
                                                        C.c_uint64(capacity), _stream()), what)
         else:
-            _check(self.lib.FSEHIP_planes_split_xor_dbatch(_ptr(planes), _ptr(poff), _ptr(res), _ptr(src), _ptr(base), _ptr(soff), SZ(n), C.c_uint(E),
-                                                           C.c_uint64(capacity), _stream()), what)
+            _check(_call_base(self, "FSEHIP_planes_split_xor_dbatch", op, 4, _ptr(planes), _ptr(poff), _ptr(res), _ptr(src), _ptr(base), _ptr(soff), SZ(n), C.c_uint(E),
+                              C.c_uint64(capacity), _stream()), what)
         if g is not None:
             g.check(what)
         return planes, poff, res
@@ -1362,15 +1404,16 @@ def _planes_methods():
         dst's size), a plane's error, -4 (sizes that are not the planes of one tensor), -2 (slot too small): such a tensor is not written."""
         return _merge(self, planes, plane_offsets, plane_sizes, None, dst_offsets, elem_bytes, dst, capacity, results)
 
-    def planes_merge_xor_dbatch(self, planes, plane_offsets, plane_sizes, base, dst_offsets, elem_bytes, dst=None, capacity=None, results=None):
+    def planes_merge_xor_dbatch(self, planes, plane_offsets, plane_sizes, base, dst_offsets, elem_bytes, dst=None, capacity=None, results=None, delta_op=0):
         """planes_merge_dbatch, every rebuilt tensor XORed with `base`, which is laid out as dst is (dst_offsets, at least `capacity` bytes): the
         inverse of planes_split_xor_dbatch.  dst may be `base` itself -- IN PLACE: base then holds the new tensors, and a tensor whose result is
-        an error keeps its old bytes.  Any other overlap of dst and base is an error of the caller's that is not checked."""
+        an error keeps its old bytes.  Any other overlap of dst and base is an error of the caller's that is not checked.
+        delta_op 1 ("sub"): base + unzigzag(the rebuilt tensor) instead (FSEHIP_planes_merge_op_dbatch), in place too."""
         if base is None:
             raise ValueError("planes_merge_xor_dbatch needs a base")
-        return _merge(self, planes, plane_offsets, plane_sizes, base, dst_offsets, elem_bytes, dst, capacity, results)
+        return _merge(self, planes, plane_offsets, plane_sizes, base, dst_offsets, elem_bytes, dst, capacity, results, _delta_op(delta_op))
 
-    def _merge(self, planes, plane_offsets, plane_sizes, base, dst_offsets, elem_bytes, dst, capacity, results):
+    def _merge(self, planes, plane_offsets, plane_sizes, base, dst_offsets, elem_bytes, dst, capacity, results, op=0):
         E = _elem(elem_bytes)
         self._flat(planes, "planes")
         doff, dhost = self._offsets(dst_offsets, planes.device, dst is None)
@@ -1386,8 +1429,8 @@ def _planes_methods():
         else:
             what = "planes_merge_xor_dbatch"
             _base(self, base, planes, capacity, "dst")
-            _check(self.lib.FSEHIP_planes_merge_xor_dbatch(_ptr(dst), _ptr(doff), _ptr(res), _ptr(planes), _ptr(poff), _ptr(psz), _ptr(base), SZ(n), C.c_uint(E),
-                                                           C.c_uint64(capacity), _stream()), what)
+            _check(_call_base(self, "FSEHIP_planes_merge_xor_dbatch", op, 6, _ptr(dst), _ptr(doff), _ptr(res), _ptr(planes), _ptr(poff), _ptr(psz), _ptr(base), SZ(n),
+                              C.c_uint(E), C.c_uint64(capacity), _stream()), what)
         if g is not None:
             g.check(what)
         return dst, res
@@ -1404,26 +1447,27 @@ def _planes_methods():
 
     def tensor_compress_delta_dbatch(self, src, base, src_offsets, elem_bytes, block_size_id=5, codec=0, capacity=None, dst=None, dst_capacity=None,
                                      max_total_blocks=None, align_log=0, frame_offsets=None, frame_results=None, tensor_results=None, planes=None, plane_offsets=None,
-                                     workspace=None):
+                                     workspace=None, delta_op=0):
         """tensor_compress_dbatch of src XOR base (planes_split_xor_dbatch, then the packed writer over the planes): frame i*E+p is the .fse frame
-        of plane p of tensor_i XOR base_i.  `base` is laid out as src is.  `planes` is scratch for every elem_bytes, 1 included."""
+        of plane p of tensor_i XOR base_i.  `base` is laid out as src is.  `planes` is scratch for every elem_bytes, 1 included.
+        delta_op 1 ("sub"): of zigzag(tensor_i - base_i) instead (FSEHIP_tensor_compress_delta_op_dbatch)."""
         if base is None:
             raise ValueError("tensor_compress_delta_dbatch needs a base")
         return _compress(self, src, base, src_offsets, elem_bytes, block_size_id, codec, capacity, dst, dst_capacity, max_total_blocks, align_log, frame_offsets,
-                         frame_results, tensor_results, planes, plane_offsets, workspace)
+                         frame_results, tensor_results, planes, plane_offsets, workspace, op=_delta_op(delta_op))
 
     def tensor_compress_mixed_dbatch(self, src, src_offsets, elem_bytes, base=None, codecs=None, tolerance_permille=0, block_size_id=5, capacity=None, dst=None,
                                      dst_capacity=None, max_total_blocks=None, align_log=0, frame_offsets=None, frame_results=None, tensor_results=None, planes=None,
-                                     plane_offsets=None, workspace=None):
+                                     plane_offsets=None, workspace=None, delta_op=0):
         """-> (dst, frame_offsets, frame_results, tensor_results, codecs): tensor_compress_dbatch (base None) or tensor_compress_delta_dbatch with
         a codec per plane, as frame_compress_packed_mixed_dbatch has it: `codecs` (a CUDA uint8 tensor of n*E entries, entry i*E+p for plane p of
         tensor i) is given, or None -- then chosen by size at tolerance_permille and returned.  The workspace is the mixed writer's
-        (frame_mixed_workspace_bound for n*E frames)."""
+        (frame_mixed_workspace_bound for n*E frames).  delta_op: what a base means, 0 ("xor") or 1 ("sub")."""
         return _compress(self, src, base, src_offsets, elem_bytes, block_size_id, None, capacity, dst, dst_capacity, max_total_blocks, align_log, frame_offsets,
-                         frame_results, tensor_results, planes, plane_offsets, workspace, mixed=(codecs, tolerance_permille))
+                         frame_results, tensor_results, planes, plane_offsets, workspace, mixed=(codecs, tolerance_permille), op=_delta_op(delta_op))
 
     def _compress(self, src, base, src_offsets, elem_bytes, block_size_id, codec, capacity, dst, dst_capacity, max_total_blocks, align_log, frame_offsets,
-                  frame_results, tensor_results, planes, plane_offsets, workspace, mixed=None):
+                  frame_results, tensor_results, planes, plane_offsets, workspace, mixed=None, op=0):
         E = _elem(elem_bytes)
         align_log = _align_log(align_log)
         self._flat(src, "src")
@@ -1447,11 +1491,10 @@ def _planes_methods():
         poff = _i64(self, plane_offsets, n * E + 1, src.device, "plane_offsets")
         workspace = _writer_workspace(self, workspace, n * E, max_total_blocks, block_size_id, codec, mixed is not None, choose, src.device)
         if mixed is not None:
-            _check(self.lib.FSEHIP_tensor_compress_mixed_dbatch(_ptr(dst), C.c_uint64(int(dst_capacity)), _ptr(foff), _ptr(fres), _ptr(tres), _ptr(src), _ptr(base),
-                                                                _ptr(soff), SZ(n), C.c_uint(E), C.c_uint64(capacity), SZ(max_total_blocks), C.c_uint(block_size_id),
-                                                                _ptr(codecs if codecs.numel() else codecs.new_zeros(1)),
-                                                                C.c_int(CODECS_CHOOSE if choose else CODECS_GIVEN), C.c_uint(int(tol) if choose else 0),
-                                                                C.c_uint(align_log), _ptr(planes), _ptr(poff), _ptr(workspace), SZ(workspace.numel()), _stream()), what)
+            _check(_call_base(self, "FSEHIP_tensor_compress_mixed_dbatch", op, 6, _ptr(dst), C.c_uint64(int(dst_capacity)), _ptr(foff), _ptr(fres), _ptr(tres), _ptr(src),
+                              _ptr(base), _ptr(soff), SZ(n), C.c_uint(E), C.c_uint64(capacity), SZ(max_total_blocks), C.c_uint(block_size_id),
+                              _ptr(codecs if codecs.numel() else codecs.new_zeros(1)), C.c_int(CODECS_CHOOSE if choose else CODECS_GIVEN),
+                              C.c_uint(int(tol) if choose else 0), C.c_uint(align_log), _ptr(planes), _ptr(poff), _ptr(workspace), SZ(workspace.numel()), _stream()), what)
             _check_codecs(cgu, n * E, what)
             if g is not None:
                 g.check(what)
@@ -1461,8 +1504,8 @@ def _planes_methods():
         if base is None:
             _check(self.lib.FSEHIP_tensor_compress_dbatch(_ptr(dst), C.c_uint64(int(dst_capacity)), _ptr(foff), _ptr(fres), _ptr(tres), _ptr(src), _ptr(soff), *tail), what)
         else:
-            _check(self.lib.FSEHIP_tensor_compress_delta_dbatch(_ptr(dst), C.c_uint64(int(dst_capacity)), _ptr(foff), _ptr(fres), _ptr(tres), _ptr(src), _ptr(base),
-                                                                _ptr(soff), *tail), what)
+            _check(_call_base(self, "FSEHIP_tensor_compress_delta_dbatch", op, 6, _ptr(dst), C.c_uint64(int(dst_capacity)), _ptr(foff), _ptr(fres), _ptr(tres), _ptr(src),
+                              _ptr(base), _ptr(soff), *tail), what)
         if g is not None:
             g.check(what)
         return dst, foff, fres, tres
@@ -1479,17 +1522,17 @@ def _planes_methods():
                            plane_results, workspace, results)
 
     def tensor_decompress_delta_dbatch(self, frames, frame_offsets, base, dst_offsets, elem_bytes, dst=None, dst_capacity=None, max_total_blocks=None, planes=None,
-                                       planes_capacity=None, plane_offsets=None, plane_results=None, workspace=None, results=None):
+                                       planes_capacity=None, plane_offsets=None, plane_results=None, workspace=None, results=None, delta_op=0):
         """tensor_decompress_dbatch of frames that tensor_compress_delta_dbatch wrote: the packed reader into `planes`, then planes_merge_xor_dbatch
         against `base`, which is laid out as dst is.  dst may be `base` itself (in place): a tensor whose result is an error keeps the base's
-        bytes."""
+        bytes.  delta_op: what the frames were written with, 0 ("xor") or 1 ("sub"); they do not say."""
         if base is None:
             raise ValueError("tensor_decompress_delta_dbatch needs a base")
         return _decompress(self, frames, frame_offsets, base, dst_offsets, elem_bytes, dst, dst_capacity, max_total_blocks, planes, planes_capacity, plane_offsets,
-                           plane_results, workspace, results)
+                           plane_results, workspace, results, _delta_op(delta_op))
 
     def _decompress(self, frames, frame_offsets, base, dst_offsets, elem_bytes, dst, dst_capacity, max_total_blocks, planes, planes_capacity, plane_offsets,
-                    plane_results, workspace, results):
+                    plane_results, workspace, results, op=0):
         E = _elem(elem_bytes)
         self._flat(frames, "frames")
         foff, _ = self._offsets(frame_offsets, frames.device, False)
@@ -1514,9 +1557,9 @@ def _planes_methods():
         else:
             what = "tensor_decompress_delta_dbatch"
             _base(self, base, frames, dst_capacity, "dst")
-            _check(self.lib.FSEHIP_tensor_decompress_delta_dbatch(_ptr(dst), _ptr(doff), C.c_uint64(dst_capacity), _ptr(base), _ptr(res), _ptr(frames), _ptr(foff), SZ(n),
-                                                                  C.c_uint(E), SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity), _ptr(poff), _ptr(pres),
-                                                                  _ptr(workspace), SZ(workspace.numel()), _stream()), what)
+            _check(_call_base(self, "FSEHIP_tensor_decompress_delta_dbatch", op, 3, _ptr(dst), _ptr(doff), C.c_uint64(dst_capacity), _ptr(base), _ptr(res), _ptr(frames),
+                              _ptr(foff), SZ(n), C.c_uint(E), SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity), _ptr(poff), _ptr(pres),
+                              _ptr(workspace), SZ(workspace.numel()), _stream()), what)
         if g is not None:
             g.check(what)
         return dst, res
@@ -1609,8 +1652,8 @@ def _planes_methods():
 
     def tensor_compress_seg_dbatch(self, src, src_offsets, elem_bytes, segment_log, seg_first=None, n_segments=None, base=None, codec=0, codecs=None,
                                    block_size_id=5, capacity=None, dst=None, dst_capacity=None, max_total_blocks=None, align_log=0, frame_offsets=None,
-                                   frame_results=None, tensor_results=None, planes=None, plane_offsets=None, seg_offsets=None, workspace=None):
-        """-> (dst, frame_offsets, frame_results, tensor_results, codecs): the split (against `base` if one is given), planes_segments_dbatch,
+                                   frame_results=None, tensor_results=None, planes=None, plane_offsets=None, seg_offsets=None, workspace=None, delta_op=0):
+        """-> (dst, frame_offsets, frame_results, tensor_results, codecs): the split (against `base` if one is given, by delta_op), planes_segments_dbatch,
         then the packed writer over the segments -- frame q = dst[frame_offsets[q] : .. + frame_results[q]] is the .fse frame of segment
         q - seg_first[j] of the plane j that holds it.  codec 0 / 1: the packed writer, codecs returned None.  codec an AutoCodec: a codec per
         segment chosen by size and returned; `codecs` (CUDA uint8, one per segment): given.  seg_first None: planes_segment_first of the
@@ -1624,6 +1667,7 @@ def _planes_methods():
         n = soff.numel() - 1
         capacity = _room(self, src, capacity, "src")
         what = "tensor_compress_seg_dbatch"
+        op = _delta_op(delta_op)
         _base(self, base, src, capacity, "src")
         if seg_first is None:
             seg_first = planes_segment_first(self, np.diff(shost.astype(np.int64)).clip(min=0), E, L)
@@ -1640,8 +1684,8 @@ def _planes_methods():
         so = _i64(self, seg_offsets, nseg + 1, src.device, "seg_offsets")
         workspace = _writer_workspace(self, workspace, nseg, max_total_blocks, block_size_id, codec, mixed, choose, src.device)
         tol = codec.tolerance_permille if choose and isinstance(codec, AutoCodec) else 0
-        _check(self.lib.FSEHIP_tensor_compress_seg_dbatch(
-            _ptr(dst), C.c_uint64(int(dst_capacity)), _ptr(foff), _ptr(fres), _ptr(tres), _ptr(src), _ptr(base), _ptr(soff), SZ(n), C.c_uint(E), C.c_uint64(capacity),
+        _check(_call_base(
+            self, "FSEHIP_tensor_compress_seg_dbatch", op, 6, _ptr(dst), C.c_uint64(int(dst_capacity)), _ptr(foff), _ptr(fres), _ptr(tres), _ptr(src), _ptr(base), _ptr(soff), SZ(n), C.c_uint(E), C.c_uint64(capacity),
             _ptr(sf), SZ(nseg), C.c_uint(L), SZ(max_total_blocks), C.c_uint(block_size_id), C.c_int(0 if mixed else codec),
             _ptr((codecs if codecs.numel() else codecs.new_zeros(1)) if mixed else None), C.c_int(CODECS_CHOOSE if choose else CODECS_GIVEN), C.c_uint(tol),
             C.c_uint(align_log), _ptr(planes), _ptr(poff), _ptr(so), _ptr(workspace), SZ(workspace.numel()), _stream()), what)
@@ -1652,9 +1696,9 @@ def _planes_methods():
 
     def tensor_decompress_seg_dbatch(self, frames, frame_offsets, dst_offsets, elem_bytes, segment_log, seg_first=None, n_segments=None, base=None, dst=None,
                                      dst_capacity=None, max_total_blocks=None, planes=None, planes_capacity=None, seg_offsets=None, seg_results=None, plane_offsets=None,
-                                     plane_sizes=None, workspace=None, results=None):
+                                     plane_sizes=None, workspace=None, results=None, delta_op=0):
         """-> (dst, results): frame_decompress_packed_dbatch of the n_segments frames into `planes`, planes_fold_segments_dbatch, then the merge
-        (against `base` if one is given; dst may be `base` itself) into the slots dst_offsets.  results[i] = the tensor's size, or the error of
+        (against `base` if one is given, by delta_op; dst may be `base` itself) into the slots dst_offsets.  results[i] = the tensor's size, or the error of
         the first of its segments that fails, or the fold's or the merge's own; such a tensor's slot is not written.  seg_first None:
         planes_segment_first of the slots' sizes.  seg_offsets (n_segments+1), seg_results (n_segments), plane_offsets and plane_sizes (n*E
         each) are outputs / scratch; the workspace is the packed reader's for n_segments frames.  max_total_blocks None: the exact count from
@@ -1681,9 +1725,10 @@ def _planes_methods():
         res = _i64(self, results, n, frames.device, "results")
         workspace = _reader_workspace(self, workspace, nseg, max_total_blocks, frames.device)
         what = "tensor_decompress_seg_dbatch"
+        op = _delta_op(delta_op)
         _base(self, base, frames, dst_capacity, "dst")
-        _check(self.lib.FSEHIP_tensor_decompress_seg_dbatch(
-            _ptr(dst), _ptr(doff), C.c_uint64(dst_capacity), _ptr(base), _ptr(res), _ptr(frames), _ptr(foff), SZ(n), C.c_uint(E), _ptr(sf), SZ(nseg), C.c_uint(L),
+        _check(_call_base(
+            self, "FSEHIP_tensor_decompress_seg_dbatch", op, 3, _ptr(dst), _ptr(doff), C.c_uint64(dst_capacity), _ptr(base), _ptr(res), _ptr(frames), _ptr(foff), SZ(n), C.c_uint(E), _ptr(sf), SZ(nseg), C.c_uint(L),
             SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity), _ptr(so), _ptr(sres), _ptr(poff), _ptr(psz), _ptr(workspace), SZ(workspace.numel()),
             _stream()), what)
         if g is not None:
@@ -1816,9 +1861,9 @@ def _planes_methods():
     def tensor_decompress_window_dbatch(self, frames, frame_offsets, src_offsets, windows, dst_offsets, elem_bytes, segment_log, seg_first=None, n_segments=None,
                                         sel_first=None, n_selected=None, base=None, dst=None, dst_capacity=None, max_total_blocks=None, block_size_id=5, planes=None,
                                         planes_capacity=None, sel_frame_offsets=None, sel_offsets=None, sel_results=None, plane_offsets=None, plane_sizes=None,
-                                        workspace=None, results=None):
+                                        workspace=None, results=None, delta_op=0):
         """-> (dst, results): elements [a, b) of every tensor of a segmented batch -- planes_select_window_dbatch, frame_decompress_packed_dbatch over
-        the n_selected extents into `planes`, planes_fold_window_dbatch, then the merge (against `base` if one is given, which holds the same
+        the n_selected extents into `planes`, planes_fold_window_dbatch, then the merge (against `base` if one is given, by delta_op, which holds the same
         windows in dst's layout; dst may be `base` itself) into the slots dst_offsets: slot i receives the E * (b - a) bytes
         tensor_i[a * E : b * E], results[i] is that size or an error, and such a tensor's slot is not written.  src_offsets is the SENDER'S
         layout (the sizes the tensors were compressed with), frame_offsets all n_segments frames'.  seg_first None: planes_segment_first of
@@ -1858,12 +1903,13 @@ def _planes_methods():
         res = _i64(self, results, n, frames.device, "results")
         workspace = _reader_workspace(self, workspace, nsel, max_total_blocks, frames.device)
         what = "tensor_decompress_window_dbatch"
+        op = _delta_op(delta_op)
         _base(self, base, frames, dst_capacity, "dst")
 
         def some(t):                                             # (an array of no entries still needs an address)
             return t if t.numel() else t.new_zeros(1)
-        _check(self.lib.FSEHIP_tensor_decompress_window_dbatch(
-            _ptr(some(dst)), _ptr(doff), C.c_uint64(dst_capacity), _ptr(base), _ptr(some(res)), _ptr(some(frames)), _ptr(foff), _ptr(soff), _ptr(some(win)), SZ(n),
+        _check(_call_base(
+            self, "FSEHIP_tensor_decompress_window_dbatch", op, 3, _ptr(some(dst)), _ptr(doff), C.c_uint64(dst_capacity), _ptr(base), _ptr(some(res)), _ptr(some(frames)), _ptr(foff), _ptr(soff), _ptr(some(win)), SZ(n),
             C.c_uint(E), _ptr(sf), SZ(nseg), C.c_uint(L), _ptr(wf), SZ(nsel), SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity), _ptr(sfo), _ptr(so),
             _ptr(some(sres)), _ptr(some(poff)), _ptr(some(psz)), _ptr(workspace), SZ(workspace.numel()), _stream()), what)
         if g is not None:
@@ -1892,10 +1938,10 @@ def _planes_methods():
         return np.concatenate([[0], np.cumsum(m, dtype=np.int64)]).astype(np.uint64)
 
     def planes_split_window_dbatch(self, src, src_offsets, windows, elem_bytes, segment_log, stage_offsets=None, base=None, capacity=None, stage=None,
-                                   stage_capacity=None, plane_offsets=None, results=None):
+                                   stage_capacity=None, plane_offsets=None, results=None, delta_op=0):
         """-> (stage, plane_offsets, results): per tensor the planes of the bytes its selected segments cover (planes_stage_offsets), staged back to
         back at stage_offsets -- plane p of staged tensor i = stage[plane_offsets[i*E+p] : plane_offsets[i*E+p+1]] is segments k0 .. k1 of plane
-        p of the tensor (of tensor XOR base where a base is given).  results[i] = the staged bytes, or -1 for a tensor with a bad window, one
+        p of the tensor (of tensor XOR base where a base is given, of zigzag(tensor - base) with delta_op 1).  results[i] = the staged bytes, or -1 for a tensor with a bad window, one
         that ends behind `capacity`, or a pair of stage offsets that does not hold exactly those bytes below stage_capacity.  stage_offsets
         None: planes_stage_offsets (src_offsets and windows then on the host); on the device they need stage or stage_capacity."""
         E, L = _elem(elem_bytes), _seg_log(segment_log)
@@ -1921,8 +1967,8 @@ def _planes_methods():
         poff = _i64(self, plane_offsets, n * E + 1, src.device, "plane_offsets")
         res = _i64(self, results, n, src.device, "results")
         what = "planes_split_window_dbatch"
-        _check(self.lib.FSEHIP_planes_split_window_dbatch(_ptr(stage), _ptr(poff), _ptr(_some(res)), _ptr(_some(src)), _ptr(base), _ptr(soff), _ptr(_some(win)),
-                                                          _ptr(toff), SZ(n), C.c_uint(E), C.c_uint(L), C.c_uint64(capacity), C.c_uint64(stage_capacity), _stream()), what)
+        _check(_call_base(self, "FSEHIP_planes_split_window_dbatch", _delta_op(delta_op), 4, _ptr(stage), _ptr(poff), _ptr(_some(res)), _ptr(_some(src)), _ptr(base),
+                          _ptr(soff), _ptr(_some(win)), _ptr(toff), SZ(n), C.c_uint(E), C.c_uint(L), C.c_uint64(capacity), C.c_uint64(stage_capacity), _stream()), what)
         if g is not None:
             g.check(what)
         return stage, poff, res
@@ -2024,11 +2070,11 @@ def _planes_methods():
                                    capacity=None, frames_capacity=None, max_total_blocks=None, align_log=0, out=None, out_capacity=None, out_offsets=None,
                                    out_results=None, out_codecs=None, tensor_results=None, stage=None, stage_capacity=None, stage_plane_offsets=None,
                                    stage_seg_offsets=None, stage_results=None, new_frames=None, new_capacity=None, new_offsets=None, new_results=None, scratch=None,
-                                   workspace=None):
+                                   workspace=None, delta_op=0):
         """-> (out, out_offsets, out_results, tensor_results, out_codecs): the object (frames, frame_offsets, frame_results, codecs) of
         tensor_compress_seg_dbatch brought up to date with `src`, the WHOLE current tensors in the layout src_offsets they were compressed in,
         which changed inside one window (a, b) of elements each.  The segments a >> segment_log .. (b - 1) >> segment_log of every plane are
-        coded anew from src (XOR base), all other frames are the old ones byte for byte: planes_split_window_dbatch, planes_segments_dbatch
+        coded anew from src (XOR base, or zigzag(src - base) with delta_op 1), all other frames are the old ones byte for byte: planes_split_window_dbatch, planes_segments_dbatch
         over the stage, the packed writer, planes_splice_dbatch.  WHOLE SEGMENTS are replaced: inside a selected segment the bytes of src win
         outside the window too, elsewhere the old ones stay, so src must equal the object's content outside the windows (not checked).  For
         tensors that differ inside the windows only, the result is tensor_compress_seg_dbatch of src, byte for byte.
@@ -2047,6 +2093,7 @@ def _planes_methods():
         if src.device != dev:
             raise ValueError("src is on %s, the frames on %s" % (src.device, dev))
         what = "tensor_patch_window_dbatch"
+        op = _delta_op(delta_op)
         foff, _ = self._offsets(frame_offsets, dev, False)
         need_first = sel_first is None or max_total_blocks is None or stage_offsets is None
         soff, shost = self._offsets(src_offsets, dev, seg_first is None or need_first)
@@ -2107,8 +2154,8 @@ def _planes_methods():
             scratch = torch.empty(planes_splice_scratch_bound(self, n, E, nseg), dtype=torch.uint8, device=dev)
         workspace = _writer_workspace(self, workspace, nsel, max_total_blocks, block_size_id, codec, mixed, choose, dev)
         tol = codec.tolerance_permille if choose else 0
-        _check(self.lib.FSEHIP_tensor_patch_window_dbatch(
-            _ptr(out), C.c_uint64(out_capacity), _ptr(ooff), _ptr(_some(ores)), _ptr(_some(out_codecs)), _ptr(_some(tres)), _ptr(_some(frames)),
+        _check(_call_base(
+            self, "FSEHIP_tensor_patch_window_dbatch", op, 12, _ptr(out), C.c_uint64(out_capacity), _ptr(ooff), _ptr(_some(ores)), _ptr(_some(out_codecs)), _ptr(_some(tres)), _ptr(_some(frames)),
             C.c_uint64(frames_capacity), _ptr(foff), _ptr(_some(fres)), _ptr(_some(codecs)), _ptr(_some(src)), _ptr(base), _ptr(soff), C.c_uint64(capacity),
             _ptr(_some(win)), SZ(n), C.c_uint(E), _ptr(sf), SZ(nseg), C.c_uint(L), _ptr(wf), SZ(nsel), _ptr(toff), C.c_uint64(stage_capacity), SZ(max_total_blocks),
             C.c_uint(block_size_id), C.c_int(0 if mixed else codec), _ptr(_some(new_codecs)), C.c_int(CODECS_CHOOSE if choose else CODECS_GIVEN), C.c_uint(tol),
@@ -2134,9 +2181,7 @@ def _planes_methods():
         seg_log = getattr(obj, "segment_log", None)
         if seg_log is None:
             raise ValueError("patch_tensor_windows: the object is not segmented (compress_tensors_segmented writes those)")
-        if getattr(obj, "delta", False) != (base is not None):
-            raise ValueError("patch_tensor_windows: the object holds deltas and needs its base" if base is None else
-                             "patch_tensor_windows: the object holds no deltas, a base does not belong to it")
+        base, op = _read_base(obj, base, "patch_tensor_windows")
         tensors, windows = list(tensors), list(windows)
         if len(tensors) != len(obj.dtypes) or len(windows) != len(obj.dtypes):
             raise ValueError("patch_tensor_windows: %d tensors and %d windows for %d tensors" % (len(tensors), len(windows), len(obj.dtypes)))
@@ -2170,7 +2215,7 @@ def _planes_methods():
                 out, ooff, ores, tres, ocod = self.tensor_patch_window_dbatch(
                     g["frames"], g["frame_offsets"], g["frame_results"], src, offs, gw, E, seg_log, g["seg_first"], sel_first=first, stage_offsets=toff, base=bsrc,
                     codec=obj.codec if auto or "codecs" not in g else 0, codecs=g.get("codecs"), block_size_id=obj.block_size_id, max_total_blocks=blocks,
-                    out_capacity=cap)
+                    out_capacity=cap, delta_op=op)
                 got = torch.cat([ooff[-1:], tres]).cpu().tolist()
                 if got[1:] != sizes or got[0] > cap:
                     raise RuntimeError("patch_tensor_windows: element size %d, results %s for tensors of %s bytes" % (E, got[1:9], sizes[:8]))
@@ -2183,12 +2228,26 @@ def _planes_methods():
                 if "codecs" in g:
                     new["codecs"] = g["codecs"].clone()
             groups.append(new)
-        return _segmented(CompressedTensors(groups, list(obj.dtypes), list(obj.shapes), obj.device, obj.codec, obj.block_size_id, obj.delta), seg_log)
+        return _segmented(CompressedTensors(groups, list(obj.dtypes), list(obj.shapes), obj.device, obj.codec, obj.block_size_id, obj.delta), seg_log,
+                          getattr(obj, "delta_op", "xor"))
 
     for f in (planes_stage_offsets, planes_split_window_dbatch, planes_splice_scratch_bound, planes_splice_dbatch, tensor_patch_window_dbatch, patch_tensor_windows):
         setattr(FseHip, f.__name__, f)
 
     # ---- the user-facing pair
+    def _read_base(obj, base, what):
+        """the `base` of a reading call -> the plain sequence (or None) and the op of `obj`: a base iff the object holds deltas, and a
+        DeltaBase only of the object's own op"""
+        if getattr(obj, "delta", False) != (base is not None):
+            raise ValueError(what + ": the object holds deltas and needs its base" if base is None else
+                             what + ": the object holds no deltas, a base does not belong to it")
+        op = getattr(obj, "delta_op", "xor")
+        if isinstance(base, DeltaBase):
+            if base.op != op:
+                raise ValueError("%s: the base says op %r, the object was written with %r" % (what, base.op, op))
+            base = base.tensors
+        return base, _delta_op(op)
+
     def _bases(base, dtypes, shapes, device):
         """the `base` of the pair: one CUDA tensor per tensor, of its dtype, shape and device -> their bytes, flat"""
         base = list(base)
@@ -2209,7 +2268,9 @@ def _planes_methods():
         group's bytes beside the inputs; the object keeps only the frames at their real total.
         base: a sequence of CUDA tensors matching `tensors` one to one in dtype, shape and device (TypeError / ValueError otherwise, before any
         launch) -- what the receiver already holds.  The frames then hold `tensor XOR base` (the object's `delta` is True), far fewer bytes where
-        most bytes did not change, and decompress_tensors needs the same base.
+        most bytes did not change, and decompress_tensors needs the same base.  A DeltaBase(tensors, "sub") as base: the frames hold
+        zigzag(tensor - base) of the elements' bit patterns instead, fewer bytes again on weight updates; the object's `delta_op` is "sub"
+        and the reading calls take the op from the object.
         codec: 0 (FSE), 1 (Huff0), an AutoCodec -- every plane's frame gets the codec chosen for it by size (tensor_compress_mixed_dbatch; each
         group dict gains "codecs", a CUDA uint8 tensor with entry i*E+p for plane p of the group's tensor i, and the object's `codec` is the
         AutoCodec) -- or a CompressedTensors an AutoCodec call returned for tensors of the same dtypes and shapes (ValueError otherwise, before
@@ -2230,14 +2291,20 @@ def _planes_methods():
         return _compress_tensors(self, tensors, codec, block_size_id, base,
                                  _seg_log(segment_log, block_size_id if isinstance(block_size_id, numbers.Integral) and 0 <= block_size_id <= 6 else 0))
 
-    def _segmented(obj, segment_log):
+    def _segmented(obj, segment_log, delta_op="xor"):
         if segment_log is not None:
             obj.segment_log = int(segment_log)
+        if delta_op != "xor":
+            obj.delta_op = delta_op
         return obj
 
     def _compress_tensors(self, tensors, codec, block_size_id, base, segment_log):
         tensors = list(tensors)
         earlier = None
+        opname = "xor"
+        if isinstance(base, DeltaBase):                     # the base with its op beside it; a plain sequence means XOR
+            base, opname = base.tensors, base.op
+        op = _delta_op(opname)
         if isinstance(codec, CompressedTensors):            # the codecs an earlier AutoCodec call chose, given again
             earlier, codec = codec, codec.codec
             if any("codecs" not in g for g in earlier.groups):
@@ -2253,7 +2320,7 @@ def _planes_methods():
         if not tensors:
             if base is not None and len(list(base)):
                 raise ValueError("base: tensors for none")
-            return _segmented(CompressedTensors([], [], [], None, codec, block_size_id, base is not None), segment_log)
+            return _segmented(CompressedTensors([], [], [], None, codec, block_size_id, base is not None), segment_log, opname)
         device = tensors[0].device
         for t in tensors:
             if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
@@ -2274,14 +2341,14 @@ def _planes_methods():
                 given = None if earlier is None else [g for g in earlier.groups if g["elem_bytes"] == E][0]["codecs"]
                 sfirst = self.planes_segment_first(np.diff(offs.astype(np.int64)), E, segment_log)
                 dst, foff, fres, tres, codecs = self.tensor_compress_seg_dbatch(src, offs, E, segment_log, sfirst, base=bsrc, codec=codec, codecs=given,
-                                                                                block_size_id=block_size_id)
+                                                                                block_size_id=block_size_id, delta_op=op)
             elif isinstance(codec, AutoCodec):
                 given = None if earlier is None else [g for g in earlier.groups if g["elem_bytes"] == E][0]["codecs"]
-                dst, foff, fres, tres, codecs = self.tensor_compress_mixed_dbatch(src, offs, E, bsrc, given, codec.tolerance_permille, block_size_id)
+                dst, foff, fres, tres, codecs = self.tensor_compress_mixed_dbatch(src, offs, E, bsrc, given, codec.tolerance_permille, block_size_id, delta_op=op)
             elif braw is None:
                 dst, foff, fres, tres = self.tensor_compress_dbatch(src, offs, E, block_size_id, codec)
             else:
-                dst, foff, fres, tres = self.tensor_compress_delta_dbatch(src, bsrc, offs, E, block_size_id, codec)
+                dst, foff, fres, tres = self.tensor_compress_delta_dbatch(src, bsrc, offs, E, block_size_id, codec, delta_op=op)
             got = torch.cat([foff[-1:], fres, tres]).cpu().tolist()
             if min(got) < 0:
                 bad = [k for k, r in enumerate(got[1:1 + fres.numel()]) if r < 0]
@@ -2293,7 +2360,7 @@ def _planes_methods():
             if sfirst is not None:
                 groups[-1]["seg_first"] = sfirst
         return _segmented(CompressedTensors(groups, [t.dtype for t in tensors], [tuple(t.shape) for t in tensors], device, codec, block_size_id, braw is not None),
-                          segment_log)
+                          segment_log, opname if braw is not None else "xor")
 
     def decompress_tensors(self, obj, base=None):
         """-> the tensors compress_tensors was given, in their order: same dtype, shape and device, the same bytes.  Every tensor owns its memory
@@ -2301,10 +2368,9 @@ def _planes_methods():
         before the results.
         base: for an object with `delta` set, the tensors compress_tensors was given as base (checked for dtype, shape and device, not for
         content: the frames do not say what they are a delta against).  ValueError for a delta object without a base and for a base with a plain
-        object.  The bases are not changed: a group is rebuilt in place over a copy of its bases."""
-        if getattr(obj, "delta", False) != (base is not None):
-            raise ValueError("decompress_tensors: the object holds deltas and needs its base" if base is None else
-                             "decompress_tensors: the object holds no deltas, a base does not belong to it")
+        object.  The bases are not changed: a group is rebuilt in place over a copy of its bases.  The delta's op ("xor" or "sub") is the
+        object's `delta_op`; the base is the plain sequence, or a DeltaBase of the same op (ValueError for another, before any launch)."""
+        base, op = _read_base(obj, base, "decompress_tensors")
         braw = None if base is None else _bases(base, obj.dtypes, obj.shapes, obj.device)
         out = [None] * len(obj.dtypes)
         for g in obj.groups:
@@ -2315,12 +2381,12 @@ def _planes_methods():
             if seg_log is not None:
                 dst = None if braw is None else torch.cat([braw[i] for i in g["index"]]) if sum(sizes) else torch.zeros(1, dtype=torch.uint8, device=obj.device)[:0]
                 dst, res = self.tensor_decompress_seg_dbatch(g["frames"], g["frame_offsets"], offs, E, seg_log, g["seg_first"], base=dst, dst=dst,
-                                                             max_total_blocks=blocks)
+                                                             max_total_blocks=blocks, delta_op=op)
             elif braw is None:
                 dst, res = self.tensor_decompress_dbatch(g["frames"], g["frame_offsets"], offs, E, max_total_blocks=blocks)
             else:
                 dst = torch.cat([braw[i] for i in g["index"]]) if sum(sizes) else torch.zeros(1, dtype=torch.uint8, device=obj.device)[:0]
-                dst, res = self.tensor_decompress_delta_dbatch(g["frames"], g["frame_offsets"], dst, offs, E, dst=dst, max_total_blocks=blocks)
+                dst, res = self.tensor_decompress_delta_dbatch(g["frames"], g["frame_offsets"], dst, offs, E, dst=dst, max_total_blocks=blocks, delta_op=op)
             got = res.cpu().tolist()
             if got != sizes:
                 raise RuntimeError("decompress_tensors: element size %d, results %s for tensors of %s bytes" % (E, got[:8], sizes[:8]))
@@ -2339,9 +2405,7 @@ def _planes_methods():
         seg_log = getattr(obj, "segment_log", None)
         if seg_log is None:
             raise ValueError("decompress_tensor_windows: the object is not segmented (compress_tensors_segmented writes those)")
-        if getattr(obj, "delta", False) != (base is not None):
-            raise ValueError("decompress_tensor_windows: the object holds deltas and needs its base" if base is None else
-                             "decompress_tensor_windows: the object holds no deltas, a base does not belong to it")
+        base, op = _read_base(obj, base, "decompress_tensor_windows")
         windows = list(windows)
         if len(windows) != len(obj.dtypes):
             raise ValueError("decompress_tensor_windows: %d windows for %d tensors" % (len(windows), len(obj.dtypes)))
@@ -2371,7 +2435,7 @@ def _planes_methods():
             if braw is not None:
                 dst = torch.cat([braw[i][E * a:E * b] for i, (a, b) in zip(g["index"], gw)])             # a copy: rebuilt in place, the bases stay
             dst, res = self.tensor_decompress_window_dbatch(g["frames"], g["frame_offsets"], soff, gw, doff, E, seg_log, g["seg_first"], base=dst, dst=dst,
-                                                            block_size_id=obj.block_size_id)
+                                                            block_size_id=obj.block_size_id, delta_op=op)
             got, want = res.cpu().tolist(), [E * (b - a) for a, b in gw]
             if got != want:
                 raise RuntimeError("decompress_tensor_windows: element size %d, results %s for windows of %s bytes" % (E, got[:8], want[:8]))

@@ -332,24 +332,25 @@ size_t exscan_partials(size_t n);
 
 // ---- byte planes of tensors (planes.hip) ------------------------------------------------------------------
 // PLANES_TILE: bytes of the flat axis per workgroup of the two data kernels (fsehip.h, "byte planes": the work mapping).  The launchers check
-// nothing: the C calls of the plane files do.  `base` null: the plain form, else the XOR form (fsehip.h, "tensor deltas").
+// nothing: the C calls of the plane files do.  `base` null: the plain form, else the delta form by deltaOp (FSEHIP_DELTA_XOR, FSEHIP_DELTA_SUB;
+// fsehip.h, "tensor deltas" and "arithmetic tensor deltas").
 // launch_planes_split: the offsets and results kernel, then (E > 1, or a base) the data kernel.  launch_planes_merge: the verdicts kernel,
 // then the data kernel -- the tail of every decompress composite (planes.hip, planes_seg.hip, planes_win.hip).
 #define PLANES_TILE ((u64)32768)
-hipError_t launch_planes_split(u8* planes, u64* planeOff, size_t* tensorRes, const u8* src, const u8* base, const u64* srcOff, size_t nTensors, unsigned E, u64 capacity,
-                               hipStream_t s);
+hipError_t launch_planes_split(u8* planes, u64* planeOff, size_t* tensorRes, const u8* src, const u8* base, unsigned deltaOp, const u64* srcOff, size_t nTensors,
+                               unsigned E, u64 capacity, hipStream_t s);
 hipError_t launch_planes_merge(u8* dst, const u64* dstOff, size_t* results, const u8* planes, const u64* planeOff, const size_t* planeSizes, const u8* base,
-                               size_t nTensors, unsigned E, u64 dstCapacity, hipStream_t s);
+                               unsigned deltaOp, size_t nTensors, unsigned E, u64 dstCapacity, hipStream_t s);
 // the segments kernel of planes_seg.hip, as the compress path chains it
 hipError_t launch_segments(u64* segOff, size_t* tensorRes, const u64* planeOff, const u64* srcOff, const u64* segFirst, size_t nTensors, unsigned E, size_t nSeg,
                            unsigned segLog, hipStream_t s);
 // what a compress composite hands on to the packed writer: d_codecs null -> `codec` for every frame (FSEHIP_frame_compress_packed_dbatch),
 // else a codec per frame by `policy` (FSEHIP_frame_compress_packed_mixed_dbatch)
 struct PlWriter { size_t maxTotalBlocks; unsigned blockSizeId; int codec; uint8_t* d_codecs; int policy; unsigned tolerancePermille, slotAlignLog; void* d_workspace; size_t workspaceBytes; };
-// the compress path of all four compress composites (planes.hip): argument checks, (XOR) split, segments where d_segFirst is given, writer
+// the compress path of all four compress composites (planes.hip): argument checks, (delta) split, segments where d_segFirst is given, writer
 int planes_compress(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults, const void* d_src, const void* d_base,
-                    const uint64_t* d_srcOffsets, size_t nTensors, unsigned E, uint64_t capacity, const uint64_t* d_segFirst, size_t nSegments, unsigned segLog,
-                    void* d_planes, uint64_t* d_planeOffsets, uint64_t* d_segOffsets, const PlWriter& w, void* stream);
+                    unsigned deltaOp, const uint64_t* d_srcOffsets, size_t nTensors, unsigned E, uint64_t capacity, const uint64_t* d_segFirst, size_t nSegments,
+                    unsigned segLog, void* d_planes, uint64_t* d_planeOffsets, uint64_t* d_segOffsets, const PlWriter& w, void* stream);
 
 // ---- kernel timing probe (HIP events on the launch stream; used by bench.py for the live roofline figure) ----
 enum { PK_HIST = 0, PK_FSE_CPREP, PK_FSE_ENCODE, PK_FSE_DPREP, PK_FSE_DECODE, PK_HUF_CPREP, PK_HUF_ENCODE, PK_HUF_DPREP, PK_HUF_DECODE, PK_FSE_ENCODE_WAVE, PK_COUNT };

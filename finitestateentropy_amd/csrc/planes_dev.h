@@ -1,5 +1,5 @@
-// planes_dev.h -- what the plane files (planes.hip: byte planes of tensors and their XOR forms; planes_seg.hip; planes_win.hip; planes_patch.hip) share: the byte
-// shuffle, the plane arithmetic, the search behind every work mapping, a workgroup's share of a tensor, the merge's verdict, the fold of a
+// planes_dev.h -- what the plane files (planes.hip: byte planes of tensors and their delta forms; planes_seg.hip; planes_win.hip; planes_patch.hip) share: the byte
+// shuffle, the delta ops (XOR, subtract and zigzag), the plane arithmetic, the search behind every work mapping, a workgroup's share of a tensor, the merge's verdict, the fold of a
 // plane's segment results, the dispatch over the element size and the argument checks of the C calls.  Device helpers are inlined into the
 // kernels of the file that includes this; nothing here is a kernel.
 #pragma once
@@ -41,18 +41,122 @@ template <int E> DEV void pl_interleave(u32* w, const u32 (*o)[4], int p0 = 0, i
     }
 }
 
-// w ^= the 16 bytes at `from` (the base stream of the XOR forms; any alignment)
-DEV void pl_xor16(u32* w, const u8* from)
-{
-    u32 t[4];
-    __builtin_memcpy(t, from, 16);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) w[k] ^= t[k];
-}
-
 // size of plane p of a tensor of n bytes, and where it starts inside the tensor (the sizes of the planes in front of it)
 HDEV u64 pl_size(u64 n, u32 p, u32 E) { return n > p ? (n - p + E - 1) / E : 0; }
 HDEV u64 pl_start(u64 n, u32 p, u32 E) { const u64 r = n % E; return (u64)p * (n / E) + (p < r ? p : r); }
+
+// ---- the delta ops (fsehip.h, "arithmetic tensor deltas") ----
+// what the data kernels do with the base: nothing (it is never read), XOR, or SUB -- zigzag(tensor - base) on the elements' bit patterns
+enum { PL_NONE = 0, PL_XOR = 1, PL_SUB = 2 };
+// the template argument for a nullable base and a deltaOp of the C calls (bad_op has let it through)
+inline int pl_op(const void* base, unsigned deltaOp) { return !base ? PL_NONE : deltaOp == FSEHIP_DELTA_SUB ? PL_SUB : PL_XOR; }
+inline bool bad_op(unsigned deltaOp) { return deltaOp > FSEHIP_DELTA_SUB; }
+
+// One element of E bytes as a number below 2^(8 E): z = zigzag((t - b) mod 2^W), and t from z and b.  The bytewise head and tail of the
+// SUB kernels, and what the dword forms below must agree with bit for bit
+template <int E> DEV u64 pl_zz(u64 t, u64 b)
+{
+    constexpr u64 M = E == 8 ? ~(u64)0 : (((u64)1 << (8 * (E & 7))) - 1);
+    const u64 d = (t - b) & M;
+    return ((d << 1) & M) ^ (((d >> (8 * E - 1)) & 1) ? M : 0);
+}
+template <int E> DEV u64 pl_unzz(u64 z, u64 b)
+{
+    constexpr u64 M = E == 8 ? ~(u64)0 : (((u64)1 << (8 * (E & 7))) - 1);
+    const u64 d = (z >> 1) ^ ((z & 1) ? M : 0);
+    return (b + d) & M;
+}
+// The same on the dwords of a chunk, which hold whole elements: w[0 .. 4) = zigzag(w - b), or (INV) w = b + unzigzag(w).
+//   E == 1: four bytes per dword, SWAR -- the top bit of every byte is taken out of the subtraction (addition) and put back by XOR, so no
+//           borrow (carry) crosses a byte; the sign byte masks are (bit * 0xFF)
+//   E == 2: two elements per dword, the packed 16-bit forms (v_pk_sub_u16 / v_pk_add_u16, v_pk_lshlrev_b16, v_pk_ashrrev_i16)
+//   E == 4: plain 32-bit
+//   E == 8: the dword pair w[2 k], w[2 k + 1] as one 64-bit number (v_sub_co / v_subb, the shift over 64 bits)
+typedef unsigned short pl_u16x2 __attribute__((ext_vector_type(2)));
+typedef short pl_i16x2 __attribute__((ext_vector_type(2)));
+template <int E, bool INV> DEV void pl_sub4(u32* w, const u32* b)
+{
+    constexpr u32 H = 0x80808080u, L = 0x7F7F7F7Fu, ONE = 0x01010101u;
+    if constexpr (E == 1) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if constexpr (!INV) {
+                const u32 d = ((w[k] | H) - (b[k] & L)) ^ ((w[k] ^ ~b[k]) & H);
+                w[k] = ((d & L) << 1) ^ (((d >> 7) & ONE) * 0xFFu);
+            } else {
+                const u32 d = ((w[k] >> 1) & L) ^ ((w[k] & ONE) * 0xFFu);
+                w[k] = ((b[k] & L) + (d & L)) ^ ((b[k] ^ d) & H);
+            }
+        }
+    } else if constexpr (E == 2) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            pl_u16x2 x, y;
+            __builtin_memcpy(&x, &w[k], 4); __builtin_memcpy(&y, &b[k], 4);
+            if constexpr (!INV) {
+                const pl_u16x2 d = x - y;
+                x = (d << 1) ^ (pl_u16x2)((pl_i16x2)d >> 15);
+            } else {
+                const pl_u16x2 d = (x >> 1) ^ (pl_u16x2)(-(pl_i16x2)(x & (unsigned short)1));
+                x = y + d;
+            }
+            __builtin_memcpy(&w[k], &x, 4);
+        }
+    } else if constexpr (E == 4) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if constexpr (!INV) { const u32 d = w[k] - b[k]; w[k] = (d << 1) ^ (u32)((int)d >> 31); }
+            else { const u32 d = (w[k] >> 1) ^ (0u - (w[k] & 1u)); w[k] = b[k] + d; }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const u64 x = (u64)w[2 * k] | ((u64)w[2 * k + 1] << 32), y = (u64)b[2 * k] | ((u64)b[2 * k + 1] << 32);
+            const u64 r = INV ? pl_unzz<8>(x, y) : pl_zz<8>(x, y);
+            w[2 * k] = (u32)r; w[2 * k + 1] = (u32)(r >> 32);
+        }
+    }
+}
+// w = op(w, the 16 bytes at `from`): the base stream of the delta forms, any alignment, combined into its words as it arrives
+template <int E, int OP, bool INV> DEV void pl_base16(u32* w, const u8* from)
+{
+    u32 t[4];
+    __builtin_memcpy(t, from, 16);
+    if constexpr (OP == PL_XOR) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w[k] ^= t[k];
+    } else pl_sub4<E, INV>(w, t);
+}
+// element e of the tensor at sb (n bytes, base bb) as the SUB kernels' head and tail take it, a thread per element: its bytes into the
+// planes at pb, or back from them into db.  The partial last element of a tensor whose size is no multiple of E goes byte by byte, E == 1 form
+template <int E> DEV void pl_sub_elem_split(u8* pb, const u8* sb, const u8* bb, u64 n, u64 e)
+{
+    const u64 k0 = e * E;
+    if (k0 + E <= n) {
+        u64 t = 0, b = 0;
+#pragma unroll
+        for (int p = 0; p < E; ++p) { t |= (u64)sb[k0 + p] << (8 * p); b |= (u64)bb[k0 + p] << (8 * p); }
+        const u64 z = pl_zz<E>(t, b);
+#pragma unroll
+        for (int p = 0; p < E; ++p) pb[pl_start(n, p, E) + e] = (u8)(z >> (8 * p));
+    } else {
+        for (u64 k = k0; k < n; ++k) pb[pl_start(n, (u32)(k - k0), E) + e] = (u8)pl_zz<1>(sb[k], bb[k]);
+    }
+}
+template <int E, class PlaneAt> DEV void pl_sub_elem_merge(u8* db, const u8* bb, u64 n, u64 e, PlaneAt planeAt)
+{
+    const u64 k0 = e * E;
+    if (k0 + E <= n) {
+        u64 z = 0, b = 0;
+#pragma unroll
+        for (int p = 0; p < E; ++p) { z |= (u64)planeAt(p)[e] << (8 * p); b |= (u64)bb[k0 + p] << (8 * p); }      // (in place: these loads, then the stores)
+        const u64 t = pl_unzz<E>(z, b);
+#pragma unroll
+        for (int p = 0; p < E; ++p) db[k0 + p] = (u8)(t >> (8 * p));
+    } else {
+        for (u64 k = k0; k < n; ++k) db[k] = (u8)pl_unzz<1>(planeAt((u32)(k - k0))[e], bb[k]);
+    }
+}
 
 // the largest j < n with key(j) <= q, for n >= 1 and a key that does not decrease; 0 where there is none.  The result is an index below n
 // whatever the keys hold: a caller that reads its keys from an array it does not trust indexes with the result, never with a key

@@ -41,7 +41,7 @@ __global__ void k_planes_stage_offsets(u64* P, size_t* res, const u64* S, const 
 }
 // k_planes_split's data path (planes.hip) over the STAGE axis: workgroup w takes tile w - i of the staged sub-tensor i, whose source lies at
 // S[i] + at.  E == 1 without a base is the copy
-template <int E, bool X>
+template <int E, int OP>
 __global__ __launch_bounds__(PL_THREADS) void k_planes_split_window(u8* stage, const u8* src, const u8* base, const u64* S, const u64* W, const u64* T, size_t nT,
                                                                     u32 segLog, u64 capacity, u64 stageCapacity)
 {
@@ -55,7 +55,7 @@ __global__ __launch_bounds__(PL_THREADS) void k_planes_split_window(u8* stage, c
     const u64 n = g.m;
     const u32 tid = threadIdx.x;
     const u8* const sb = src + S[i] + g.at;
-    const u8* const bb = X ? base + S[i] + g.at : nullptr;
+    const u8* const bb = OP != PL_NONE ? base + S[i] + g.at : nullptr;
     u8* const pb = stage + t0;
     const PlShare h = pl_share<E>(t0, n, lo, (u64)(uintptr_t)pb, 1);
     for (u64 c = tid; c < h.nch; c += PL_THREADS) {
@@ -63,21 +63,26 @@ __global__ __launch_bounds__(PL_THREADS) void k_planes_split_window(u8* stage, c
         u32 wv[4 * E], o[E][4];
 #pragma unroll
         for (int k = 0; k < E; ++k) __builtin_memcpy(&wv[4 * k], sb + e * E + 16 * k, 16);
-        if constexpr (X) {
+        if constexpr (OP != PL_NONE) {
 #pragma unroll
-            for (int k = 0; k < E; ++k) pl_xor16(&wv[4 * k], bb + e * E + 16 * k);
+            for (int k = 0; k < E; ++k) pl_base16<E, OP, false>(&wv[4 * k], bb + e * E + 16 * k);
         }
         pl_deinterleave<E>(wv, o);
 #pragma unroll
         for (int p = 0; p < E; ++p) __builtin_memcpy(pb + pl_start(n, p, E) + e, o[p], 16);
     }
-    const u64 nHead = (h.eb - h.e0) * E, nTail = (h.e1 - h.et) * E;
-    for (u64 j = tid; j < nHead + nTail; j += PL_THREADS) {
-        const u64 k = j < nHead ? h.e0 * E + j : h.et * E + (j - nHead);
-        if (k < n) {
-            u8 v = sb[k];
-            if constexpr (X) v ^= bb[k];
-            pb[pl_start(n, (u32)(k % E), E) + k / E] = v;
+    if constexpr (OP == PL_SUB) {                                  // (an element per thread, as in k_planes_split)
+        const u64 nHead = h.eb - h.e0, nTail = h.e1 - h.et;
+        for (u64 j = tid; j < nHead + nTail; j += PL_THREADS) pl_sub_elem_split<E>(pb, sb, bb, n, j < nHead ? h.e0 + j : h.et + (j - nHead));
+    } else {
+        const u64 nHead = (h.eb - h.e0) * E, nTail = (h.e1 - h.et) * E;
+        for (u64 j = tid; j < nHead + nTail; j += PL_THREADS) {
+            const u64 k = j < nHead ? h.e0 * E + j : h.et * E + (j - nHead);
+            if (k < n) {
+                u8 v = sb[k];
+                if constexpr (OP == PL_XOR) v ^= bb[k];
+                pb[pl_start(n, (u32)(k % E), E) + k / E] = v;
+            }
         }
     }
 }
@@ -211,7 +216,7 @@ inline PpLayout pp_layout(size_t nTensors, unsigned E, size_t nSeg)
     return L;
 }
 
-hipError_t launch_split_window(u8* stage, u64* planeOff, size_t* stageRes, const u8* src, const u8* base, const u64* srcOff, const u64* windows, const u64* stageOff,
+hipError_t launch_split_window(u8* stage, u64* planeOff, size_t* stageRes, const u8* src, const u8* base, unsigned deltaOp, const u64* srcOff, const u64* windows, const u64* stageOff,
                                size_t nTensors, unsigned E, unsigned segLog, u64 capacity, u64 stageCapacity, hipStream_t s)
 {
     hipLaunchKernelGGL(k_planes_stage_offsets, dim3(grid_for(nTensors + 1)), dim3(PL_THREADS), 0, s, planeOff, stageRes, srcOff, windows, stageOff, nTensors, (u32)E,
@@ -220,8 +225,10 @@ hipError_t launch_split_window(u8* stage, u64* planeOff, size_t* stageRes, const
     const dim3 g(tile_grid(stageCapacity, nTensors)), b(PL_THREADS);
     pl_for_elem(E, [&](auto eb) {
         constexpr int EB = decltype(eb)::value;
-        if (base) hipLaunchKernelGGL((k_planes_split_window<EB, true>), g, b, 0, s, stage, src, base, srcOff, windows, stageOff, nTensors, (u32)segLog, capacity, stageCapacity);
-        else hipLaunchKernelGGL((k_planes_split_window<EB, false>), g, b, 0, s, stage, src, base, srcOff, windows, stageOff, nTensors, (u32)segLog, capacity, stageCapacity);
+        const int op = pl_op(base, deltaOp);
+        if (op == PL_SUB) hipLaunchKernelGGL((k_planes_split_window<EB, PL_SUB>), g, b, 0, s, stage, src, base, srcOff, windows, stageOff, nTensors, (u32)segLog, capacity, stageCapacity);
+        else if (op == PL_XOR) hipLaunchKernelGGL((k_planes_split_window<EB, PL_XOR>), g, b, 0, s, stage, src, base, srcOff, windows, stageOff, nTensors, (u32)segLog, capacity, stageCapacity);
+        else hipLaunchKernelGGL((k_planes_split_window<EB, PL_NONE>), g, b, 0, s, stage, src, base, srcOff, windows, stageOff, nTensors, (u32)segLog, capacity, stageCapacity);
     });
     return hipGetLastError();
 }
@@ -247,16 +254,23 @@ hipError_t launch_splice(u8* out, u64 outCapacity, u64* outOff, size_t* outRes, 
 }
 }   // namespace
 
+extern "C" int FSEHIP_planes_split_window_op_dbatch(void* d_stage, uint64_t* d_stagePlaneOffsets, size_t* d_stageResults, const void* d_src, const void* d_base,
+                                                    unsigned deltaOp, const uint64_t* d_srcOffsets, const uint64_t* d_windows, const uint64_t* d_stageOffsets,
+                                                    size_t nTensors, unsigned elemBytes, unsigned segLog, uint64_t capacity, uint64_t stageCapacity, void* stream)
+{
+    if (bad_op(deltaOp) || bad_elem(elemBytes) || bad_seg(segLog, 0) || !d_stagePlaneOffsets || !d_stageResults || !d_srcOffsets || !d_windows || !d_stageOffsets ||
+        (stageCapacity && (!d_stage || !d_src)))
+        return (int)hipErrorInvalidValue;
+    if (bad_tensors(nTensors, elemBytes) || bad_grid(stageCapacity, nTensors)) return (int)hipErrorInvalidValue;
+    return (int)launch_split_window((u8*)d_stage, (u64*)d_stagePlaneOffsets, d_stageResults, (const u8*)d_src, (const u8*)d_base, deltaOp, (const u64*)d_srcOffsets,
+                                    (const u64*)d_windows, (const u64*)d_stageOffsets, nTensors, elemBytes, segLog, capacity, stageCapacity, (hipStream_t)stream);
+}
 extern "C" int FSEHIP_planes_split_window_dbatch(void* d_stage, uint64_t* d_stagePlaneOffsets, size_t* d_stageResults, const void* d_src, const void* d_base,
                                                  const uint64_t* d_srcOffsets, const uint64_t* d_windows, const uint64_t* d_stageOffsets, size_t nTensors,
                                                  unsigned elemBytes, unsigned segLog, uint64_t capacity, uint64_t stageCapacity, void* stream)
 {
-    if (bad_elem(elemBytes) || bad_seg(segLog, 0) || !d_stagePlaneOffsets || !d_stageResults || !d_srcOffsets || !d_windows || !d_stageOffsets ||
-        (stageCapacity && (!d_stage || !d_src)))
-        return (int)hipErrorInvalidValue;
-    if (bad_tensors(nTensors, elemBytes) || bad_grid(stageCapacity, nTensors)) return (int)hipErrorInvalidValue;
-    return (int)launch_split_window((u8*)d_stage, (u64*)d_stagePlaneOffsets, d_stageResults, (const u8*)d_src, (const u8*)d_base, (const u64*)d_srcOffsets,
-                                    (const u64*)d_windows, (const u64*)d_stageOffsets, nTensors, elemBytes, segLog, capacity, stageCapacity, (hipStream_t)stream);
+    return FSEHIP_planes_split_window_op_dbatch(d_stage, d_stagePlaneOffsets, d_stageResults, d_src, d_base, FSEHIP_DELTA_XOR, d_srcOffsets, d_windows, d_stageOffsets,
+                                                nTensors, elemBytes, segLog, capacity, stageCapacity, stream);
 }
 
 extern "C" size_t FSEHIP_planes_spliceScratchBound(size_t nTensors, unsigned elemBytes, size_t nSegments)
@@ -309,6 +323,24 @@ extern "C" int FSEHIP_tensor_patch_window_dbatch(void* d_out, uint64_t outCapaci
                                                  uint64_t newCapacity, uint64_t* d_newOffsets, size_t* d_newResults, void* d_scratch, size_t scratchBytes,
                                                  void* d_workspace, size_t workspaceBytes, void* stream)
 {
+    return FSEHIP_tensor_patch_window_op_dbatch(d_out, outCapacity, d_outOffsets, d_outResults, d_outCodecs, d_tensorResults, d_frames, framesCapacity, d_frameOffsets,
+                                                d_frameResults, d_codecs, d_src, d_base, FSEHIP_DELTA_XOR, d_srcOffsets, capacity, d_windows, nTensors, elemBytes, d_segFirst,
+                                                nSegments, segLog, d_selFirst, nSelected, d_stageOffsets, stageCapacity, maxTotalBlocks, blockSizeId, codec, d_newCodecs,
+                                                policy, tolerancePermille, slotAlignLog, d_stage, d_stagePlaneOffsets, d_stageSegOffsets, d_stageResults, d_newFrames,
+                                                newCapacity, d_newOffsets, d_newResults, d_scratch, scratchBytes, d_workspace, workspaceBytes, stream);
+}
+extern "C" int FSEHIP_tensor_patch_window_op_dbatch(void* d_out, uint64_t outCapacity, uint64_t* d_outOffsets, size_t* d_outResults, uint8_t* d_outCodecs,
+                                                    size_t* d_tensorResults, const void* d_frames, uint64_t framesCapacity, const uint64_t* d_frameOffsets,
+                                                    const size_t* d_frameResults, const uint8_t* d_codecs, const void* d_src, const void* d_base, unsigned deltaOp,
+                                                    const uint64_t* d_srcOffsets, uint64_t capacity, const uint64_t* d_windows, size_t nTensors, unsigned elemBytes,
+                                                    const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, const uint64_t* d_selFirst, size_t nSelected,
+                                                    const uint64_t* d_stageOffsets, uint64_t stageCapacity, size_t maxTotalBlocks, unsigned blockSizeId, int codec,
+                                                    uint8_t* d_newCodecs, int policy, unsigned tolerancePermille, unsigned slotAlignLog, void* d_stage,
+                                                    uint64_t* d_stagePlaneOffsets, uint64_t* d_stageSegOffsets, size_t* d_stageResults, void* d_newFrames,
+                                                    uint64_t newCapacity, uint64_t* d_newOffsets, size_t* d_newResults, void* d_scratch, size_t scratchBytes,
+                                                    void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    if (bad_op(deltaOp)) return (int)hipErrorInvalidValue;
     if (bad_splice(d_out, outCapacity, d_outOffsets, d_outResults, d_outCodecs, d_tensorResults, d_frames, d_frameOffsets, d_frameResults, d_codecs, d_newCodecs,
                    d_srcOffsets, d_windows, nTensors, elemBytes, d_segFirst, nSegments, segLog, d_selFirst, nSelected, d_scratch, scratchBytes))
         return (int)hipErrorInvalidValue;
@@ -318,7 +350,7 @@ extern "C" int FSEHIP_tensor_patch_window_dbatch(void* d_out, uint64_t outCapaci
     const PlWriter wr = { maxTotalBlocks, blockSizeId, codec, d_newCodecs, policy, tolerancePermille, slotAlignLog, d_workspace, workspaceBytes };
     if (bad_seg(segLog, blockSizeId) || bad_grid(stageCapacity, nTensors) || bad_writer(wr, nSelected)) return (int)hipErrorInvalidValue;
     const hipStream_t s = (hipStream_t)stream;
-    hipError_t e = launch_split_window((u8*)d_stage, (u64*)d_stagePlaneOffsets, d_stageResults, (const u8*)d_src, (const u8*)d_base, (const u64*)d_srcOffsets,
+    hipError_t e = launch_split_window((u8*)d_stage, (u64*)d_stagePlaneOffsets, d_stageResults, (const u8*)d_src, (const u8*)d_base, deltaOp, (const u64*)d_srcOffsets,
                                        (const u64*)d_windows, (const u64*)d_stageOffsets, nTensors, elemBytes, segLog, capacity, stageCapacity, s);
     if (e != hipSuccess) return (int)e;
     if (nSelected) {                                             // (nothing selected: the splice alone, a copy of the object)

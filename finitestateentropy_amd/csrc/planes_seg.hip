@@ -101,28 +101,49 @@ extern "C" int FSEHIP_planes_fold_segments_dbatch(uint64_t* d_planeOffsets, size
                             (hipStream_t)stream);
 }
 
+extern "C" int FSEHIP_tensor_compress_seg_op_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
+                                                    const void* d_src, const void* d_base, unsigned deltaOp, const uint64_t* d_srcOffsets, size_t nTensors,
+                                                    unsigned elemBytes, uint64_t capacity, const uint64_t* d_segFirst, size_t nSegments, unsigned segLog,
+                                                    size_t maxTotalBlocks, unsigned blockSizeId, int codec, uint8_t* d_codecs, int policy, unsigned tolerancePermille,
+                                                    unsigned slotAlignLog, void* d_planes, uint64_t* d_planeOffsets, uint64_t* d_segOffsets, void* d_workspace,
+                                                    size_t workspaceBytes, void* stream)
+{
+    if (bad_elem(elemBytes) || !d_frameOffsets || !d_frameResults || !d_tensorResults || !d_src || !d_srcOffsets || !d_segFirst || !d_planeOffsets || !d_segOffsets ||
+        ((elemBytes > 1 || d_base) && !d_planes))
+        return (int)hipErrorInvalidValue;
+    return planes_compress(d_dst, dstCapacity, d_frameOffsets, d_frameResults, d_tensorResults, d_src, d_base, deltaOp, d_srcOffsets, nTensors, elemBytes, capacity,
+                           d_segFirst, nSegments, segLog, d_planes, d_planeOffsets, d_segOffsets,
+                           PlWriter{ maxTotalBlocks, blockSizeId, codec, d_codecs, policy, tolerancePermille, slotAlignLog, d_workspace, workspaceBytes }, stream);
+}
 extern "C" int FSEHIP_tensor_compress_seg_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
                                                  const void* d_src, const void* d_base, const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes,
                                                  uint64_t capacity, const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, size_t maxTotalBlocks,
                                                  unsigned blockSizeId, int codec, uint8_t* d_codecs, int policy, unsigned tolerancePermille, unsigned slotAlignLog,
                                                  void* d_planes, uint64_t* d_planeOffsets, uint64_t* d_segOffsets, void* d_workspace, size_t workspaceBytes, void* stream)
 {
-    if (bad_elem(elemBytes) || !d_frameOffsets || !d_frameResults || !d_tensorResults || !d_src || !d_srcOffsets || !d_segFirst || !d_planeOffsets || !d_segOffsets ||
-        ((elemBytes > 1 || d_base) && !d_planes))
-        return (int)hipErrorInvalidValue;
-    return planes_compress(d_dst, dstCapacity, d_frameOffsets, d_frameResults, d_tensorResults, d_src, d_base, d_srcOffsets, nTensors, elemBytes, capacity, d_segFirst,
-                           nSegments, segLog, d_planes, d_planeOffsets, d_segOffsets,
-                           PlWriter{ maxTotalBlocks, blockSizeId, codec, d_codecs, policy, tolerancePermille, slotAlignLog, d_workspace, workspaceBytes }, stream);
+    return FSEHIP_tensor_compress_seg_op_dbatch(d_dst, dstCapacity, d_frameOffsets, d_frameResults, d_tensorResults, d_src, d_base, FSEHIP_DELTA_XOR, d_srcOffsets, nTensors,
+                                                elemBytes, capacity, d_segFirst, nSegments, segLog, maxTotalBlocks, blockSizeId, codec, d_codecs, policy, tolerancePermille,
+                                                slotAlignLog, d_planes, d_planeOffsets, d_segOffsets, d_workspace, workspaceBytes, stream);
 }
 
-// the argument checks of all three steps in front of the first launch
 extern "C" int FSEHIP_tensor_decompress_seg_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base, size_t* d_results,
                                                    const void* d_frames, const uint64_t* d_frameOffsets, size_t nTensors, unsigned elemBytes,
                                                    const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, size_t maxTotalBlocks,
                                                    void* d_planes, uint64_t planesCapacity, uint64_t* d_segOffsets, size_t* d_segResults,
                                                    uint64_t* d_planeOffsets, size_t* d_planeSizes, void* d_workspace, size_t workspaceBytes, void* stream)
 {
-    if (bad_elem(elemBytes) || !d_dst || !d_dstOffsets || !d_results || !d_frames || !d_frameOffsets || !d_segFirst || !d_planes || !d_segOffsets || !d_segResults ||
+    return FSEHIP_tensor_decompress_seg_op_dbatch(d_dst, d_dstOffsets, dstCapacity, d_base, FSEHIP_DELTA_XOR, d_results, d_frames, d_frameOffsets, nTensors, elemBytes,
+                                                  d_segFirst, nSegments, segLog, maxTotalBlocks, d_planes, planesCapacity, d_segOffsets, d_segResults, d_planeOffsets,
+                                                  d_planeSizes, d_workspace, workspaceBytes, stream);
+}
+// the argument checks of all three steps in front of the first launch
+extern "C" int FSEHIP_tensor_decompress_seg_op_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base, unsigned deltaOp,
+                                                      size_t* d_results, const void* d_frames, const uint64_t* d_frameOffsets, size_t nTensors, unsigned elemBytes,
+                                                      const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, size_t maxTotalBlocks,
+                                                      void* d_planes, uint64_t planesCapacity, uint64_t* d_segOffsets, size_t* d_segResults,
+                                                      uint64_t* d_planeOffsets, size_t* d_planeSizes, void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    if (bad_op(deltaOp) || bad_elem(elemBytes) || !d_dst || !d_dstOffsets || !d_results || !d_frames || !d_frameOffsets || !d_segFirst || !d_planes || !d_segOffsets || !d_segResults ||
         !d_planeOffsets || !d_planeSizes)
         return (int)hipErrorInvalidValue;
     if (bad_seg(segLog, 0) || bad_counts(nTensors, elemBytes, nSegments) || bad_grid(dstCapacity, nTensors) || bad_reader(d_workspace, workspaceBytes, nSegments, maxTotalBlocks))
@@ -135,5 +156,5 @@ extern "C" int FSEHIP_tensor_decompress_seg_dbatch(void* d_dst, const uint64_t* 
                                      segLog, s);
     if (e != hipSuccess) return (int)e;
     return (int)launch_planes_merge((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeSizes, (const u8*)d_base,
-                                    nTensors, elemBytes, dstCapacity, s);
+                                    deltaOp, nTensors, elemBytes, dstCapacity, s);
 }

@@ -129,7 +129,6 @@ extern "C" int FSEHIP_planes_fold_window_dbatch(uint64_t* d_planeOffsets, size_t
                                    (const u64*)d_segFirst, (const u64*)d_selFirst, nTensors, elemBytes, nSelected, segLog, (hipStream_t)stream);
 }
 
-// the argument checks of all four steps in front of the first launch
 extern "C" int FSEHIP_tensor_decompress_window_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base, size_t* d_results,
                                                       const void* d_frames, const uint64_t* d_frameOffsets, const uint64_t* d_srcOffsets, const uint64_t* d_windows,
                                                       size_t nTensors, unsigned elemBytes, const uint64_t* d_segFirst, size_t nSegments, unsigned segLog,
@@ -137,7 +136,19 @@ extern "C" int FSEHIP_tensor_decompress_window_dbatch(void* d_dst, const uint64_
                                                       uint64_t* d_selFrameOffsets, uint64_t* d_selOffsets, size_t* d_selResults, uint64_t* d_planeOffsets,
                                                       size_t* d_planeSizes, void* d_workspace, size_t workspaceBytes, void* stream)
 {
-    if (bad_elem(elemBytes) || !d_dst || !d_dstOffsets || !d_results || !d_frames || !d_frameOffsets || !d_srcOffsets || !d_windows || !d_segFirst || !d_selFirst ||
+    return FSEHIP_tensor_decompress_window_op_dbatch(d_dst, d_dstOffsets, dstCapacity, d_base, FSEHIP_DELTA_XOR, d_results, d_frames, d_frameOffsets, d_srcOffsets, d_windows,
+                                                     nTensors, elemBytes, d_segFirst, nSegments, segLog, d_selFirst, nSelected, maxTotalBlocks, d_planes, planesCapacity,
+                                                     d_selFrameOffsets, d_selOffsets, d_selResults, d_planeOffsets, d_planeSizes, d_workspace, workspaceBytes, stream);
+}
+// the argument checks of all four steps in front of the first launch
+extern "C" int FSEHIP_tensor_decompress_window_op_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base, unsigned deltaOp,
+                                                         size_t* d_results, const void* d_frames, const uint64_t* d_frameOffsets, const uint64_t* d_srcOffsets,
+                                                         const uint64_t* d_windows, size_t nTensors, unsigned elemBytes, const uint64_t* d_segFirst, size_t nSegments,
+                                                         unsigned segLog, const uint64_t* d_selFirst, size_t nSelected, size_t maxTotalBlocks, void* d_planes,
+                                                         uint64_t planesCapacity, uint64_t* d_selFrameOffsets, uint64_t* d_selOffsets, size_t* d_selResults,
+                                                         uint64_t* d_planeOffsets, size_t* d_planeSizes, void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    if (bad_op(deltaOp) || bad_elem(elemBytes) || !d_dst || !d_dstOffsets || !d_results || !d_frames || !d_frameOffsets || !d_srcOffsets || !d_windows || !d_segFirst || !d_selFirst ||
         !d_planes || !d_selFrameOffsets || !d_selOffsets || !d_selResults || !d_planeOffsets || !d_planeSizes)
         return (int)hipErrorInvalidValue;
     if (bad_seg(segLog, 0) || bad_counts(nTensors, elemBytes, nSelected) || nSegments >= ((size_t)1 << 31) || nSelected > nSegments || bad_grid(dstCapacity, nTensors))
@@ -154,5 +165,5 @@ extern "C" int FSEHIP_tensor_decompress_window_dbatch(void* d_dst, const uint64_
                            (const u64*)d_segFirst, (const u64*)d_selFirst, nTensors, elemBytes, nSelected, segLog, s);
     if (e != hipSuccess) return (int)e;
     return (int)launch_planes_merge((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeSizes, (const u8*)d_base,
-                                    nTensors, elemBytes, dstCapacity, s);
+                                    deltaOp, nTensors, elemBytes, dstCapacity, s);
 }

@@ -2,11 +2,12 @@
 _decompress_delta_dbatch) next to the plain byte-plane calls, on a bf16 weight update generated on the device -- the base is N(0, 0.02), the
 new tensors are base + N(0, 2e-5) added in float32, both cut to bf16 -- at 1024 tensors of 1 MiB, the workload of planebench.py:
   (a) a device-to-device copy of the same bytes (dst.copy_(src))
-  (b) the plain split and merge, then the XOR split, the XOR merge into a destination of its own and the XOR merge in place (dst == base);
-      "vs_plain" = the XOR kernel's GB/s over the plain kernel's of this run, "bar" = whether that reaches 0.6 (3 n bytes of traffic instead
-      of 2 n, less a tenth for the third stream)
+  (b) the plain split and merge, then the XOR split, the XOR merge into a destination of its own and the XOR merge in place (dst == base),
+      then the same three with SUB (zigzag(new - base), delta_op 1); "vs_plain" = the delta kernel's GB/s over the plain kernel's of this
+      run, "bar" = whether that reaches 0.6 (3 n bytes of traffic instead of 2 n, less a tenth for the third stream), "sub_vs_xor" = the SUB
+      kernel's GB/s over the XOR kernel's
   (c) per codec: tensor_compress / tensor_decompress of the new tensors, then the delta composites against the base (separate destination and
-      in place), with the frames' share of the bytes
+      in place) with XOR and with SUB, with the frames' share of the bytes ("sub_over_xor": the SUB frames' bytes over the XOR frames')
 Device events around the calls, repeated until the timed region is at least MIN_MS long, after one warm-up call of the same shape.  GB/s =
 content bytes (the new tensors' bytes) / time.  Prints one JSON line per figure.
 Usage: deltabench.py [--tensors 1024] [--tensor-kib 1024] [--block-size-id 5]"""
@@ -76,21 +77,38 @@ def against(what, gbps, plain):
     return dict(vs_plain=round(gbps / plain, 3), bar="%s %.1f of the plain %s" % ("meets" if gbps >= BAR * plain else "MISSES", BAR, what))
 
 
-ms = timed(lambda: hip.planes_split_xor_dbatch(src, base, soff, E, planes=planes, plane_offsets=poff, results=tres))
-report("planes split XOR base", "-", total, ms, **against("split", total / ms / 1e6, split))
-x = src[:tbytes] ^ base[:tbytes]
-assert bool((tres == tbytes).all()) and torch.equal(planes[:tbytes // 2], x[::2]) and torch.equal(planes[tbytes // 2:tbytes], x[1::2])
-other.zero_()
-ms = timed(lambda: hip.planes_merge_xor_dbatch(planes, poff, psz, base, soff, E, dst=other, results=mres))
-report("planes merge XOR base, separate dst", "-", total, ms, **against("merge", total / ms / 1e6, merge))
-assert bool((mres == tbytes).all()) and torch.equal(other, src)
-# in place: the buffer is the base before a call and the new tensors after it -- and the base again after the next one (XOR twice), so every
-# timed call does the same work; checked on one call over a fresh copy of the base
-resident = base.clone()
-hip.planes_merge_xor_dbatch(planes, poff, psz, resident, soff, E, dst=resident, results=mres)
-assert bool((mres == tbytes).all()) and torch.equal(resident, src)
-ms = timed(lambda: hip.planes_merge_xor_dbatch(planes, poff, psz, resident, soff, E, dst=resident, results=mres))
-report("planes merge XOR base, in place (dst == base)", "-", total, ms, **against("merge", total / ms / 1e6, merge))
+def zigzag_sub(t, b):
+    """zigzag(t - b) of the bf16 elements' bit patterns, with torch: what the SUB split's planes are the planes of"""
+    d = t.view(torch.int16) - b.view(torch.int16)
+    return ((d << 1) ^ (d >> 15)).view(torch.uint8)
+
+
+# XOR, then SUB (zigzag(new - base) on the elements' bit patterns): the same data, the same buffers, the same run; "sub_vs_xor" = the SUB
+# kernel's GB/s over the XOR kernel's
+kernel_rate = {}
+for op, tag in ((0, "XOR"), (1, "SUB")):
+    def versus(what, row, gbps, plain):
+        more = against(what, gbps, plain)
+        if op:
+            more["sub_vs_xor"] = round(gbps / kernel_rate[row], 3)
+        else:
+            kernel_rate[row] = gbps
+        return more
+    ms = timed(lambda: hip.planes_split_xor_dbatch(src, base, soff, E, planes=planes, plane_offsets=poff, results=tres, delta_op=op))
+    report("planes split %s base" % tag, "-", total, ms, **versus("split", "split", total / ms / 1e6, split))
+    x = zigzag_sub(src[:tbytes], base[:tbytes]) if op else src[:tbytes] ^ base[:tbytes]
+    assert bool((tres == tbytes).all()) and torch.equal(planes[:tbytes // 2], x[::2]) and torch.equal(planes[tbytes // 2:tbytes], x[1::2])
+    other.zero_()
+    ms = timed(lambda: hip.planes_merge_xor_dbatch(planes, poff, psz, base, soff, E, dst=other, results=mres, delta_op=op))
+    report("planes merge %s base, separate dst" % tag, "-", total, ms, **versus("merge", "merge", total / ms / 1e6, merge))
+    assert bool((mres == tbytes).all()) and torch.equal(other, src)
+    # in place: the buffer is the base before a call and the new tensors after it -- and the base again after the next one (XOR twice; with SUB
+    # it moves on by the same difference each time), so every timed call does the same work; checked on one call over a fresh copy of the base
+    resident = base.clone()
+    hip.planes_merge_xor_dbatch(planes, poff, psz, resident, soff, E, dst=resident, results=mres, delta_op=op)
+    assert bool((mres == tbytes).all()) and torch.equal(resident, src)
+    ms = timed(lambda: hip.planes_merge_xor_dbatch(planes, poff, psz, resident, soff, E, dst=resident, results=mres, delta_op=op))
+    report("planes merge %s base, in place (dst == base)" % tag, "-", total, ms, **versus("merge", "merge in place", total / ms / 1e6, merge))
 
 blocks = hip.planes_block_bound(total, n, E, BSID)
 L = hip.lib
@@ -111,24 +129,38 @@ for codec, name in ((0, "fse"), (1, "huf")):
                                                         workspace=dws, results=mres))
     report("tensor_decompress of the new tensors", name, total, comp_r)
     assert bool((mres == tbytes).all()) and torch.equal(other, src)
-    # the delta composites against the base
-    delta_w = timed(lambda: hip.tensor_compress_delta_dbatch(src, base, soff, E, BSID, codec, dst=frames, max_total_blocks=blocks, frame_offsets=foff, frame_results=fres,
-                                                             tensor_results=tres, planes=planes, plane_offsets=poff, workspace=kws))
-    delta_bytes = int(foff[n * E].item())
-    assert bool((fres > 0).all()) and bool((tres == tbytes).all())
-    report("tensor_compress_delta (new XOR base)", name, total, delta_w, frame_bytes=delta_bytes, ratio=round(delta_bytes / total, 4),
-           delta_over_plain=round(delta_bytes / plain_bytes, 4), extra_ms=round(delta_w - comp_w, 3))
-    other.zero_()
-    delta_r = timed(lambda: hip.tensor_decompress_delta_dbatch(frames, foff, base, soff, E, dst=other, max_total_blocks=blocks, planes=planes, plane_offsets=poff2,
-                                                               plane_results=pres, workspace=dws, results=mres))
-    report("tensor_decompress_delta, separate dst", name, total, delta_r, extra_ms=round(delta_r - comp_r, 3))
-    assert bool((mres == tbytes).all()) and torch.equal(other, src)
-    resident.copy_(base)
-    hip.tensor_decompress_delta_dbatch(frames, foff, resident, soff, E, dst=resident, max_total_blocks=blocks, planes=planes, plane_offsets=poff2, plane_results=pres,
-                                       workspace=dws, results=mres)
-    assert bool((mres == tbytes).all()) and torch.equal(resident, src)
-    delta_i = timed(lambda: hip.tensor_decompress_delta_dbatch(frames, foff, resident, soff, E, dst=resident, max_total_blocks=blocks, planes=planes, plane_offsets=poff2,
-                                                               plane_results=pres, workspace=dws, results=mres))
-    report("tensor_decompress_delta, in place (dst == base)", name, total, delta_i, extra_ms=round(delta_i - comp_r, 3))
+    # the delta composites against the base: XOR, then SUB; "sub_vs_xor" = the SUB call's GB/s over the XOR call's, "sub_over_xor" = its frame bytes
+    # over the XOR frames'
+    xor = {}
+    for op, tag, form in ((0, "XOR", "new XOR base"), (1, "SUB", "zigzag(new - base)")):
+        def versus(row, ms, **more):
+            if op:
+                more["sub_vs_xor"] = round(xor[row] / ms, 3)
+            else:
+                xor[row] = ms
+            return more
+        delta_w = timed(lambda: hip.tensor_compress_delta_dbatch(src, base, soff, E, BSID, codec, dst=frames, max_total_blocks=blocks, frame_offsets=foff,
+                                                                 frame_results=fres, tensor_results=tres, planes=planes, plane_offsets=poff, workspace=kws, delta_op=op))
+        delta_bytes = int(foff[n * E].item())
+        assert bool((fres > 0).all()) and bool((tres == tbytes).all())
+        more = versus("compress", delta_w)
+        if op:
+            more["sub_over_xor"] = round(delta_bytes / xor["bytes"], 4)
+        else:
+            xor["bytes"] = delta_bytes
+        report("tensor_compress_delta %s (%s)" % (tag, form), name, total, delta_w, frame_bytes=delta_bytes, ratio=round(delta_bytes / total, 4),
+               delta_over_plain=round(delta_bytes / plain_bytes, 4), extra_ms=round(delta_w - comp_w, 3), **more)
+        other.zero_()
+        delta_r = timed(lambda: hip.tensor_decompress_delta_dbatch(frames, foff, base, soff, E, dst=other, max_total_blocks=blocks, planes=planes, plane_offsets=poff2,
+                                                                   plane_results=pres, workspace=dws, results=mres, delta_op=op))
+        report("tensor_decompress_delta %s, separate dst" % tag, name, total, delta_r, extra_ms=round(delta_r - comp_r, 3), **versus("decompress", delta_r))
+        assert bool((mres == tbytes).all()) and torch.equal(other, src)
+        resident.copy_(base)
+        hip.tensor_decompress_delta_dbatch(frames, foff, resident, soff, E, dst=resident, max_total_blocks=blocks, planes=planes, plane_offsets=poff2, plane_results=pres,
+                                           workspace=dws, results=mres, delta_op=op)
+        assert bool((mres == tbytes).all()) and torch.equal(resident, src)
+        delta_i = timed(lambda: hip.tensor_decompress_delta_dbatch(frames, foff, resident, soff, E, dst=resident, max_total_blocks=blocks, planes=planes,
+                                                                   plane_offsets=poff2, plane_results=pres, workspace=dws, results=mres, delta_op=op))
+        report("tensor_decompress_delta %s, in place (dst == base)" % tag, name, total, delta_i, extra_ms=round(delta_i - comp_r, 3), **versus("in place", delta_i))
     del kws, dws, frames
     torch.cuda.empty_cache()
