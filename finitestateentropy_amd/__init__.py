@@ -8,12 +8,13 @@ library has not been built (``python -c 'import __graft_entry__ as g; g.build()'
 """
 from ._lib import build_library, library_path  # noqa: F401
 
-__all__ = ["build_library", "library_path", "DeltaBase"]
+__all__ = ["build_library", "library_path", "DeltaBase", "SparsePlanes"]
 
 
 def __getattr__(name):
-    # DeltaBase (the `base` of compress_tensors with its op, "sub" or "xor") lives in .api, which needs torch and the built library: on first use
-    if name == "DeltaBase":
-        from .api import DeltaBase
-        return DeltaBase
+    # DeltaBase (the `base` of compress_tensors with its op, "sub" or "xor") and SparsePlanes (its `codec` with the sparse threshold) live in
+    # .api, which needs torch and the built library: on first use
+    if name in ("DeltaBase", "SparsePlanes"):
+        from . import api
+        return getattr(api, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

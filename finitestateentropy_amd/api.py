@@ -43,6 +43,30 @@ class AutoCodec:
         return hash(("AutoCodec", self.tolerance_permille))
 
 
+class SparsePlanes:
+    """`codec` of compress_tensors and compress_tensors_segmented: the planes (segments) go to the frame writers as SPARSE contents -- a zero
+    mask of one bit per byte and the non-zero bytes -- wherever at most permille / 1000 of a plane's bytes are non-zero and that form is
+    shorter (include/fsehip.h "sparse planes").  `codec` is what codes the contents: 0 (FSE), 1 (Huff0) or an AutoCodec.  The reason is the
+    sign / exponent plane of a tensor delta, almost all zeros: as a sparse content its Huff0 frame shrinks from 33 KB to under 5 KB per
+    256 KB, and FSE has a fraction of the symbols to decode.  The object written carries `sparse_permille`; decompress_tensors reads it."""
+
+    def __init__(self, codec=0, permille=500):
+        if not isinstance(codec, AutoCodec) and (isinstance(codec, bool) or codec not in (0, 1)):
+            raise ValueError("SparsePlanes: codec %r, 0 (FSE), 1 (Huff0) or an AutoCodec is needed" % (codec,))
+        if not isinstance(permille, numbers.Integral) or isinstance(permille, bool) or not 0 <= permille <= 1000:
+            raise ValueError("SparsePlanes: permille %r, 0 .. 1000 is needed" % (permille,))
+        self.codec, self.permille = codec if isinstance(codec, AutoCodec) else int(codec), int(permille)
+
+    def __repr__(self):
+        return "SparsePlanes(%r, %d)" % (self.codec, self.permille)
+
+    def __eq__(self, other):
+        return isinstance(other, SparsePlanes) and other.codec == self.codec and other.permille == self.permille
+
+    def __hash__(self):
+        return hash(("SparsePlanes", self.codec, self.permille))
+
+
 DELTA_OPS = {"xor": 0, "sub": 1}        # FSEHIP_DELTA_XOR / FSEHIP_DELTA_SUB (include/fsehip.h)
 
 
@@ -1210,9 +1234,12 @@ class CompressedTensors:
     bytes with a frame each; frame_offsets, frame_results and codecs are then per segment and every group carries `seg_first` (numpy uint64,
     the first segment of every plane and the segment count).  `delta_op` ("xor", or "sub" where compress_tensors was given a
     DeltaBase(..., "sub")): what the frames of an object with `delta` set hold -- `tensor XOR base` or zigzag(tensor - base); the reading
-    calls take it from here."""
+    calls take it from here.  `sparse_permille` (None, or the integer of the SparsePlanes the object was written with): the frames hold sparse
+    contents -- `codec` is then that SparsePlanes -- and decompress_tensors reads them as such; windows and patches of such an object are
+    refused."""
     segment_log = None
     delta_op = "xor"
+    sparse_permille = None
 
     def __init__(self, groups, dtypes, shapes, device, codec, block_size_id, delta=False):
         self.groups, self.dtypes, self.shapes, self.device, self.codec, self.block_size_id = groups, dtypes, shapes, device, codec, block_size_id
@@ -1320,16 +1347,17 @@ def _planes_methods():
             raise ValueError("planes holds %d bytes, the capacity is %d" % (planes.numel(), capacity))
         return planes
 
+    def _writer_need(self, n_frames, max_total_blocks, block_size_id, codec, mixed, choose):
+        if mixed:
+            return self.frame_mixed_workspace_bound(n_frames, max_total_blocks, min(block_size_id, 6), choose)
+        self.lib.FSEHIP_frame_compress_packed_dbatch_workspaceSize.restype = SZ
+        return int(self.lib.FSEHIP_frame_compress_packed_dbatch_workspaceSize(SZ(n_frames), SZ(max_total_blocks), C.c_uint(min(block_size_id, 6)),
+                                                                              C.c_int(codec if codec in (0, 1) else 0)))
+
     def _writer_workspace(self, workspace, n_frames, max_total_blocks, block_size_id, codec, mixed, choose, device):
         if workspace is not None:
             return workspace
-        if mixed:
-            need = self.frame_mixed_workspace_bound(n_frames, max_total_blocks, min(block_size_id, 6), choose)
-        else:
-            self.lib.FSEHIP_frame_compress_packed_dbatch_workspaceSize.restype = SZ
-            need = int(self.lib.FSEHIP_frame_compress_packed_dbatch_workspaceSize(SZ(n_frames), SZ(max_total_blocks), C.c_uint(min(block_size_id, 6)),
-                                                                                  C.c_int(codec if codec in (0, 1) else 0)))
-        return torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+        return torch.empty(max(_writer_need(self, n_frames, max_total_blocks, block_size_id, codec, mixed, choose), 1), dtype=torch.uint8, device=device)
 
     # ---- ... and the merge and decompress wrappers
     def _dst_room(self, dst, capacity, dhost, device):
@@ -1347,11 +1375,14 @@ def _planes_methods():
         planes_capacity = default if planes_capacity is None else int(planes_capacity)
         return torch.empty(max(planes_capacity, 1), dtype=torch.uint8, device=device), planes_capacity
 
+    def _reader_need(self, n_frames, max_total_blocks):
+        self.lib.FSEHIP_frame_decompress_packed_dbatch_workspaceSize.restype = SZ
+        return int(self.lib.FSEHIP_frame_decompress_packed_dbatch_workspaceSize(SZ(n_frames), SZ(max_total_blocks)))
+
     def _reader_workspace(self, workspace, n_frames, max_total_blocks, device):
         if workspace is not None:
             return workspace
-        self.lib.FSEHIP_frame_decompress_packed_dbatch_workspaceSize.restype = SZ
-        return torch.empty(max(int(self.lib.FSEHIP_frame_decompress_packed_dbatch_workspaceSize(SZ(n_frames), SZ(max_total_blocks))), 1), dtype=torch.uint8, device=device)
+        return torch.empty(max(_reader_need(self, n_frames, max_total_blocks), 1), dtype=torch.uint8, device=device)
 
     def planes_split_dbatch(self, src, src_offsets, elem_bytes, capacity=None, planes=None, plane_offsets=None, results=None):
         """-> (planes, plane_offsets, results): tensor i = src[src_offsets[i] : src_offsets[i+1]]; plane p of it (its bytes p, p + E, ..) =
@@ -2181,6 +2212,7 @@ def _planes_methods():
         seg_log = getattr(obj, "segment_log", None)
         if seg_log is None:
             raise ValueError("patch_tensor_windows: the object is not segmented (compress_tensors_segmented writes those)")
+        _not_sparse(obj, "patch_tensor_windows")
         base, op = _read_base(obj, base, "patch_tensor_windows")
         tensors, windows = list(tensors), list(windows)
         if len(tensors) != len(obj.dtypes) or len(windows) != len(obj.dtypes):
@@ -2233,6 +2265,228 @@ def _planes_methods():
 
     for f in (planes_stage_offsets, planes_split_window_dbatch, planes_splice_scratch_bound, planes_splice_dbatch, tensor_patch_window_dbatch, patch_tensor_windows):
         setattr(FseHip, f.__name__, f)
+
+    # ---- sparse planes (csrc/planes_sparse.hip; fsehip.h "sparse planes"): a unit of n bytes as a zero mask of ceil(n / 8) bytes and its
+    # non-zero bytes where that is shorter and the unit sparse enough, ahead of the frame writers and behind the frame reader
+    def _permille(permille):
+        if not isinstance(permille, numbers.Integral) or isinstance(permille, bool) or not 0 <= permille <= 1000:
+            raise ValueError("sparse permille %r: 0 .. 1000" % (permille,))
+        return int(permille)
+
+    def sparse_workspace_bound(self, capacity, n_units):
+        """the workspace of sparse_pack_dbatch / sparse_expand_dbatch for n_units units inside `capacity` bytes.  Host arithmetic: needs no device."""
+        self.lib.FSEHIP_sparse_workspaceBound.restype = SZ
+        r = int(self.lib.FSEHIP_sparse_workspaceBound(C.c_uint64(int(capacity)), SZ(int(n_units))))
+        if r >= (1 << 62):
+            raise ValueError("sparse_workspace_bound(%r, %r)" % (capacity, n_units))
+        return r
+
+    def _sparse_ws(self, workspace, capacity, n_units, rest, device):
+        """the caller's workspace, or one of sparse_workspace_bound + `rest` (the writer's or the reader's need) bytes"""
+        if workspace is not None:
+            return workspace
+        return torch.empty(sparse_workspace_bound(self, capacity, n_units) + max(int(rest), 1), dtype=torch.uint8, device=device)
+
+    def sparse_pack_dbatch(self, units, unit_offsets, permille=500, capacity=None, contents=None, content_offsets=None, workspace=None):
+        """-> (contents, content_offsets): unit u = units[unit_offsets[u] : unit_offsets[u+1]] becomes content u =
+        contents[content_offsets[u] : content_offsets[u+1]] -- its zero mask and its non-zero bytes if at most permille / 1000 of its bytes
+        are non-zero and that is shorter, else the unit itself.  content_offsets (n + 1) are directly the src_offsets of the packed writers.
+        `capacity` (default: units' size) is the size of both buffers; `contents` must not overlap `units`."""
+        self._flat(units, "units")
+        uoff, _ = self._offsets(unit_offsets, units.device, False)
+        n = uoff.numel() - 1
+        capacity = _room(self, units, capacity, "units")
+        g = None
+        if contents is None:
+            contents, g = self._dst(1, capacity, units.device)
+            contents = contents[0]
+        elif _room(self, contents, None, "contents") < capacity:
+            raise ValueError("contents holds %d bytes, the capacity is %d" % (contents.numel(), capacity))
+        coff = _i64(self, content_offsets, n + 1, units.device, "content_offsets")
+        workspace = _sparse_ws(self, workspace, capacity, n, 0, units.device)
+        _check(self.lib.FSEHIP_sparse_pack_dbatch(_ptr(contents), _ptr(coff), _ptr(units), _ptr(uoff), SZ(n), C.c_uint64(capacity), C.c_uint(_permille(permille)),
+                                                  _ptr(workspace), SZ(workspace.numel()), _stream()), "sparse_pack_dbatch")
+        if g is not None:
+            g.check("sparse_pack_dbatch")
+        return contents, coff
+
+    def sparse_expand_dbatch(self, contents, content_offsets, content_results, unit_offsets, units=None, capacity=None, contents_capacity=None, results=None,
+                             workspace=None):
+        """-> (units, results): the inverse.  content u = contents[content_offsets[u] : + content_results[u]] (what frame_decompress_packed_dbatch
+        leaves in dst_offsets / results: negative results are errors and pass through), unit u is rebuilt at units[unit_offsets[u]:], its size
+        EXACTLY unit_offsets[u+1] - unit_offsets[u].  results[u] = that size, the reader's error, or -4 (corruption_detected: a content longer
+        than its unit or shorter than its mask, a popcount that is not the number of values, a set padding bit, a zero among the values);
+        such a unit is not written."""
+        self._flat(contents, "contents")
+        uoff, uhost = self._offsets(unit_offsets, contents.device, units is None)
+        n = uoff.numel() - 1
+        coff = _i64(self, content_offsets, n + 1, contents.device, "content_offsets")
+        cres = _i64(self, content_results, n, contents.device, "content_results")
+        contents_capacity = _room(self, contents, contents_capacity, "contents")
+        units, capacity, g = _dst_room(self, units, capacity, uhost, contents.device)
+        res = _i64(self, results, n, contents.device, "results")
+        workspace = _sparse_ws(self, workspace, capacity, n, 0, contents.device)
+        _check(self.lib.FSEHIP_sparse_expand_dbatch(_ptr(units), _ptr(res), _ptr(uoff), SZ(n), C.c_uint64(capacity), _ptr(contents), C.c_uint64(contents_capacity),
+                                                    _ptr(coff), _ptr(cres), _ptr(workspace), SZ(workspace.numel()), _stream()), "sparse_expand_dbatch")
+        if g is not None:
+            g.check("sparse_expand_dbatch")
+        return units, res
+
+    def _compress_sparse(self, what, src, src_offsets, elem_bytes, permille, segment_log, seg_first, n_segments, base, codec, codecs, block_size_id, capacity, dst,
+                         dst_capacity, max_total_blocks, align_log, frame_offsets, frame_results, tensor_results, planes, plane_offsets, seg_offsets, contents,
+                         content_offsets, workspace, delta_op):
+        E = _elem(elem_bytes)
+        align_log = _align_log(align_log)
+        permille = _permille(permille)
+        seg = segment_log is not None
+        L = _seg_log(segment_log, min(block_size_id, 6)) if seg else 0
+        self._flat(src, "src")
+        soff, shost = self._offsets(src_offsets, src.device, (seg and seg_first is None) or max_total_blocks is None or (dst is None and dst_capacity is None))
+        n = soff.numel() - 1
+        capacity = _room(self, src, capacity, "src")
+        op = _delta_op(delta_op)
+        _base(self, base, src, capacity, "src")
+        if seg:
+            if seg_first is None:
+                seg_first = planes_segment_first(self, np.diff(shost.astype(np.int64)).clip(min=0), E, L)
+            sf, nf = _seg_first(self, seg_first, n_segments, src.device, n * E)
+        else:
+            sf, nf = None, n * E
+        mixed = codecs is not None or isinstance(codec, AutoCodec)
+        choose = mixed and codecs is None
+        codecs, cgu = _codecs(self, codecs, nf, src.device) if mixed else (None, None)
+        max_total_blocks, dst, dst_capacity, g = _frames_room(self, shost, n, E, nf, block_size_id, max_total_blocks, dst, dst_capacity, align_log, src.device)
+        planes = _split_room(self, planes, src, capacity, E > 1 or base is not None)
+        foff = _i64(self, frame_offsets, nf + 1, src.device, "frame_offsets")
+        fres = _i64(self, frame_results, nf, src.device, "frame_results")
+        tres = _i64(self, tensor_results, n, src.device, "tensor_results")
+        poff = _i64(self, plane_offsets, n * E + 1, src.device, "plane_offsets")
+        so = _i64(self, seg_offsets, nf + 1, src.device, "seg_offsets") if seg else None
+        cg = None
+        if contents is None:
+            contents, cg = self._dst(1, capacity, src.device)
+            contents = contents[0]
+        elif _room(self, contents, None, "contents") < capacity:
+            raise ValueError("contents holds %d bytes, the capacity is %d" % (contents.numel(), capacity))
+        coff = _i64(self, content_offsets, nf + 1, src.device, "content_offsets")
+        if workspace is None:
+            workspace = _sparse_ws(self, None, capacity, nf, _writer_need(self, nf, max_total_blocks, block_size_id, codec, mixed, choose), src.device)
+        tol = codec.tolerance_permille if choose and isinstance(codec, AutoCodec) else 0
+        head = (_ptr(dst), C.c_uint64(int(dst_capacity)), _ptr(foff), _ptr(fres), _ptr(tres), _ptr(src), _ptr(base), C.c_uint(op), _ptr(soff), SZ(n), C.c_uint(E),
+                C.c_uint64(capacity))
+        writer = (SZ(max_total_blocks), C.c_uint(block_size_id), C.c_int(0 if mixed else codec),
+                  _ptr((codecs if codecs.numel() else codecs.new_zeros(1)) if mixed else None), C.c_int(CODECS_CHOOSE if choose else CODECS_GIVEN), C.c_uint(tol),
+                  C.c_uint(align_log), C.c_uint(permille), _ptr(planes), _ptr(poff))
+        tail = (_ptr(contents), _ptr(coff), _ptr(workspace), SZ(workspace.numel()), _stream())
+        if seg:
+            _check(self.lib.FSEHIP_tensor_compress_seg_sparse_dbatch(*head, _ptr(sf), SZ(nf), C.c_uint(L), *writer, _ptr(so), *tail), what)
+        else:
+            _check(self.lib.FSEHIP_tensor_compress_sparse_dbatch(*head, *writer, *tail), what)
+        _check_codecs(cgu, nf, what)
+        for x in (g, cg):
+            if x is not None:
+                x.check(what)
+        return dst, foff, fres, tres, (codecs[:nf] if mixed else None)
+
+    def tensor_compress_sparse_dbatch(self, src, src_offsets, elem_bytes, permille=500, base=None, codec=0, codecs=None, block_size_id=5, capacity=None, dst=None,
+                                      dst_capacity=None, max_total_blocks=None, align_log=0, frame_offsets=None, frame_results=None, tensor_results=None, planes=None,
+                                      plane_offsets=None, contents=None, content_offsets=None, workspace=None, delta_op=0):
+        """-> (dst, frame_offsets, frame_results, tensor_results, codecs): the split (against `base` if one is given, by delta_op),
+        sparse_pack_dbatch over the planes at `permille`, then the packed writer over the contents -- frame i*E+p is the .fse frame of the
+        content of plane p of tensor i.  codec / codecs as tensor_compress_seg_dbatch takes them (0 / 1, an AutoCodec, or a codec per frame
+        given).  planes, plane_offsets (n*E+1), contents (`capacity` bytes) and content_offsets (n*E+1) are scratch; the workspace is
+        sparse_workspace_bound(capacity, n*E) followed by the (mixed) writer's.  With everything given the call is launches only."""
+        return _compress_sparse(self, "tensor_compress_sparse_dbatch", src, src_offsets, elem_bytes, permille, None, None, None, base, codec, codecs, block_size_id,
+                                capacity, dst, dst_capacity, max_total_blocks, align_log, frame_offsets, frame_results, tensor_results, planes, plane_offsets, None,
+                                contents, content_offsets, workspace, delta_op)
+
+    def tensor_compress_seg_sparse_dbatch(self, src, src_offsets, elem_bytes, segment_log, permille=500, seg_first=None, n_segments=None, base=None, codec=0,
+                                          codecs=None, block_size_id=5, capacity=None, dst=None, dst_capacity=None, max_total_blocks=None, align_log=0,
+                                          frame_offsets=None, frame_results=None, tensor_results=None, planes=None, plane_offsets=None, seg_offsets=None, contents=None,
+                                          content_offsets=None, workspace=None, delta_op=0):
+        """tensor_compress_seg_dbatch with sparse_pack_dbatch between the segments kernel and the writer: a unit is a SEGMENT of a plane, every
+        segment decides for itself.  contents and content_offsets (n_segments+1) are scratch beside the segmented call's; the workspace is
+        sparse_workspace_bound(capacity, n_segments) followed by the (mixed) writer's for n_segments frames."""
+        return _compress_sparse(self, "tensor_compress_seg_sparse_dbatch", src, src_offsets, elem_bytes, permille, segment_log, seg_first, n_segments, base, codec,
+                                codecs, block_size_id, capacity, dst, dst_capacity, max_total_blocks, align_log, frame_offsets, frame_results, tensor_results, planes,
+                                plane_offsets, seg_offsets, contents, content_offsets, workspace, delta_op)
+
+    def _decompress_sparse(self, what, frames, frame_offsets, dst_offsets, elem_bytes, segment_log, seg_first, n_segments, base, dst, dst_capacity, max_total_blocks,
+                           contents, contents_capacity, content_offsets, content_results, planes, planes_capacity, seg_offsets, seg_results, plane_offsets, plane_sizes,
+                           workspace, results, delta_op):
+        E = _elem(elem_bytes)
+        seg = segment_log is not None
+        L = _seg_log(segment_log) if seg else 0
+        self._flat(frames, "frames")
+        foff, _ = self._offsets(frame_offsets, frames.device, False)
+        doff, dhost = self._offsets(dst_offsets, frames.device, dst is None or planes is None or contents is None or (seg and seg_first is None))
+        n = doff.numel() - 1
+        if seg:
+            if seg_first is None:
+                seg_first = planes_segment_first(self, np.diff(dhost.astype(np.int64)).clip(min=0), E, L)
+            sf, nf = _seg_first(self, seg_first, n_segments, frames.device, n * E)
+        else:
+            sf, nf = None, n * E
+        if foff.numel() != nf + 1:
+            raise ValueError("frame_offsets: one entry per frame (%d) and one more" % nf)
+        if max_total_blocks is None:
+            _, bfirst = self.frame_plan_dbatch(frames, foff, None, 0)
+            max_total_blocks = int(bfirst[nf].item())
+        dst, dst_capacity, g = _dst_room(self, dst, dst_capacity, dhost, frames.device)
+        planes, planes_capacity = _planes_room(self, planes, planes_capacity, None if planes is not None else int(dhost[-1]), frames.device)
+        contents, contents_capacity = _planes_room(self, contents, contents_capacity, None if contents is not None else int(dhost[-1]), frames.device)
+        coff = _i64(self, content_offsets, nf + 1, frames.device, "content_offsets")
+        cres = _i64(self, content_results, nf, frames.device, "content_results")
+        poff = _i64(self, plane_offsets, n * E + 1, frames.device, "plane_offsets")
+        psz = _i64(self, plane_sizes, n * E, frames.device, "plane_sizes")
+        res = _i64(self, results, n, frames.device, "results")
+        if workspace is None:
+            workspace = _sparse_ws(self, None, min(dst_capacity, planes_capacity), nf, _reader_need(self, nf, max_total_blocks), frames.device)
+        op = _delta_op(delta_op)
+        _base(self, base, frames, dst_capacity, "dst")
+        head = (_ptr(dst), _ptr(doff), C.c_uint64(dst_capacity), _ptr(base), C.c_uint(op), _ptr(res), _ptr(frames), _ptr(foff), SZ(n), C.c_uint(E))
+        mid = (SZ(max_total_blocks), _ptr(contents), C.c_uint64(contents_capacity), _ptr(coff), _ptr(cres), _ptr(planes), C.c_uint64(planes_capacity))
+        tail = (_ptr(poff), _ptr(psz), _ptr(workspace), SZ(workspace.numel()), _stream())
+        if seg:
+            so = _i64(self, seg_offsets, nf + 1, frames.device, "seg_offsets")
+            sres = _i64(self, seg_results, nf, frames.device, "seg_results")
+            _check(self.lib.FSEHIP_tensor_decompress_seg_sparse_dbatch(*head, _ptr(sf), SZ(nf), C.c_uint(L), *mid, _ptr(so), _ptr(sres), *tail), what)
+        else:
+            _check(self.lib.FSEHIP_tensor_decompress_sparse_dbatch(*head, *mid, *tail), what)
+        if g is not None:
+            g.check(what)
+        return dst, res
+
+    def tensor_decompress_sparse_dbatch(self, frames, frame_offsets, dst_offsets, elem_bytes, base=None, dst=None, dst_capacity=None, max_total_blocks=None,
+                                        contents=None, contents_capacity=None, content_offsets=None, content_results=None, planes=None, planes_capacity=None,
+                                        plane_offsets=None, plane_results=None, workspace=None, results=None, delta_op=0):
+        """-> (dst, results): the packed reader into `contents`, sparse_expand_dbatch into `planes`, then the merge (against `base` if one is
+        given, by delta_op; dst may be `base` itself) into the slots dst_offsets.  A tensor's size is EXACTLY its slot -- stricter than
+        tensor_decompress_dbatch: the reader has to know every plane's size to tell a sparse content from a dense one.  It reads frames of
+        tensor_compress_dbatch and its delta and mixed forms as well (all contents dense).  results[i] = the tensor's size, or the error
+        of the first of its frames or contents that fails; such a tensor's slot is not written.  The workspace is
+        sparse_workspace_bound(min(dst_capacity, planes_capacity), n*E) followed by the packed reader's."""
+        return _decompress_sparse(self, "tensor_decompress_sparse_dbatch", frames, frame_offsets, dst_offsets, elem_bytes, None, None, None, base, dst, dst_capacity,
+                                  max_total_blocks, contents, contents_capacity, content_offsets, content_results, planes, planes_capacity, None, None, plane_offsets,
+                                  plane_results, workspace, results, delta_op)
+
+    def tensor_decompress_seg_sparse_dbatch(self, frames, frame_offsets, dst_offsets, elem_bytes, segment_log, seg_first=None, n_segments=None, base=None, dst=None,
+                                            dst_capacity=None, max_total_blocks=None, contents=None, contents_capacity=None, content_offsets=None, content_results=None,
+                                            planes=None, planes_capacity=None, seg_offsets=None, seg_results=None, plane_offsets=None, plane_sizes=None, workspace=None,
+                                            results=None, delta_op=0):
+        """tensor_decompress_seg_dbatch for frames of tensor_compress_seg_sparse_dbatch: the packed reader into `contents`, sparse_expand_dbatch
+        over the segment layout of the slots into `planes`, the fold, the merge.  A tensor's size is exactly its slot."""
+        return _decompress_sparse(self, "tensor_decompress_seg_sparse_dbatch", frames, frame_offsets, dst_offsets, elem_bytes, segment_log, seg_first, n_segments, base,
+                                  dst, dst_capacity, max_total_blocks, contents, contents_capacity, content_offsets, content_results, planes, planes_capacity, seg_offsets,
+                                  seg_results, plane_offsets, plane_sizes, workspace, results, delta_op)
+
+    for f in (sparse_workspace_bound, sparse_pack_dbatch, sparse_expand_dbatch, tensor_compress_sparse_dbatch, tensor_decompress_sparse_dbatch,
+              tensor_compress_seg_sparse_dbatch, tensor_decompress_seg_sparse_dbatch):
+        setattr(FseHip, f.__name__, f)
+
+    def _not_sparse(obj, what):
+        if getattr(obj, "sparse_permille", None) is not None:
+            raise ValueError(what + ": the object holds sparse planes (SparsePlanes); windows and patches of those are not supported")
 
     # ---- the user-facing pair
     def _read_base(obj, base, what):
@@ -2291,11 +2545,13 @@ def _planes_methods():
         return _compress_tensors(self, tensors, codec, block_size_id, base,
                                  _seg_log(segment_log, block_size_id if isinstance(block_size_id, numbers.Integral) and 0 <= block_size_id <= 6 else 0))
 
-    def _segmented(obj, segment_log, delta_op="xor"):
+    def _segmented(obj, segment_log, delta_op="xor", sparse=None):
         if segment_log is not None:
             obj.segment_log = int(segment_log)
         if delta_op != "xor":
             obj.delta_op = delta_op
+        if sparse is not None:
+            obj.sparse_permille = int(sparse)
         return obj
 
     def _compress_tensors(self, tensors, codec, block_size_id, base, segment_log):
@@ -2317,10 +2573,13 @@ def _planes_methods():
             for k, (t, dt, sh) in enumerate(zip(tensors, earlier.dtypes, earlier.shapes)):
                 if isinstance(t, torch.Tensor) and (t.dtype != dt or tuple(t.shape) != tuple(sh)):
                     raise ValueError("compress_tensors: tensor %d is %s %s, the earlier object's was %s %s" % (k, t.dtype, tuple(t.shape), dt, tuple(sh)))
+        sparse, outer = None, codec
+        if isinstance(codec, SparsePlanes):                 # the contents' codec inside, the threshold beside it
+            sparse, codec = codec.permille, codec.codec
         if not tensors:
             if base is not None and len(list(base)):
                 raise ValueError("base: tensors for none")
-            return _segmented(CompressedTensors([], [], [], None, codec, block_size_id, base is not None), segment_log, opname)
+            return _segmented(CompressedTensors([], [], [], None, outer, block_size_id, base is not None), segment_log, opname, sparse)
         device = tensors[0].device
         for t in tensors:
             if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
@@ -2337,7 +2596,16 @@ def _planes_methods():
             src = torch.cat(raw) if int(offs[-1]) else torch.zeros(1, dtype=torch.uint8, device=device)[:0]
             bsrc = None if braw is None else torch.cat([braw[i] for i in idx]) if int(offs[-1]) else src
             codecs = sfirst = None
-            if segment_log is not None:
+            if sparse is not None:
+                given = None if earlier is None else [g for g in earlier.groups if g["elem_bytes"] == E][0]["codecs"]
+                if segment_log is not None:
+                    sfirst = self.planes_segment_first(np.diff(offs.astype(np.int64)), E, segment_log)
+                    dst, foff, fres, tres, codecs = self.tensor_compress_seg_sparse_dbatch(src, offs, E, segment_log, sparse, sfirst, base=bsrc, codec=codec,
+                                                                                           codecs=given, block_size_id=block_size_id, delta_op=op)
+                else:
+                    dst, foff, fres, tres, codecs = self.tensor_compress_sparse_dbatch(src, offs, E, sparse, base=bsrc, codec=codec, codecs=given,
+                                                                                       block_size_id=block_size_id, delta_op=op)
+            elif segment_log is not None:
                 given = None if earlier is None else [g for g in earlier.groups if g["elem_bytes"] == E][0]["codecs"]
                 sfirst = self.planes_segment_first(np.diff(offs.astype(np.int64)), E, segment_log)
                 dst, foff, fres, tres, codecs = self.tensor_compress_seg_dbatch(src, offs, E, segment_log, sfirst, base=bsrc, codec=codec, codecs=given,
@@ -2359,8 +2627,8 @@ def _planes_methods():
                 groups[-1]["codecs"] = codecs.clone()
             if sfirst is not None:
                 groups[-1]["seg_first"] = sfirst
-        return _segmented(CompressedTensors(groups, [t.dtype for t in tensors], [tuple(t.shape) for t in tensors], device, codec, block_size_id, braw is not None),
-                          segment_log, opname if braw is not None else "xor")
+        return _segmented(CompressedTensors(groups, [t.dtype for t in tensors], [tuple(t.shape) for t in tensors], device, outer, block_size_id, braw is not None),
+                          segment_log, opname if braw is not None else "xor", sparse)
 
     def decompress_tensors(self, obj, base=None):
         """-> the tensors compress_tensors was given, in their order: same dtype, shape and device, the same bytes.  Every tensor owns its memory
@@ -2378,7 +2646,14 @@ def _planes_methods():
             offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
             blocks = self.planes_block_bound(sum(sizes), len(sizes), E, obj.block_size_id)
             seg_log = getattr(obj, "segment_log", None)
-            if seg_log is not None:
+            if getattr(obj, "sparse_permille", None) is not None:
+                dst = None if braw is None else torch.cat([braw[i] for i in g["index"]]) if sum(sizes) else torch.zeros(1, dtype=torch.uint8, device=obj.device)[:0]
+                if seg_log is not None:
+                    dst, res = self.tensor_decompress_seg_sparse_dbatch(g["frames"], g["frame_offsets"], offs, E, seg_log, g["seg_first"], base=dst, dst=dst,
+                                                                        max_total_blocks=blocks, delta_op=op)
+                else:
+                    dst, res = self.tensor_decompress_sparse_dbatch(g["frames"], g["frame_offsets"], offs, E, base=dst, dst=dst, max_total_blocks=blocks, delta_op=op)
+            elif seg_log is not None:
                 dst = None if braw is None else torch.cat([braw[i] for i in g["index"]]) if sum(sizes) else torch.zeros(1, dtype=torch.uint8, device=obj.device)[:0]
                 dst, res = self.tensor_decompress_seg_dbatch(g["frames"], g["frame_offsets"], offs, E, seg_log, g["seg_first"], base=dst, dst=dst,
                                                              max_total_blocks=blocks, delta_op=op)
@@ -2405,6 +2680,7 @@ def _planes_methods():
         seg_log = getattr(obj, "segment_log", None)
         if seg_log is None:
             raise ValueError("decompress_tensor_windows: the object is not segmented (compress_tensors_segmented writes those)")
+        _not_sparse(obj, "decompress_tensor_windows")
         base, op = _read_base(obj, base, "decompress_tensor_windows")
         windows = list(windows)
         if len(windows) != len(obj.dtypes):

@@ -341,16 +341,26 @@ hipError_t launch_planes_split(u8* planes, u64* planeOff, size_t* tensorRes, con
                                unsigned E, u64 capacity, hipStream_t s);
 hipError_t launch_planes_merge(u8* dst, const u64* dstOff, size_t* results, const u8* planes, const u64* planeOff, const size_t* planeSizes, const u8* base,
                                unsigned deltaOp, size_t nTensors, unsigned E, u64 dstCapacity, hipStream_t s);
+// the offsets and results kernel of the split alone: the plane layout of tensors that lie at srcOff (planes_sparse.hip: of a destination)
+hipError_t launch_planes_offsets(u64* planeOff, size_t* tensorRes, const u64* srcOff, size_t nTensors, unsigned E, u64 capacity, hipStream_t s);
 // the segments kernel of planes_seg.hip, as the compress path chains it
 hipError_t launch_segments(u64* segOff, size_t* tensorRes, const u64* planeOff, const u64* srcOff, const u64* segFirst, size_t nTensors, unsigned E, size_t nSeg,
                            unsigned segLog, hipStream_t s);
 // what a compress composite hands on to the packed writer: d_codecs null -> `codec` for every frame (FSEHIP_frame_compress_packed_dbatch),
 // else a codec per frame by `policy` (FSEHIP_frame_compress_packed_mixed_dbatch)
 struct PlWriter { size_t maxTotalBlocks; unsigned blockSizeId; int codec; uint8_t* d_codecs; int policy; unsigned tolerancePermille, slotAlignLog; void* d_workspace; size_t workspaceBytes; };
-// the compress path of all four compress composites (planes.hip): argument checks, (delta) split, segments where d_segFirst is given, writer
+// sparse planes (planes_sparse.hip; fsehip.h, "sparse planes"): what a compress composite needs to put FSEHIP_sparse_pack_dbatch between its
+// units and the writer -- the threshold and the caller's scratch for the contents.  sparse_workspace: the bytes pack and expand take from the
+// head of a workspace (a multiple of 256; the writer's or the reader's follows); bad_sparse: their launch and workspace checks
+struct PlSparse { unsigned permille; void* d_contents; uint64_t* d_contentOffsets; };
+size_t sparse_workspace(u64 capacity, size_t nUnits);
+bool bad_sparse(u64 capacity, size_t nUnits, const void* d_workspace, size_t workspaceBytes);
+hipError_t launch_sparse_pack(u8* contents, u64* contentOff, const u8* units, const u64* unitOff, size_t nUnits, u64 capacity, unsigned permille, u8* ws, hipStream_t s);
+// the compress path of all compress composites (planes.hip): argument checks, (delta) split, segments where d_segFirst is given, pack where
+// `sparse` is given, writer
 int planes_compress(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults, const void* d_src, const void* d_base,
                     unsigned deltaOp, const uint64_t* d_srcOffsets, size_t nTensors, unsigned E, uint64_t capacity, const uint64_t* d_segFirst, size_t nSegments,
-                    unsigned segLog, void* d_planes, uint64_t* d_planeOffsets, uint64_t* d_segOffsets, const PlWriter& w, void* stream);
+                    unsigned segLog, void* d_planes, uint64_t* d_planeOffsets, uint64_t* d_segOffsets, const PlWriter& w, void* stream, const PlSparse* sparse = nullptr);
 
 // ---- kernel timing probe (HIP events on the launch stream; used by bench.py for the live roofline figure) ----
 enum { PK_HIST = 0, PK_FSE_CPREP, PK_FSE_ENCODE, PK_FSE_DPREP, PK_FSE_DECODE, PK_HUF_CPREP, PK_HUF_ENCODE, PK_HUF_DPREP, PK_HUF_DECODE, PK_FSE_ENCODE_WAVE, PK_COUNT };

@@ -181,11 +181,18 @@ __global__ __launch_bounds__(PL_THREADS) void k_planes_merge(u8* dst, const u64*
 
 // base null: the plain kernels, and no data kernel at all for E == 1 (the planes of such a tensor are the tensor).  The offsets kernel runs
 // even for no tensors: it writes the last entry
+// the split's first step by itself: the plane layout and the tensor results that a set of tensor offsets implies (planes_sparse.hip reads
+// the layout of a destination from it)
+hipError_t launch_planes_offsets(u64* planeOff, size_t* tensorRes, const u64* srcOff, size_t nTensors, unsigned E, u64 capacity, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_planes_offsets, dim3(grid_for(nTensors + 1)), dim3(PL_THREADS), 0, s, planeOff, tensorRes, srcOff, nTensors, (u32)E, capacity);
+    return hipGetLastError();
+}
 hipError_t launch_planes_split(u8* planes, u64* planeOff, size_t* tensorRes, const u8* src, const u8* base, unsigned deltaOp, const u64* srcOff, size_t nTensors,
                                unsigned E, u64 capacity, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_planes_offsets, dim3(grid_for(nTensors + 1)), dim3(PL_THREADS), 0, s, planeOff, tensorRes, srcOff, nTensors, (u32)E, capacity);
-    if ((E == 1 && !base) || nTensors == 0 || capacity == 0) return hipGetLastError();
+    const hipError_t e0 = launch_planes_offsets(planeOff, tensorRes, srcOff, nTensors, E, capacity, s);
+    if (e0 != hipSuccess || (E == 1 && !base) || nTensors == 0 || capacity == 0) return e0;
     const dim3 g(tile_grid(capacity, nTensors)), b(PL_THREADS);
     pl_for_elem(E, [&](auto eb) {
         constexpr int EB = decltype(eb)::value;
@@ -218,14 +225,23 @@ hipError_t launch_planes_merge(u8* dst, const u64* dstOff, size_t* results, cons
 // The one compress path of the four composites, each of which has checked its own pointers: the remaining argument checks of all steps in
 // front of the first launch (fsehip.h: what the guarantee covers), the split (d_base given: the split of the delta by deltaOp), the segments kernel where
 // d_segFirst is given, then the packed writer -- a codec per frame where w.d_codecs is given -- over the planes or their segments, read
-// from d_src itself where the split moved nothing
+// from d_src itself where the split moved nothing.  `sparse` given (planes_sparse.hip): pack stands between the units and the writer, which
+// then reads the contents; pack's workspace is the head of the caller's, the writer's the rest
 int planes_compress(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults, const void* d_src, const void* d_base,
                     unsigned deltaOp, const uint64_t* d_srcOffsets, size_t nTensors, unsigned E, uint64_t capacity, const uint64_t* d_segFirst, size_t nSegments,
-                    unsigned segLog, void* d_planes, uint64_t* d_planeOffsets, uint64_t* d_segOffsets, const PlWriter& w, void* stream)
+                    unsigned segLog, void* d_planes, uint64_t* d_planeOffsets, uint64_t* d_segOffsets, const PlWriter& writer, void* stream, const PlSparse* sparse)
 {
     if (bad_op(deltaOp)) return (int)hipErrorInvalidValue;
-    if (d_segFirst ? bad_seg(segLog, w.blockSizeId) || bad_counts(nTensors, E, nSegments) : bad_tensors(nTensors, E)) return (int)hipErrorInvalidValue;
+    if (d_segFirst ? bad_seg(segLog, writer.blockSizeId) || bad_counts(nTensors, E, nSegments) : bad_tensors(nTensors, E)) return (int)hipErrorInvalidValue;
     const size_t nFrames = d_segFirst ? nSegments : nTensors * E;
+    PlWriter w = writer;
+    u8* const packWs = (u8*)writer.d_workspace;
+    if (sparse) {
+        if (sparse->permille > 1000 || bad_sparse(capacity, nFrames, w.d_workspace, w.workspaceBytes)) return (int)hipErrorInvalidValue;
+        const size_t head = sparse_workspace(capacity, nFrames);
+        w.d_workspace = packWs + head;
+        w.workspaceBytes -= head;
+    }
     if (bad_grid(capacity, nTensors) || bad_writer(w, nFrames)) return (int)hipErrorInvalidValue;
     const hipStream_t s = (hipStream_t)stream;
     hipError_t e = launch_planes_split((u8*)d_planes, (u64*)d_planeOffsets, d_tensorResults, (const u8*)d_src, (const u8*)d_base, deltaOp, (const u64*)d_srcOffsets, nTensors,
@@ -233,8 +249,13 @@ int planes_compress(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets,
     if (e == hipSuccess && d_segFirst)
         e = launch_segments((u64*)d_segOffsets, d_tensorResults, (const u64*)d_planeOffsets, (const u64*)d_srcOffsets, (const u64*)d_segFirst, nTensors, E, nSegments, segLog, s);
     if (e != hipSuccess) return (int)e;
-    const void* const from = !d_base && E == 1 ? d_src : d_planes;
-    const uint64_t* const fromOff = d_segFirst ? d_segOffsets : d_planeOffsets;
+    const void* from = !d_base && E == 1 ? d_src : d_planes;
+    const uint64_t* fromOff = d_segFirst ? d_segOffsets : d_planeOffsets;
+    if (sparse) {
+        e = launch_sparse_pack((u8*)sparse->d_contents, (u64*)sparse->d_contentOffsets, (const u8*)from, (const u64*)fromOff, nFrames, capacity, sparse->permille, packWs, s);
+        if (e != hipSuccess) return (int)e;
+        from = sparse->d_contents; fromOff = sparse->d_contentOffsets;
+    }
     if (w.d_codecs)
         return FSEHIP_frame_compress_packed_mixed_dbatch(d_dst, dstCapacity, d_frameOffsets, d_frameResults, from, fromOff, nFrames, w.maxTotalBlocks, w.blockSizeId,
                                                          w.d_codecs, w.policy, w.tolerancePermille, w.slotAlignLog, w.d_workspace, w.workspaceBytes, stream);

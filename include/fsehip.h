@@ -1005,6 +1005,102 @@ FSEHIP_API int FSEHIP_tensor_patch_window_op_dbatch(void* d_out, uint64_t outCap
                                                     uint64_t newCapacity, uint64_t* d_newOffsets, size_t* d_newResults, void* d_scratch, size_t scratchBytes,
                                                     void* d_workspace, size_t workspaceBytes, void* stream);
 
+/* Sparse planes (planes_sparse.hip): ZERO MASK AND PACKED NON-ZEROS ahead of the frame writers.  The sign / exponent plane of a tensor delta
+ * is almost all zeros, and an order-0 coder still sends every one of its n symbols through its chains (FSE, which decodes such a plane at
+ * its slowest) or spends at least a bit on each (Huff0: 33 KB for a 256 KB plane that FSE codes in 1.8 KB).  A plane of n bytes of which nnz
+ * are non-zero is handed to the writer as a bit mask of ceil(n / 8) bytes followed by the nnz non-zero bytes: the same order-0 information in
+ * up to 8x fewer symbols, masks and values in blocks with tables of their own.  No frame byte format changes: a content is coded into an
+ * ordinary .fse frame by the packed writers and read by the packed reader; nothing in a frame says which form it holds.  The transform is one
+ * more layer between split and writer and between reader and merge, as the delta ops are.
+ * Like the calls above: launches on `stream` only, capturable, no size leaves the device, argument errors (also: sparsePermille > 1000, 2^31
+ * units or more, a null, misaligned -- 256 bytes -- or too small workspace) are hipErrorInvalidValue, decided before any device call, with
+ * nothing written.
+ *
+ *   The transform.  A UNIT is a run of n bytes: a whole plane in the unsegmented calls, a segment of a plane in the segmented ones.  nnz = the
+ *     number of its non-zero bytes, m = ceil(n / 8).
+ *     Writer rule: the unit is SPARSE iff nnz * 1000 <= n * sparsePermille and m + nnz < n, in 64-bit integers (sparsePermille 0 .. 1000).
+ *     Sparse content: m mask bytes, then the nnz non-zero bytes in order; bit i & 7 (LSB first) of mask byte i >> 3 is set iff byte i is
+ *       non-zero, padding bits are zero; c = m + nnz < n.  Dense content: the unit itself, c = n -- the frame is byte for byte that of the
+ *       calls without _sparse.  With sparsePermille 0 only units without a non-zero byte (and n >= 2) are sparse.
+ *     Reader rule: the reader neither knows sparsePermille nor needs a flag -- the content size c says which form it is.  For a unit of n
+ *       bytes, in this order: an error of the frame reader passes through; c == n: dense, copied; c > n: corruption_detected; otherwise
+ *       sparse, and corruption_detected unless c >= m, popcount(mask) == c - m, every padding bit is zero and every value byte is non-zero
+ *       (these four keep the transform a bijection).  Otherwise the result is n.  The verdict stands before any unit byte is written: a
+ *       unit that fails is not written at all.
+ *     THE READER NEEDS EXACT SIZES: it has to know n per unit.  In the sparse reading calls a tensor's size IS its slot,
+ *       d_dstOffsets[i + 1] - d_dstOffsets[i]: the plane layout P and the segment layout follow from those sizes alone (the offsets step of
+ *       the split and FSEHIP_planes_segments_dbatch over d_dstOffsets).  This is STRICTER than FSEHIP_planes_merge_dbatch, whose slots may
+ *       be larger than the tensors: pass the tensors' own offsets.
+ *
+ *   FSEHIP_sparse_workspaceBound   host arithmetic (works without a device): the workspace of the two calls below for units inside a buffer
+ *     of `capacity` bytes -- a count per work item (ceil(capacity / 32 KB) + nUnits of them), the scans' partial sums, a flag per unit; a
+ *     multiple of 256.  GENERIC for 2^31 units or a capacity whose launch reaches 2^24 workgroups.
+ *
+ *   FSEHIP_sparse_pack_dbatch   d_units + d_unitOffsets (nUnits + 1 entries: unit u is [U[u], U[u + 1]), back to back, any alignment) ->
+ *     d_contents (the contents back to back; at most `capacity` bytes in all, since c <= n) and d_contentOffsets (nUnits + 1 entries, directly
+ *     the d_srcOffsets of the packed writers).  `capacity` is the byte size of d_units and of d_contents and sizes the launch.  A unit with
+ *     U[u + 1] > capacity or U[u] > U[u + 1] -- collapsed offsets of a tensor refused upstream, n = 0 -- is an empty content.  d_contents must
+ *     not overlap d_units.  Three passes over the work items of the ragged mapping of "byte planes" (32 KB tiles of the flat axis plus one
+ *     workgroup per unit boundary, bytes dealt out by mask byte): non-zeros per item; two scans and the writer rule per unit; then every item
+ *     again -- a lane takes 16 bytes a round, its position among the values is a wave prefix plus the totals of the waves in front, masks and
+ *     values are staged in LDS on the 16-byte grid of their destination and stored in 16-byte pieces (fewer than 16 bytes at either end
+ *     bytewise); a dense unit is copied in the same pass.  No workgroup waits on another: the scans are launches of their own.
+ *
+ *   FSEHIP_sparse_expand_dbatch   d_contents + d_contentOffsets + d_contentResults (the packed reader's d_dstOffsets and d_results;
+ *     contentsCapacity = the size of d_contents) + the dense layout d_unitOffsets (capacity = the size of d_units) -> d_units (the dense
+ *     bytes at their offsets) and d_unitResults[u] by the reader rule; a content that does not lie inside d_contents with its result is
+ *     corruption_detected.  (d_unitOffsets, d_unitResults) are then exactly what the fold and the merge take.  Passes: set bits per mask
+ *     tile, with zero value bytes and padding bits into a flag per unit; a scan; the verdict per unit; then the expansion of the good units --
+ *     a lane takes 8 mask bytes and writes 64 unit bytes in 16-byte stores, the round's values staged in LDS.  Nothing outside the dense
+ *     range of a good unit is written.
+ *
+ *   The composites take one more scratch buffer, d_contents (`capacity` bytes; reading: contentsCapacity, the tensors' total is sufficient)
+ *     with d_contentOffsets (one entry per frame and one more; reading also d_contentResults, one per frame).  Their workspace is
+ *     FSEHIP_sparse_workspaceBound(capacity, nFrames) -- reading: of min(dstCapacity, planesCapacity) -- followed by the writer's or the
+ *     reader's for nFrames frames, nFrames = nTensors * E or nSegments.  FSEHIP_planes_blockBound stays a sufficient maxTotalBlocks (c <= n).
+ *   FSEHIP_tensor_compress_sparse_dbatch       the split (d_base == NULL), else the split of the delta by deltaOp -> pack over the plane
+ *     offsets -> FSEHIP_frame_compress_packed_dbatch with `codec` (d_codecs == NULL) or the mixed writer with d_codecs (nTensors * E entries),
+ *     policy and tolerancePermille, as FSEHIP_tensor_compress_seg_dbatch takes them.  Frame j is byte for byte FSEHIP_frame_compress of the
+ *     content of plane j.  With a sparsePermille under which no unit qualifies every output is that of the call without _sparse, bit for bit.
+ *   FSEHIP_tensor_decompress_sparse_dbatch     the plane layout of d_dstOffsets -> the packed reader (slot alignment 0) into d_contents ->
+ *     expand into d_planes (d_planeOffsets, nTensors * E + 1, the layout; d_planeResults, nTensors * E, the units' results) -> the merge,
+ *     plain or by deltaOp against d_base, IN PLACE (d_base == d_dst) allowed: the expansion writes scratch only, so a tensor one of whose
+ *     frames or contents is damaged keeps its old bytes.
+ *   FSEHIP_tensor_compress_seg_sparse_dbatch   split -> segments -> pack over the SEGMENT offsets -> writer: a unit is a segment.
+ *   FSEHIP_tensor_decompress_seg_sparse_dbatch layout and segment layout of d_dstOffsets (d_segOffsets, nSegments + 1) -> reader -> expand
+ *     (d_segResults, nSegments) -> fold (d_planeOffsets, d_planeSizes) -> merge.
+ *   Out of scope, and refused by the callers of these (no call combines them): windows and patches of sparse segmented objects; a threshold
+ *     per unit; run-length forms. */
+FSEHIP_API size_t FSEHIP_sparse_workspaceBound(uint64_t capacity, size_t nUnits);
+FSEHIP_API int FSEHIP_sparse_pack_dbatch(void* d_contents, uint64_t* d_contentOffsets, const void* d_units, const uint64_t* d_unitOffsets, size_t nUnits, uint64_t capacity,
+                                         unsigned sparsePermille, void* d_workspace, size_t workspaceBytes, void* stream);
+FSEHIP_API int FSEHIP_sparse_expand_dbatch(void* d_units, size_t* d_unitResults, const uint64_t* d_unitOffsets, size_t nUnits, uint64_t capacity, const void* d_contents,
+                                           uint64_t contentsCapacity, const uint64_t* d_contentOffsets, const size_t* d_contentResults, void* d_workspace,
+                                           size_t workspaceBytes, void* stream);
+FSEHIP_API int FSEHIP_tensor_compress_sparse_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
+                                                    const void* d_src, const void* d_base, unsigned deltaOp, const uint64_t* d_srcOffsets, size_t nTensors,
+                                                    unsigned elemBytes, uint64_t capacity, size_t maxTotalBlocks, unsigned blockSizeId, int codec, uint8_t* d_codecs,
+                                                    int policy, unsigned tolerancePermille, unsigned slotAlignLog, unsigned sparsePermille, void* d_planes,
+                                                    uint64_t* d_planeOffsets, void* d_contents, uint64_t* d_contentOffsets, void* d_workspace, size_t workspaceBytes,
+                                                    void* stream);
+FSEHIP_API int FSEHIP_tensor_decompress_sparse_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base, unsigned deltaOp,
+                                                      size_t* d_results, const void* d_frames, const uint64_t* d_frameOffsets, size_t nTensors, unsigned elemBytes,
+                                                      size_t maxTotalBlocks, void* d_contents, uint64_t contentsCapacity, uint64_t* d_contentOffsets,
+                                                      size_t* d_contentResults, void* d_planes, uint64_t planesCapacity, uint64_t* d_planeOffsets, size_t* d_planeResults,
+                                                      void* d_workspace, size_t workspaceBytes, void* stream);
+FSEHIP_API int FSEHIP_tensor_compress_seg_sparse_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
+                                                        const void* d_src, const void* d_base, unsigned deltaOp, const uint64_t* d_srcOffsets, size_t nTensors,
+                                                        unsigned elemBytes, uint64_t capacity, const uint64_t* d_segFirst, size_t nSegments, unsigned segLog,
+                                                        size_t maxTotalBlocks, unsigned blockSizeId, int codec, uint8_t* d_codecs, int policy, unsigned tolerancePermille,
+                                                        unsigned slotAlignLog, unsigned sparsePermille, void* d_planes, uint64_t* d_planeOffsets, uint64_t* d_segOffsets,
+                                                        void* d_contents, uint64_t* d_contentOffsets, void* d_workspace, size_t workspaceBytes, void* stream);
+FSEHIP_API int FSEHIP_tensor_decompress_seg_sparse_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base, unsigned deltaOp,
+                                                          size_t* d_results, const void* d_frames, const uint64_t* d_frameOffsets, size_t nTensors, unsigned elemBytes,
+                                                          const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, size_t maxTotalBlocks, void* d_contents,
+                                                          uint64_t contentsCapacity, uint64_t* d_contentOffsets, size_t* d_contentResults, void* d_planes,
+                                                          uint64_t planesCapacity, uint64_t* d_segOffsets, size_t* d_segResults, uint64_t* d_planeOffsets,
+                                                          size_t* d_planeSizes, void* d_workspace, size_t workspaceBytes, void* stream);
+
 /* ---- FSE for 16-bit symbols (lib/fseU16.h:62-80, lib/fseU16.c) -- SURVEY 8(f) rank 4.  Alphabets of up to
  * FSEHIP_FSEU16_MAX_SYMBOL_VALUE + 1 symbols, table logs up to 13 (default 12), ONE tANS state per stream: a different format from
  * the byte coder's.  Sizes of the uncompressed side are in SYMBOLS (as in the reference), strides in bytes.
