@@ -114,6 +114,7 @@ typedef const __attribute__((address_space(3))) u16* lds_u16_ptr;
 typedef const __attribute__((address_space(3))) u32* lds_u32_ptr;
 DEV u32 lds_cell(u32 addr) { return *(lds_u16_ptr)(uintptr_t)addr; }   // absolute LDS byte address -> table cell
 
+DEV bool wave_all(bool p) { return __builtin_amdgcn_ballot_w64(p) == __builtin_amdgcn_ballot_w64(true); }   // __all without the round trip through a VGPR
 DEV u32 dpp_swap(u32 v) { return (u32)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true); }   // value of the neighbour lane (quad_perm [1,0,3,2])
 
 // One phase = FSE_CHECK_EVERY iterations, registers + LDS only.
@@ -925,6 +926,47 @@ __global__ __launch_bounds__(FSE_DEC_THREADS) void k_fse_decode(FseDecArgs a)
                 TIMING(if (!__all(rdy)) { const unsigned long long tB = __builtin_readcyclecounter(); tWait += tB - tA; ++nWait; tA = tB; });
             } while (!__all(rdy));
             if (!__any(can)) break;                                              // uniform
+            // ---- every chain of the wave runs (all rounds of a uniform batch but the last one or two): a loop of its own over rounds
+            //      without the zombies' machinery, which hands back to the round above and below as soon as one chain of the wave is
+            //      through with its long phases.  State, cursor and counters are simply the phase's; the ring position is iters modulo
+            //      the ring size; both lanes of a pair hold the same cursor and counters, so both store the (same) control words and the
+            //      store needs no exec mask; each of the two decisions is ONE compare whose result is the vote's operand as it stands
+            //      (an `&` of two compares goes through a VGPR and a second compare before it can be voted on).
+            if (__all(can)) {
+                u32 qp;                                                          // q + 8
+                for (;;) {
+                    unsigned long long tI = 0; (void)tI;
+                    TIMING(tI = __builtin_readcyclecounter(););
+                    fse_bulk_phase_rev<FSE_CHECK_EVERY>(bs.s, P, Phead, tl + 1u, 4u, tabOff, myIn, maskB & 31u, myRing + (iters & (FSE_DEC_RING - 1)));
+                    TIMING(tInner += __builtin_readcyclecounter() - tI;);
+                    iters += FSE_CHECK_EVERY; grp -= FSE_CHECK_EVERY;
+                    const u32 B = R8 - P;
+                    qp = 4u * (B >> 5);
+                    const u32 Bp = B - inA8;
+                    // Bp >= 785 and grp >= 16: either difference wraps to 2^32 - 785 or more when it falls short, and is at most 2^31
+                    // otherwise (S < 2^28 bytes, grp <= 2^30)
+                    const u32 shortBy = max(Bp - (65u + 48u * (FSE_CHECK_EVERY - 1)), (u32)grp - (u32)FSE_CHECK_EVERY);
+                    can = shortBy < 0xC0000000u;
+                    const bool more = can | ((Bp >= 65u + 48u * (FSE_FINISH_EVERY - 1)) & (grp >= FSE_FINISH_EVERY));
+                    ctl_store2(&ctl->pubIters, iters, more ? qp : (qp | 0x80000000u));
+                    TIMING(const unsigned long long tB = __builtin_readcyclecounter(); tRun += tB - tA; ++nRun; tA = tB;);
+                    if (!wave_all(can)) break;                                   // uniform: back to the rounds with zombies
+                    // the poll of the round head: iters + 16 - fl <= ring size and max(q - 92, 0) >= vlo, as min(.., ..) >= 0 (iters and
+                    // fl are record counts below 2^30; 0 <= need < 2^31 and vlo > -2^31, so neither difference overflows)
+                    const int needF = max((int)qp - 8 - 4 * ((48 * (FSE_CHECK_EVERY - 1) + 31) / 32), 0);
+                    const int roomF = FSE_DEC_RING - FSE_CHECK_EVERY - (int)iters;
+                    bool rdyF;
+                    do {
+                        const int fl = (int)(u32)srvNext;
+                        const int vlo = (int)(u32)(srvNext >> 32);
+                        srvNext = ctl_peek2(&ctl->srvFlushed);
+                        rdyF = min(roomF + fl, needF - vlo) >= 0;
+                        TIMING(if (!wave_all(rdyF)) { const unsigned long long tB = __builtin_readcyclecounter(); tWait += tB - tA; ++nWait; tA = tB; });
+                    } while (!wave_all(rdyF));
+                }
+                bs.q = qp - 8u; rpos = iters & (FSE_DEC_RING - 1);
+                continue;
+            }
             uint2* const ring = can ? myRing + rpos : dummyRing;
             u32 sN = bs.s, Pn = P, PhN = Phead;
             unsigned long long tI = 0; (void)tI;
