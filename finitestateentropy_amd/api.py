@@ -74,12 +74,17 @@ class DeltaBase:
     """`base` of compress_tensors with the delta's operation beside it: "sub" -- the elements' bit patterns subtracted as integers and
     zigzag-folded (FSEHIP_DELTA_SUB, include/fsehip.h "arithmetic tensor deltas"), 11 to 19 % fewer frame bytes than XOR on weight updates
     -- or "xor", which is what a plain sequence as `base` means.  The object written carries the op as `delta_op`; the reading calls take
-    the op from the object and the base as a plain sequence, or as a DeltaBase of the same op."""
+    the op from the object and the base as a plain sequence, or as a DeltaBase of the same op.
+    check=True: the writing call digests the base tensors on the device (include/fsehip.h "tensor digests and checked deltas") and the
+    object carries them as `base_digests`; decompress_tensors then digests the base it is given and refuses (ValueError, nothing written)
+    a base that is not the one the deltas were made against.  The digest is not cryptographic: it catches accidents, not adversaries."""
 
-    def __init__(self, tensors, op="sub"):
+    def __init__(self, tensors, op="sub", check=False):
         if not isinstance(op, str) or op not in DELTA_OPS:
             raise ValueError("DeltaBase: op %r, \"sub\" or \"xor\" is needed" % (op,))
-        self.tensors, self.op = list(tensors), op
+        if not isinstance(check, bool):
+            raise ValueError("DeltaBase: check %r, True or False is needed" % (check,))
+        self.tensors, self.op, self.check = list(tensors), op, check
 
     def __len__(self):
         return len(self.tensors)
@@ -88,7 +93,7 @@ class DeltaBase:
         return iter(self.tensors)
 
     def __repr__(self):
-        return "DeltaBase(%d tensors, op=%r)" % (len(self.tensors), self.op)
+        return "DeltaBase(%d tensors, op=%r%s)" % (len(self.tensors), self.op, ", check=True" if self.check else "")
 
 
 def fse_compress_bound(n):      # lib/fse.h:290-292
@@ -1236,10 +1241,12 @@ class CompressedTensors:
     DeltaBase(..., "sub")): what the frames of an object with `delta` set hold -- `tensor XOR base` or zigzag(tensor - base); the reading
     calls take it from here.  `sparse_permille` (None, or the integer of the SparsePlanes the object was written with): the frames hold sparse
     contents -- `codec` is then that SparsePlanes -- and decompress_tensors reads them as such; windows and patches of such an object are
-    refused."""
+    refused.  `base_digests` (None, or one int per tensor in tensor order where the object was written against a DeltaBase(..., check=True)):
+    the 64-bit digests of the base tensors; decompress_tensors refuses a base whose digests differ."""
     segment_log = None
     delta_op = "xor"
     sparse_permille = None
+    base_digests = None
 
     def __init__(self, groups, dtypes, shapes, device, codec, block_size_id, delta=False):
         self.groups, self.dtypes, self.shapes, self.device, self.codec, self.block_size_id = groups, dtypes, shapes, device, codec, block_size_id
@@ -2208,7 +2215,8 @@ def _planes_methods():
         segment_log, block_size_id, delta, codec and seg_first; an object written with an AutoCodec has the codecs of the new frames chosen
         anew.  base: for an object with `delta` set, the whole base tensors as compress_tensors takes them.  ValueError / TypeError before any
         launch: an object that is not segmented, a wrong number of tensors or windows, a tensor of another dtype, shape or device, a window
-        that is not one, a base / delta mismatch."""
+        that is not one, a base / delta mismatch.  `base_digests` of the object are not checked here and are carried over to the new one: the
+        patch is a delta against the same base."""
         seg_log = getattr(obj, "segment_log", None)
         if seg_log is None:
             raise ValueError("patch_tensor_windows: the object is not segmented (compress_tensors_segmented writes those)")
@@ -2261,7 +2269,7 @@ def _planes_methods():
                     new["codecs"] = g["codecs"].clone()
             groups.append(new)
         return _segmented(CompressedTensors(groups, list(obj.dtypes), list(obj.shapes), obj.device, obj.codec, obj.block_size_id, obj.delta), seg_log,
-                          getattr(obj, "delta_op", "xor"))
+                          getattr(obj, "delta_op", "xor"), None, getattr(obj, "base_digests", None))
 
     for f in (planes_stage_offsets, planes_split_window_dbatch, planes_splice_scratch_bound, planes_splice_dbatch, tensor_patch_window_dbatch, patch_tensor_windows):
         setattr(FseHip, f.__name__, f)
@@ -2484,6 +2492,104 @@ def _planes_methods():
               tensor_compress_seg_sparse_dbatch, tensor_decompress_seg_sparse_dbatch):
         setattr(FseHip, f.__name__, f)
 
+    # ---- tensor digests and checked deltas (csrc/planes_digest.hip; fsehip.h "tensor digests and checked deltas"): a 64-bit digest per
+    # tensor at the memory rate, and the gate that turns a digest mismatch into frames every reader refuses
+    def tensor_digest_workspace_bound(self, capacity, n_tensors):
+        """the workspace of tensor_digest_dbatch for n_tensors tensors inside `capacity` bytes.  Host arithmetic: needs no device."""
+        self.lib.FSEHIP_tensor_digest_workspaceBound.restype = SZ
+        r = int(self.lib.FSEHIP_tensor_digest_workspaceBound(C.c_uint64(int(capacity)), SZ(int(n_tensors))))
+        if r >= (1 << 62):
+            raise ValueError("tensor_digest_workspace_bound(%r, %r)" % (capacity, n_tensors))
+        return r
+
+    def tensor_digest_dbatch(self, src, src_offsets, capacity=None, digests=None, results=None, workspace=None):
+        """-> (digests, results): digests[i] = the 64-bit digest of tensor i = src[src_offsets[i] : src_offsets[i+1]] as an int64 (the same 64
+        bits; & (2**64 - 1) gives the unsigned value), results[i] = its size; a slot whose offsets decrease or that ends behind `capacity`
+        (default: src's size) gets -1 and digest 0.  The digest depends on the tensor's bytes alone, not on where it lies.  With src_offsets
+        on the device and digests, results and workspace given the call is launches only."""
+        self._flat(src, "src")
+        soff, _ = self._offsets(src_offsets, src.device, False)
+        n = soff.numel() - 1
+        capacity = _room(self, src, capacity, "src")
+        dig = _i64(self, digests, n, src.device, "digests")
+        res = _i64(self, results, n, src.device, "results")
+        if workspace is None:
+            workspace = torch.empty(max(tensor_digest_workspace_bound(self, capacity, n), 1), dtype=torch.uint8, device=src.device)
+        _check(self.lib.FSEHIP_tensor_digest_dbatch(_ptr(dig), _ptr(res), VP(src.data_ptr() or workspace.data_ptr()), _ptr(soff), SZ(n), C.c_uint64(capacity),
+                                                    _ptr(workspace), SZ(workspace.numel()), _stream()), "tensor_digest_dbatch")
+        return dig, res
+
+    def tensor_gate_dbatch(self, frame_offsets, digests, digest_results, expected, elem_bytes, frame_first=None, n_frames=None, gated_offsets=None, results=None):
+        """-> (gated_offsets, results): frame_offsets with every frame of a tensor whose digest is not the expected one (or whose digest result
+        is an error) turned into an empty extent at the start of the next tensor's first frame -- the readers answer those with -3
+        (srcSize_wrong) and the tensor keeps its bytes; the frames of the others are unchanged.  results[i] = digest_results[i] for a tensor that
+        passes, the digest's error, or -4 (corruption_detected) for a mismatch.  Tensor i owns the frames i*E .. (i+1)*E - 1, or with
+        frame_first (the seg_first of a segmented object) frame_first[i*E] .. frame_first[(i+1)*E] - 1.  gated_offsets goes wherever
+        frame_offsets goes in the reading calls.  digests / expected: int64 tensors of the 64 bits (tensor_digest_dbatch), or sequences of ints."""
+        E = _elem(elem_bytes)
+        foff, _ = self._offsets(frame_offsets, torch.device("cuda") if not isinstance(frame_offsets, torch.Tensor) else frame_offsets.device, False)
+        device = foff.device
+        nf = foff.numel() - 1 if n_frames is None else int(n_frames)
+        if nf < 0 or nf + 1 > foff.numel():
+            raise ValueError("frame_offsets: %d entries for %d frames" % (foff.numel(), nf))
+
+        def bits(t, what):
+            if isinstance(t, torch.Tensor):
+                return _i64(self, t, 0, device, what)
+            a = np.asarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in t], dtype=np.uint64).astype(np.int64)
+            return torch.from_numpy(a).to(device)
+        dig, exp = bits(digests, "digests"), bits(expected, "expected")
+        n = exp.numel()
+        dres = _i64(self, digest_results, n, device, "digest_results")
+        if dig.numel() < n:
+            raise ValueError("digests: %d entries for %d tensors" % (dig.numel(), n))
+        sf = None
+        if frame_first is not None:
+            sf, _ = _seg_first(self, frame_first, nf, device, n * E)
+        elif nf != n * E:
+            raise ValueError("frame_offsets: %d frames for %d tensors of %d planes" % (nf, n, E))
+        gated = _i64(self, gated_offsets, nf + 1, device, "gated_offsets")
+        res = _i64(self, results, n, device, "results")
+        some = gated if n == 0 else None                      # (arrays of no entries still need an address)
+        _check(self.lib.FSEHIP_tensor_gate_dbatch(_ptr(gated), _ptr(some if some is not None else res), _ptr(foff), SZ(nf), _ptr(sf), C.c_uint(E),
+                                                  _ptr(some if some is not None else dig), _ptr(some if some is not None else dres),
+                                                  _ptr(some if some is not None else exp), SZ(n), _stream()), "tensor_gate_dbatch")
+        return gated, res
+
+    def tensor_digests(self, tensors):
+        """-> one int (0 .. 2**64 - 1) per tensor: the digest of its contiguous bytes (tensor_digest_dbatch; fsehip.h "tensor digests and checked
+        deltas").  CUDA tensors of any dtype, shape and device; the tensors of a device are digested in one call over their concatenated
+        bytes, and the values do not depend on that grouping.  Not cryptographic.  A single tensor of a device is digested where it
+        lies; the concatenation of several is a copy -- one more read and write
+        of the bytes around a kernel that runs at the memory rate: a caller whose tensors already lie in one flat resident buffer calls
+        tensor_digest_dbatch on it with their offsets, which copies nothing."""
+        tensors = list(tensors)
+        for t in tensors:
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise TypeError("tensor_digests takes CUDA tensors")
+        out = [None] * len(tensors)
+        for device in sorted({t.device for t in tensors}, key=str):
+            idx = [i for i, t in enumerate(tensors) if t.device == device]
+            with torch.cuda.device(device):
+                for i, d in zip(idx, _group_digests(self, [tensors[i].contiguous().reshape(-1).view(torch.uint8) for i in idx], device)):
+                    out[i] = d
+        return out
+
+    def _group_digests(self, raw, device, src=None):
+        """the digests of the flat uint8 tensors `raw` (src: their concatenation, where the caller has it) as ints"""
+        offs = np.concatenate([[0], np.cumsum([r.numel() for r in raw])]).astype(np.uint64)
+        if src is None:
+            src = raw[0] if len(raw) == 1 and raw[0].numel() else torch.cat(raw) if int(offs[-1]) else torch.zeros(1, dtype=torch.uint8, device=device)[:0]
+        dig, res = tensor_digest_dbatch(self, src, offs)
+        got = torch.cat([dig, res]).cpu().tolist()
+        n = len(raw)
+        if got[n:] != [int(x) for x in np.diff(offs.astype(np.int64))]:
+            raise RuntimeError("tensor_digests: results %s" % (got[n:n + 8],))
+        return [d & 0xFFFFFFFFFFFFFFFF for d in got[:n]]
+
+    for f in (tensor_digest_workspace_bound, tensor_digest_dbatch, tensor_gate_dbatch, tensor_digests):
+        setattr(FseHip, f.__name__, f)
+
     def _not_sparse(obj, what):
         if getattr(obj, "sparse_permille", None) is not None:
             raise ValueError(what + ": the object holds sparse planes (SparsePlanes); windows and patches of those are not supported")
@@ -2545,20 +2651,24 @@ def _planes_methods():
         return _compress_tensors(self, tensors, codec, block_size_id, base,
                                  _seg_log(segment_log, block_size_id if isinstance(block_size_id, numbers.Integral) and 0 <= block_size_id <= 6 else 0))
 
-    def _segmented(obj, segment_log, delta_op="xor", sparse=None):
+    def _segmented(obj, segment_log, delta_op="xor", sparse=None, digests=None):
         if segment_log is not None:
             obj.segment_log = int(segment_log)
         if delta_op != "xor":
             obj.delta_op = delta_op
         if sparse is not None:
             obj.sparse_permille = int(sparse)
+        if digests is not None:
+            obj.base_digests = [int(d) for d in digests]
         return obj
 
     def _compress_tensors(self, tensors, codec, block_size_id, base, segment_log):
         tensors = list(tensors)
         earlier = None
         opname = "xor"
+        digests = None
         if isinstance(base, DeltaBase):                     # the base with its op beside it; a plain sequence means XOR
+            digests = [None] * len(tensors) if base.check else None
             base, opname = base.tensors, base.op
         op = _delta_op(opname)
         if isinstance(codec, CompressedTensors):            # the codecs an earlier AutoCodec call chose, given again
@@ -2579,7 +2689,7 @@ def _planes_methods():
         if not tensors:
             if base is not None and len(list(base)):
                 raise ValueError("base: tensors for none")
-            return _segmented(CompressedTensors([], [], [], None, outer, block_size_id, base is not None), segment_log, opname, sparse)
+            return _segmented(CompressedTensors([], [], [], None, outer, block_size_id, base is not None), segment_log, opname, sparse, digests)
         device = tensors[0].device
         for t in tensors:
             if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
@@ -2627,8 +2737,38 @@ def _planes_methods():
                 groups[-1]["codecs"] = codecs.clone()
             if sfirst is not None:
                 groups[-1]["seg_first"] = sfirst
+            if digests is not None:                         # the base's digests: what the receiver's base has to show
+                for i, d in zip(idx, _group_digests(self, [braw[i] for i in idx], device, bsrc)):
+                    digests[i] = d
         return _segmented(CompressedTensors(groups, [t.dtype for t in tensors], [tuple(t.shape) for t in tensors], device, outer, block_size_id, braw is not None),
-                          segment_log, opname if braw is not None else "xor", sparse)
+                          segment_log, opname if braw is not None else "xor", sparse, digests)
+
+    def _base_copy(braw, g, device, held=None):
+        """the bases of a group back to back, as the copy a group is rebuilt over in place (held: the one that was digested)"""
+        if held is not None:
+            return held
+        return torch.cat([braw[i] for i in g["index"]]) if sum(g["sizes"]) else torch.zeros(1, dtype=torch.uint8, device=device)[:0]
+
+    def _gate_groups(self, obj, braw):
+        """decompress_tensors of an object with base_digests: per group the copy of the given bases, digested, and the gated frame offsets.
+        ValueError naming the tensors whose base is not the one the object was written against -- before any decode launch"""
+        expected = obj.base_digests
+        if braw is None or len(expected) != len(obj.dtypes):
+            raise ValueError("decompress_tensors: base_digests holds %d entries for %d tensors" % (len(expected), len(obj.dtypes)))
+        checked, verdicts = [], []
+        for g in obj.groups:
+            E, idx = g["elem_bytes"], g["index"]
+            offs = np.concatenate([[0], np.cumsum(g["sizes"])]).astype(np.uint64)
+            held = _base_copy(braw, g, obj.device)
+            dig, res = tensor_digest_dbatch(self, held, offs)
+            gated, gres = tensor_gate_dbatch(self, g["frame_offsets"], dig, res, [expected[i] for i in idx], E, g.get("seg_first"))
+            checked.append((held, gated))
+            verdicts.append(gres)
+        got = torch.cat(verdicts).cpu().tolist() if verdicts else []
+        bad = sorted(i for i, r in zip([i for g in obj.groups for i in g["index"]], got) if r < 0)
+        if bad:
+            raise ValueError("decompress_tensors: the base of tensors %s is not the one the object was written against (its digest differs)" % (bad,))
+        return checked
 
     def decompress_tensors(self, obj, base=None):
         """-> the tensors compress_tensors was given, in their order: same dtype, shape and device, the same bytes.  Every tensor owns its memory
@@ -2637,31 +2777,36 @@ def _planes_methods():
         base: for an object with `delta` set, the tensors compress_tensors was given as base (checked for dtype, shape and device, not for
         content: the frames do not say what they are a delta against).  ValueError for a delta object without a base and for a base with a plain
         object.  The bases are not changed: a group is rebuilt in place over a copy of its bases.  The delta's op ("xor" or "sub") is the
-        object's `delta_op`; the base is the plain sequence, or a DeltaBase of the same op (ValueError for another, before any launch)."""
+        object's `delta_op`; the base is the plain sequence, or a DeltaBase of the same op (ValueError for another, before any launch).
+        An object with `base_digests` (written against a DeltaBase(..., check=True)): the given base is digested and compared on the device
+        (tensor_digest_dbatch, tensor_gate_dbatch; one read-back of the verdicts) and ValueError names the tensors whose base is not the one
+        the deltas were made against -- before any decode launch, nothing is written; the readers then run over the gated offsets."""
         base, op = _read_base(obj, base, "decompress_tensors")
         braw = None if base is None else _bases(base, obj.dtypes, obj.shapes, obj.device)
+        checked = _gate_groups(self, obj, braw) if getattr(obj, "base_digests", None) is not None else None
         out = [None] * len(obj.dtypes)
-        for g in obj.groups:
+        for gi, g in enumerate(obj.groups):
             E, sizes = g["elem_bytes"], g["sizes"]
             offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
             blocks = self.planes_block_bound(sum(sizes), len(sizes), E, obj.block_size_id)
             seg_log = getattr(obj, "segment_log", None)
+            held, foff = checked[gi] if checked is not None else (None, g["frame_offsets"])     # (checked: the copy that was digested, the gated offsets)
             if getattr(obj, "sparse_permille", None) is not None:
-                dst = None if braw is None else torch.cat([braw[i] for i in g["index"]]) if sum(sizes) else torch.zeros(1, dtype=torch.uint8, device=obj.device)[:0]
+                dst = None if braw is None else _base_copy(braw, g, obj.device, held)
                 if seg_log is not None:
-                    dst, res = self.tensor_decompress_seg_sparse_dbatch(g["frames"], g["frame_offsets"], offs, E, seg_log, g["seg_first"], base=dst, dst=dst,
+                    dst, res = self.tensor_decompress_seg_sparse_dbatch(g["frames"], foff, offs, E, seg_log, g["seg_first"], base=dst, dst=dst,
                                                                         max_total_blocks=blocks, delta_op=op)
                 else:
-                    dst, res = self.tensor_decompress_sparse_dbatch(g["frames"], g["frame_offsets"], offs, E, base=dst, dst=dst, max_total_blocks=blocks, delta_op=op)
+                    dst, res = self.tensor_decompress_sparse_dbatch(g["frames"], foff, offs, E, base=dst, dst=dst, max_total_blocks=blocks, delta_op=op)
             elif seg_log is not None:
-                dst = None if braw is None else torch.cat([braw[i] for i in g["index"]]) if sum(sizes) else torch.zeros(1, dtype=torch.uint8, device=obj.device)[:0]
-                dst, res = self.tensor_decompress_seg_dbatch(g["frames"], g["frame_offsets"], offs, E, seg_log, g["seg_first"], base=dst, dst=dst,
+                dst = None if braw is None else _base_copy(braw, g, obj.device, held)
+                dst, res = self.tensor_decompress_seg_dbatch(g["frames"], foff, offs, E, seg_log, g["seg_first"], base=dst, dst=dst,
                                                              max_total_blocks=blocks, delta_op=op)
             elif braw is None:
-                dst, res = self.tensor_decompress_dbatch(g["frames"], g["frame_offsets"], offs, E, max_total_blocks=blocks)
+                dst, res = self.tensor_decompress_dbatch(g["frames"], foff, offs, E, max_total_blocks=blocks)
             else:
-                dst = torch.cat([braw[i] for i in g["index"]]) if sum(sizes) else torch.zeros(1, dtype=torch.uint8, device=obj.device)[:0]
-                dst, res = self.tensor_decompress_delta_dbatch(g["frames"], g["frame_offsets"], dst, offs, E, dst=dst, max_total_blocks=blocks, delta_op=op)
+                dst = _base_copy(braw, g, obj.device, held)
+                dst, res = self.tensor_decompress_delta_dbatch(g["frames"], foff, dst, offs, E, dst=dst, max_total_blocks=blocks, delta_op=op)
             got = res.cpu().tolist()
             if got != sizes:
                 raise RuntimeError("decompress_tensors: element size %d, results %s for tensors of %s bytes" % (E, got[:8], sizes[:8]))
@@ -2676,7 +2821,8 @@ def _planes_methods():
         hold a window are decoded (tensor_decompress_window_dbatch): time and scratch follow the windows, not the tensors.
         base: for an object with `delta` set, the WHOLE base tensors as decompress_tensors takes them; the call slices them and does not change
         them.  ValueError for an object without segment_log, a window that is not one, a wrong number of windows, and a base / delta
-        mismatch as in decompress_tensors -- all before any launch."""
+        mismatch as in decompress_tensors -- all before any launch.  `base_digests` of the object are NOT checked here: a digest covers a whole
+        base tensor and would cost more than the window saves."""
         seg_log = getattr(obj, "segment_log", None)
         if seg_log is None:
             raise ValueError("decompress_tensor_windows: the object is not segmented (compress_tensors_segmented writes those)")
@@ -2762,6 +2908,11 @@ def decompress_tensor_windows(obj, windows, base=None):
 def patch_tensor_windows(obj, tensors, windows, base=None):
     """FseHip.patch_tensor_windows on a library handle of the module's own"""
     return _default().patch_tensor_windows(obj, tensors, windows, base)
+
+
+def tensor_digests(tensors):
+    """FseHip.tensor_digests on a library handle of the module's own"""
+    return _default().tensor_digests(tensors)
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -52,6 +52,7 @@ inline unsigned grid_for(size_t n) { return (unsigned)((n + FD_THREADS - 1) / FD
 //  Measured (scripts/framedevbench.py): 0.24 GB/s per item in one lane, 1.5 GB/s in a quad with its loads far enough ahead (below) --
 //  1024 items of 1 MiB in 0.69 instead of 4.3 ms.  A batch only loses to the one-lane form once quads fill every SIMD of the device
 //  (beyond ~16k items), where the call runs at the memory rate either way.  Items start at any alignment (unaligned dword loads).
+//  k_dg_top of planes_digest.hip is a TWIN of this chain (ring and middle loop, two seeds in one launch): a fix here goes there too.
 // =====================================================================================================
 #define XP1 2654435761u
 #define XP2 2246822519u

@@ -1101,6 +1101,66 @@ FSEHIP_API int FSEHIP_tensor_decompress_seg_sparse_dbatch(void* d_dst, const uin
                                                           uint64_t planesCapacity, uint64_t* d_segOffsets, size_t* d_segResults, uint64_t* d_planeOffsets,
                                                           size_t* d_planeSizes, void* d_workspace, size_t workspaceBytes, void* stream);
 
+/* Tensor digests and checked deltas (planes_digest.hip): A DIGEST OF THE BASE AND A GATE AGAINST A WRONG ONE.  Every reading call above
+ * protects the resident tensor from a damaged frame or content; none can tell that the receiver's base is not the one the sender's delta was
+ * made against (a missed step, a rank restored from an older checkpoint, two updates out of order): every frame is intact then, and the
+ * in-place merge writes garbage over good weights and reports success.  The sender digests its base and sends the digests along; the receiver
+ * digests what it holds, and the gate turns a mismatch into frames that every reader refuses.
+ * Like the calls above: launches on `stream` only, capturable, no size leaves the device, argument errors (a null array, 2^31 tensors or
+ * more, a capacity whose launch reaches 2^24 workgroups, a null, misaligned -- 256 bytes -- or too small workspace, elemBytes not 1 / 2 / 4
+ * / 8, 2^31 frames, a frame count that does not fit) are hipErrorInvalidValue, decided before any device call, with nothing written.
+ * THE DIGEST IS NOT CRYPTOGRAPHIC: it is built to catch accidents, not adversaries -- two bases that differ by chance collide with
+ * probability about 2^-64; someone who wants a collision can make one.
+ *
+ *   The digest (normative).  All hashing is XXH32 (the public algorithm, FSEHIP_XXH32_batch) with the seeds S0 = 0 and S1 = 0x9E3779B1;
+ *     T = 32768.  A tensor of n bytes has nt = ceil(n / T) tiles; tile k is its bytes [k T, min((k + 1) T, n)), L of them, counted from the
+ *     tensor's first byte -- the digest depends on nothing but the tensor's bytes: not on its address, its alignment, its neighbours in the
+ *     batch or its slot in d_srcOffsets.
+ *     Lane streams: the tile is cut into 16-byte pieces q = 0 .. ceil(L / 16) - 1, of which only the last may be shorter.  Lane l (0 .. 63)
+ *       owns the pieces with q mod 64 == l; its stream is those pieces concatenated in rising q (512 bytes in a full tile, possibly empty in a
+ *       partial one), and h[l] = XXH32(stream_l, S0).  All 64 lanes produce a hash: an empty stream gives the XXH32 of no bytes.
+ *     Tile digest: H = the 64 values h[l] as 256 bytes, little endian, in lane order; lo = XXH32(H, S0), hi = XXH32(H, S1).
+ *     Tensor digest: A = the tile digests in tile order, each as lo then hi in little-endian 32-bit words, followed by the 8 bytes of n,
+ *       little endian (n = 0: just those 8 zero bytes).  digest = XXH32(A, S0) | (uint64_t)XXH32(A, S1) << 32.
+ *
+ *   FSEHIP_tensor_digest_workspaceBound   host arithmetic (works without a device): eight bytes per work item and per tensor, for the tile
+ *     digests and the sizes behind them; a multiple of 256.  GENERIC for 2^31 tensors or a capacity whose launch reaches 2^24 workgroups.
+ *   FSEHIP_tensor_digest_dbatch   tensor i = [S[i], S[i + 1]) of d_src (S = d_srcOffsets, nTensors + 1 entries, any sizes and alignments;
+ *     `capacity` = the size of d_src, it sizes the launch) -> d_digests[i] and d_results[i] = n_i.  Where S[i] > S[i + 1] or S[i + 1] >
+ *     capacity, d_results[i] = GENERIC and d_digests[i] = 0, and nothing of that tensor is read.  nTensors == 0 is legal.  Offsets are
+ *     expected non-decreasing, as everywhere: around a slot that decreases a tensor may be given tiles of another (never a byte outside
+ *     [0, capacity)) and a digest that is not its own, which the gate then refuses.
+ *     The work: ceil(capacity / T) + nTensors work items in the ragged mapping of "byte planes" (item w takes tile w - first(i) of the tensor
+ *     the search gives it, idle where the tensor has no such tile), a WAVE per item: a round is one coalesced 1 KB read, a lane one 16-byte
+ *     load (unaligned where the tensor is), the loads of eight rounds in flight ahead of the lane's four accumulators; the 64 -> 1 fold by
+ *     cross-lane reads, a lane quad per seed.  No scan, no workgroup waits on another.  The top level is one more launch, a lane quad per
+ *     tensor and seed over the tensor's 8 nt + 8 bytes with the chain of the frame calls' XXH32 kernel: a serial chain per tensor, 256 KB
+ *     of it for one tensor of 1 GiB (about 1.5 GB/s: the known cost of a single giant tensor).
+ *
+ *   FSEHIP_tensor_gate_dbatch   F = d_frameOffsets (nFrames + 1 entries) -> G = d_gatedOffsets (nFrames + 1) and d_gateResults (nTensors).
+ *     Tensor i owns a range of frames: with d_frameFirst == NULL the frames i E .. (i + 1) E - 1, E = elemBytes (nFrames != nTensors * E is
+ *     an argument error); otherwise d_frameFirst is the segFirst of a segmented object (nTensors * E + 1 entries) and tensor i owns the
+ *     frames segFirst[i E] .. segFirst[(i + 1) E] - 1 =: end_i - 1, every value clamped to nFrames.
+ *     Tensor i PASSES iff d_digestResults[i] is no error and d_digests[i] == d_expected[i].
+ *       pass: G[q] = F[q] for its frames; d_gateResults[i] = d_digestResults[i].
+ *       fail: G[q] = F[end_i] for ALL its frames -- the start of the next tensor's first frame; d_gateResults[i] = the digest's own error,
+ *             or corruption_detected for a mismatch.
+ *     G[nFrames] = F[nFrames] either way, and a frame that no tensor owns keeps its offset.
+ *     With a non-decreasing F, G is non-decreasing; every frame of a failed tensor is an EMPTY EXTENT, which every reader answers with
+ *     srcSize_wrong, so the merge refuses the tensor and it keeps every old byte, in place too; the frame in front of a failed tensor runs
+ *     on over frames that are not its own, and a reader stops at its frame's end mark (the windows rely on the same).  G therefore goes
+ *     wherever d_frameOffsets goes above, with no reader changed: the delta calls and their _op siblings, the segmented calls, the window
+ *     calls (G is the full array they select from), the four sparse calls.  d_gateResults tells a wrong base (corruption_detected) from
+ *     damage (the readers' own results).  One thread per entry.
+ *   Out of scope: cryptographic strength; a record of the digest inside the frames (the caller carries the digests beside them); gating of
+ *     FSEHIP_tensor_patch_window_dbatch. */
+FSEHIP_API size_t FSEHIP_tensor_digest_workspaceBound(uint64_t capacity, size_t nTensors);
+FSEHIP_API int FSEHIP_tensor_digest_dbatch(uint64_t* d_digests, size_t* d_results, const void* d_src, const uint64_t* d_srcOffsets, size_t nTensors, uint64_t capacity,
+                                           void* d_workspace, size_t workspaceBytes, void* stream);
+FSEHIP_API int FSEHIP_tensor_gate_dbatch(uint64_t* d_gatedOffsets, size_t* d_gateResults, const uint64_t* d_frameOffsets, size_t nFrames, const uint64_t* d_frameFirst,
+                                         unsigned elemBytes, const uint64_t* d_digests, const size_t* d_digestResults, const uint64_t* d_expected, size_t nTensors,
+                                         void* stream);
+
 /* ---- FSE for 16-bit symbols (lib/fseU16.h:62-80, lib/fseU16.c) -- SURVEY 8(f) rank 4.  Alphabets of up to
  * FSEHIP_FSEU16_MAX_SYMBOL_VALUE + 1 symbols, table logs up to 13 (default 12), ONE tANS state per stream: a different format from
  * the byte coder's.  Sizes of the uncompressed side are in SYMBOLS (as in the reference), strides in bytes.
