@@ -7,6 +7,7 @@ Single-block functions take numpy arrays (host pointers) and have the reference'
 """
 import contextlib
 import ctypes as C
+import json
 import numbers
 
 import numpy as np
@@ -1256,6 +1257,17 @@ class CompressedTensors:
     def nbytes(self):
         """bytes of all frames"""
         return sum(int(g["frames"].numel()) for g in self.groups)
+
+
+class ArchiveInfo(C.Structure):
+    """FSEHIP_ArchiveInfo (include/fsehip.h, "tensor archives"): the 64 header bytes of an archive as they lie in it, and headBytes"""
+    _fields_ = [("magic", C.c_uint32), ("version", C.c_uint16), ("flags", C.c_uint16), ("elemBytes", C.c_uint8), ("blockSizeId", C.c_uint8), ("segLog", C.c_uint8),
+                ("deltaOp", C.c_uint8), ("sparsePermille", C.c_uint16), ("reserved", C.c_uint16), ("nTensors", C.c_uint64), ("nFrames", C.c_uint64),
+                ("totalBytes", C.c_uint64), ("maxTotalBlocks", C.c_uint64), ("metaBytes", C.c_uint64), ("framesBytes", C.c_uint64), ("headBytes", C.c_uint64)]
+
+
+ARCHIVE_MAGIC, ARCHIVE_VERSION = 0x41545346, 1                                       # the bytes F S T A
+ARCHIVE_CODECS, ARCHIVE_DIGESTS, ARCHIVE_SPARSE, ARCHIVE_DELTA = 1, 2, 4, 8          # FSEHIP_ARCHIVE_* (include/fsehip.h)
 
 
 def _planes_methods():
@@ -2590,6 +2602,265 @@ def _planes_methods():
     for f in (tensor_digest_workspace_bound, tensor_digest_dbatch, tensor_gate_dbatch, tensor_digests):
         setattr(FseHip, f.__name__, f)
 
+    # ---- tensor archives (csrc/planes_archive.hip; fsehip.h "tensor archives"): head | frames in one device buffer, sealed behind the frames a
+    # compress call wrote at archive[head_bytes:], opened into the arrays the reading calls take
+    def archive_head_bytes(self, n_tensors, n_frames, flags=0, meta_bytes=0):
+        """the size of an archive's head for these counts (a multiple of 256): the frames start there.  Host arithmetic: needs no device."""
+        self.lib.FSEHIP_archive_headBytes.restype = SZ
+        r = int(self.lib.FSEHIP_archive_headBytes(C.c_uint64(int(n_tensors)), C.c_uint64(int(n_frames)), C.c_uint(int(flags)), C.c_uint64(int(meta_bytes))))
+        if r >= (1 << 62):
+            raise ValueError("archive_head_bytes(%r, %r, %r, %r)" % (n_tensors, n_frames, flags, meta_bytes))
+        return r
+
+    def archive_info(self, elem_bytes, n_tensors, n_frames, total_bytes, flags=0, block_size_id=5, segment_log=0, delta_op=0, sparse_permille=0, max_total_blocks=0,
+                     meta_bytes=0):
+        """the ArchiveInfo a sender hands to archive_seal_dbatch, with head_bytes filled in (framesBytes is the device's to say)"""
+        info = ArchiveInfo(ARCHIVE_MAGIC, ARCHIVE_VERSION, int(flags), _elem(elem_bytes), int(block_size_id), int(segment_log or 0), _delta_op(delta_op),
+                           int(sparse_permille or 0), 0, int(n_tensors), int(n_frames), int(total_bytes), int(max_total_blocks), int(meta_bytes), 0, 0)
+        info.headBytes = archive_head_bytes(self, n_tensors, n_frames, flags, meta_bytes)
+        return info
+
+    def archive_inspect(self, header, archive_bytes):
+        """FSEHIP_archive_inspect: the first 64 bytes of an archive (host bytes / numpy) and the archive's size -> its ArchiveInfo; ValueError
+        with the library's error name and the fields as read where a header rule refuses it.  Needs no device."""
+        raw = np.frombuffer(bytes(header), dtype=np.uint8) if not isinstance(header, np.ndarray) else np.ascontiguousarray(header, dtype=np.uint8)
+        if raw.size < 64:
+            raise ValueError("archive_inspect: %d bytes, the header has 64" % raw.size)
+        info = ArchiveInfo()
+        self.lib.FSEHIP_archive_inspect.restype = SZ
+        r = int(self.lib.FSEHIP_archive_inspect(C.byref(info), VP(raw.ctypes.data), C.c_uint64(int(archive_bytes))))
+        if r >= (1 << 62):
+            raise ValueError("archive header refused (%s) in %d bytes: %s" % (ERROR_NAMES.get((1 << 64) - r, "?"), archive_bytes,
+                                                                              ", ".join("%s=%d" % (k, getattr(info, k)) for k, _ in ArchiveInfo._fields_)))
+        return info
+
+    def archive_workspace_bound(self, n_tensors, n_frames, head_bytes):
+        """the workspace of archive_seal_dbatch and archive_open_dbatch.  Host arithmetic: needs no device."""
+        self.lib.FSEHIP_archive_workspaceBound.restype = SZ
+        r = int(self.lib.FSEHIP_archive_workspaceBound(C.c_uint64(int(n_tensors)), C.c_uint64(int(n_frames)), C.c_uint64(int(head_bytes))))
+        if r >= (1 << 62):
+            raise ValueError("archive_workspace_bound(%r, %r, %r)" % (n_tensors, n_frames, head_bytes))
+        return r
+
+    def _archive_ws(self, workspace, info, device):
+        if workspace is None:
+            return torch.empty(archive_workspace_bound(self, info.nTensors, info.nFrames, info.headBytes), dtype=torch.uint8, device=device)
+        return self._flat(workspace, "workspace")
+
+    def archive_seal_dbatch(self, archive, info, src_offsets, frame_offsets, frame_results, tensor_results, codecs=None, digests=None, meta=None, capacity=None,
+                            result=None, workspace=None):
+        """-> result (a CUDA int64 tensor of one entry: the archive's size head_bytes + framesBytes, or -2 where only the capacity was short and
+        -1 for any other refusal -- the magic is then 0): writes the head of `archive` (a flat CUDA uint8 tensor) in front of the frames that a
+        compress call wrote to archive[info.headBytes:].  src_offsets, frame_offsets, frame_results and tensor_results are that call's arrays
+        as they are; codecs (uint8, with ARCHIVE_CODECS), digests (int64 bits, with ARCHIVE_DIGESTS) and meta (a CUDA uint8 tensor of
+        info.metaBytes) as the flags say.  With src_offsets on the device, result and workspace given the call is launches only."""
+        self._flat(archive, "archive")
+        capacity = _room(self, archive, capacity, "archive")
+        device = archive.device
+        soff, _ = self._offsets(src_offsets, device, False)
+        foff, _ = self._offsets(frame_offsets, device, False)
+        nT, nF = int(info.nTensors), int(info.nFrames)
+        if soff.numel() < nT + 1 or foff.numel() < nF + 1:
+            raise ValueError("archive_seal_dbatch: %d source and %d frame offsets for %d tensors and %d frames" % (soff.numel(), foff.numel(), nT, nF))
+        for what, t, n in (("frame_results", frame_results, nF), ("tensor_results", tensor_results, nT)):
+            if t is None and n:
+                raise ValueError("archive_seal_dbatch: %s of the compress call are needed" % what)
+        res = _i64(self, result, 1, device, "result")
+        fres = _i64(self, _some(frame_results), nF, device, "frame_results") if nF else res      # (an array of no entries still needs an address)
+        tres = _i64(self, _some(tensor_results), nT, device, "tensor_results") if nT else res
+        if info.flags & ARCHIVE_CODECS:
+            codecs = _u8(_some(codecs), nF, device, "codecs")
+        if info.flags & ARCHIVE_DIGESTS:
+            if not isinstance(digests, torch.Tensor):
+                digests = torch.from_numpy(np.asarray([int(d) & 0xFFFFFFFFFFFFFFFF for d in digests], dtype=np.uint64).astype(np.int64)).to(device)
+            digests = _i64(self, _some(digests), nT, device, "digests")
+        if info.metaBytes:
+            meta = _u8(meta, int(info.metaBytes), device, "meta")
+        workspace = _archive_ws(self, workspace, info, device)
+        _check(self.lib.FSEHIP_archive_seal_dbatch(_ptr(archive), C.c_uint64(capacity), _ptr(res), C.byref(info), _ptr(soff), _ptr(foff), _ptr(fres), _ptr(tres),
+                                                   _ptr(codecs if info.flags & ARCHIVE_CODECS else None), _ptr(digests if info.flags & ARCHIVE_DIGESTS else None),
+                                                   _ptr(meta if info.metaBytes else None), _ptr(workspace), SZ(workspace.numel()), _stream()), "archive_seal_dbatch")
+        return res
+
+    def archive_open_dbatch(self, archive, info, archive_bytes=None, src_offsets=None, frame_offsets=None, codecs=None, digests=None, seg_first=None, verdict=None,
+                            workspace=None):
+        """-> dict(verdict, src_offsets, frame_offsets, codecs, digests, seg_first): the arrays of the archive at the start of `archive` (a flat
+        CUDA uint8 tensor; `info` from archive_inspect of its first 64 bytes) as the reading calls take them, with frames =
+        archive[info.headBytes:].  verdict (one int64 entry): the archive's size, or -4 -- then EVERY frame offset is 0 and every reader refuses
+        every frame.  codecs / digests / seg_first are None where the archive has none.  With the outputs and the workspace given the call is
+        launches only."""
+        self._flat(archive, "archive")
+        nbytes = _room(self, archive, archive_bytes, "archive")
+        device = archive.device
+        nT, nF, E = int(info.nTensors), int(info.nFrames), int(info.elemBytes)
+        soff = _i64(self, src_offsets, nT + 1, device, "src_offsets")
+        foff = _i64(self, frame_offsets, nF + 1, device, "frame_offsets")
+        cod = dig = first = None
+        if info.flags & ARCHIVE_CODECS:
+            cod = torch.zeros(max(nF, 1), dtype=torch.uint8, device=device) if codecs is None else _u8(codecs, nF, device, "codecs")
+        if info.flags & ARCHIVE_DIGESTS:
+            dig = _i64(self, digests if digests is not None or nT else torch.zeros(1, dtype=torch.int64, device=device), nT, device, "digests")
+        if info.segLog:
+            first = _i64(self, seg_first, nT * E + 1, device, "seg_first")
+        ver = _i64(self, verdict, 1, device, "verdict")
+        workspace = _archive_ws(self, workspace, info, device)
+        _check(self.lib.FSEHIP_archive_open_dbatch(_ptr(soff), _ptr(foff), _ptr(cod), _ptr(dig), _ptr(first), _ptr(ver), _ptr(archive), C.c_uint64(nbytes), C.byref(info),
+                                                   _ptr(workspace), SZ(workspace.numel()), _stream()), "archive_open_dbatch")
+        return dict(verdict=ver, src_offsets=soff, frame_offsets=foff, codecs=None if cod is None else cod[:nF], digests=None if dig is None else dig[:nT],
+                    seg_first=first)
+
+    def _codec_to_json(codec):
+        if isinstance(codec, SparsePlanes):
+            return {"sparse": _codec_to_json(codec.codec), "permille": codec.permille}
+        if isinstance(codec, AutoCodec):
+            return {"auto": codec.tolerance_permille}
+        return int(codec)
+
+    def _codec_from_json(j):
+        if isinstance(j, dict) and "sparse" in j:
+            return SparsePlanes(_codec_from_json(j["sparse"]), j["permille"])
+        if isinstance(j, dict) and "auto" in j:
+            return AutoCodec(j["auto"])
+        return int(j)
+
+    def archive_tensors(self, obj):
+        """a CompressedTensors -> ONE flat CUDA uint8 tensor that holds all of it (include/fsehip.h "tensor archives"): one archive per group of
+        obj.groups back to back, each at a multiple of 256 (an object without groups: one archive of no tensors), ready to be sent or written
+        as it lies; open_archive restores the object from it.  A group's head carries its sizes, frame offsets, codecs, the digests of
+        its bases and the scalars (element size, block_size_id, segment_log, delta_op, sparse_permille, the block promise); what C has no
+        notion of -- the group's tensor indices, the dtypes and shapes, the number of groups and of tensors, obj.codec -- travels as JSON in
+        the head's meta bytes.  THE FRAMES ARE COPIED HERE, device to device, behind their head: the object owns its frames elsewhere.  The
+        path without a copy is the C one, where the compress call writes at d_archive + headBytes (archive_head_bytes, archive_seal_dbatch).
+        One read-back per group (the seal's result); RuntimeError where the device refuses to seal."""
+        if not isinstance(obj, CompressedTensors):
+            raise TypeError("archive_tensors takes a CompressedTensors")
+        device = obj.device if obj.device is not None else torch.device("cuda", torch.cuda.current_device())
+        seg, sparse, digs = getattr(obj, "segment_log", None), getattr(obj, "sparse_permille", None), getattr(obj, "base_digests", None)
+        n_groups = len(obj.groups)
+        parts = []
+        for gi, g in enumerate(obj.groups or [None]):
+            E, idx, sizes = (1, [], []) if g is None else (g["elem_bytes"], list(g["index"]), list(g["sizes"]))
+            meta = json.dumps(dict(v=1, group=gi, groups=n_groups, tensors=len(obj.dtypes), index=idx, dtypes=[str(obj.dtypes[i]).replace("torch.", "") for i in idx],
+                                   shapes=[list(obj.shapes[i]) for i in idx], codec=_codec_to_json(obj.codec), device_index=device.index),
+                              separators=(",", ":")).encode()
+            flags = (ARCHIVE_DELTA if obj.delta else 0) | (ARCHIVE_SPARSE if sparse is not None else 0)
+            flags |= (ARCHIVE_CODECS if g is not None and "codecs" in g else 0) | (ARCHIVE_DIGESTS if digs is not None and obj.delta else 0)
+            nF = 0 if g is None else g["frame_offsets"].numel() - 1
+            info = archive_info(self, E, len(sizes), nF, sum(sizes), flags, obj.block_size_id, seg or 0, getattr(obj, "delta_op", "xor") if obj.delta else 0,
+                                sparse or 0, self.planes_block_bound(sum(sizes), len(sizes), E, obj.block_size_id), len(meta))
+            head = int(info.headBytes)
+            fb = 0 if g is None else int(g["frames"].numel())
+            with torch.cuda.device(device):
+                buf = torch.zeros((head + fb + 255) // 256 * 256, dtype=torch.uint8, device=device)
+                if fb:
+                    buf[head:head + fb] = g["frames"]
+                zero = torch.zeros(1, dtype=torch.int64, device=device)
+                res = archive_seal_dbatch(self, buf, info, np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64), zero if g is None else g["frame_offsets"],
+                                          None if g is None else g["frame_results"], None if g is None else g["tensor_results"],
+                                          codecs=g["codecs"] if flags & ARCHIVE_CODECS else None,
+                                          digests=[digs[i] for i in idx] if flags & ARCHIVE_DIGESTS else None,
+                                          meta=torch.from_numpy(np.frombuffer(meta, np.uint8).copy()).to(device), capacity=head + fb)
+                got = int(res.item())
+            if got != head + fb:
+                raise RuntimeError("archive_tensors: group %d was not sealed (%d for %d bytes)" % (gi, got, head + fb))
+            parts.append(buf)
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+    def open_archive(self, buf):
+        """what archive_tensors wrote -> the CompressedTensors: a flat CUDA uint8 tensor, or host bytes / a numpy uint8 array (uploaded to the
+        current device).  The groups' frames are VIEWS into the buffer; segment_log, delta, delta_op, sparse_permille, base_digests, codec,
+        dtypes and shapes are restored.  frame_results are the extents of the frame offsets and tensor_results the sizes: an archive exists
+        only of frames that succeeded.  Per archive one 64-byte read-back for the header, FSEHIP_archive_open_dbatch, and one read-back of the
+        verdict, the sizes and the meta bytes.  ValueError names what was refused: the header (with the library's error and the fields), the
+        archive on the device (its digest, an index rule or a header that differs), or the meta bytes."""
+        if not isinstance(buf, torch.Tensor):
+            host = np.frombuffer(bytes(buf), dtype=np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+            buf = torch.from_numpy(host.copy()).cuda()
+        self._flat(buf, "buf")
+        device, total = buf.device, buf.numel()
+        if total == 0:
+            raise ValueError("open_archive: no bytes")
+        groups, metas, at = [], [], 0
+        with torch.cuda.device(device):
+            while at < total:
+                k = len(groups)
+                if total - at < 64:
+                    raise ValueError("open_archive: archive %d at byte %d: %d bytes, the header has 64" % (k, at, total - at))
+                try:
+                    info = archive_inspect(self, buf[at:at + 64].cpu().numpy(), total - at)
+                except ValueError as e:
+                    raise ValueError("open_archive: archive %d at byte %d: %s" % (k, at, e)) from None
+                head, fb, nT, nF = int(info.headBytes), int(info.framesBytes), int(info.nTensors), int(info.nFrames)
+                view = buf[at:at + head + fb]
+                out = archive_open_dbatch(self, view, info)
+                moff = 64 + 8 * nT + 8 * (nF + 1) + (8 * nT if info.flags & ARCHIVE_DIGESTS else 0) + ((nF + 7) // 8 * 8 if info.flags & ARCHIVE_CODECS else 0)
+                got = torch.cat([out["verdict"], out["src_offsets"], out["digests"] if out["digests"] is not None else out["verdict"][:0]]).cpu().tolist()
+                if got[0] != head + fb:
+                    raise ValueError("open_archive: archive %d at byte %d was refused on the device (%s): its digest, an index rule or its header"
+                                     % (k, at, ERROR_NAMES.get(-got[0], got[0])))
+                try:
+                    meta = json.loads(bytes(view[moff:moff + int(info.metaBytes)].cpu().numpy()).decode())
+                    assert meta["v"] == 1 and meta["group"] == k and len(meta["index"]) == len(meta["dtypes"]) == len(meta["shapes"]) == nT
+                    dtypes = [getattr(torch, d) for d in meta["dtypes"]]
+                    assert all(isinstance(d, torch.dtype) for d in dtypes)
+                    codec = _codec_from_json(meta["codec"])
+                except Exception as e:
+                    raise ValueError("open_archive: archive %d at byte %d: its meta bytes are not archive_tensors' (%s)" % (k, at, e)) from None
+                S = got[1:nT + 2]
+                g = dict(elem_bytes=int(info.elemBytes), index=[int(i) for i in meta["index"]], sizes=[b - a for a, b in zip(S, S[1:])], frames=view[head:head + fb],
+                         frame_offsets=out["frame_offsets"], frame_results=out["frame_offsets"][1:] - out["frame_offsets"][:-1],
+                         tensor_results=out["src_offsets"][1:] - out["src_offsets"][:-1])
+                if out["codecs"] is not None:
+                    g["codecs"] = out["codecs"]
+                if out["seg_first"] is not None:
+                    g["seg_first"] = out["seg_first"].cpu().numpy().astype(np.uint64)
+                g["_info"], g["_meta"], g["_dtypes"], g["_codec"] = info, meta, dtypes, codec
+                g["_digests"] = [d & 0xFFFFFFFFFFFFFFFF for d in got[nT + 2:]] if out["digests"] is not None else None
+                groups.append(g)
+                at += (head + fb + 255) // 256 * 256
+                if len(groups) >= max(meta["groups"], 1):
+                    break
+        first, m0 = groups[0]["_info"], groups[0]["_meta"]
+        n = int(m0["tensors"])
+        if any(g["_meta"]["groups"] != m0["groups"] or g["_meta"]["tensors"] != n for g in groups) or len(groups) != max(m0["groups"], 1):
+            raise ValueError("open_archive: %d archives of an object of %d groups" % (len(groups), m0["groups"]))
+        dtypes, shapes = [None] * n, [None] * n
+        digests = [None] * n if any(g["_digests"] is not None for g in groups) else None
+        for g in groups:
+            for k, i in enumerate(g["index"]):
+                if not 0 <= i < n or dtypes[i] is not None:
+                    raise ValueError("open_archive: tensor index %r of %d tensors" % (i, n))
+                dtypes[i], shapes[i] = g["_dtypes"][k], tuple(int(x) for x in g["_meta"]["shapes"][k])
+                if digests is not None:
+                    digests[i] = g["_digests"][k]
+        if any(d is None for d in dtypes):
+            raise ValueError("open_archive: the archives hold %d of %d tensors" % (sum(d is not None for d in dtypes), n))
+        delta = bool(first.flags & ARCHIVE_DELTA)
+        codec = groups[0]["_codec"]
+        for g in groups:
+            for k in ("_info", "_meta", "_dtypes", "_codec", "_digests"):
+                del g[k]
+        obj = CompressedTensors(groups if m0["groups"] else [], dtypes, shapes, device if n else None, codec, int(first.blockSizeId), delta)
+        return _segmented(obj, int(first.segLog) if first.segLog else None, "sub" if delta and first.deltaOp else "xor",
+                          int(first.sparsePermille) if first.flags & ARCHIVE_SPARSE else None, digests)
+
+    def save_tensors(self, obj, path):
+        """archive_tensors(obj) written to the file `path` as it lies -> the number of bytes"""
+        data = archive_tensors(self, obj).cpu().numpy()
+        with open(path, "wb") as f:
+            f.write(data.tobytes())
+        return int(data.size)
+
+    def load_tensors(self, path, device="cuda"):
+        """open_archive of the file save_tensors wrote, uploaded to `device`"""
+        with open(path, "rb") as f:
+            data = np.frombuffer(f.read(), dtype=np.uint8)
+        return open_archive(self, torch.from_numpy(data.copy()).to(device))
+
+    for f in (archive_head_bytes, archive_info, archive_inspect, archive_workspace_bound, archive_seal_dbatch, archive_open_dbatch, archive_tensors, open_archive,
+              save_tensors, load_tensors):
+        setattr(FseHip, f.__name__, f)
+
     def _not_sparse(obj, what):
         if getattr(obj, "sparse_permille", None) is not None:
             raise ValueError(what + ": the object holds sparse planes (SparsePlanes); windows and patches of those are not supported")
@@ -2913,6 +3184,26 @@ def patch_tensor_windows(obj, tensors, windows, base=None):
 def tensor_digests(tensors):
     """FseHip.tensor_digests on a library handle of the module's own"""
     return _default().tensor_digests(tensors)
+
+
+def archive_tensors(obj):
+    """FseHip.archive_tensors on a library handle of the module's own"""
+    return _default().archive_tensors(obj)
+
+
+def open_archive(buf):
+    """FseHip.open_archive on a library handle of the module's own"""
+    return _default().open_archive(buf)
+
+
+def save_tensors(obj, path):
+    """FseHip.save_tensors on a library handle of the module's own"""
+    return _default().save_tensors(obj, path)
+
+
+def load_tensors(path, device="cuda"):
+    """FseHip.load_tensors on a library handle of the module's own"""
+    return _default().load_tensors(path, device)
 
 
 # ---------------------------------------------------------------------------------------------------------

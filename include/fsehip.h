@@ -1161,6 +1161,99 @@ FSEHIP_API int FSEHIP_tensor_gate_dbatch(uint64_t* d_gatedOffsets, size_t* d_gat
                                          unsigned elemBytes, const uint64_t* d_digests, const size_t* d_digestResults, const uint64_t* d_expected, size_t nTensors,
                                          void* stream);
 
+/* Tensor archives (planes_archive.hip): ONE SEALED DEVICE BUFFER PER BATCH, OPENED ON THE DEVICE.  Every tensor call above leaves a piece of
+ * state outside the frames -- the sizes, the frame offsets, the op of a delta, segLog, the sparse threshold, the codecs, the digests of the
+ * base -- and a receiver that gets one of them wrong decodes garbage.  An archive is `head | frames`: one contiguous buffer that a sender
+ * hands to a send call or writes to a file as it lies, and that a receiver opens with launches only into exactly the arrays the reading calls
+ * above take.  No frame byte and no call above changes: the archive is a head in front of the frames the compress composites (or the patch
+ * composite) already write.  headBytes is host arithmetic over counts alone, so the sender gives the composite `d_archive + headBytes` as its
+ * destination and the frames are written in place: there is no copy pass.
+ *
+ *   The format (normative, little endian; a model in tests/archive_corpus.py).  headBytes is a multiple of 256.
+ *     Header, 64 bytes:
+ *        0  u32  magic: the bytes 'F' 'S' 'T' 'A' (FSEHIP_ARCHIVE_MAGIC as a little-endian number)
+ *        4  u16  version = 1
+ *        6  u16  flags: FSEHIP_ARCHIVE_CODECS | _DIGESTS | _SPARSE | _DELTA, every other bit zero; DIGESTS only with DELTA
+ *        8  u8   elemBytes (1, 2, 4, 8)          9  u8  blockSizeId (0 .. 6)
+ *       10  u8   segLog: 0 = unsegmented, else 10 + blockSizeId .. 30 (the rule of "segmented planes")
+ *       11  u8   deltaOp: FSEHIP_DELTA_XOR / _SUB; 0 unless DELTA
+ *       12  u16  sparsePermille (<= 1000); 0 unless SPARSE           14  u16  zero
+ *       16  u64  nTensors        24  u64  nFrames (unsegmented: exactly nTensors * elemBytes; segmented: at least that; below 2^31)
+ *       32  u64  totalBytes = the sum of the tensor sizes.  nTensors and totalBytes stay inside the launch limit of the composites:
+ *                totalBytes < 2^46 and floor(totalBytes / 32768) + 1 + nTensors < 2^24
+ *       40  u64  maxTotalBlocks (< 2^31): a block promise under which the packed reader accepts these frames -- what the sender gave its writer
+ *       48  u64  metaBytes (< 2^31)      56  u64  framesBytes = frameOffsets[nFrames]
+ *     Index, from byte 64, every array 8-byte aligned:
+ *       1. the tensor sizes, nTensors x u64
+ *       2. the frame offsets relative to the first frame byte, (nFrames + 1) x u64: the first is 0, they do not decrease, the last is framesBytes
+ *       3. with DIGESTS: the digests of the base tensors, nTensors x u64
+ *       4. with CODECS: nFrames codec bytes (0 = FSE, 1 = Huff0), zero-padded to a multiple of 8
+ *       5. metaBytes opaque bytes of the caller's, zero-padded to a multiple of 8
+ *       6. zeros up to headBytes - 8
+ *       7. the last 8 bytes of the head: the digest of the bytes [0, headBytes - 8), as FSEHIP_tensor_digest_dbatch defines it for one tensor
+ *     headBytes = 64 + the index + 8, rounded up to 256.  The frames keep their own XXH32.  NOT CRYPTOGRAPHIC, like the digest itself.
+ *     segFirst is not stored: it is FSEHIP_planes_segmentFirst of the sizes, elemBytes and segLog; open recomputes it on the device and checks
+ *     its total against nFrames.
+ *
+ *   FSEHIP_archive_headBytes   host arithmetic: headBytes for these counts, or GENERIC (an unknown flag bit, nTensors >= 2^24, nFrames or
+ *     metaBytes >= 2^31).
+ *   FSEHIP_archive_inspect   parses and validates the 64 header bytes at h_header64 (host memory: the one small transfer a receiver makes,
+ *     as FSEHIP_frame_inspect needs for a frame) of an archive of archiveBytes bytes; fills *out with every field and headBytes; returns
+ *     headBytes or: GENERIC (a null argument, a wrong magic, another version), corruption_detected (a field outside its range above, an
+ *     unknown flag bit, a broken coupling, nTensors == 0 with totalBytes != 0), srcSize_wrong (archiveBytes < 64, headBytes > archiveBytes,
+ *     framesBytes > archiveBytes - headBytes).  On an error *out holds the fields as far as they were read, headBytes 0.
+ *   FSEHIP_archive_workspaceBound   host arithmetic, a multiple of 256, for seal and open alike; GENERIC for counts headBytes refuses or a
+ *     headBytes that is no multiple of 256.
+ *
+ *   Both device calls: launches on `stream` only, capturable; every argument error (a null array that the flags need, d_archive not 8-byte
+ *   aligned, a workspace that is null, not 256-byte aligned or below the bound, an info that inspect would refuse or whose headBytes is not
+ *   FSEHIP_archive_headBytes of its counts, a capacity below headBytes) is hipErrorInvalidValue, decided before the first launch with nothing
+ *   written.
+ *   FSEHIP_archive_seal_dbatch   writes the head in front of the frames that lie at d_archive + info->headBytes.  The inputs are the writer's
+ *     outputs as they are: d_srcOffsets (nTensors + 1), d_frameOffsets (nFrames + 1, relative to the first frame byte), d_frameResults
+ *     (nFrames), d_tensorResults (nTensors); d_codecs (nFrames bytes) with CODECS, d_digests (nTensors) with DIGESTS, d_meta (metaBytes, host
+ *     order of bytes) where metaBytes > 0.  info->framesBytes and info->magic / version are ignored: framesBytes is read from the device.
+ *     A thread per 8-byte word of the head writes it (coalesced stores) and checks what it wrote; the verdict is the OR over all of them, and
+ *     the head is accepted only if: every frame result and tensor result is a success and no frame result exceeds its extent; the frame
+ *     offsets start at 0, do not decrease and end within archiveCapacity - headBytes; the source offsets do not decrease and span totalBytes;
+ *     every codec byte is <= 1.  Then the digest of the head and the stamp: *d_result = headBytes + framesBytes, the archive's size -- or,
+ *     on refusal, dstSize_tooSmall (only the capacity was short) or GENERIC, and THE MAGIC IS WRITTEN AS 0: an unsealed buffer can never be
+ *     opened.
+ *   FSEHIP_archive_open_dbatch   d_archive of archiveBytes and the info that inspect filled from its first 64 bytes -> d_srcOffsets
+ *     (nTensors + 1: the exclusive scan of the sizes from 0), d_frameOffsets (nFrames + 1), with CODECS d_codecs (nFrames bytes), with
+ *     DIGESTS d_digests (nTensors), for a segmented archive d_segFirst (nTensors * elemBytes + 1: the per-plane segment counts, scanned on
+ *     the device) and *d_verdict = headBytes + framesBytes or corruption_detected.  The readers are then called with d_frames = d_archive +
+ *     headBytes.  The host's copy of the header is not trusted: the device header must equal info word for word.  Refused are: a header that
+ *     differs from info, a digest mismatch, a size above totalBytes or sizes that do not sum to it, a segment total that is not nFrames,
+ *     frame offsets that break a rule of the format, a codec byte above 1, a non-zero padding byte.  ON REFUSAL EVERY d_frameOffsets ENTRY
+ *     IS 0: empty extents, which every reader refuses (the gate of "tensor digests and checked deltas" relies on the same), so a damaged
+ *     archive opened over resident weights and read in place leaves them untouched.  No value read from the archive is used as an index;
+ *     codec bytes are stored clamped to 1.
+ *   Out of scope: encryption or cryptographic integrity; archives that span element sizes (a caller concatenates one archive per element
+ *     size, each at a multiple of 256, as the Python layer does); streaming a partially received archive; big-endian hosts; a compress call
+ *     that allocates its frames inside an archive by itself. */
+#define FSEHIP_ARCHIVE_MAGIC 0x41545346u
+#define FSEHIP_ARCHIVE_VERSION 1u
+#define FSEHIP_ARCHIVE_CODECS 1u
+#define FSEHIP_ARCHIVE_DIGESTS 2u
+#define FSEHIP_ARCHIVE_SPARSE 4u
+#define FSEHIP_ARCHIVE_DELTA 8u
+typedef struct {                 /* the first 64 bytes are the header as it lies in the archive */
+    uint32_t magic; uint16_t version; uint16_t flags;
+    uint8_t elemBytes, blockSizeId, segLog, deltaOp; uint16_t sparsePermille; uint16_t reserved;
+    uint64_t nTensors, nFrames, totalBytes, maxTotalBlocks, metaBytes, framesBytes;
+    uint64_t headBytes;
+} FSEHIP_ArchiveInfo;
+FSEHIP_API size_t FSEHIP_archive_headBytes(uint64_t nTensors, uint64_t nFrames, unsigned flags, uint64_t metaBytes);
+FSEHIP_API size_t FSEHIP_archive_inspect(FSEHIP_ArchiveInfo* out, const void* h_header64, uint64_t archiveBytes);
+FSEHIP_API size_t FSEHIP_archive_workspaceBound(uint64_t nTensors, uint64_t nFrames, uint64_t headBytes);
+FSEHIP_API int FSEHIP_archive_seal_dbatch(void* d_archive, uint64_t archiveCapacity, size_t* d_result, const FSEHIP_ArchiveInfo* info, const uint64_t* d_srcOffsets,
+                                          const uint64_t* d_frameOffsets, const size_t* d_frameResults, const size_t* d_tensorResults, const uint8_t* d_codecs,
+                                          const uint64_t* d_digests, const void* d_meta, void* d_workspace, size_t workspaceBytes, void* stream);
+FSEHIP_API int FSEHIP_archive_open_dbatch(uint64_t* d_srcOffsets, uint64_t* d_frameOffsets, uint8_t* d_codecs, uint64_t* d_digests, uint64_t* d_segFirst, size_t* d_verdict,
+                                          const void* d_archive, uint64_t archiveBytes, const FSEHIP_ArchiveInfo* info, void* d_workspace, size_t workspaceBytes,
+                                          void* stream);
+
 /* ---- FSE for 16-bit symbols (lib/fseU16.h:62-80, lib/fseU16.c) -- SURVEY 8(f) rank 4.  Alphabets of up to
  * FSEHIP_FSEU16_MAX_SYMBOL_VALUE + 1 symbols, table logs up to 13 (default 12), ONE tANS state per stream: a different format from
  * the byte coder's.  Sizes of the uncompressed side are in SYMBOLS (as in the reference), strides in bytes.
