@@ -666,6 +666,33 @@ def _huf_methods():
             g.check("HUF_buildCTable_batch")
         return ct, hdr, res
 
+    # the Huff0 table glue on the caller's statistics (include/fsehip.h "Table glue, step by step"; lib/huf.h:204-218)
+    def huf_build_ctable_from_count_batch(self, counts, max_symbol_values, max_nb_bits=0, ctables=None, ctable_stride_u32=256, results=None):
+        """HUF_buildCTable per row of `counts` (n, 256) int32: (ctables (n, ctable_stride_u32) int32 HUF_CElt -- zero above each row's
+        maxSymbolValue --, results = table log or error).  Entries of a row above its maxSymbolValue are ignored."""
+        n = counts.shape[0]
+        if ctables is None:
+            ctables = torch.zeros((n, ctable_stride_u32), dtype=torch.int32, device=counts.device)
+        res = torch.zeros(n, dtype=torch.int64, device=counts.device) if results is None else results
+        _check(self.lib.FSEHIP_HUF_buildCTable_fromCount_batch(_ptr(ctables), SZ(ctables.stride(0)), _ptr(counts), SZ(counts.stride(0)), _ptr(max_symbol_values),
+                                                               C.c_uint(max_nb_bits), SZ(n), _ptr(res), _stream()), "HUF_buildCTable_fromCount_batch")
+        return ctables, res
+
+    def huf_write_ctable_batch(self, ctables, max_symbol_values, huff_log, header_capacity=256, header_stride=None, results=None):
+        """HUF_writeCTable per row of `ctables` (n, >= 256) int32 HUF_CElt: (headers (n, header_stride or header_capacity) uint8 pre-filled with
+        0xA5, results = header bytes or error).  Entries of a row above its maxSymbolValue are ignored."""
+        n = ctables.shape[0]
+        hdr, g = self._dst(n, max(header_stride or 0, header_capacity), ctables.device)
+        hdr.fill_(0xA5)
+        res = torch.zeros(n, dtype=torch.int64, device=ctables.device) if results is None else results
+        _check(self.lib.FSEHIP_HUF_writeCTable_batch(_ptr(hdr), SZ(hdr.stride(0)), SZ(header_capacity), _ptr(ctables), SZ(ctables.stride(0)), _ptr(max_symbol_values),
+                                                     C.c_uint(huff_log), SZ(n), _ptr(res), _stream()), "HUF_writeCTable_batch")
+        if g:                                                  # the guard bytes behind the row, and what lies between the capacity and the row's end
+            g.check("HUF_writeCTable_batch")
+            if bool((hdr[:, header_capacity:] != 0xA5).any().item()):
+                raise AssertionError("HUF_writeCTable_batch wrote past its header capacity (%d) inside the row" % header_capacity)
+        return hdr, res
+
     def huf_read_dtable_x1_batch(self, csrc, csizes, max_table_log=11):
         """HUF_readDTableX1_batch: (dtables (n, 1 + (1 << max_table_log)) int32, results = header bytes or error)"""
         n = _blocks(csrc, "csrc").shape[0]
@@ -847,7 +874,7 @@ def _huf_methods():
         return self._single("FSEHIP_HUF_decompress4X_usingDTable", dst_size, csrc, dt.ctypes.data_as(VP))
 
     for f in (huf_decompress1x1_using_dtable_batch, huf_decompress1x_using_dtable_batch, huf_decompress1x1_using_dtable, huf_decompress1x_using_dtable,
-              huf_decompress_packed_batch, huf_build_ctable_batch, huf_read_dtable_x1_batch, huf_workspace, huf_compress_batch, huf_decompress_batch, huf_compress4x_using_ctable_batch, huf_compress1x_using_ctable_batch,
+              huf_decompress_packed_batch, huf_build_ctable_batch, huf_build_ctable_from_count_batch, huf_write_ctable_batch, huf_read_dtable_x1_batch, huf_workspace, huf_compress_batch, huf_decompress_batch, huf_compress4x_using_ctable_batch, huf_compress1x_using_ctable_batch,
               huf_decompress4x1_using_dtable_batch, huf_decompress4x_using_dtable_batch, huf_compress2, huf_decompress, huf_compress1x_using_ctable,
               huf_compress4x_using_ctable, huf_decompress4x1_using_dtable, huf_decompress4x_using_dtable,
               huf_build_ctable, huf_write_ctable, huf_read_dtable_x1, huf_compress1x, huf_decompress4x1, huf_decompress1x1,

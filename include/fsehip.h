@@ -332,7 +332,9 @@ FSEHIP_API int FSEHIP_HUF_buildCTable_batch(FSEHIP_HUF_CElt* d_ctables, size_t c
                                             unsigned maxSymbolValue, unsigned tableLog, size_t nBlocks, void* d_workspace, size_t workspaceBytes, void* stream);
 /*   HUF_buildCTable_fromCount / HUF_writeCTable : the two halves of HUF_buildCTable_batch on the CALLER's statistics -- d_counts + b*256 holds
  *                            count[0 .. d_maxSymbolValues[b]] (countStride must be 256), d_ctables + b*ctableStrideU32 the 256 HUF_CElt of table b
- *                            (ctableStrideU32 >= 256, a multiple of 4); d_results[b] = the table log / the header size, or an error. */
+ *                            (ctableStrideU32 >= 256, a multiple of 4: anything else is hipErrorInvalidValue from both calls, nothing launched);
+ *                            d_results[b] = the table log / the header size, or an error.  Entries of count[] and of the HUF_CElt row above
+ *                            d_maxSymbolValues[b] are ignored and may hold anything (the built table is zero there). */
 FSEHIP_API int FSEHIP_HUF_buildCTable_fromCount_batch(FSEHIP_HUF_CElt* d_ctables, size_t ctableStrideU32, const unsigned* d_counts, size_t countStride,
                                                       const unsigned* d_maxSymbolValues, unsigned maxNbBits, size_t nBlocks, size_t* d_results, void* stream);
 FSEHIP_API int FSEHIP_HUF_writeCTable_batch(void* d_headers, size_t headerStride, size_t headerCapacity, const FSEHIP_HUF_CElt* d_ctables, size_t ctableStrideU32,
