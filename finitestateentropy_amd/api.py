@@ -68,6 +68,28 @@ class SparsePlanes:
         return hash(("SparsePlanes", self.codec, self.permille))
 
 
+class PredictedPlanes:
+    """`codec` of compress_tensors and compress_tensors_segmented: the planes are those of zigzag(element - the element in front of it), the
+    elements taken as unsigned integers and the predecessor as 0 at the start of every run of 1024 elements (include/fsehip.h "predicted
+    planes").  `codec` is what codes them: 0 (FSE), 1 (Huff0) or an AutoCodec.  For tensors whose neighbours are close -- sorted indices,
+    offsets, position ids, sampled fields, audio; weights get worse.  Opt-in, never chosen automatically.  The object written carries
+    `predictor` ("prev"); decompress_tensors reads it.  Not combined with a base or with SparsePlanes; no windows, no patches."""
+
+    def __init__(self, codec=0):
+        if not isinstance(codec, AutoCodec) and (isinstance(codec, (bool, SparsePlanes, PredictedPlanes)) or codec not in (0, 1)):
+            raise ValueError("PredictedPlanes: codec %r, 0 (FSE), 1 (Huff0) or an AutoCodec is needed" % (codec,))
+        self.codec = codec if isinstance(codec, AutoCodec) else int(codec)
+
+    def __repr__(self):
+        return "PredictedPlanes(%r)" % (self.codec,)
+
+    def __eq__(self, other):
+        return isinstance(other, PredictedPlanes) and other.codec == self.codec
+
+    def __hash__(self):
+        return hash(("PredictedPlanes", self.codec))
+
+
 DELTA_OPS = {"xor": 0, "sub": 1}        # FSEHIP_DELTA_XOR / FSEHIP_DELTA_SUB (include/fsehip.h)
 
 
@@ -1270,11 +1292,14 @@ class CompressedTensors:
     calls take it from here.  `sparse_permille` (None, or the integer of the SparsePlanes the object was written with): the frames hold sparse
     contents -- `codec` is then that SparsePlanes -- and decompress_tensors reads them as such; windows and patches of such an object are
     refused.  `base_digests` (None, or one int per tensor in tensor order where the object was written against a DeltaBase(..., check=True)):
-    the 64-bit digests of the base tensors; decompress_tensors refuses a base whose digests differ."""
+    the 64-bit digests of the base tensors; decompress_tensors refuses a base whose digests differ.  `predictor` (None, or "prev" where the
+    object was written with a PredictedPlanes -- `codec` is then that PredictedPlanes): the frames hold the planes of the neighbour
+    differences, and decompress_tensors sums them back; windows and patches of such an object are refused."""
     segment_log = None
     delta_op = "xor"
     sparse_permille = None
     base_digests = None
+    predictor = None
 
     def __init__(self, groups, dtypes, shapes, device, codec, block_size_id, delta=False):
         self.groups, self.dtypes, self.shapes, self.device, self.codec, self.block_size_id = groups, dtypes, shapes, device, codec, block_size_id
@@ -2531,6 +2556,168 @@ def _planes_methods():
               tensor_compress_seg_sparse_dbatch, tensor_decompress_seg_sparse_dbatch):
         setattr(FseHip, f.__name__, f)
 
+    # ---- predicted planes (csrc/planes_pred.hip; fsehip.h "predicted planes"): the planes of zigzag(element - the element in front of it)
+    # in runs of 1024 elements, the difference fused into the split and the run sums into the merge
+    def planes_split_pred_dbatch(self, src, src_offsets, elem_bytes, capacity=None, planes=None, plane_offsets=None, results=None):
+        """planes_split_dbatch of the neighbour differences: the same layout, offsets and results.  For every elem_bytes, 1 included, `planes`
+        is a buffer of its own and is written; src is only read."""
+        E = _elem(elem_bytes)
+        self._flat(src, "src")
+        soff, _ = self._offsets(src_offsets, src.device, False)
+        n = soff.numel() - 1
+        capacity = _room(self, src, capacity, "src")
+        what = "planes_split_pred_dbatch"
+        g = None
+        if planes is None:
+            planes, g = self._dst(1, src.numel(), src.device)
+            planes = planes[0]
+        elif _room(self, planes, None, "planes") < capacity:
+            raise ValueError("planes holds %d bytes, the capacity is %d" % (planes.numel(), capacity))
+        poff = _i64(self, plane_offsets, n * E + 1, src.device, "plane_offsets")
+        res = _i64(self, results, n, src.device, "results")
+        _check(self.lib.FSEHIP_planes_split_pred_dbatch(_ptr(planes), _ptr(poff), _ptr(res), _ptr(src), _ptr(soff), SZ(n), C.c_uint(E), C.c_uint64(capacity), _stream()),
+               what)
+        if g is not None:
+            g.check(what)
+        return planes, poff, res
+
+    def planes_merge_pred_dbatch(self, planes, plane_offsets, plane_sizes, dst_offsets, elem_bytes, dst=None, capacity=None, results=None):
+        """planes_merge_dbatch, every run of a rebuilt tensor summed back: the inverse of planes_split_pred_dbatch, with the plain merge's
+        results and rules.  dst must not overlap planes."""
+        E = _elem(elem_bytes)
+        self._flat(planes, "planes")
+        doff, dhost = self._offsets(dst_offsets, planes.device, dst is None)
+        n = doff.numel() - 1
+        poff = _i64(self, plane_offsets, n * E, planes.device, "plane_offsets")
+        psz = _i64(self, plane_sizes, n * E, planes.device, "plane_sizes")
+        dst, capacity, g = _dst_room(self, dst, capacity, dhost, planes.device)
+        res = _i64(self, results, n, planes.device, "results")
+        what = "planes_merge_pred_dbatch"
+        _check(self.lib.FSEHIP_planes_merge_pred_dbatch(_ptr(dst), _ptr(doff), _ptr(res), _ptr(planes), _ptr(poff), _ptr(psz), SZ(n), C.c_uint(E), C.c_uint64(capacity),
+                                                        _stream()), what)
+        if g is not None:
+            g.check(what)
+        return dst, res
+
+    def _compress_pred(self, what, src, src_offsets, elem_bytes, segment_log, seg_first, n_segments, codec, codecs, block_size_id, capacity, dst, dst_capacity,
+                       max_total_blocks, align_log, frame_offsets, frame_results, tensor_results, planes, plane_offsets, seg_offsets, workspace):
+        E = _elem(elem_bytes)
+        align_log = _align_log(align_log)
+        seg = segment_log is not None
+        L = _seg_log(segment_log, min(block_size_id, 6)) if seg else 0
+        self._flat(src, "src")
+        soff, shost = self._offsets(src_offsets, src.device, (seg and seg_first is None) or max_total_blocks is None or (dst is None and dst_capacity is None))
+        n = soff.numel() - 1
+        capacity = _room(self, src, capacity, "src")
+        if seg:
+            if seg_first is None:
+                seg_first = planes_segment_first(self, np.diff(shost.astype(np.int64)).clip(min=0), E, L)
+            sf, nf = _seg_first(self, seg_first, n_segments, src.device, n * E)
+        else:
+            sf, nf = None, n * E
+        mixed = codecs is not None or isinstance(codec, AutoCodec)
+        choose = mixed and codecs is None
+        codecs, cgu = _codecs(self, codecs, nf, src.device) if mixed else (None, None)
+        max_total_blocks, dst, dst_capacity, g = _frames_room(self, shost, n, E, nf, block_size_id, max_total_blocks, dst, dst_capacity, align_log, src.device)
+        planes = _split_room(self, planes, src, capacity, True)
+        foff = _i64(self, frame_offsets, nf + 1, src.device, "frame_offsets")
+        fres = _i64(self, frame_results, nf, src.device, "frame_results")
+        tres = _i64(self, tensor_results, n, src.device, "tensor_results")
+        poff = _i64(self, plane_offsets, n * E + 1, src.device, "plane_offsets")
+        so = _i64(self, seg_offsets, nf + 1, src.device, "seg_offsets") if seg else None
+        workspace = _writer_workspace(self, workspace, nf, max_total_blocks, block_size_id, codec, mixed, choose, src.device)
+        tol = codec.tolerance_permille if choose and isinstance(codec, AutoCodec) else 0
+        head = (_ptr(dst), C.c_uint64(int(dst_capacity)), _ptr(foff), _ptr(fres), _ptr(tres), _ptr(src), _ptr(soff), SZ(n), C.c_uint(E), C.c_uint64(capacity))
+        writer = (SZ(max_total_blocks), C.c_uint(block_size_id), C.c_int(0 if mixed else codec),
+                  _ptr((codecs if codecs.numel() else codecs.new_zeros(1)) if mixed else None), C.c_int(CODECS_CHOOSE if choose else CODECS_GIVEN), C.c_uint(tol),
+                  C.c_uint(align_log), _ptr(planes), _ptr(poff))
+        tail = (_ptr(workspace), SZ(workspace.numel()), _stream())
+        if seg:
+            _check(self.lib.FSEHIP_tensor_compress_seg_pred_dbatch(*head, _ptr(sf), SZ(nf), C.c_uint(L), *writer, _ptr(so), *tail), what)
+        else:
+            _check(self.lib.FSEHIP_tensor_compress_pred_dbatch(*head, *writer, *tail), what)
+        _check_codecs(cgu, nf, what)
+        if g is not None:
+            g.check(what)
+        return dst, foff, fres, tres, (codecs[:nf] if mixed else None)
+
+    def tensor_compress_pred_dbatch(self, src, src_offsets, elem_bytes, codec=0, codecs=None, block_size_id=5, capacity=None, dst=None, dst_capacity=None,
+                                    max_total_blocks=None, align_log=0, frame_offsets=None, frame_results=None, tensor_results=None, planes=None, plane_offsets=None,
+                                    workspace=None):
+        """-> (dst, frame_offsets, frame_results, tensor_results, codecs): planes_split_pred_dbatch, then the packed writer over the planes --
+        frame i*E+p is the .fse frame of plane p of the neighbour differences of tensor i.  codec / codecs as tensor_compress_seg_dbatch takes
+        them (0 / 1, an AutoCodec, or a codec per frame given).  planes (for every elem_bytes) and plane_offsets (n*E+1) are scratch; the
+        workspace is the (mixed) writer's for n*E frames.  With everything given the call is launches only."""
+        return _compress_pred(self, "tensor_compress_pred_dbatch", src, src_offsets, elem_bytes, None, None, None, codec, codecs, block_size_id, capacity, dst,
+                              dst_capacity, max_total_blocks, align_log, frame_offsets, frame_results, tensor_results, planes, plane_offsets, None, workspace)
+
+    def tensor_compress_seg_pred_dbatch(self, src, src_offsets, elem_bytes, segment_log, seg_first=None, n_segments=None, codec=0, codecs=None, block_size_id=5,
+                                        capacity=None, dst=None, dst_capacity=None, max_total_blocks=None, align_log=0, frame_offsets=None, frame_results=None,
+                                        tensor_results=None, planes=None, plane_offsets=None, seg_offsets=None, workspace=None):
+        """tensor_compress_seg_dbatch of the neighbour differences: a run of 1024 elements divides every segment, so the frames are one per
+        segment of the predicted planes with no rule of their own."""
+        return _compress_pred(self, "tensor_compress_seg_pred_dbatch", src, src_offsets, elem_bytes, segment_log, seg_first, n_segments, codec, codecs, block_size_id,
+                              capacity, dst, dst_capacity, max_total_blocks, align_log, frame_offsets, frame_results, tensor_results, planes, plane_offsets, seg_offsets,
+                              workspace)
+
+    def _decompress_pred(self, what, frames, frame_offsets, dst_offsets, elem_bytes, segment_log, seg_first, n_segments, dst, dst_capacity, max_total_blocks, planes,
+                         planes_capacity, seg_offsets, seg_results, plane_offsets, plane_sizes, workspace, results):
+        E = _elem(elem_bytes)
+        seg = segment_log is not None
+        L = _seg_log(segment_log) if seg else 0
+        self._flat(frames, "frames")
+        foff, _ = self._offsets(frame_offsets, frames.device, False)
+        doff, dhost = self._offsets(dst_offsets, frames.device, dst is None or planes is None or (seg and seg_first is None))
+        n = doff.numel() - 1
+        if seg:
+            if seg_first is None:
+                seg_first = planes_segment_first(self, np.diff(dhost.astype(np.int64)).clip(min=0), E, L)
+            sf, nf = _seg_first(self, seg_first, n_segments, frames.device, n * E)
+        else:
+            sf, nf = None, n * E
+        if foff.numel() != nf + 1:
+            raise ValueError("frame_offsets: one entry per frame (%d) and one more" % nf)
+        if max_total_blocks is None:
+            _, bfirst = self.frame_plan_dbatch(frames, foff, None, 0)
+            max_total_blocks = int(bfirst[nf].item())
+        dst, dst_capacity, g = _dst_room(self, dst, dst_capacity, dhost, frames.device)
+        planes, planes_capacity = _planes_room(self, planes, planes_capacity, None if planes is not None else int(dhost[-1]), frames.device)
+        poff = _i64(self, plane_offsets, n * E + 1, frames.device, "plane_offsets")
+        psz = _i64(self, plane_sizes, n * E, frames.device, "plane_sizes")
+        res = _i64(self, results, n, frames.device, "results")
+        workspace = _reader_workspace(self, workspace, nf, max_total_blocks, frames.device)
+        head = (_ptr(dst), _ptr(doff), C.c_uint64(dst_capacity), _ptr(res), _ptr(frames), _ptr(foff), SZ(n), C.c_uint(E))
+        tail = (_ptr(poff), _ptr(psz), _ptr(workspace), SZ(workspace.numel()), _stream())
+        if seg:
+            so = _i64(self, seg_offsets, nf + 1, frames.device, "seg_offsets")
+            sres = _i64(self, seg_results, nf, frames.device, "seg_results")
+            _check(self.lib.FSEHIP_tensor_decompress_seg_pred_dbatch(*head, _ptr(sf), SZ(nf), C.c_uint(L), SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity),
+                                                                     _ptr(so), _ptr(sres), *tail), what)
+        else:
+            _check(self.lib.FSEHIP_tensor_decompress_pred_dbatch(*head, SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity), *tail), what)
+        if g is not None:
+            g.check(what)
+        return dst, res
+
+    def tensor_decompress_pred_dbatch(self, frames, frame_offsets, dst_offsets, elem_bytes, dst=None, dst_capacity=None, max_total_blocks=None, planes=None,
+                                      planes_capacity=None, plane_offsets=None, plane_results=None, workspace=None, results=None):
+        """tensor_decompress_dbatch of frames that tensor_compress_pred_dbatch wrote: the packed reader into `planes`, then
+        planes_merge_pred_dbatch.  The frames do not say that they hold differences."""
+        return _decompress_pred(self, "tensor_decompress_pred_dbatch", frames, frame_offsets, dst_offsets, elem_bytes, None, None, None, dst, dst_capacity,
+                                max_total_blocks, planes, planes_capacity, None, None, plane_offsets, plane_results, workspace, results)
+
+    def tensor_decompress_seg_pred_dbatch(self, frames, frame_offsets, dst_offsets, elem_bytes, segment_log, seg_first=None, n_segments=None, dst=None,
+                                          dst_capacity=None, max_total_blocks=None, planes=None, planes_capacity=None, seg_offsets=None, seg_results=None,
+                                          plane_offsets=None, plane_sizes=None, workspace=None, results=None):
+        """tensor_decompress_seg_dbatch of frames that tensor_compress_seg_pred_dbatch wrote: the packed reader, the fold, then
+        planes_merge_pred_dbatch."""
+        return _decompress_pred(self, "tensor_decompress_seg_pred_dbatch", frames, frame_offsets, dst_offsets, elem_bytes, segment_log, seg_first, n_segments, dst,
+                                dst_capacity, max_total_blocks, planes, planes_capacity, seg_offsets, seg_results, plane_offsets, plane_sizes, workspace, results)
+
+    for f in (planes_split_pred_dbatch, planes_merge_pred_dbatch, tensor_compress_pred_dbatch, tensor_decompress_pred_dbatch, tensor_compress_seg_pred_dbatch,
+              tensor_decompress_seg_pred_dbatch):
+        setattr(FseHip, f.__name__, f)
+
     # ---- tensor digests and checked deltas (csrc/planes_digest.hip; fsehip.h "tensor digests and checked deltas"): a 64-bit digest per
     # tensor at the memory rate, and the gate that turns a digest mismatch into frames every reader refuses
     def tensor_digest_workspace_bound(self, capacity, n_tensors):
@@ -2739,6 +2926,8 @@ def _planes_methods():
     def _codec_to_json(codec):
         if isinstance(codec, SparsePlanes):
             return {"sparse": _codec_to_json(codec.codec), "permille": codec.permille}
+        if isinstance(codec, PredictedPlanes):
+            return {"pred": _codec_to_json(codec.codec)}
         if isinstance(codec, AutoCodec):
             return {"auto": codec.tolerance_permille}
         return int(codec)
@@ -2746,6 +2935,8 @@ def _planes_methods():
     def _codec_from_json(j):
         if isinstance(j, dict) and "sparse" in j:
             return SparsePlanes(_codec_from_json(j["sparse"]), j["permille"])
+        if isinstance(j, dict) and "pred" in j:
+            return PredictedPlanes(_codec_from_json(j["pred"]))
         if isinstance(j, dict) and "auto" in j:
             return AutoCodec(j["auto"])
         return int(j)
@@ -2869,7 +3060,7 @@ def _planes_methods():
                 del g[k]
         obj = CompressedTensors(groups if m0["groups"] else [], dtypes, shapes, device if n else None, codec, int(first.blockSizeId), delta)
         return _segmented(obj, int(first.segLog) if first.segLog else None, "sub" if delta and first.deltaOp else "xor",
-                          int(first.sparsePermille) if first.flags & ARCHIVE_SPARSE else None, digests)
+                          int(first.sparsePermille) if first.flags & ARCHIVE_SPARSE else None, digests, "prev" if isinstance(codec, PredictedPlanes) else None)
 
     def save_tensors(self, obj, path):
         """archive_tensors(obj) written to the file `path` as it lies -> the number of bytes"""
@@ -2891,6 +3082,8 @@ def _planes_methods():
     def _not_sparse(obj, what):
         if getattr(obj, "sparse_permille", None) is not None:
             raise ValueError(what + ": the object holds sparse planes (SparsePlanes); windows and patches of those are not supported")
+        if getattr(obj, "predictor", None) is not None:
+            raise ValueError(what + ": the object holds predicted planes (PredictedPlanes); windows and patches of those are not supported")
 
     # ---- the user-facing pair
     def _read_base(obj, base, what):
@@ -2933,7 +3126,9 @@ def _planes_methods():
         group dict gains "codecs", a CUDA uint8 tensor with entry i*E+p for plane p of the group's tensor i, and the object's `codec` is the
         AutoCodec) -- or a CompressedTensors an AutoCodec call returned for tensors of the same dtypes and shapes (ValueError otherwise, before
         any launch): its codecs are given again, nothing is tried twice.  An object compress_tensors_segmented wrote is refused here
-        (ValueError): its codecs are per segment.  For tensors above a few MiB use compress_tensors_segmented."""
+        (ValueError): its codecs are per segment.  A SparsePlanes or a PredictedPlanes around 0, 1 or an AutoCodec: sparse contents, or the
+        planes of the neighbour differences (the object's `predictor` is "prev"; ValueError with a base, before any launch).  For tensors
+        above a few MiB use compress_tensors_segmented."""
         return _compress_tensors(self, tensors, codec, block_size_id, base, None)
 
     def compress_tensors_segmented(self, tensors, segment_log=18, codec=0, block_size_id=5, base=None):
@@ -2949,7 +3144,9 @@ def _planes_methods():
         return _compress_tensors(self, tensors, codec, block_size_id, base,
                                  _seg_log(segment_log, block_size_id if isinstance(block_size_id, numbers.Integral) and 0 <= block_size_id <= 6 else 0))
 
-    def _segmented(obj, segment_log, delta_op="xor", sparse=None, digests=None):
+    def _segmented(obj, segment_log, delta_op="xor", sparse=None, digests=None, predictor=None):
+        if predictor is not None:
+            obj.predictor = predictor
         if segment_log is not None:
             obj.segment_log = int(segment_log)
         if delta_op != "xor":
@@ -2984,10 +3181,15 @@ def _planes_methods():
         sparse, outer = None, codec
         if isinstance(codec, SparsePlanes):                 # the contents' codec inside, the threshold beside it
             sparse, codec = codec.permille, codec.codec
+        pred = None
+        if isinstance(codec, PredictedPlanes):              # the planes' codec inside; the differences need no base and take none
+            if base is not None:
+                raise ValueError("compress_tensors: PredictedPlanes predicts from the tensor itself, a base does not go with it")
+            pred, codec = "prev", codec.codec
         if not tensors:
             if base is not None and len(list(base)):
                 raise ValueError("base: tensors for none")
-            return _segmented(CompressedTensors([], [], [], None, outer, block_size_id, base is not None), segment_log, opname, sparse, digests)
+            return _segmented(CompressedTensors([], [], [], None, outer, block_size_id, base is not None), segment_log, opname, sparse, digests, pred)
         device = tensors[0].device
         for t in tensors:
             if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
@@ -3004,7 +3206,15 @@ def _planes_methods():
             src = torch.cat(raw) if int(offs[-1]) else torch.zeros(1, dtype=torch.uint8, device=device)[:0]
             bsrc = None if braw is None else torch.cat([braw[i] for i in idx]) if int(offs[-1]) else src
             codecs = sfirst = None
-            if sparse is not None:
+            if pred is not None:
+                given = None if earlier is None else [g for g in earlier.groups if g["elem_bytes"] == E][0]["codecs"]
+                if segment_log is not None:
+                    sfirst = self.planes_segment_first(np.diff(offs.astype(np.int64)), E, segment_log)
+                    dst, foff, fres, tres, codecs = self.tensor_compress_seg_pred_dbatch(src, offs, E, segment_log, sfirst, codec=codec, codecs=given,
+                                                                                         block_size_id=block_size_id)
+                else:
+                    dst, foff, fres, tres, codecs = self.tensor_compress_pred_dbatch(src, offs, E, codec=codec, codecs=given, block_size_id=block_size_id)
+            elif sparse is not None:
                 given = None if earlier is None else [g for g in earlier.groups if g["elem_bytes"] == E][0]["codecs"]
                 if segment_log is not None:
                     sfirst = self.planes_segment_first(np.diff(offs.astype(np.int64)), E, segment_log)
@@ -3039,7 +3249,7 @@ def _planes_methods():
                 for i, d in zip(idx, _group_digests(self, [braw[i] for i in idx], device, bsrc)):
                     digests[i] = d
         return _segmented(CompressedTensors(groups, [t.dtype for t in tensors], [tuple(t.shape) for t in tensors], device, outer, block_size_id, braw is not None),
-                          segment_log, opname if braw is not None else "xor", sparse, digests)
+                          segment_log, opname if braw is not None else "xor", sparse, digests, pred)
 
     def _base_copy(braw, g, device, held=None):
         """the bases of a group back to back, as the copy a group is rebuilt over in place (held: the one that was digested)"""
@@ -3080,6 +3290,8 @@ def _planes_methods():
         (tensor_digest_dbatch, tensor_gate_dbatch; one read-back of the verdicts) and ValueError names the tensors whose base is not the one
         the deltas were made against -- before any decode launch, nothing is written; the readers then run over the gated offsets."""
         base, op = _read_base(obj, base, "decompress_tensors")
+        if getattr(obj, "predictor", None) not in (None, "prev"):
+            raise ValueError("decompress_tensors: predictor %r, \"prev\" is the one there is" % (obj.predictor,))
         braw = None if base is None else _bases(base, obj.dtypes, obj.shapes, obj.device)
         checked = _gate_groups(self, obj, braw) if getattr(obj, "base_digests", None) is not None else None
         out = [None] * len(obj.dtypes)
@@ -3089,7 +3301,12 @@ def _planes_methods():
             blocks = self.planes_block_bound(sum(sizes), len(sizes), E, obj.block_size_id)
             seg_log = getattr(obj, "segment_log", None)
             held, foff = checked[gi] if checked is not None else (None, g["frame_offsets"])     # (checked: the copy that was digested, the gated offsets)
-            if getattr(obj, "sparse_permille", None) is not None:
+            if getattr(obj, "predictor", None) is not None:
+                if seg_log is not None:
+                    dst, res = self.tensor_decompress_seg_pred_dbatch(g["frames"], foff, offs, E, seg_log, g["seg_first"], max_total_blocks=blocks)
+                else:
+                    dst, res = self.tensor_decompress_pred_dbatch(g["frames"], foff, offs, E, max_total_blocks=blocks)
+            elif getattr(obj, "sparse_permille", None) is not None:
                 dst = None if braw is None else _base_copy(braw, g, obj.device, held)
                 if seg_log is not None:
                     dst, res = self.tensor_decompress_seg_sparse_dbatch(g["frames"], foff, offs, E, seg_log, g["seg_first"], base=dst, dst=dst,

@@ -357,10 +357,18 @@ size_t sparse_workspace(u64 capacity, size_t nUnits);
 bool bad_sparse(u64 capacity, size_t nUnits, const void* d_workspace, size_t workspaceBytes);
 hipError_t launch_sparse_pack(u8* contents, u64* contentOff, const u8* units, const u64* unitOff, size_t nUnits, u64 capacity, unsigned permille, u8* ws, hipStream_t s);
 // the compress path of all compress composites (planes.hip): argument checks, (delta) split, segments where d_segFirst is given, pack where
-// `sparse` is given, writer
+// `sparse` is given, writer.  `pred` (no base with it): the predicted split in place of the plain one
 int planes_compress(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults, const void* d_src, const void* d_base,
                     unsigned deltaOp, const uint64_t* d_srcOffsets, size_t nTensors, unsigned E, uint64_t capacity, const uint64_t* d_segFirst, size_t nSegments,
-                    unsigned segLog, void* d_planes, uint64_t* d_planeOffsets, uint64_t* d_segOffsets, const PlWriter& w, void* stream, const PlSparse* sparse = nullptr);
+                    unsigned segLog, void* d_planes, uint64_t* d_planeOffsets, uint64_t* d_segOffsets, const PlWriter& w, void* stream, const PlSparse* sparse = nullptr,
+                    bool pred = false);
+// predicted planes (planes_pred.hip; fsehip.h, "predicted planes"): the split on zigzag(element - the element in front of it), every E, and
+// the merge that sums the runs back.  launch_planes_verdicts (planes.hip): the merge's first step by itself, a result per tensor
+hipError_t launch_planes_split_pred(u8* planes, u64* planeOff, size_t* tensorRes, const u8* src, const u64* srcOff, size_t nTensors, unsigned E, u64 capacity,
+                                    hipStream_t s);
+hipError_t launch_planes_merge_pred(u8* dst, const u64* dstOff, size_t* results, const u8* planes, const u64* planeOff, const size_t* planeSizes, size_t nTensors,
+                                    unsigned E, u64 dstCapacity, hipStream_t s);
+hipError_t launch_planes_verdicts(size_t* results, const u64* dstOff, const size_t* planeSizes, size_t nTensors, unsigned E, u64 dstCapacity, hipStream_t s);
 
 // ---- kernel timing probe (HIP events on the launch stream; used by bench.py for the live roofline figure) ----
 enum { PK_HIST = 0, PK_FSE_CPREP, PK_FSE_ENCODE, PK_FSE_DPREP, PK_FSE_DECODE, PK_HUF_CPREP, PK_HUF_ENCODE, PK_HUF_DPREP, PK_HUF_DECODE, PK_FSE_ENCODE_WAVE, PK_COUNT };

@@ -7,6 +7,7 @@
 //   FSEHIP_tensor_compress_dbatch  : the split -> FSEHIP_frame_compress_packed_dbatch over the planes (the plane offsets are its source offsets)
 //   FSEHIP_tensor_decompress_dbatch: FSEHIP_frame_decompress_packed_dbatch into the planes buffer -> the merge over the offsets and results it leaves
 // (The device helpers all of them are made of are in planes_dev.h, shared with planes_seg.hip and planes_win.hip.)
+// (planes_pred.hip: the same calls on the neighbour differences, with data kernels of its own in front of and behind the steps here.)
 //
 // TENSOR DELTAS (fsehip.h, "tensor deltas"): the same calls on `tensor XOR base`, the XOR fused into the two data kernels.  The receiver of a
 // tensor often holds an earlier version of it (weights after a step, the checkpoint before this one); XOR against that version zeroes every
@@ -204,13 +205,19 @@ hipError_t launch_planes_split(u8* planes, u64* planeOff, size_t* tensorRes, con
     return hipGetLastError();
 }
 
+// the merge's first step by itself (planes_pred.hip puts a data kernel of its own behind it); nTensors > 0
+hipError_t launch_planes_verdicts(size_t* results, const u64* dstOff, const size_t* planeSizes, size_t nTensors, unsigned E, u64 dstCapacity, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_planes_verdicts, dim3(grid_for(nTensors)), dim3(PL_THREADS), 0, s, results, dstOff, planeSizes, nTensors, (u32)E, dstCapacity);
+    return hipGetLastError();
+}
 // base null: the plain merge.  The tail of every decompress composite, over whatever plane offsets and sizes the steps in front of it left
 hipError_t launch_planes_merge(u8* dst, const u64* dstOff, size_t* results, const u8* planes, const u64* planeOff, const size_t* planeSizes, const u8* base,
                                unsigned deltaOp, size_t nTensors, unsigned E, u64 dstCapacity, hipStream_t s)
 {
     if (nTensors == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_planes_verdicts, dim3(grid_for(nTensors)), dim3(PL_THREADS), 0, s, results, dstOff, planeSizes, nTensors, (u32)E, dstCapacity);
-    if (dstCapacity == 0) return hipGetLastError();
+    const hipError_t e0 = launch_planes_verdicts(results, dstOff, planeSizes, nTensors, E, dstCapacity, s);
+    if (dstCapacity == 0 || e0 != hipSuccess) return e0;
     const dim3 g(tile_grid(dstCapacity, nTensors)), b(PL_THREADS);
     pl_for_elem(E, [&](auto eb) {
         constexpr int EB = decltype(eb)::value;
@@ -226,12 +233,13 @@ hipError_t launch_planes_merge(u8* dst, const u64* dstOff, size_t* results, cons
 // front of the first launch (fsehip.h: what the guarantee covers), the split (d_base given: the split of the delta by deltaOp), the segments kernel where
 // d_segFirst is given, then the packed writer -- a codec per frame where w.d_codecs is given -- over the planes or their segments, read
 // from d_src itself where the split moved nothing.  `sparse` given (planes_sparse.hip): pack stands between the units and the writer, which
-// then reads the contents; pack's workspace is the head of the caller's, the writer's the rest
+// then reads the contents; pack's workspace is the head of the caller's, the writer's the rest.  `pred` (planes_pred.hip): the predicted
+// split in place of the plain one, which moves every element size
 int planes_compress(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults, const void* d_src, const void* d_base,
                     unsigned deltaOp, const uint64_t* d_srcOffsets, size_t nTensors, unsigned E, uint64_t capacity, const uint64_t* d_segFirst, size_t nSegments,
-                    unsigned segLog, void* d_planes, uint64_t* d_planeOffsets, uint64_t* d_segOffsets, const PlWriter& writer, void* stream, const PlSparse* sparse)
+                    unsigned segLog, void* d_planes, uint64_t* d_planeOffsets, uint64_t* d_segOffsets, const PlWriter& writer, void* stream, const PlSparse* sparse, bool pred)
 {
-    if (bad_op(deltaOp)) return (int)hipErrorInvalidValue;
+    if (bad_op(deltaOp) || (pred && d_base)) return (int)hipErrorInvalidValue;
     if (d_segFirst ? bad_seg(segLog, writer.blockSizeId) || bad_counts(nTensors, E, nSegments) : bad_tensors(nTensors, E)) return (int)hipErrorInvalidValue;
     const size_t nFrames = d_segFirst ? nSegments : nTensors * E;
     PlWriter w = writer;
@@ -244,12 +252,13 @@ int planes_compress(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets,
     }
     if (bad_grid(capacity, nTensors) || bad_writer(w, nFrames)) return (int)hipErrorInvalidValue;
     const hipStream_t s = (hipStream_t)stream;
-    hipError_t e = launch_planes_split((u8*)d_planes, (u64*)d_planeOffsets, d_tensorResults, (const u8*)d_src, (const u8*)d_base, deltaOp, (const u64*)d_srcOffsets, nTensors,
-                                       E, capacity, s);
+    hipError_t e = pred ? launch_planes_split_pred((u8*)d_planes, (u64*)d_planeOffsets, d_tensorResults, (const u8*)d_src, (const u64*)d_srcOffsets, nTensors, E, capacity, s)
+                        : launch_planes_split((u8*)d_planes, (u64*)d_planeOffsets, d_tensorResults, (const u8*)d_src, (const u8*)d_base, deltaOp, (const u64*)d_srcOffsets,
+                                              nTensors, E, capacity, s);
     if (e == hipSuccess && d_segFirst)
         e = launch_segments((u64*)d_segOffsets, d_tensorResults, (const u64*)d_planeOffsets, (const u64*)d_srcOffsets, (const u64*)d_segFirst, nTensors, E, nSegments, segLog, s);
     if (e != hipSuccess) return (int)e;
-    const void* from = !d_base && E == 1 ? d_src : d_planes;
+    const void* from = !d_base && !pred && E == 1 ? d_src : d_planes;
     const uint64_t* fromOff = d_segFirst ? d_segOffsets : d_planeOffsets;
     if (sparse) {
         e = launch_sparse_pack((u8*)sparse->d_contents, (u64*)sparse->d_contentOffsets, (const u8*)from, (const u64*)fromOff, nFrames, capacity, sparse->permille, packWs, s);

@@ -1,5 +1,5 @@
 // planes_dev.h -- what the plane files (planes.hip: byte planes of tensors and their delta forms; planes_seg.hip; planes_win.hip; planes_patch.hip) share: the byte
-// shuffle, the delta ops (XOR, subtract and zigzag), the plane arithmetic, the search behind every work mapping, a workgroup's share of a tensor, the merge's verdict, the fold of a
+// shuffle, the delta ops (XOR, subtract and zigzag), the register forms of the predicted planes (planes_pred.hip), the plane arithmetic, the search behind every work mapping, a workgroup's share of a tensor, the merge's verdict, the fold of a
 // plane's segment results, the dispatch over the element size and the argument checks of the C calls.  Device helpers are inlined into the
 // kernels of the file that includes this; nothing here is a kernel.
 #pragma once
@@ -155,6 +155,110 @@ template <int E, class PlaneAt> DEV void pl_sub_elem_merge(u8* db, const u8* bb,
         for (int p = 0; p < E; ++p) db[k0 + p] = (u8)(t >> (8 * p));
     } else {
         for (u64 k = k0; k < n; ++k) db[k] = (u8)pl_unzz<1>(planeAt((u32)(k - k0))[e], bb[k]);
+    }
+}
+
+// ---- predicted planes (planes_pred.hip; fsehip.h, "predicted planes") ----
+// z[j] = zigzag(t[j] - t[j - 1]) inside runs of PP_RUN elements whose first element is predicted by 0; the inverse sums a run back.  The
+// dword forms work, as pl_sub4 does, on a lane's chunk of 16 whole elements (4 E dwords), and no carry crosses an element
+#define PP_RUN ((u64)1 << FSEHIP_PRED_RUN_LOG)
+static_assert(PP_RUN == 16 * WAVE && PLANES_TILE % (8 * PP_RUN) == 0, "a run is one round of one wave, and a tile holds whole runs of every element size");
+// pv = the chunk w moved up by one element: every element's predecessor.  The first one's is the E bytes in front of `at` (where the
+// chunk lies in the source), or 0 where the chunk starts a run -- nothing in front of it is read then
+template <int E> DEV void pp_prev(u32* pv, const u32* w, const u8* at, bool runStart)
+{
+    u32 f[2] = { 0, 0 };
+    if (!runStart) __builtin_memcpy(f, at - E, E);
+    if constexpr (E >= 4) {
+        constexpr int FD = E / 4;
+#pragma unroll
+        for (int j = 0; j < 4 * E; ++j) pv[j] = j < FD ? f[j] : w[j - FD];
+    } else {
+        pv[0] = __builtin_amdgcn_alignbyte(w[0], f[0] << (32 - 8 * E), 4 - E);
+#pragma unroll
+        for (int j = 1; j < 4 * E; ++j) pv[j] = __builtin_amdgcn_alignbyte(w[j], w[j - 1], 4 - E);
+    }
+}
+// x + y on the two 16-bit halves (v_pk_add_u16), and on the four bytes (the top bits kept out of the addition, as in pl_sub4)
+DEV u32 pp_add16x2(u32 x, u32 y)
+{
+    pl_u16x2 a, b;
+    __builtin_memcpy(&a, &x, 4); __builtin_memcpy(&b, &y, 4);
+    a += b;
+    __builtin_memcpy(&x, &a, 4);
+    return x;
+}
+DEV u32 pp_add8x4(u32 x, u32 y) { return ((x & 0x7F7F7F7Fu) + (y & 0x7F7F7F7Fu)) ^ ((x ^ y) & 0x80808080u); }
+// the chunk's differences d -> their inclusive prefix sums mod 2^(8 E), in place; returns the last one, the chunk's total
+//   E == 1: the even and the odd bytes of a dword as two 16-bit fields each -- four bytes and a carry stay below 2^16 -- summed there
+//   E == 2: the upper half takes the lower one by a shift; the running total is added to both halves at once
+template <int E> DEV u64 pp_prefix(u32* w)
+{
+    if constexpr (E == 1) {
+        u32 c = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const u32 ev = w[k] & 0x00FF00FFu, od = (w[k] >> 8) & 0x00FF00FFu;
+            const u32 evp = ev + (ev << 16), odp = od + (od << 16);
+            const u32 e2 = evp + (odp << 16) + c * 0x00010001u, o2 = evp + odp + c * 0x00010001u;
+            w[k] = (e2 & 0x00FF00FFu) | ((o2 & 0x00FF00FFu) << 8);
+            c = w[k] >> 24;
+        }
+        return c;
+    } else if constexpr (E == 2) {
+        u32 c = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            w[k] = pp_add16x2(w[k] + (w[k] << 16), c * 0x00010001u);
+            c = w[k] >> 16;
+        }
+        return c;
+    } else if constexpr (E == 4) {
+#pragma unroll
+        for (int k = 1; k < 16; ++k) w[k] += w[k - 1];
+        return w[15];
+    } else {
+        u64 acc = 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            acc += (u64)w[2 * k] | ((u64)w[2 * k + 1] << 32);
+            w[2 * k] = (u32)acc; w[2 * k + 1] = (u32)(acc >> 32);
+        }
+        return acc;
+    }
+}
+// every element of the chunk plus c, mod 2^(8 E): the lane's carry-in
+template <int E> DEV void pp_carry(u32* w, u64 c)
+{
+#pragma unroll
+    for (int k = 0; k < 4 * E; ++k) {
+        if constexpr (E == 1) w[k] = pp_add8x4(w[k], ((u32)c & 0xFFu) * 0x01010101u);
+        else if constexpr (E == 2) w[k] = pp_add16x2(w[k], ((u32)c & 0xFFFFu) * 0x00010001u);
+        else if constexpr (E == 4) w[k] += (u32)c;
+        else if ((k & 1) == 0) {
+            const u64 x = ((u64)w[k] | ((u64)w[k + 1] << 32)) + c;
+            w[k] = (u32)x; w[k + 1] = (u32)(x >> 32);
+        }
+    }
+}
+// element e of the tensor at sb (n bytes) a thread per element, the split's head and tail: its difference into the planes at pb.  The
+// partial last element of a tensor passes unchanged
+template <int E> DEV void pp_elem_split(u8* pb, const u8* sb, u64 n, u64 e)
+{
+    const u64 k0 = e * E;
+    if (k0 + E <= n) {
+        u64 t = 0, b = 0;
+#pragma unroll
+        for (int p = 0; p < E; ++p) t |= (u64)sb[k0 + p] << (8 * p);
+        if (e & (PP_RUN - 1)) {
+#pragma unroll
+            for (int p = 0; p < E; ++p) b |= (u64)sb[k0 - E + p] << (8 * p);
+        }
+        const u64 z = pl_zz<E>(t, b);
+#pragma unroll
+        for (int p = 0; p < E; ++p) pb[pl_start(n, p, E) + e] = (u8)(z >> (8 * p));
+    } else {
+        for (u64 k = k0; k < n; ++k) pb[pl_start(n, (u32)(k - k0), E) + e] = sb[k];
     }
 }
 

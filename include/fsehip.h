@@ -1256,6 +1256,63 @@ FSEHIP_API int FSEHIP_archive_open_dbatch(uint64_t* d_srcOffsets, uint64_t* d_fr
                                           const void* d_archive, uint64_t archiveBytes, const FSEHIP_ArchiveInfo* info, void* d_workspace, size_t workspaceBytes,
                                           void* stream);
 
+/* Predicted planes (planes_pred.hip): NEIGHBOUR DELTA IN THE SPLIT, RUN SCANS IN THE MERGE.  The planes above compress a tensor whose bytes
+ * are skewed at order 0.  A tensor whose neighbouring elements are close -- sorted indices, offsets, position ids, sampled fields, audio --
+ * is skewed only after the previous element is subtracted from each one, as integers.  These calls are the plain calls on that difference:
+ * the same plane layout, the same offsets, results and refusals, ordinary .fse frames; nothing in a frame records the predictor, the caller
+ * carries it as it carries a delta's op.  Opt-in: no call chooses prediction by itself.
+ *
+ *   The transform (normative; a numpy model in tests/planes_pred_corpus.py).  For a tensor of n bytes and elemBytes E: W = 8 E, m =
+ *   floor(n / E) whole elements t[0 .. m), little-endian unsigned integers counted from the tensor's start whatever its address.  A RUN is
+ *   R = 1 << FSEHIP_PRED_RUN_LOG = 1024 elements.
+ *     forward:  p[j] = 0 where j mod R == 0, else t[j - 1];  z[j] = zigzag((t[j] - p[j]) mod 2^W), the zigzag of "arithmetic tensor deltas"
+ *     inverse:  d[j] = unzigzag(z[j]);  t[j] = the sum of d[k] over k = R floor(j / R) .. j, mod 2^W
+ *   The trailing n mod E bytes pass unchanged.  A bijection for every bit pattern, no float arithmetic; independent of where the tensor
+ *   lies in the batch.  The planes are the plain planes of z.  A run divides every plane segment (segLog >= 10), so segment frames of
+ *   predicted planes are those of "segmented planes" with no rule of their own.
+ *
+ *   FSEHIP_planes_split_pred_dbatch   FSEHIP_planes_split_dbatch on z: the same arguments, offsets and results.  d_planes and d_src are
+ *     required for elemBytes == 1 too (the differences have to be written somewhere), as with XOR.  The source is only read.
+ *   FSEHIP_planes_merge_pred_dbatch   FSEHIP_planes_merge_dbatch with the inverse: the same arguments, verdicts and rules for what is
+ *     written (a refused tensor: nothing).  d_dst must not overlap d_planes.  Work item w belongs to the largest tensor i with
+ *     floor(D[i] / T) + i <= w and rebuilds the bytes [t T, (t + 1) T) OF THAT TENSOR, t = w - floor(D[i] / T) - i: tiles are relative to
+ *     the tensor, so that a workgroup owns whole runs (T / E / R of them).  One run is one round of one wave: a lane sums its 16 elements
+ *     in registers, a wave scan of the lane totals gives its carry-in.  No LDS, no workspace, no workgroup waits on another.
+ *   FSEHIP_tensor_compress_pred_dbatch   the predicted split, then the packed writer with `codec`, or -- d_codecs given -- the mixed writer
+ *     with policy and tolerancePermille: FSEHIP_tensor_compress_mixed_dbatch without d_base, codec and d_codecs taken as
+ *     FSEHIP_tensor_compress_seg_dbatch takes them.  d_planes is required.
+ *   FSEHIP_tensor_decompress_pred_dbatch   FSEHIP_tensor_decompress_dbatch with the predicted merge.
+ *   FSEHIP_tensor_compress_seg_pred_dbatch / FSEHIP_tensor_decompress_seg_pred_dbatch   the segmented pair: the _seg_op_ calls without d_base
+ *     and deltaOp.
+ *   All six: launches only (capturable); every argument error is hipErrorInvalidValue before any device call, with nothing written;
+ *   workspaces are the writers' and readers' own.
+ *   Out of scope: strides other than 1 (interleaved channels); higher-order or float-aware predictors; prediction combined with a base or
+ *   with sparse planes; windows and patches of predicted tensors; a record of the predictor in frames or in the archive head. */
+#define FSEHIP_PRED_RUN_LOG 10
+FSEHIP_API int FSEHIP_planes_split_pred_dbatch(void* d_planes, uint64_t* d_planeOffsets, size_t* d_tensorResults, const void* d_src, const uint64_t* d_srcOffsets,
+                                               size_t nTensors, unsigned elemBytes, uint64_t capacity, void* stream);
+FSEHIP_API int FSEHIP_planes_merge_pred_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_planes, const uint64_t* d_planeOffsets,
+                                               const size_t* d_planeSizes, size_t nTensors, unsigned elemBytes, uint64_t dstCapacity, void* stream);
+FSEHIP_API int FSEHIP_tensor_compress_pred_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
+                                                  const void* d_src, const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes, uint64_t capacity,
+                                                  size_t maxTotalBlocks, unsigned blockSizeId, int codec, uint8_t* d_codecs, int policy, unsigned tolerancePermille,
+                                                  unsigned slotAlignLog, void* d_planes, uint64_t* d_planeOffsets, void* d_workspace, size_t workspaceBytes,
+                                                  void* stream);
+FSEHIP_API int FSEHIP_tensor_decompress_pred_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, size_t* d_results, const void* d_frames,
+                                                    const uint64_t* d_frameOffsets, size_t nTensors, unsigned elemBytes, size_t maxTotalBlocks, void* d_planes,
+                                                    uint64_t planesCapacity, uint64_t* d_planeOffsets, size_t* d_planeResults, void* d_workspace, size_t workspaceBytes,
+                                                    void* stream);
+FSEHIP_API int FSEHIP_tensor_compress_seg_pred_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
+                                                      const void* d_src, const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes, uint64_t capacity,
+                                                      const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, size_t maxTotalBlocks, unsigned blockSizeId,
+                                                      int codec, uint8_t* d_codecs, int policy, unsigned tolerancePermille, unsigned slotAlignLog, void* d_planes,
+                                                      uint64_t* d_planeOffsets, uint64_t* d_segOffsets, void* d_workspace, size_t workspaceBytes, void* stream);
+FSEHIP_API int FSEHIP_tensor_decompress_seg_pred_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, size_t* d_results, const void* d_frames,
+                                                        const uint64_t* d_frameOffsets, size_t nTensors, unsigned elemBytes, const uint64_t* d_segFirst,
+                                                        size_t nSegments, unsigned segLog, size_t maxTotalBlocks, void* d_planes, uint64_t planesCapacity,
+                                                        uint64_t* d_segOffsets, size_t* d_segResults, uint64_t* d_planeOffsets, size_t* d_planeSizes, void* d_workspace,
+                                                        size_t workspaceBytes, void* stream);
+
 /* ---- FSE for 16-bit symbols (lib/fseU16.h:62-80, lib/fseU16.c) -- SURVEY 8(f) rank 4.  Alphabets of up to
  * FSEHIP_FSEU16_MAX_SYMBOL_VALUE + 1 symbols, table logs up to 13 (default 12), ONE tANS state per stream: a different format from
  * the byte coder's.  Sizes of the uncompressed side are in SYMBOLS (as in the reference), strides in bytes.
