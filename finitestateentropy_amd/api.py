@@ -1311,6 +1311,26 @@ class CompressedTensors:
         return sum(int(g["frames"].numel()) for g in self.groups)
 
 
+EST_NAMES = ("plain", "pred", "xor", "sub")      # FSEHIP_EST_PLAIN / _PRED / _XOR / _SUB (include/fsehip.h, "plane estimates"): candidate id = position
+
+
+class TensorBundle:
+    """What compress_tensors_auto returns: the tensors of a mixed list, each compressed with the plane transform chosen for it from the
+    device estimates (include/fsehip.h "plane estimates").  `parts` maps the transform name ("plain", "pred", "xor", "sub"; only those
+    that were chosen) to an ordinary CompressedTensors -- what compress_tensors returns for that part, and what archive_tensors /
+    save_tensors take; `index` maps the same names to the positions of the part's tensors in the input list (every position in exactly one
+    part); `estimates` holds one record per input tensor, as estimate_tensors returns them.  decompress_tensors takes the bundle and, where
+    it holds an "xor" or a "sub" part, the base of the whole list."""
+
+    def __init__(self, parts, index, estimates, n_tensors):
+        self.parts, self.index, self.estimates, self.n_tensors = parts, index, estimates, int(n_tensors)
+
+    @property
+    def nbytes(self):
+        """bytes of all frames of all parts"""
+        return sum(p.nbytes for p in self.parts.values())
+
+
 class ArchiveInfo(C.Structure):
     """FSEHIP_ArchiveInfo (include/fsehip.h, "tensor archives"): the 64 header bytes of an archive as they lie in it, and headBytes"""
     _fields_ = [("magic", C.c_uint32), ("version", C.c_uint16), ("flags", C.c_uint16), ("elemBytes", C.c_uint8), ("blockSizeId", C.c_uint8), ("segLog", C.c_uint8),
@@ -2816,6 +2836,47 @@ def _planes_methods():
     for f in (tensor_digest_workspace_bound, tensor_digest_dbatch, tensor_gate_dbatch, tensor_digests):
         setattr(FseHip, f.__name__, f)
 
+    # ---- plane estimates (csrc/planes_estimate.hip; fsehip.h "plane estimates"): per tensor and candidate transform the order-0 cost of
+    # every plane from one read of the tensors, an estimated size and a choice
+    def planes_estimate_workspace_bound(self, n_tensors, elem_bytes, candidate_mask):
+        """the workspace of planes_estimate_dbatch: per tensor and requested candidate elem_bytes histograms of 256 counters.  Host
+        arithmetic: needs no device."""
+        self.lib.FSEHIP_planes_estimate_workspaceBound.restype = SZ
+        r = int(self.lib.FSEHIP_planes_estimate_workspaceBound(SZ(int(n_tensors)), C.c_uint(int(elem_bytes)), C.c_uint(int(candidate_mask) & 0xFFFFFFFF)))
+        if r >= (1 << 62):
+            raise ValueError("planes_estimate_workspace_bound(%r, %r, %r)" % (n_tensors, elem_bytes, candidate_mask))
+        return r
+
+    def planes_estimate_dbatch(self, src, src_offsets, elem_bytes, candidate_mask=3, margin_permille=50, base=None, capacity=None, plane_bits=None, est_bytes=None,
+                               choice=None, results=None, workspace=None):
+        """-> (plane_bits, est_bytes, choice, results) for tensor i = src[src_offsets[i] : src_offsets[i+1]] and candidate c (bit 1 << c of
+        candidate_mask; 0 plain, 1 pred, 2 xor, 3 sub -- the last two need `base`, laid out as src is): plane_bits[(i*4+c)*E+p] = the
+        order-0 cost of plane p in 1/256 bits, est_bytes[i*4+c] = the estimated bytes of the tensor, choice[i] (uint8) = the chosen
+        candidate under margin_permille, results[i] = its size.  int64 tensors of the library's 64 bits: a slot of a candidate that was
+        not requested, or of a refused tensor (results -1: its offsets decrease or it ends behind `capacity`, default src's size; -3: it
+        holds 2^32 bytes or more; choice 0xFF), reads -1.  src and base are only read.  With src_offsets on the device and the outputs
+        and the workspace given the call is launches only and can be captured into a graph; it zeroes its workspace itself."""
+        E = _elem(elem_bytes)
+        self._flat(src, "src")
+        soff, _ = self._offsets(src_offsets, src.device, False)
+        n = soff.numel() - 1
+        capacity = _room(self, src, capacity, "src")
+        _base(self, base, src, capacity, "src")
+        need = planes_estimate_workspace_bound(self, n, E, candidate_mask)
+        pb = _i64(self, plane_bits, n * 4 * E, src.device, "plane_bits")
+        eb = _i64(self, est_bytes, n * 4, src.device, "est_bytes")
+        ch = torch.zeros(max(n, 1), dtype=torch.uint8, device=src.device)[:n] if choice is None else _u8(choice, n, src.device, "choice")
+        res = _i64(self, results, n, src.device, "results")
+        if workspace is None:
+            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=src.device)
+        _check(self.lib.FSEHIP_planes_estimate_dbatch(_ptr(pb), _ptr(eb), _ptr(ch), _ptr(res), VP(src.data_ptr() or workspace.data_ptr()), _ptr(base), _ptr(soff), SZ(n),
+                                                      C.c_uint(E), C.c_uint64(capacity), C.c_uint(int(candidate_mask)), C.c_uint(int(margin_permille)), _ptr(workspace),
+                                                      SZ(workspace.numel()), _stream()), "planes_estimate_dbatch")
+        return pb, eb, ch, res
+
+    for f in (planes_estimate_workspace_bound, planes_estimate_dbatch):
+        setattr(FseHip, f.__name__, f)
+
     # ---- tensor archives (csrc/planes_archive.hip; fsehip.h "tensor archives"): head | frames in one device buffer, sealed behind the frames a
     # compress call wrote at archive[head_bytes:], opened into the arrays the reading calls take
     def archive_head_bytes(self, n_tensors, n_frames, flags=0, meta_bytes=0):
@@ -3288,7 +3349,11 @@ def _planes_methods():
         object's `delta_op`; the base is the plain sequence, or a DeltaBase of the same op (ValueError for another, before any launch).
         An object with `base_digests` (written against a DeltaBase(..., check=True)): the given base is digested and compared on the device
         (tensor_digest_dbatch, tensor_gate_dbatch; one read-back of the verdicts) and ValueError names the tensors whose base is not the one
-        the deltas were made against -- before any decode launch, nothing is written; the readers then run over the gated offsets."""
+        the deltas were made against -- before any decode launch, nothing is written; the readers then run over the gated offsets.
+        A TensorBundle (compress_tensors_auto): every part is read as above and the tensors come back in the input order; `base` is the base
+        of the WHOLE list, each delta part is handed its slice of it; ValueError before any launch where a delta part has no base."""
+        if isinstance(obj, TensorBundle):                    # compress_tensors_auto's: part by part, each with its slice of the base
+            return _decompress_bundle(self, obj, base)
         base, op = _read_base(obj, base, "decompress_tensors")
         if getattr(obj, "predictor", None) not in (None, "prev"):
             raise ValueError("decompress_tensors: predictor %r, \"prev\" is the one there is" % (obj.predictor,))
@@ -3327,6 +3392,134 @@ def _planes_methods():
                 raise RuntimeError("decompress_tensors: element size %d, results %s for tensors of %s bytes" % (E, got[:8], sizes[:8]))
             for k, i in enumerate(g["index"]):
                 out[i] = dst[int(offs[k]):int(offs[k + 1])].clone().view(obj.dtypes[i]).reshape(obj.shapes[i])
+        return out
+
+    def _margin(margin_permille, what):
+        if not isinstance(margin_permille, numbers.Integral) or isinstance(margin_permille, bool) or not 0 <= margin_permille <= 1000:
+            raise ValueError("%s: margin_permille %r, 0 .. 1000 is needed" % (what, margin_permille))
+        return int(margin_permille)
+
+    def estimate_tensors(self, tensors, base=None, candidates=None, margin_permille=50):
+        """CUDA tensors of one device and of 1, 2, 4 or 8 bytes per element -> one record per tensor, in input order: dict(bytes=its size,
+        estimates={name: estimated bytes of its frames under that plane transform}, choice=name).  The names: "plain" (compress_tensors as
+        it is), "pred" (PredictedPlanes), "xor" (base=...), "sub" (DeltaBase(..., "sub")).  One read of the tensors (and of the bases) on the
+        device (planes_estimate_dbatch; fsehip.h "plane estimates": the order-0 cost of every candidate's planes in integers, no plane
+        buffer, no coder), one call and one read-back per group of one element size; the tensors of a group are concatenated as
+        compress_tensors does it.
+        base: a sequence matching `tensors` one to one as compress_tensors takes it (or a DeltaBase: its tensors, the op is what is being
+        chosen).  candidates: names out of the four, default ("plain", "pred") without a base and all four with one; "xor" and "sub" need
+        a base.  The choice: the first candidate in the order above, replaced by a later one only if that is more than margin_permille /
+        1000 smaller than the best so far -- hysteresis towards the simpler form, a policy like AutoCodec's tolerance.  An estimate has
+        no term for frame headers or tables.  TypeError / ValueError as compress_tensors raises them, before any launch."""
+        margin = _margin(margin_permille, "estimate_tensors")
+        tensors = list(tensors)
+        if isinstance(base, DeltaBase):
+            base = base.tensors
+        if candidates is None:
+            candidates = EST_NAMES[:2] if base is None else EST_NAMES
+        if isinstance(candidates, str) or not len(candidates) or any(not isinstance(c, str) or c not in EST_NAMES for c in candidates):
+            raise ValueError("estimate_tensors: candidates %r, names out of %r are needed" % (candidates, EST_NAMES))
+        mask = 0
+        for c in candidates:
+            mask |= 1 << EST_NAMES.index(c)
+        if (mask & 12) and base is None:
+            raise ValueError("estimate_tensors: \"xor\" and \"sub\" are deltas against a base, none was given")
+        if not tensors:
+            if base is not None and len(list(base)):
+                raise ValueError("base: tensors for none")
+            return []
+        device = tensors[0].device if isinstance(tensors[0], torch.Tensor) else None
+        for k, t in enumerate(tensors):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
+                raise TypeError("estimate_tensors takes CUDA tensors of one device")
+            _elem(t.element_size())
+            if t.numel() * t.element_size() >= 1 << 32:
+                raise ValueError("estimate_tensors: tensor %d holds 2^32 bytes or more, the counts are 32 bits wide" % k)
+        braw = None if base is None else _bases(base, [t.dtype for t in tensors], [tuple(t.shape) for t in tensors], device)
+        out = [None] * len(tensors)
+        with torch.cuda.device(device):
+            for E in (1, 2, 4, 8):
+                idx = [i for i, t in enumerate(tensors) if t.element_size() == E]
+                if not idx:
+                    continue
+                raw = [tensors[i].contiguous().reshape(-1).view(torch.uint8) for i in idx]
+                offs = np.concatenate([[0], np.cumsum([r.numel() for r in raw])]).astype(np.uint64)
+                one = len(raw) == 1 and raw[0].numel() > 0          # a single tensor is estimated where it lies
+                src = raw[0] if one else torch.cat(raw) if int(offs[-1]) else torch.zeros(1, dtype=torch.uint8, device=device)[:0]
+                bsrc = None if braw is None or not (mask & 12) else braw[idx[0]] if one else torch.cat([braw[i] for i in idx]) if int(offs[-1]) else src
+                _, eb, ch, res = planes_estimate_dbatch(self, src, offs, E, mask, margin, bsrc)
+                got = torch.cat([eb, ch.to(torch.int64), res]).cpu().tolist()
+                n = len(idx)
+                if got[5 * n:] != [int(x) for x in np.diff(offs.astype(np.int64))]:
+                    raise RuntimeError("estimate_tensors: element size %d, results %s" % (E, got[5 * n:5 * n + 8]))
+                for k, i in enumerate(idx):
+                    out[i] = dict(bytes=got[5 * n + k], estimates={name: got[4 * k + c] for c, name in enumerate(EST_NAMES) if (mask >> c) & 1},
+                                  choice=EST_NAMES[got[4 * n + k]])
+        return out
+
+    def compress_tensors_auto(self, tensors, base=None, codec=0, block_size_id=5, segment_log=None, margin_permille=50):
+        """A mixed list of CUDA tensors (a state_dict's values: weights, index buffers, position ids, masks, statistics) -> a TensorBundle:
+        estimate_tensors chooses the plane transform per tensor, the list is cut by choice, and every non-empty part goes through the
+        existing call once -- compress_tensors (or, with segment_log, compress_tensors_segmented) as it is, with PredictedPlanes(codec),
+        with base= the part's bases, or with DeltaBase(the part's bases, "sub").  Without a base the candidates are "plain" and "pred", with
+        one all four.  codec: 0, 1 or an AutoCodec -- the coder of every part; block_size_id, segment_log: the existing calls'.  The frames
+        are ordinary frames: nothing in them records the choice, the bundle does.  decompress_tensors(bundle, base) gives the list back.
+        A tensor of 0 bytes (every estimate 0) is filed with the first part that holds bytes of its element size -- the frame writers take
+        no group of no bytes -- and its record's choice says so."""
+        margin = _margin(margin_permille, "compress_tensors_auto")
+        pred = PredictedPlanes(codec)                          # (0, 1 or an AutoCodec, or ValueError -- whether or not a tensor will want it)
+        if segment_log is not None:
+            segment_log = _seg_log(segment_log, block_size_id if isinstance(block_size_id, numbers.Integral) and 0 <= block_size_id <= 6 else 0)
+        tensors = list(tensors)
+        if isinstance(base, DeltaBase):
+            base = base.tensors
+        base = None if base is None else list(base)
+        records = estimate_tensors(self, tensors, base, None, margin)
+        for i, r in enumerate(records):                        # a tensor of no bytes has nothing to choose: it goes where its element size has company
+            if r["bytes"] == 0:
+                held = [q["choice"] for t, q in zip(tensors, records) if q["bytes"] and t.element_size() == tensors[i].element_size()]
+                r["choice"] = next((name for name in EST_NAMES if name in held), r["choice"])
+
+        def part(sub, codec, base):
+            if segment_log is None:
+                return compress_tensors(self, sub, codec, block_size_id, base)
+            return compress_tensors_segmented(self, sub, segment_log, codec, block_size_id, base)
+        parts, index = {}, {}
+        for name in EST_NAMES:
+            idx = [i for i, r in enumerate(records) if r["choice"] == name]
+            if not idx:
+                continue
+            sub = [tensors[i] for i in idx]
+            index[name] = idx
+            if name == "plain":
+                parts[name] = part(sub, codec, None)
+            elif name == "pred":
+                parts[name] = part(sub, pred, None)
+            elif name == "xor":
+                parts[name] = part(sub, codec, [base[i] for i in idx])
+            else:
+                parts[name] = part(sub, codec, DeltaBase([base[i] for i in idx], "sub"))
+        return TensorBundle(parts, index, records, len(tensors))
+
+    def _decompress_bundle(self, bundle, base):
+        if isinstance(base, DeltaBase):
+            base = base.tensors
+        base = None if base is None else list(base)
+        n = bundle.n_tensors
+        if sorted(i for idx in bundle.index.values() for i in idx) != list(range(n)) or set(bundle.index) != set(bundle.parts) or not set(bundle.parts) <= set(EST_NAMES):
+            raise ValueError("decompress_tensors: the bundle's parts do not partition its %d tensors" % n)
+        if base is None and any(name in ("xor", "sub") for name in bundle.parts):
+            raise ValueError("decompress_tensors: the bundle holds deltas and needs its base")
+        if base is not None and len(base) != n:
+            raise ValueError("base: %d tensors for %d" % (len(base), n))
+        out = [None] * n
+        for name in EST_NAMES:
+            if name not in bundle.parts:
+                continue
+            idx = bundle.index[name]
+            back = decompress_tensors(self, bundle.parts[name], [base[i] for i in idx] if name in ("xor", "sub") else None)
+            for i, t in zip(idx, back):
+                out[i] = t
         return out
 
     def decompress_tensor_windows(self, obj, windows, base=None):
@@ -3383,6 +3576,8 @@ def _planes_methods():
 
     for f in (planes_window_first, planes_select_window_dbatch, planes_fold_window_dbatch, tensor_decompress_window_dbatch, decompress_tensor_windows):
         setattr(FseHip, f.__name__, f)
+    for f in (estimate_tensors, compress_tensors_auto):
+        setattr(FseHip, f.__name__, f)
     for f in (planes_block_bound, planes_split_dbatch, planes_merge_dbatch, tensor_compress_dbatch, tensor_decompress_dbatch, compress_tensors, decompress_tensors,
               planes_split_xor_dbatch, planes_merge_xor_dbatch, tensor_compress_delta_dbatch, tensor_decompress_delta_dbatch, tensor_compress_mixed_dbatch,
               planes_segment_first, planes_segments_dbatch, planes_fold_segments_dbatch, tensor_compress_seg_dbatch, tensor_decompress_seg_dbatch, compress_tensors_segmented):
@@ -3413,6 +3608,16 @@ def compress_tensors_segmented(tensors, segment_log=18, codec=0, block_size_id=5
 def decompress_tensors(obj, base=None):
     """FseHip.decompress_tensors on a library handle of the module's own"""
     return _default().decompress_tensors(obj, base)
+
+
+def estimate_tensors(tensors, base=None, candidates=None, margin_permille=50):
+    """FseHip.estimate_tensors on a library handle of the module's own"""
+    return _default().estimate_tensors(tensors, base, candidates, margin_permille)
+
+
+def compress_tensors_auto(tensors, base=None, codec=0, block_size_id=5, segment_log=None, margin_permille=50):
+    """FseHip.compress_tensors_auto on a library handle of the module's own"""
+    return _default().compress_tensors_auto(tensors, base, codec, block_size_id, segment_log, margin_permille)
 
 
 def decompress_tensor_windows(obj, windows, base=None):

@@ -1313,6 +1313,63 @@ FSEHIP_API int FSEHIP_tensor_decompress_seg_pred_dbatch(void* d_dst, const uint6
                                                         uint64_t* d_segOffsets, size_t* d_segResults, uint64_t* d_planeOffsets, size_t* d_planeSizes, void* d_workspace,
                                                         size_t workspaceBytes, void* stream);
 
+/* Plane estimates (planes_estimate.hip): THE TRANSFORM CHOSEN PER TENSOR FROM DEVICE HISTOGRAMS.  The tensor line has four ways to turn a
+ * tensor into byte planes -- plain, predicted, XOR against a base, SUB against a base -- each opt-in and per call, and a wrong guess costs
+ * a lot either way: a bf16 gaussian grows by 5 % under prediction, sorted int64 shrinks by a third, position ids by a factor of hundreds.
+ * What decides is the byte histogram of every candidate's planes, and that is one read of the tensor (and of its base): no plane buffer,
+ * no coder.  This call returns, per tensor and candidate, the order-0 cost of every plane, an estimated size, and a choice.  It changes
+ * no other call and no frame byte; the caller hands the chosen transform to the compress calls above.
+ *
+ *   The cost (normative, in integers; a numpy model in tests/planes_estimate_corpus.py -- device and model agree to the last bit).
+ *     T[f] = floor(256 log2(1 + f / 256) + 0.5) for f = 0 .. 255, a constant table; T[0] = 0.
+ *     L(x) for an integer x >= 1:  e = floor(log2 x);  f = the eight bits below the leading one, ((x << (63 - e)) >> 55) & 0xFF on 64
+ *       bits;  L(x) = 256 e + T[f].  L does not decrease, L(2^k) = 256 k, and |L(x) / 256 - log2 x| < 1.95 / 256 (the truncation to eight
+ *       bits, log2(1 + 1 / 256), plus half a unit of rounding; 1.87 / 256 is the largest seen over 1 .. 69999).
+ *     A plane with counts c[0 .. 255], N = their sum:  bits256 = the sum over s with c[s] > 0 of c[s] (L(N) - L(c[s])), in uint64.
+ *     estBytes(plane) = min(N, (bits256 + 2047) >> 11) -- the min stands for a raw block;  estBytes(tensor, candidate) = the sum over its
+ *       E planes.  No term for headers or tables: every candidate writes the same number of frames and blocks.
+ *   The planes are exactly the ones the corresponding split writes, the trailing n mod E bytes included: candidate
+ *     FSEHIP_EST_PLAIN  FSEHIP_planes_split_dbatch          FSEHIP_EST_PRED  FSEHIP_planes_split_pred_dbatch
+ *     FSEHIP_EST_XOR    FSEHIP_planes_split_xor_dbatch      FSEHIP_EST_SUB   FSEHIP_planes_split_op_dbatch with FSEHIP_DELTA_SUB
+ *   Candidate c is requested with bit 1u << c of candidateMask.
+ *   The choice of a tensor: best = the lowest requested id; every further requested c, in rising order, replaces it iff
+ *     estBytes[c] * 1000 < estBytes[best] * (1000 - marginPermille).  marginPermille (0 .. 1000) is hysteresis towards the simpler form, a
+ *     policy argument as the mixed writer's tolerancePermille is, not a measurement.
+ *
+ *   FSEHIP_planes_estimate_workspaceBound   host arithmetic, a multiple of 256: per tensor and REQUESTED candidate E histograms of 256
+ *     32-bit counters.  GENERIC for an elemBytes other than 1, 2, 4, 8, a candidateMask of 0 or with an unknown bit, or 2^24 tensors.
+ *   FSEHIP_planes_estimate_dbatch   tensor i = [S[i], S[i + 1]) of d_src (S = d_srcOffsets, nTensors + 1 entries, any sizes and alignments;
+ *     `capacity` = the size of d_src, it sizes the launch); d_base, read only where XOR or SUB is requested, is laid out as d_src is.  ->
+ *       d_planeBits[(i * 4 + c) * E + p]   bits256 of plane p of tensor i under candidate c
+ *       d_estBytes[i * 4 + c]              estBytes(tensor i, c)
+ *       d_choice[i]                        the chosen candidate id
+ *       d_results[i]                       n_i
+ *     Slots of candidates that were not requested are all-ones.  A tensor of 0 bytes: estimates 0, the lowest requested id, result 0.
+ *     Where S[i] > S[i + 1] or S[i + 1] > capacity: d_results[i] = GENERIC, d_choice[i] = 0xFF, all its d_estBytes and d_planeBits entries
+ *     all-ones, and nothing of that tensor is read.  COUNTS ARE EXACT AND 32 BITS WIDE: a tensor of 2^32 bytes or more is refused in the
+ *     same way with srcSize_wrong (cut it, as the segmented calls do).  Offsets are expected non-decreasing, as everywhere: around a slot
+ *     that decreases a tensor may miss tiles of its own (never a byte outside [0, capacity) is read) and its estimate is then too low.
+ *     The source and the base are only read.  nTensors == 0 is legal.
+ *     The work: a launch that zeroes the counters (the call does so itself, every time: a replayed graph returns the same numbers); the
+ *     counting kernel in the ragged mapping of "byte planes" -- ceil(capacity / T) + nTensors workgroups, chunks of 16 elements per lane
+ *     counted from the tensor's start, head and tail an element per thread -- where a lane loads its chunk (and the base's) once, derives
+ *     every requested candidate in registers and counts where the split would store, into LDS histograms per (candidate, plane) -- 8 / E
+ *     columns per bin, 32 KB -- that are flushed to the tensor's counters by integer atomics; a lane, or a whole wave, whose 16 bytes of a
+ *     plane are one value adds them in one addition (the zero planes of a delta); then a wave per tensor for L(), the sums and the choice.
+ *     Launches only (capturable).  Every argument error is hipErrorInvalidValue before any device call, with nothing written: a null
+ *     output, d_src or d_srcOffsets; candidateMask == 0 or an unknown bit; XOR or SUB requested with d_base == NULL; elemBytes not 1, 2, 4
+ *     or 8; marginPermille > 1000; a launch beyond the limits of "byte planes"; a workspace that is misaligned (256) or below the bound.
+ *   Out of scope: sparse planes as a candidate (the sparse pack selects itself per plane); a record of the choice inside frames; costs
+ *   beyond order 0. */
+#define FSEHIP_EST_PLAIN 0
+#define FSEHIP_EST_PRED 1
+#define FSEHIP_EST_XOR 2
+#define FSEHIP_EST_SUB 3
+FSEHIP_API size_t FSEHIP_planes_estimate_workspaceBound(size_t nTensors, unsigned elemBytes, unsigned candidateMask);
+FSEHIP_API int FSEHIP_planes_estimate_dbatch(uint64_t* d_planeBits, uint64_t* d_estBytes, uint8_t* d_choice, size_t* d_results, const void* d_src, const void* d_base,
+                                             const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes, uint64_t capacity, unsigned candidateMask,
+                                             unsigned marginPermille, void* d_workspace, size_t workspaceBytes, void* stream);
+
 /* ---- FSE for 16-bit symbols (lib/fseU16.h:62-80, lib/fseU16.c) -- SURVEY 8(f) rank 4.  Alphabets of up to
  * FSEHIP_FSEU16_MAX_SYMBOL_VALUE + 1 symbols, table logs up to 13 (default 12), ONE tANS state per stream: a different format from
  * the byte coder's.  Sizes of the uncompressed side are in SYMBOLS (as in the reference), strides in bytes.
