@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from oracle.oracle import Ref, is_error
+from u16_corpus import _write_ncount     # (the NCount writer for any table log lives with the corpus: one copy)
 
 pytestmark = pytest.mark.gpu
 MAXSV = 286
@@ -184,53 +185,6 @@ def test_decompress_u16_damaged_streams(hip, ref):
     for size in (0, 1):                                   # fseU16.c:317
         r, _ = hip.fse_decompress_u16(np.zeros(size, np.uint8), 10)
         assert r == ref.fse_decompress_u16(np.zeros(size, np.uint8), 10)[0] and is_error(r)
-
-
-def _write_ncount(norm, max_sv, tl):
-    """The NCount header (format: SURVEY A.2, written by lib/fse_compress.c:227-320) for any table log -- the reference's writer is
-    the byte coder's object and refuses 13.  Checked against the reference's bytes at table log 12 by the test below."""
-    out = bytearray()
-    bit_stream, bit_count = tl - 5, 4
-    remaining, threshold, nb = (1 << tl) + 1, 1 << tl, tl + 1
-    sym, prev0, alphabet = 0, False, max_sv + 1
-
-    def flush16():
-        nonlocal bit_stream, bit_count
-        out.append(bit_stream & 0xFF); out.append((bit_stream >> 8) & 0xFF)
-        bit_stream >>= 16; bit_count -= 16
-    while sym < alphabet and remaining > 1:
-        if prev0:
-            start = sym
-            while sym < alphabet and norm[sym] == 0:
-                sym += 1
-            assert sym < alphabet
-            while sym >= start + 24:
-                start += 24
-                bit_stream += 0xFFFF << bit_count
-                bit_count += 16; flush16()
-            while sym >= start + 3:
-                start += 3
-                bit_stream += 3 << bit_count; bit_count += 2
-            bit_stream += (sym - start) << bit_count; bit_count += 2
-            if bit_count > 16:
-                flush16()
-        count = int(norm[sym]); sym += 1
-        mx = (2 * threshold - 1) - remaining
-        remaining -= abs(count)
-        count += 1
-        if count >= threshold:
-            count += mx
-        bit_stream += count << bit_count
-        bit_count += nb - (1 if count < mx else 0)
-        prev0 = count == 1
-        assert remaining >= 1
-        while remaining < threshold:
-            nb -= 1; threshold >>= 1
-        if bit_count > 16:
-            flush16()
-    assert remaining == 1
-    out.append(bit_stream & 0xFF); out.append((bit_stream >> 8) & 0xFF)
-    return np.frombuffer(bytes(out[:len(out) - 2 + (bit_count + 7) // 8]), dtype=np.uint8).copy()
 
 
 def test_decompress_u16_table_log_13(hip, ref):
