@@ -1291,7 +1291,9 @@ class CompressedTensors:
     DeltaBase(..., "sub")): what the frames of an object with `delta` set hold -- `tensor XOR base` or zigzag(tensor - base); the reading
     calls take it from here.  `sparse_permille` (None, or the integer of the SparsePlanes the object was written with): the frames hold sparse
     contents -- `codec` is then that SparsePlanes -- and decompress_tensors reads them as such; windows and patches of such an object are
-    refused.  `base_digests` (None, or one int per tensor in tensor order where the object was written against a DeltaBase(..., check=True)):
+    refused.  `transforms` (None, or one name per tensor out of "plain", "pred", "xor", "sub" where compress_tensors_each wrote the object): every
+    tensor's planes are those of its own transform, and decompress_tensors merges each accordingly (a base only where a name is "xor" or
+    "sub"); windows and patches of such an object are refused.  `base_digests` (None, or one int per tensor in tensor order where the object was written against a DeltaBase(..., check=True)):
     the 64-bit digests of the base tensors; decompress_tensors refuses a base whose digests differ.  `predictor` (None, or "prev" where the
     object was written with a PredictedPlanes -- `codec` is then that PredictedPlanes): the frames hold the planes of the neighbour
     differences, and decompress_tensors sums them back; windows and patches of such an object are refused."""
@@ -1300,6 +1302,7 @@ class CompressedTensors:
     sparse_permille = None
     base_digests = None
     predictor = None
+    transforms = None
 
     def __init__(self, groups, dtypes, shapes, device, codec, block_size_id, delta=False):
         self.groups, self.dtypes, self.shapes, self.device, self.codec, self.block_size_id = groups, dtypes, shapes, device, codec, block_size_id
@@ -2877,6 +2880,215 @@ def _planes_methods():
     for f in (planes_estimate_workspace_bound, planes_estimate_dbatch):
         setattr(FseHip, f.__name__, f)
 
+    # ---- a transform per tensor (csrc/planes_each.hip, capi_each.hip; fsehip.h "a transform per tensor"): the split, the merge and the
+    # composites with the transform of tensor i read from a device array -- given, or chosen by the estimate inside the call and returned
+    def _transforms(transforms, n, device):
+        """the `transforms` of a call that takes them as given: a CUDA uint8 tensor of n ids (handed on as it is: the device refuses a
+        byte that is none of the four), or a sequence of n names / ids -> the CUDA uint8 tensor"""
+        if isinstance(transforms, torch.Tensor):
+            return _u8(transforms, n, device, "transforms")
+        ids = [EST_NAMES.index(t) if isinstance(t, str) and t in EST_NAMES else t for t in transforms]
+        if len(ids) != n or any(not isinstance(t, numbers.Integral) or isinstance(t, bool) or not 0 <= t <= 255 for t in ids):
+            raise ValueError("transforms: %d names out of %r (or ids 0 .. 255) are needed" % (n, EST_NAMES))
+        return torch.tensor(ids, dtype=torch.uint8).to(device) if n else torch.zeros(1, dtype=torch.uint8, device=device)[:0]
+
+    def tensor_each_workspace_head(self, n_tensors, elem_bytes, choose, candidate_mask=3):
+        """the bytes of a tensor_compress_each_dbatch workspace that lie in front of the writer's own: 0 with the transforms given, the
+        estimate's counters and outputs where the call chooses.  Host arithmetic: needs no device."""
+        self.lib.FSEHIP_tensor_each_workspaceHead.restype = SZ
+        r = int(self.lib.FSEHIP_tensor_each_workspaceHead(SZ(int(n_tensors)), C.c_uint(int(elem_bytes)), C.c_int(1 if choose else 0),
+                                                          C.c_uint(int(candidate_mask) & 0xFFFFFFFF)))
+        if r >= (1 << 62):
+            raise ValueError("tensor_each_workspace_head(%r, %r, %r, %r)" % (n_tensors, elem_bytes, choose, candidate_mask))
+        return r
+
+    def planes_split_each_dbatch(self, src, src_offsets, elem_bytes, transforms, base=None, capacity=None, planes=None, plane_offsets=None, results=None):
+        """-> (planes, plane_offsets, results): tensor i split as transforms[i] says (0 plain, 1 pred, 2 xor, 3 sub; names or a CUDA uint8
+        tensor) -- byte for byte what planes_split_dbatch, planes_split_pred_dbatch or planes_split_xor_dbatch (delta_op 0 / 1) writes for
+        it.  base: laid out as src, read for xor and sub tensors only; a tensor whose byte is none of the four, or xor / sub without a
+        base, is refused: results -1, nothing of it read or written.  `planes` is written for every elem_bytes."""
+        E = _elem(elem_bytes)
+        self._flat(src, "src")
+        soff, _ = self._offsets(src_offsets, src.device, False)
+        n = soff.numel() - 1
+        capacity = _room(self, src, capacity, "src")
+        _base(self, base, src, capacity, "src")
+        tr = _transforms(transforms, n, src.device)
+        what = "planes_split_each_dbatch"
+        g = None
+        if planes is None:
+            planes, g = self._dst(1, src.numel(), src.device)
+            planes = planes[0]
+        elif _room(self, planes, None, "planes") < capacity:
+            raise ValueError("planes holds %d bytes, the capacity is %d" % (planes.numel(), capacity))
+        poff = _i64(self, plane_offsets, n * E + 1, src.device, "plane_offsets")
+        res = _i64(self, results, n, src.device, "results")
+        _check(self.lib.FSEHIP_planes_split_each_dbatch(_ptr(planes), _ptr(poff), _ptr(res), _ptr(src), _ptr(base), VP(tr.data_ptr() or res.data_ptr()), _ptr(soff), SZ(n),
+                                                        C.c_uint(E), C.c_uint64(capacity), _stream()), what)
+        if g is not None:
+            g.check(what)
+        return planes, poff, res
+
+    def planes_merge_each_dbatch(self, planes, plane_offsets, plane_sizes, dst_offsets, elem_bytes, transforms, base=None, dst=None, capacity=None, results=None):
+        """-> (dst, results): the inverse of planes_split_each_dbatch with the merges' results and rules.  base may be dst itself (the
+        resident tensors are updated where they lie; a plain or pred tensor overwrites its bytes, a refused one keeps them).  dst must not
+        overlap planes."""
+        E = _elem(elem_bytes)
+        self._flat(planes, "planes")
+        doff, dhost = self._offsets(dst_offsets, planes.device, dst is None)
+        n = doff.numel() - 1
+        poff = _i64(self, plane_offsets, n * E, planes.device, "plane_offsets")
+        psz = _i64(self, plane_sizes, n * E, planes.device, "plane_sizes")
+        dst, capacity, g = _dst_room(self, dst, capacity, dhost, planes.device)
+        _base(self, base, planes, capacity, "dst")
+        tr = _transforms(transforms, n, planes.device)
+        res = _i64(self, results, n, planes.device, "results")
+        what = "planes_merge_each_dbatch"
+        _check(self.lib.FSEHIP_planes_merge_each_dbatch(_ptr(dst), _ptr(doff), _ptr(res), _ptr(planes), _ptr(poff), _ptr(psz), _ptr(base),
+                                                        VP(tr.data_ptr() or res.data_ptr()), SZ(n), C.c_uint(E), C.c_uint64(capacity), _stream()), what)
+        if g is not None:
+            g.check(what)
+        return dst, res
+
+    def _compress_each(self, what, src, src_offsets, elem_bytes, transforms, base, candidate_mask, margin_permille, est_bytes, segment_log, seg_first, n_segments, codec,
+                       codecs, block_size_id, capacity, dst, dst_capacity, max_total_blocks, align_log, frame_offsets, frame_results, tensor_results, planes,
+                       plane_offsets, seg_offsets, workspace, chosen):
+        E = _elem(elem_bytes)
+        align_log = _align_log(align_log)
+        seg = segment_log is not None
+        L = _seg_log(segment_log, min(block_size_id, 6)) if seg else 0
+        self._flat(src, "src")
+        soff, shost = self._offsets(src_offsets, src.device, (seg and seg_first is None) or max_total_blocks is None or (dst is None and dst_capacity is None))
+        n = soff.numel() - 1
+        capacity = _room(self, src, capacity, "src")
+        _base(self, base, src, capacity, "src")
+        pick = transforms is None                               # the call chooses and returns the choice
+        if pick and candidate_mask is None:
+            candidate_mask = 3 if base is None else 15
+        if not pick:
+            tr = _transforms(transforms, n, src.device)
+        else:
+            tr = torch.zeros(max(n, 1), dtype=torch.uint8, device=src.device)[:n] if chosen is None else _u8(chosen, n, src.device, "chosen")[:n]
+        eb = None if est_bytes is None else _i64(self, est_bytes, n * 4, src.device, "est_bytes")
+        if seg:
+            if seg_first is None:
+                seg_first = planes_segment_first(self, np.diff(shost.astype(np.int64)).clip(min=0), E, L)
+            sf, nf = _seg_first(self, seg_first, n_segments, src.device, n * E)
+        else:
+            sf, nf = None, n * E
+        mixed = codecs is not None or isinstance(codec, AutoCodec)
+        choose = mixed and codecs is None
+        codecs, cgu = _codecs(self, codecs, nf, src.device) if mixed else (None, None)
+        max_total_blocks, dst, dst_capacity, g = _frames_room(self, shost, n, E, nf, block_size_id, max_total_blocks, dst, dst_capacity, align_log, src.device)
+        planes = _split_room(self, planes, src, capacity, True)
+        foff = _i64(self, frame_offsets, nf + 1, src.device, "frame_offsets")
+        fres = _i64(self, frame_results, nf, src.device, "frame_results")
+        tres = _i64(self, tensor_results, n, src.device, "tensor_results")
+        poff = _i64(self, plane_offsets, n * E + 1, src.device, "plane_offsets")
+        so = _i64(self, seg_offsets, nf + 1, src.device, "seg_offsets") if seg else None
+        if workspace is None:
+            need = tensor_each_workspace_head(self, n, E, pick, candidate_mask or 0) + _writer_need(self, nf, max_total_blocks, block_size_id, codec, mixed, choose)
+            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=src.device)
+        tol = codec.tolerance_permille if choose and isinstance(codec, AutoCodec) else 0
+        head = (_ptr(dst), C.c_uint64(int(dst_capacity)), _ptr(foff), _ptr(fres), _ptr(tres), _ptr(src), _ptr(base), VP(tr.data_ptr() or tres.data_ptr()),
+                C.c_int(1 if pick else 0), C.c_uint(int(candidate_mask or 0)), C.c_uint(int(margin_permille)), _ptr(eb), _ptr(soff), SZ(n), C.c_uint(E), C.c_uint64(capacity))
+        writer = (SZ(max_total_blocks), C.c_uint(block_size_id), C.c_int(0 if mixed else codec),
+                  _ptr((codecs if codecs.numel() else codecs.new_zeros(1)) if mixed else None), C.c_int(CODECS_CHOOSE if choose else CODECS_GIVEN), C.c_uint(tol),
+                  C.c_uint(align_log), _ptr(planes), _ptr(poff))
+        tail = (_ptr(workspace), SZ(workspace.numel()), _stream())
+        if seg:
+            _check(self.lib.FSEHIP_tensor_compress_seg_each_dbatch(*head, _ptr(sf), SZ(nf), C.c_uint(L), *writer, _ptr(so), *tail), what)
+        else:
+            _check(self.lib.FSEHIP_tensor_compress_each_dbatch(*head, *writer, *tail), what)
+        _check_codecs(cgu, nf, what)
+        if g is not None:
+            g.check(what)
+        return dst, foff, fres, tres, (codecs[:nf] if mixed else None), tr
+
+    def tensor_compress_each_dbatch(self, src, src_offsets, elem_bytes, transforms=None, base=None, candidate_mask=None, margin_permille=50, est_bytes=None, codec=0,
+                                    codecs=None, block_size_id=5, capacity=None, dst=None, dst_capacity=None, max_total_blocks=None, align_log=0, frame_offsets=None,
+                                    frame_results=None, tensor_results=None, planes=None, plane_offsets=None, workspace=None, chosen=None):
+        """-> (dst, frame_offsets, frame_results, tensor_results, codecs, transforms): planes_split_each_dbatch, then the packed (mixed) writer
+        -- frame i*E+p is the frame that the dedicated composite writes for plane p of tensor i under transforms[i].  transforms given (names,
+        ids or a CUDA uint8 tensor): read.  transforms None: CHOSEN on the device by planes_estimate_dbatch with candidate_mask (default
+        plain | pred without a base, all four with one) and margin_permille, with no host read in between, and returned (in `chosen`, a CUDA
+        uint8 tensor of n entries, where one is given) -- give them back to a later call.  est_bytes (n*4 int64, optional): the estimates of a choosing call.  codec / codecs as tensor_compress_pred_dbatch
+        takes them.  The workspace: tensor_each_workspace_head bytes in front of the (mixed) writer's.  With everything given the call is
+        launches only and can be captured into a graph."""
+        return _compress_each(self, "tensor_compress_each_dbatch", src, src_offsets, elem_bytes, transforms, base, candidate_mask, margin_permille, est_bytes, None, None,
+                              None, codec, codecs, block_size_id, capacity, dst, dst_capacity, max_total_blocks, align_log, frame_offsets, frame_results, tensor_results,
+                              planes, plane_offsets, None, workspace, chosen)
+
+    def tensor_compress_seg_each_dbatch(self, src, src_offsets, elem_bytes, segment_log, transforms=None, base=None, candidate_mask=None, margin_permille=50,
+                                        est_bytes=None, seg_first=None, n_segments=None, codec=0, codecs=None, block_size_id=5, capacity=None, dst=None,
+                                        dst_capacity=None, max_total_blocks=None, align_log=0, frame_offsets=None, frame_results=None, tensor_results=None,
+                                        planes=None, plane_offsets=None, seg_offsets=None, workspace=None, chosen=None):
+        """tensor_compress_each_dbatch with a frame per segment of every plane, as tensor_compress_seg_pred_dbatch cuts them."""
+        return _compress_each(self, "tensor_compress_seg_each_dbatch", src, src_offsets, elem_bytes, transforms, base, candidate_mask, margin_permille, est_bytes,
+                              segment_log, seg_first, n_segments, codec, codecs, block_size_id, capacity, dst, dst_capacity, max_total_blocks, align_log, frame_offsets,
+                              frame_results, tensor_results, planes, plane_offsets, seg_offsets, workspace, chosen)
+
+    def _decompress_each(self, what, frames, frame_offsets, dst_offsets, elem_bytes, transforms, base, segment_log, seg_first, n_segments, dst, dst_capacity,
+                         max_total_blocks, planes, planes_capacity, seg_offsets, seg_results, plane_offsets, plane_sizes, workspace, results):
+        E = _elem(elem_bytes)
+        seg = segment_log is not None
+        L = _seg_log(segment_log) if seg else 0
+        self._flat(frames, "frames")
+        foff, _ = self._offsets(frame_offsets, frames.device, False)
+        doff, dhost = self._offsets(dst_offsets, frames.device, dst is None or planes is None or (seg and seg_first is None))
+        n = doff.numel() - 1
+        if seg:
+            if seg_first is None:
+                seg_first = planes_segment_first(self, np.diff(dhost.astype(np.int64)).clip(min=0), E, L)
+            sf, nf = _seg_first(self, seg_first, n_segments, frames.device, n * E)
+        else:
+            sf, nf = None, n * E
+        if foff.numel() != nf + 1:
+            raise ValueError("frame_offsets: one entry per frame (%d) and one more" % nf)
+        if max_total_blocks is None:
+            _, bfirst = self.frame_plan_dbatch(frames, foff, None, 0)
+            max_total_blocks = int(bfirst[nf].item())
+        dst, dst_capacity, g = _dst_room(self, dst, dst_capacity, dhost, frames.device)
+        _base(self, base, frames, dst_capacity, "dst")
+        tr = _transforms(transforms, n, frames.device)
+        planes, planes_capacity = _planes_room(self, planes, planes_capacity, None if planes is not None else int(dhost[-1]), frames.device)
+        poff = _i64(self, plane_offsets, n * E + 1, frames.device, "plane_offsets")
+        psz = _i64(self, plane_sizes, n * E, frames.device, "plane_sizes")
+        res = _i64(self, results, n, frames.device, "results")
+        workspace = _reader_workspace(self, workspace, nf, max_total_blocks, frames.device)
+        head = (_ptr(dst), _ptr(doff), C.c_uint64(dst_capacity), _ptr(base), VP(tr.data_ptr() or res.data_ptr()), _ptr(res), _ptr(frames), _ptr(foff), SZ(n), C.c_uint(E))
+        tail = (_ptr(poff), _ptr(psz), _ptr(workspace), SZ(workspace.numel()), _stream())
+        if seg:
+            so = _i64(self, seg_offsets, nf + 1, frames.device, "seg_offsets")
+            sres = _i64(self, seg_results, nf, frames.device, "seg_results")
+            _check(self.lib.FSEHIP_tensor_decompress_seg_each_dbatch(*head, _ptr(sf), SZ(nf), C.c_uint(L), SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity),
+                                                                     _ptr(so), _ptr(sres), *tail), what)
+        else:
+            _check(self.lib.FSEHIP_tensor_decompress_each_dbatch(*head, SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity), *tail), what)
+        if g is not None:
+            g.check(what)
+        return dst, res
+
+    def tensor_decompress_each_dbatch(self, frames, frame_offsets, dst_offsets, elem_bytes, transforms, base=None, dst=None, dst_capacity=None, max_total_blocks=None,
+                                      planes=None, planes_capacity=None, plane_offsets=None, plane_results=None, workspace=None, results=None):
+        """tensor_decompress_dbatch of frames that tensor_compress_each_dbatch wrote with these transforms (always given here): the packed
+        reader into `planes`, then planes_merge_each_dbatch.  base (may be dst: in place) for xor and sub tensors."""
+        return _decompress_each(self, "tensor_decompress_each_dbatch", frames, frame_offsets, dst_offsets, elem_bytes, transforms, base, None, None, None, dst,
+                                dst_capacity, max_total_blocks, planes, planes_capacity, None, None, plane_offsets, plane_results, workspace, results)
+
+    def tensor_decompress_seg_each_dbatch(self, frames, frame_offsets, dst_offsets, elem_bytes, segment_log, transforms, base=None, seg_first=None, n_segments=None,
+                                          dst=None, dst_capacity=None, max_total_blocks=None, planes=None, planes_capacity=None, seg_offsets=None, seg_results=None,
+                                          plane_offsets=None, plane_sizes=None, workspace=None, results=None):
+        """tensor_decompress_seg_dbatch of frames that tensor_compress_seg_each_dbatch wrote: the packed reader, the fold, then
+        planes_merge_each_dbatch."""
+        return _decompress_each(self, "tensor_decompress_seg_each_dbatch", frames, frame_offsets, dst_offsets, elem_bytes, transforms, base, segment_log, seg_first,
+                                n_segments, dst, dst_capacity, max_total_blocks, planes, planes_capacity, seg_offsets, seg_results, plane_offsets, plane_sizes, workspace,
+                                results)
+
+    for f in (tensor_each_workspace_head, planes_split_each_dbatch, planes_merge_each_dbatch, tensor_compress_each_dbatch, tensor_compress_seg_each_dbatch,
+              tensor_decompress_each_dbatch, tensor_decompress_seg_each_dbatch):
+        setattr(FseHip, f.__name__, f)
+
     # ---- tensor archives (csrc/planes_archive.hip; fsehip.h "tensor archives"): head | frames in one device buffer, sealed behind the frames a
     # compress call wrote at archive[head_bytes:], opened into the arrays the reading calls take
     def archive_head_bytes(self, n_tensors, n_frames, flags=0, meta_bytes=0):
@@ -3019,9 +3231,11 @@ def _planes_methods():
         parts = []
         for gi, g in enumerate(obj.groups or [None]):
             E, idx, sizes = (1, [], []) if g is None else (g["elem_bytes"], list(g["index"]), list(g["sizes"]))
-            meta = json.dumps(dict(v=1, group=gi, groups=n_groups, tensors=len(obj.dtypes), index=idx, dtypes=[str(obj.dtypes[i]).replace("torch.", "") for i in idx],
-                                   shapes=[list(obj.shapes[i]) for i in idx], codec=_codec_to_json(obj.codec), device_index=device.index),
-                              separators=(",", ":")).encode()
+            fields = dict(v=1, group=gi, groups=n_groups, tensors=len(obj.dtypes), index=idx, dtypes=[str(obj.dtypes[i]).replace("torch.", "") for i in idx],
+                          shapes=[list(obj.shapes[i]) for i in idx], codec=_codec_to_json(obj.codec), device_index=device.index)
+            if getattr(obj, "transforms", None) is not None:    # compress_tensors_each's: the names travel as the predictor does, C has no notion of them
+                fields["transforms"] = [obj.transforms[i] for i in idx]
+            meta = json.dumps(fields, separators=(",", ":")).encode()
             flags = (ARCHIVE_DELTA if obj.delta else 0) | (ARCHIVE_SPARSE if sparse is not None else 0)
             flags |= (ARCHIVE_CODECS if g is not None and "codecs" in g else 0) | (ARCHIVE_DIGESTS if digs is not None and obj.delta else 0)
             nF = 0 if g is None else g["frame_offsets"].numel() - 1
@@ -3116,10 +3330,21 @@ def _planes_methods():
             raise ValueError("open_archive: the archives hold %d of %d tensors" % (sum(d is not None for d in dtypes), n))
         delta = bool(first.flags & ARCHIVE_DELTA)
         codec = groups[0]["_codec"]
+        transforms = None
+        if any("transforms" in g["_meta"] for g in groups):
+            transforms = [None] * n
+            for g in groups:
+                names = g["_meta"].get("transforms")
+                if not isinstance(names, list) or len(names) != len(g["index"]) or any(t not in EST_NAMES for t in names):
+                    raise ValueError("open_archive: the transforms in the meta bytes are not compress_tensors_each's (%r)" % (names,))
+                for i, t in zip(g["index"], names):
+                    transforms[i] = t
         for g in groups:
             for k in ("_info", "_meta", "_dtypes", "_codec", "_digests"):
                 del g[k]
         obj = CompressedTensors(groups if m0["groups"] else [], dtypes, shapes, device if n else None, codec, int(first.blockSizeId), delta)
+        if transforms is not None:
+            obj.transforms = transforms
         return _segmented(obj, int(first.segLog) if first.segLog else None, "sub" if delta and first.deltaOp else "xor",
                           int(first.sparsePermille) if first.flags & ARCHIVE_SPARSE else None, digests, "prev" if isinstance(codec, PredictedPlanes) else None)
 
@@ -3145,6 +3370,8 @@ def _planes_methods():
             raise ValueError(what + ": the object holds sparse planes (SparsePlanes); windows and patches of those are not supported")
         if getattr(obj, "predictor", None) is not None:
             raise ValueError(what + ": the object holds predicted planes (PredictedPlanes); windows and patches of those are not supported")
+        if getattr(obj, "transforms", None) is not None:
+            raise ValueError(what + ": the object holds a transform per tensor (compress_tensors_each); windows and patches of those are not supported")
 
     # ---- the user-facing pair
     def _read_base(obj, base, what):
@@ -3229,6 +3456,8 @@ def _planes_methods():
         op = _delta_op(opname)
         if isinstance(codec, CompressedTensors):            # the codecs an earlier AutoCodec call chose, given again
             earlier, codec = codec, codec.codec
+            if getattr(earlier, "transforms", None) is not None:
+                raise ValueError("compress_tensors: the earlier object holds a transform per tensor (compress_tensors_each), its codecs belong to those planes")
             if any("codecs" not in g for g in earlier.groups):
                 raise ValueError("compress_tensors: the earlier object carries no codecs (it was not written with an AutoCodec)")
             if getattr(earlier, "segment_log", None) != segment_log:
@@ -3351,9 +3580,13 @@ def _planes_methods():
         (tensor_digest_dbatch, tensor_gate_dbatch; one read-back of the verdicts) and ValueError names the tensors whose base is not the one
         the deltas were made against -- before any decode launch, nothing is written; the readers then run over the gated offsets.
         A TensorBundle (compress_tensors_auto): every part is read as above and the tensors come back in the input order; `base` is the base
-        of the WHOLE list, each delta part is handed its slice of it; ValueError before any launch where a delta part has no base."""
+        of the WHOLE list, each delta part is handed its slice of it; ValueError before any launch where a delta part has no base.
+        An object with `transforms` (compress_tensors_each): tensor_decompress_each_dbatch per group; `base` is the base of the whole list and
+        is needed only where a tensor's transform is "xor" or "sub" (ValueError before any launch without it)."""
         if isinstance(obj, TensorBundle):                    # compress_tensors_auto's: part by part, each with its slice of the base
             return _decompress_bundle(self, obj, base)
+        if getattr(obj, "transforms", None) is not None:     # compress_tensors_each's: one object, a transform per tensor
+            return _decompress_each_obj(self, obj, base)
         base, op = _read_base(obj, base, "decompress_tensors")
         if getattr(obj, "predictor", None) not in (None, "prev"):
             raise ValueError("decompress_tensors: predictor %r, \"prev\" is the one there is" % (obj.predictor,))
@@ -3522,6 +3755,125 @@ def _planes_methods():
                 out[i] = t
         return out
 
+    def compress_tensors_each(self, tensors, transforms="auto", base=None, codec=0, block_size_id=5, segment_log=None, margin_permille=50):
+        """A mixed list of CUDA tensors -> ONE CompressedTensors whose `transforms` lists the plane transform of every tensor ("plain", "pred",
+        "xor", "sub"): what compress_tensors_auto chooses, without cutting the list -- per group of one element size one
+        tensor_compress_each_dbatch (with segment_log: tensor_compress_seg_each_dbatch), which estimates, chooses, splits and writes on the
+        device, and ONE read-back at the end: the frame total, the results and the choices.  The object is an ordinary one: archive_tensors,
+        open_archive, save_tensors and load_tensors carry it (the names travel in the meta bytes), decompress_tensors(obj, base) reads it.
+        transforms: "auto" -- the candidates are "plain" and "pred" without a base and all four with one, margin_permille as
+        estimate_tensors takes it -- or one name per tensor, given ("choose once, then give": obj.transforms of an earlier call).
+        base: a sequence matching `tensors` one to one (or a DeltaBase without check: its tensors); needed where a given name is "xor" or
+        "sub".  codec: 0, 1 or an AutoCodec.  A tensor of 0 bytes takes the lowest candidate and needs no company.
+        Out of scope, each a ValueError before any launch: a SparsePlanes or PredictedPlanes as codec, an earlier object as codec, a
+        DeltaBase(check=True); windows and patches of the object (decompress_tensor_windows, patch_tensor_windows)."""
+        what = "compress_tensors_each"
+        margin = _margin(margin_permille, what)
+        if isinstance(codec, bool) or not (isinstance(codec, AutoCodec) or (isinstance(codec, numbers.Integral) and codec in (0, 1))):
+            raise ValueError("%s: codec %r; 0, 1 or an AutoCodec is needed (sparse planes, predicted planes and earlier objects do not go around a transform per "
+                             "tensor)" % (what, codec))
+        if isinstance(base, DeltaBase):
+            if base.check:
+                raise ValueError(what + ": DeltaBase(check=True) -- digests and gating are not supported with a transform per tensor")
+            base = base.tensors
+        base = None if base is None else list(base)
+        if segment_log is not None:
+            segment_log = _seg_log(segment_log, block_size_id if isinstance(block_size_id, numbers.Integral) and 0 <= block_size_id <= 6 else 0)
+        tensors = list(tensors)
+        auto = isinstance(transforms, str)
+        if auto and transforms != "auto":
+            raise ValueError("%s: transforms %r; \"auto\" or one name per tensor out of %r is needed" % (what, transforms, EST_NAMES))
+        if not auto:
+            transforms = list(transforms)
+            if len(transforms) != len(tensors) or any(not isinstance(t, str) or t not in EST_NAMES for t in transforms):
+                raise ValueError("%s: transforms %r; \"auto\" or one name per tensor (%d) out of %r is needed" % (what, transforms[:8], len(tensors), EST_NAMES))
+            if base is None and any(t in ("xor", "sub") for t in transforms):
+                raise ValueError(what + ": \"xor\" and \"sub\" are deltas against a base, none was given")
+        if not tensors:
+            if base is not None and len(base):
+                raise ValueError("base: tensors for none")
+            obj = _segmented(CompressedTensors([], [], [], None, codec, block_size_id), segment_log)
+            obj.transforms = []
+            return obj
+        device = tensors[0].device if isinstance(tensors[0], torch.Tensor) else None
+        for k, t in enumerate(tensors):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
+                raise TypeError(what + " takes CUDA tensors of one device")
+            _elem(t.element_size())
+            if auto and t.numel() * t.element_size() >= 1 << 32:
+                raise ValueError("%s: tensor %d holds 2^32 bytes or more, the estimate's counts are 32 bits wide" % (what, k))
+        braw = None if base is None else _bases(base, [t.dtype for t in tensors], [tuple(t.shape) for t in tensors], device)
+        names, groups = [None] * len(tensors), []
+        with torch.cuda.device(device):
+            for E in (1, 2, 4, 8):
+                idx = [i for i, t in enumerate(tensors) if t.element_size() == E]
+                if not idx:
+                    continue
+                raw = [tensors[i].contiguous().reshape(-1).view(torch.uint8) for i in idx]
+                offs = np.concatenate([[0], np.cumsum([r.numel() for r in raw])]).astype(np.uint64)
+                src = torch.cat(raw) if int(offs[-1]) else torch.zeros(1, dtype=torch.uint8, device=device)[:0]
+                bsrc = None if braw is None else torch.cat([braw[i] for i in idx]) if int(offs[-1]) else src
+                given = None if auto else [transforms[i] for i in idx]
+                sfirst = None
+                if segment_log is not None:
+                    sfirst = self.planes_segment_first(np.diff(offs.astype(np.int64)), E, segment_log)
+                    dst, foff, fres, tres, codecs, tr = tensor_compress_seg_each_dbatch(self, src, offs, E, segment_log, given, bsrc, None, margin, seg_first=sfirst,
+                                                                                        codec=codec, block_size_id=block_size_id)
+                else:
+                    dst, foff, fres, tres, codecs, tr = tensor_compress_each_dbatch(self, src, offs, E, given, bsrc, None, margin, codec=codec, block_size_id=block_size_id)
+                got = torch.cat([foff[-1:], fres, tres, tr.to(torch.int64)]).cpu().tolist()      # the one read-back of the group
+                nf, n = fres.numel(), len(idx)
+                if min(got[:1 + nf + n]) < 0 or max(got[1 + nf + n:]) > 3:
+                    bad = [k for k, r in enumerate(got[1:1 + nf]) if r < 0]
+                    raise RuntimeError("%s: element size %d, frames %s failed (%s), tensor results %s, transforms %s"
+                                       % (what, E, bad[:8], [got[1 + k] for k in bad[:8]], got[1 + nf:1 + nf + n][:8], got[1 + nf + n:][:8]))
+                for k, i in enumerate(idx):
+                    names[i] = EST_NAMES[got[1 + nf + n + k]]
+                groups.append(dict(elem_bytes=E, index=idx, sizes=[int(x) for x in np.diff(offs)], frames=dst[:got[0]].clone(), frame_offsets=foff,
+                                   frame_results=fres, tensor_results=tres))
+                if codecs is not None:
+                    groups[-1]["codecs"] = codecs.clone()
+                if sfirst is not None:
+                    groups[-1]["seg_first"] = sfirst
+        obj = _segmented(CompressedTensors(groups, [t.dtype for t in tensors], [tuple(t.shape) for t in tensors], device, codec, block_size_id), segment_log)
+        obj.transforms = names
+        return obj
+
+    def _decompress_each_obj(self, obj, base):
+        what = "decompress_tensors"
+        names = list(obj.transforms)
+        if len(names) != len(obj.dtypes) or any(t not in EST_NAMES for t in names):
+            raise ValueError("%s: transforms %r; one name per tensor (%d) out of %r is needed" % (what, names[:8], len(obj.dtypes), EST_NAMES))
+        if getattr(obj, "sparse_permille", None) is not None or getattr(obj, "base_digests", None) is not None or getattr(obj, "predictor", None) is not None:
+            raise ValueError(what + ": sparse planes, base digests and a predictor do not go with a transform per tensor")
+        if isinstance(base, DeltaBase):
+            base = base.tensors
+        needs = any(t in ("xor", "sub") for t in names)
+        if needs and base is None:
+            raise ValueError(what + ": the object holds \"xor\" or \"sub\" tensors and needs its base")
+        braw = _bases(base, obj.dtypes, obj.shapes, obj.device) if needs else None
+        seg_log = getattr(obj, "segment_log", None)
+        out = [None] * len(obj.dtypes)
+        for g in obj.groups:
+            E, sizes = g["elem_bytes"], g["sizes"]
+            offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
+            blocks = self.planes_block_bound(sum(sizes), len(sizes), E, obj.block_size_id)
+            tr = [names[i] for i in g["index"]]
+            dst = None if braw is None else _base_copy(braw, g, obj.device)       # (a copy: rebuilt in place, the bases stay)
+            if seg_log is not None:
+                dst, res = tensor_decompress_seg_each_dbatch(self, g["frames"], g["frame_offsets"], offs, E, seg_log, tr, dst, g["seg_first"], dst=dst,
+                                                             max_total_blocks=blocks)
+            else:
+                dst, res = tensor_decompress_each_dbatch(self, g["frames"], g["frame_offsets"], offs, E, tr, dst, dst=dst, max_total_blocks=blocks)
+            got = res.cpu().tolist()
+            if got != sizes:
+                raise RuntimeError("%s: element size %d, results %s for tensors of %s bytes" % (what, E, got[:8], sizes[:8]))
+            for k, i in enumerate(g["index"]):
+                out[i] = dst[int(offs[k]):int(offs[k + 1])].clone().view(obj.dtypes[i]).reshape(obj.shapes[i])
+        return out
+
+    setattr(FseHip, "compress_tensors_each", compress_tensors_each)
+
     def decompress_tensor_windows(self, obj, windows, base=None):
         """-> per tensor of `obj` (a CompressedTensors of compress_tensors_segmented) the elements [start, stop) of the FLATTENED tensor as a 1-D
         tensor of the recorded dtype that owns its memory: a row shard, a slice, a row range.  `windows` has one entry per tensor: None (the
@@ -3618,6 +3970,11 @@ def estimate_tensors(tensors, base=None, candidates=None, margin_permille=50):
 def compress_tensors_auto(tensors, base=None, codec=0, block_size_id=5, segment_log=None, margin_permille=50):
     """FseHip.compress_tensors_auto on a library handle of the module's own"""
     return _default().compress_tensors_auto(tensors, base, codec, block_size_id, segment_log, margin_permille)
+
+
+def compress_tensors_each(tensors, transforms="auto", base=None, codec=0, block_size_id=5, segment_log=None, margin_permille=50):
+    """FseHip.compress_tensors_each on a library handle of the module's own"""
+    return _default().compress_tensors_each(tensors, transforms, base, codec, block_size_id, segment_log, margin_permille)
 
 
 def decompress_tensor_windows(obj, windows, base=None):

@@ -1,0 +1,161 @@
+// capi_each.hip -- the C calls of "a transform per tensor" (fsehip.h): argument checks in front of the first launch, then launches only.
+//
+//   FSEHIP_planes_split_each_dbatch / _merge_each_dbatch : the launchers of planes_each.hip
+//   FSEHIP_tensor_compress(_seg)_each_dbatch   : [CHOOSE: FSEHIP_planes_estimate_dbatch, its choice into d_transforms] -> the split by d_transforms
+//                                                -> [the segments kernel] -> the packed (mixed) writer
+//   FSEHIP_tensor_decompress(_seg)_each_dbatch : the packed reader -> [the fold] -> the merge by d_transforms
+//
+// The workspace of a CHOOSE call: the estimate's counters, plane costs, estimates and results (each a multiple of 256) in front of the
+// writer's workspace; FSEHIP_tensor_each_workspaceHead is their sum.
+#include "planes_dev.h"
+
+namespace {
+inline size_t r256(size_t x) { return (x + 255) & ~(size_t)255; }
+struct EachHead { size_t counters, bits, est, res; size_t total() const { return counters + bits + est + res; } };
+// mask and nTensors as FSEHIP_planes_estimate_workspaceBound takes them (an error: counters holds it)
+inline EachHead each_head(size_t nTensors, unsigned E, unsigned mask)
+{
+    return { FSEHIP_planes_estimate_workspaceBound(nTensors, E, mask), r256(nTensors * 4 * E * sizeof(u64)), r256(nTensors * 4 * sizeof(u64)), r256(nTensors * sizeof(size_t)) };
+}
+inline bool bad_policy(int transformPolicy) { return transformPolicy != FSEHIP_TRANSFORMS_GIVEN && transformPolicy != FSEHIP_TRANSFORMS_CHOOSE; }
+
+// the one compress path of the two composites, each of which has checked its own pointers
+int each_compress(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults, const void* d_src, const void* d_base,
+                  uint8_t* d_transforms, int transformPolicy, unsigned candidateMask, unsigned marginPermille, uint64_t* d_estBytes, const uint64_t* d_srcOffsets,
+                  size_t nTensors, unsigned E, uint64_t capacity, const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, void* d_planes, uint64_t* d_planeOffsets,
+                  uint64_t* d_segOffsets, const PlWriter& writer, void* stream)
+{
+    if (bad_policy(transformPolicy)) return (int)hipErrorInvalidValue;
+    if (d_segFirst ? bad_seg(segLog, writer.blockSizeId) || bad_counts(nTensors, E, nSegments) : bad_tensors(nTensors, E)) return (int)hipErrorInvalidValue;
+    const size_t nFrames = d_segFirst ? nSegments : nTensors * E;
+    const bool choose = transformPolicy == FSEHIP_TRANSFORMS_CHOOSE;
+    EachHead h = { 0, 0, 0, 0 };
+    if (choose) {
+        const unsigned baseBits = (1u << FSEHIP_EST_XOR) | (1u << FSEHIP_EST_SUB);
+        if (marginPermille > 1000 || ((candidateMask & baseBits) && !d_base)) return (int)hipErrorInvalidValue;
+        h = each_head(nTensors, E, candidateMask);
+        if (FSEHIP_isError(h.counters)) return (int)hipErrorInvalidValue;   // (a mask of 0 or with an unknown bit; 2^24 tensors)
+    }
+    if (((uintptr_t)writer.d_workspace & 255u) || writer.workspaceBytes < h.total() || (h.total() && !writer.d_workspace)) return (int)hipErrorInvalidValue;
+    PlWriter w = writer;
+    u8* const ws = (u8*)writer.d_workspace;
+    if (h.total()) { w.d_workspace = ws + h.total(); w.workspaceBytes -= h.total(); }
+    if (bad_grid(capacity, nTensors) || bad_writer(w, nFrames)) return (int)hipErrorInvalidValue;
+    if (choose) {
+        u64* const bits = (u64*)(ws + h.counters);
+        u64* const est = d_estBytes ? (u64*)d_estBytes : (u64*)(ws + h.counters + h.bits);
+        size_t* const res = (size_t*)(ws + h.counters + h.bits + h.est);
+        const int r = FSEHIP_planes_estimate_dbatch(bits, est, d_transforms, res, d_src, d_base, d_srcOffsets, nTensors, E, capacity, candidateMask, marginPermille, ws,
+                                                    h.counters, stream);
+        if (r != 0) return r;
+    }
+    const hipStream_t s = (hipStream_t)stream;
+    hipError_t e = launch_planes_split_each((u8*)d_planes, (u64*)d_planeOffsets, d_tensorResults, (const u8*)d_src, (const u8*)d_base, d_transforms,
+                                            (const u64*)d_srcOffsets, nTensors, E, capacity, s);
+    if (e == hipSuccess && d_segFirst)
+        e = launch_segments((u64*)d_segOffsets, d_tensorResults, (const u64*)d_planeOffsets, (const u64*)d_srcOffsets, (const u64*)d_segFirst, nTensors, E, nSegments, segLog, s);
+    if (e != hipSuccess) return (int)e;
+    const uint64_t* const fromOff = d_segFirst ? d_segOffsets : d_planeOffsets;
+    if (w.d_codecs)
+        return FSEHIP_frame_compress_packed_mixed_dbatch(d_dst, dstCapacity, d_frameOffsets, d_frameResults, d_planes, fromOff, nFrames, w.maxTotalBlocks, w.blockSizeId,
+                                                         w.d_codecs, w.policy, w.tolerancePermille, w.slotAlignLog, w.d_workspace, w.workspaceBytes, stream);
+    return FSEHIP_frame_compress_packed_dbatch(d_dst, dstCapacity, d_frameOffsets, d_frameResults, d_planes, fromOff, nFrames, w.maxTotalBlocks, w.blockSizeId, w.codec,
+                                               w.slotAlignLog, w.d_workspace, w.workspaceBytes, stream);
+}
+}   // namespace
+
+extern "C" size_t FSEHIP_tensor_each_workspaceHead(size_t nTensors, unsigned elemBytes, int transformPolicy, unsigned candidateMask)
+{
+    if (bad_elem(elemBytes) || bad_policy(transformPolicy)) return FSEHIP_ERROR(GENERIC);
+    if (transformPolicy == FSEHIP_TRANSFORMS_GIVEN) return 0;
+    const EachHead h = each_head(nTensors, elemBytes, candidateMask);
+    return FSEHIP_isError(h.counters) ? h.counters : h.total();
+}
+
+extern "C" int FSEHIP_planes_split_each_dbatch(void* d_planes, uint64_t* d_planeOffsets, size_t* d_tensorResults, const void* d_src, const void* d_base,
+                                               const uint8_t* d_transforms, const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes, uint64_t capacity,
+                                               void* stream)
+{
+    if (bad_elem(elemBytes) || !d_planes || !d_planeOffsets || !d_tensorResults || !d_src || !d_transforms || !d_srcOffsets) return (int)hipErrorInvalidValue;
+    if (bad_tensors(nTensors, elemBytes) || bad_grid(capacity, nTensors)) return (int)hipErrorInvalidValue;
+    return (int)launch_planes_split_each((u8*)d_planes, (u64*)d_planeOffsets, d_tensorResults, (const u8*)d_src, (const u8*)d_base, d_transforms, (const u64*)d_srcOffsets,
+                                         nTensors, elemBytes, capacity, (hipStream_t)stream);
+}
+
+extern "C" int FSEHIP_planes_merge_each_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_planes, const uint64_t* d_planeOffsets,
+                                               const size_t* d_planeSizes, const void* d_base, const uint8_t* d_transforms, size_t nTensors, unsigned elemBytes,
+                                               uint64_t dstCapacity, void* stream)
+{
+    if (bad_elem(elemBytes) || !d_dst || !d_dstOffsets || !d_results || !d_planes || !d_planeOffsets || !d_planeSizes || !d_transforms) return (int)hipErrorInvalidValue;
+    if (bad_tensors(nTensors, elemBytes) || bad_grid(dstCapacity, nTensors)) return (int)hipErrorInvalidValue;
+    return (int)launch_planes_merge_each((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeSizes, (const u8*)d_base,
+                                         d_transforms, nTensors, elemBytes, dstCapacity, (hipStream_t)stream);
+}
+
+extern "C" int FSEHIP_tensor_compress_each_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
+                                                  const void* d_src, const void* d_base, uint8_t* d_transforms, int transformPolicy, unsigned candidateMask,
+                                                  unsigned marginPermille, uint64_t* d_estBytes, const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes,
+                                                  uint64_t capacity, size_t maxTotalBlocks, unsigned blockSizeId, int codec, uint8_t* d_codecs, int policy,
+                                                  unsigned tolerancePermille, unsigned slotAlignLog, void* d_planes, uint64_t* d_planeOffsets, void* d_workspace,
+                                                  size_t workspaceBytes, void* stream)
+{
+    if (bad_elem(elemBytes) || !d_frameOffsets || !d_frameResults || !d_tensorResults || !d_src || !d_transforms || !d_srcOffsets || !d_planeOffsets || !d_planes)
+        return (int)hipErrorInvalidValue;
+    return each_compress(d_dst, dstCapacity, d_frameOffsets, d_frameResults, d_tensorResults, d_src, d_base, d_transforms, transformPolicy, candidateMask, marginPermille,
+                         d_estBytes, d_srcOffsets, nTensors, elemBytes, capacity, nullptr, 0, 0, d_planes, d_planeOffsets, nullptr,
+                         PlWriter{ maxTotalBlocks, blockSizeId, codec, d_codecs, policy, tolerancePermille, slotAlignLog, d_workspace, workspaceBytes }, stream);
+}
+
+extern "C" int FSEHIP_tensor_compress_seg_each_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
+                                                      const void* d_src, const void* d_base, uint8_t* d_transforms, int transformPolicy, unsigned candidateMask,
+                                                      unsigned marginPermille, uint64_t* d_estBytes, const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes,
+                                                      uint64_t capacity, const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, size_t maxTotalBlocks,
+                                                      unsigned blockSizeId, int codec, uint8_t* d_codecs, int policy, unsigned tolerancePermille, unsigned slotAlignLog,
+                                                      void* d_planes, uint64_t* d_planeOffsets, uint64_t* d_segOffsets, void* d_workspace, size_t workspaceBytes,
+                                                      void* stream)
+{
+    if (bad_elem(elemBytes) || !d_frameOffsets || !d_frameResults || !d_tensorResults || !d_src || !d_transforms || !d_srcOffsets || !d_segFirst || !d_planeOffsets ||
+        !d_segOffsets || !d_planes)
+        return (int)hipErrorInvalidValue;
+    return each_compress(d_dst, dstCapacity, d_frameOffsets, d_frameResults, d_tensorResults, d_src, d_base, d_transforms, transformPolicy, candidateMask, marginPermille,
+                         d_estBytes, d_srcOffsets, nTensors, elemBytes, capacity, d_segFirst, nSegments, segLog, d_planes, d_planeOffsets, d_segOffsets,
+                         PlWriter{ maxTotalBlocks, blockSizeId, codec, d_codecs, policy, tolerancePermille, slotAlignLog, d_workspace, workspaceBytes }, stream);
+}
+
+// the argument checks of both steps in front of the first launch
+extern "C" int FSEHIP_tensor_decompress_each_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base, const uint8_t* d_transforms,
+                                                    size_t* d_results, const void* d_frames, const uint64_t* d_frameOffsets, size_t nTensors, unsigned elemBytes,
+                                                    size_t maxTotalBlocks, void* d_planes, uint64_t planesCapacity, uint64_t* d_planeOffsets, size_t* d_planeResults,
+                                                    void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    if (bad_elem(elemBytes) || !d_dst || !d_dstOffsets || !d_transforms || !d_results || !d_frames || !d_frameOffsets || !d_planes || !d_planeOffsets || !d_planeResults)
+        return (int)hipErrorInvalidValue;
+    if (bad_tensors(nTensors, elemBytes) || bad_grid(dstCapacity, nTensors) || bad_reader(d_workspace, workspaceBytes, nTensors * elemBytes, maxTotalBlocks))
+        return (int)hipErrorInvalidValue;
+    const int r = FSEHIP_frame_decompress_packed_dbatch(d_planes, (size_t)planesCapacity, d_planeOffsets, d_planeResults, d_frames, d_frameOffsets, nTensors * elemBytes,
+                                                        maxTotalBlocks, 0, d_workspace, workspaceBytes, stream);
+    if (r != 0) return r;
+    return (int)launch_planes_merge_each((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeResults,
+                                         (const u8*)d_base, d_transforms, nTensors, elemBytes, dstCapacity, (hipStream_t)stream);
+}
+
+extern "C" int FSEHIP_tensor_decompress_seg_each_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base, const uint8_t* d_transforms,
+                                                        size_t* d_results, const void* d_frames, const uint64_t* d_frameOffsets, size_t nTensors, unsigned elemBytes,
+                                                        const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, size_t maxTotalBlocks, void* d_planes,
+                                                        uint64_t planesCapacity, uint64_t* d_segOffsets, size_t* d_segResults, uint64_t* d_planeOffsets,
+                                                        size_t* d_planeSizes, void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    if (bad_elem(elemBytes) || !d_dst || !d_dstOffsets || !d_transforms || !d_results || !d_frames || !d_frameOffsets || !d_segFirst || !d_planes || !d_segOffsets ||
+        !d_segResults || !d_planeOffsets || !d_planeSizes)
+        return (int)hipErrorInvalidValue;
+    if (bad_seg(segLog, 0) || bad_counts(nTensors, elemBytes, nSegments) || bad_grid(dstCapacity, nTensors) || bad_reader(d_workspace, workspaceBytes, nSegments, maxTotalBlocks))
+        return (int)hipErrorInvalidValue;
+    const int r = FSEHIP_frame_decompress_packed_dbatch(d_planes, (size_t)planesCapacity, d_segOffsets, d_segResults, d_frames, d_frameOffsets, nSegments, maxTotalBlocks, 0,
+                                                        d_workspace, workspaceBytes, stream);
+    if (r != 0) return r;
+    const int f = FSEHIP_planes_fold_segments_dbatch(d_planeOffsets, d_planeSizes, d_segOffsets, d_segResults, d_segFirst, (size_t)nTensors * elemBytes, nSegments, segLog,
+                                                     stream);
+    if (f != 0) return f;
+    return (int)launch_planes_merge_each((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeSizes, (const u8*)d_base,
+                                         d_transforms, nTensors, elemBytes, dstCapacity, (hipStream_t)stream);
+}

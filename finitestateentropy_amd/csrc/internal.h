@@ -369,6 +369,12 @@ hipError_t launch_planes_split_pred(u8* planes, u64* planeOff, size_t* tensorRes
 hipError_t launch_planes_merge_pred(u8* dst, const u64* dstOff, size_t* results, const u8* planes, const u64* planeOff, const size_t* planeSizes, size_t nTensors,
                                     unsigned E, u64 dstCapacity, hipStream_t s);
 hipError_t launch_planes_verdicts(size_t* results, const u64* dstOff, const size_t* planeSizes, size_t nTensors, unsigned E, u64 dstCapacity, hipStream_t s);
+// a transform per tensor (planes_each.hip; fsehip.h, "a transform per tensor"): the split and the merge that read tensor i's transform, an
+// FSEHIP_EST_* id, from transforms[i]; base null: an XOR or SUB tensor is refused.  The C calls are in capi_each.hip
+hipError_t launch_planes_split_each(u8* planes, u64* planeOff, size_t* tensorRes, const u8* src, const u8* base, const u8* transforms, const u64* srcOff, size_t nTensors,
+                                    unsigned E, u64 capacity, hipStream_t s);
+hipError_t launch_planes_merge_each(u8* dst, const u64* dstOff, size_t* results, const u8* planes, const u64* planeOff, const size_t* planeSizes, const u8* base,
+                                    const u8* transforms, size_t nTensors, unsigned E, u64 dstCapacity, hipStream_t s);
 
 // ---- kernel timing probe (HIP events on the launch stream; used by bench.py for the live roofline figure) ----
 enum { PK_HIST = 0, PK_FSE_CPREP, PK_FSE_ENCODE, PK_FSE_DPREP, PK_FSE_DECODE, PK_HUF_CPREP, PK_HUF_ENCODE, PK_HUF_DPREP, PK_HUF_DECODE, PK_FSE_ENCODE_WAVE, PK_COUNT };

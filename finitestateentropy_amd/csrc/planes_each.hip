@@ -1,0 +1,222 @@
+// planes_each.hip -- A TRANSFORM PER TENSOR (fsehip.h, "a transform per tensor"): the split and the merge of planes.hip and planes_pred.hip with
+// the transform read from a device array, one byte per tensor -- FSEHIP_EST_PLAIN, _PRED, _XOR or _SUB, the ids that the estimate
+// (planes_estimate.hip) writes to d_choice.  No transform of its own: the planes of tensor i are byte for byte those that the dedicated
+// split writes for it under transform T[i], and the merge is that split's inverse.  Kernel launches only; the C calls are in capi_each.hip.
+//
+//   launch_planes_split_each : k_planes_offsets (planes.hip) -> k_each_refuse -> k_planes_split_each
+//   launch_planes_merge_each : k_planes_verdicts (planes.hip) -> k_each_refuse -> k_planes_merge_each
+//
+// THE SPLIT has the frame of k_planes_split_pred: the flat ragged mapping (a workgroup per (tile, tensor) intersection, pl_find) and chunks
+// of 16 whole elements per lane counted from the TENSOR's start.  That frame serves all four: SUB and PRED need whole elements per dword,
+// XOR commutes with the shuffle, and where a chunk starts changes no byte of a plane.  A workgroup has ONE tensor, so the transform is
+// uniform over the workgroup -- sixty tiny tensors in a tile are sixty workgroups -- and the branch on it is taken once, in front of the
+// loops: each arm is the body of the dedicated kernel, made of the same helpers (planes_dev.h).  The base's chunk is loaded in the XOR and
+// SUB arms only, the predecessor element in the PRED arm only.
+//
+// THE MERGE has the frame of k_planes_merge_pred: tiles relative to the tensor, a workgroup owns whole runs, one run is one round of one
+// wave, no LDS, no workspace.  The PRED arm is that kernel's round (all 64 lanes in the scan); the other three are element-wise in the
+// same rounds.  IN PLACE (base == dst) as in the delta merge: a byte of dst is read as base and written by one thread, whose base loads
+// of a chunk stand in front of its stores.  A PLAIN or PRED tensor reads no base and overwrites its bytes.
+//
+// REFUSALS: a transform byte above FSEHIP_EST_SUB (the estimate's 0xFF among them), or XOR / SUB without a base: k_each_refuse writes GENERIC
+// over the tensor's result, and the data kernels return for it in front of every load and store.
+#include "planes_dev.h"
+
+namespace {
+DEV bool pe_ok(u32 tr, const void* base) { return tr <= FSEHIP_EST_SUB && (tr < FSEHIP_EST_XOR || base); }
+
+__global__ void k_each_refuse(size_t* res, const u8* T, const u8* base, size_t nT)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nT && !pe_ok(T[i], base)) res[i] = FERR(GENERIC);
+}
+
+// ---- split -------------------------------------------------------------------------------------------------------------------------------
+// a workgroup's share of the tensor at sb (n bytes at flat position s0, base bb, planes at pb) under transform TR
+template <int E, int TR> DEV void pe_split(u8* pb, const u8* sb, const u8* bb, u64 s0, u64 n, u64 lo, u32 tid)
+{
+    const PlShare h = pl_share<E>(s0, n, lo, 0, 1);               // chunks at multiples of 16 elements of the tensor
+    for (u64 c = tid; c < h.nch; c += PL_THREADS) {
+        const u64 e = h.eb + 16 * c;
+        u32 wv[4 * E], o[E][4];
+#pragma unroll
+        for (int k = 0; k < E; ++k) __builtin_memcpy(&wv[4 * k], sb + e * E + 16 * k, 16);
+        if constexpr (TR == FSEHIP_EST_PRED) {
+            u32 pv[4 * E];
+            pp_prev<E>(pv, wv, sb + e * E, (e & (PP_RUN - 1)) == 0);
+#pragma unroll
+            for (int k = 0; k < E; ++k) pl_sub4<E, false>(&wv[4 * k], &pv[4 * k]);
+        } else if constexpr (TR != FSEHIP_EST_PLAIN) {
+#pragma unroll
+            for (int k = 0; k < E; ++k) pl_base16<E, TR == FSEHIP_EST_SUB ? PL_SUB : PL_XOR, false>(&wv[4 * k], bb + e * E + 16 * k);
+        }
+        pl_deinterleave<E>(wv, o);
+#pragma unroll
+        for (int p = 0; p < E; ++p) __builtin_memcpy(pb + pl_start(n, p, E) + e, o[p], 16);
+    }
+    // head and tail, an element per thread; the partial last element of the tensor byte by byte
+    const u64 nHead = h.eb - h.e0, nTail = h.e1 - h.et;
+    for (u64 j = tid; j < nHead + nTail; j += PL_THREADS) {
+        const u64 e = j < nHead ? h.e0 + j : h.et + (j - nHead);
+        if constexpr (TR == FSEHIP_EST_PRED) pp_elem_split<E>(pb, sb, n, e);
+        else if constexpr (TR == FSEHIP_EST_SUB) pl_sub_elem_split<E>(pb, sb, bb, n, e);
+        else {
+#pragma unroll
+            for (int p = 0; p < E; ++p) {
+                const u64 k = e * E + p;
+                if (k < n) {
+                    u8 v = sb[k];
+                    if constexpr (TR == FSEHIP_EST_XOR) v ^= bb[k];
+                    pb[pl_start(n, p, E) + e] = v;
+                }
+            }
+        }
+    }
+}
+
+template <int E>
+__global__ __launch_bounds__(PL_THREADS) void k_planes_split_each(u8* planes, const u8* src, const u8* base, const u8* T, const u64* S, size_t nT, u64 capacity)
+{
+    const u64 w = blockIdx.x;
+    size_t i;
+    if (!pl_find(S, nT, w, i)) return;                            // (uniform, like every return below)
+    const u64 s0 = S[i], s1 = S[i + 1], lo = (w - i) << PL_TILE_LOG;
+    if (!(s0 < s1) || s1 > capacity || lo >= s1 || lo + PLANES_TILE <= s0) return;
+    const u32 tr = T[i];
+    if (!pe_ok(tr, base)) return;                                 // (a refused tensor: nothing of it is read or written)
+    const u64 n = s1 - s0;
+    const u32 tid = threadIdx.x;
+    const u8* const sb = src + s0;
+    u8* const pb = planes + s0;
+    if (tr == FSEHIP_EST_PLAIN) pe_split<E, FSEHIP_EST_PLAIN>(pb, sb, nullptr, s0, n, lo, tid);
+    else if (tr == FSEHIP_EST_PRED) pe_split<E, FSEHIP_EST_PRED>(pb, sb, nullptr, s0, n, lo, tid);
+    else if (tr == FSEHIP_EST_XOR) pe_split<E, FSEHIP_EST_XOR>(pb, sb, base + s0, s0, n, lo, tid);
+    else pe_split<E, FSEHIP_EST_SUB>(pb, sb, base + s0, s0, n, lo, tid);
+}
+
+// ---- merge -------------------------------------------------------------------------------------------------------------------------------
+// the runs of tile t of the tensor at db (n bytes, base bb, plane p at planes + P[p]) under transform TR
+template <int E, int TR> DEV void pe_merge(u8* db, const u8* bb, const u8* planes, const u64* P, u64 n, u64 t)
+{
+    constexpr u32 RUNS = (u32)(PLANES_TILE / E / PP_RUN);         // whole runs of a tile
+    const u64 m = n / E;
+    const u32 lane = threadIdx.x % WAVE;
+    const u8* pp[E];
+#pragma unroll
+    for (int p = 0; p < E; ++p) pp[p] = planes + P[p];
+    for (u32 r = threadIdx.x / WAVE; r < RUNS; r += PL_THREADS / WAVE) {
+        const u64 e0 = t * (PLANES_TILE / E) + r * PP_RUN, e = e0 + 16 * lane;
+        if (e0 * E >= n) break;                                   // (uniform over the wave: the run lies behind the tensor)
+        const bool full = e + 16 <= m;
+        u32 wv[4 * E];
+        if constexpr (TR == FSEHIP_EST_PRED) {
+            u64 total = 0;
+            if (full) {
+                u32 o[E][4];
+                const u32 zero[4] = { 0, 0, 0, 0 };
+#pragma unroll
+                for (int p = 0; p < E; ++p) __builtin_memcpy(o[p], pp[p] + e, 16);
+                pl_interleave<E>(wv, o);
+#pragma unroll
+                for (int k = 0; k < E; ++k) pl_sub4<E, true>(&wv[4 * k], zero);
+                total = pp_prefix<E>(wv);
+            }
+            u64 carry;                                            // what the lanes in front of this one add up to: all 64 lanes scan
+            if constexpr (E == 8) carry = group_scan_incl_add64<64>(total, lane) - total;
+            else carry = group_scan_incl<64, ScanAdd>((u32)total, lane) - (u32)total;
+            if (full) {
+                pp_carry<E>(wv, carry);
+#pragma unroll
+                for (int k = 0; k < E; ++k) __builtin_memcpy(db + e * E + 16 * k, &wv[4 * k], 16);
+            } else if (e * E < n) {                               // the tensor's last chunk: fewer than 16 whole elements, then n mod E bytes
+                u64 acc = carry;
+                for (u64 j = e; j < m; ++j) {
+                    u64 z = 0;
+#pragma unroll
+                    for (int p = 0; p < E; ++p) z |= (u64)pp[p][j] << (8 * p);
+                    acc = pl_unzz<E>(z, acc);
+#pragma unroll
+                    for (int p = 0; p < E; ++p) db[j * E + p] = (u8)(acc >> (8 * p));
+                }
+                for (u64 k = m * E; k < n; ++k) db[k] = planes[P[k - m * E] + m];
+            }
+        } else if (full) {
+            u32 o[E][4];
+#pragma unroll
+            for (int p = 0; p < E; ++p) __builtin_memcpy(o[p], pp[p] + e, 16);
+            pl_interleave<E>(wv, o);
+            if constexpr (TR != FSEHIP_EST_PLAIN) {
+#pragma unroll
+                for (int k = 0; k < E; ++k)                       // (in place: these loads, then the stores below)
+                    pl_base16<E, TR == FSEHIP_EST_SUB ? PL_SUB : PL_XOR, true>(&wv[4 * k], bb + e * E + 16 * k);
+            }
+#pragma unroll
+            for (int k = 0; k < E; ++k) __builtin_memcpy(db + e * E + 16 * k, &wv[4 * k], 16);
+        } else if (e * E < n) {                                   // the tensor's last chunk, an element at a time (in place: its loads, then its stores)
+            if constexpr (TR == FSEHIP_EST_SUB) {
+                for (u64 j = e; j * E < n; ++j) pl_sub_elem_merge<E>(db, bb, n, j, [&](u32 p) { return planes + P[p]; });
+            } else {
+                for (u64 j = e; j * E < n; ++j) {
+                    for (u64 k = j * E; k < n && k < (j + 1) * E; ++k) {
+                        u8 v = planes[P[k - j * E] + j];
+                        if constexpr (TR == FSEHIP_EST_XOR) v ^= bb[k];
+                        db[k] = v;
+                    }
+                }
+            }
+        }
+    }
+}
+
+template <int E>
+__global__ __launch_bounds__(PL_THREADS) void k_planes_merge_each(u8* dst, const u64* D, const u8* planes, const u64* PO, const size_t* PS, const u8* base, const u8* T,
+                                                                  size_t nT, u64 dstCapacity)
+{
+    const u64 w = blockIdx.x;
+    size_t i;
+    if (!pl_find(D, nT, w, i)) return;                            // (uniform, like every return below)
+    const u64 d0 = D[i], first = (d0 >> PL_TILE_LOG) + i;
+    if (first > w) return;                                        // (offsets that decrease: the search found no tensor of this item)
+    const u64 t = w - first;
+    const u32 tr = T[i];
+    if (!pe_ok(tr, base)) return;                                 // (a refused tensor: in place its old bytes stay)
+    const size_t v = pm_verdict(D, PS, i, E, dstCapacity);
+    if (is_err(v) || (t << PL_TILE_LOG) >= (u64)v) return;        // (a good tensor: d0 + n <= D[i + 1] <= dstCapacity; t < 2^24)
+    u8* const db = dst + d0;
+    const u64* const P = PO + i * E;
+    if (tr == FSEHIP_EST_PLAIN) pe_merge<E, FSEHIP_EST_PLAIN>(db, nullptr, planes, P, v, t);
+    else if (tr == FSEHIP_EST_PRED) pe_merge<E, FSEHIP_EST_PRED>(db, nullptr, planes, P, v, t);
+    else if (tr == FSEHIP_EST_XOR) pe_merge<E, FSEHIP_EST_XOR>(db, base + d0, planes, P, v, t);
+    else pe_merge<E, FSEHIP_EST_SUB>(db, base + d0, planes, P, v, t);
+}
+}   // namespace
+
+// the offsets kernel runs even for no tensors (it writes the last entry); the data kernel moves every element size
+hipError_t launch_planes_split_each(u8* planes, u64* planeOff, size_t* tensorRes, const u8* src, const u8* base, const u8* transforms, const u64* srcOff, size_t nTensors,
+                                    unsigned E, u64 capacity, hipStream_t s)
+{
+    const hipError_t e0 = launch_planes_offsets(planeOff, tensorRes, srcOff, nTensors, E, capacity, s);
+    if (e0 != hipSuccess || nTensors == 0) return e0;
+    hipLaunchKernelGGL(k_each_refuse, dim3(grid_for(nTensors)), dim3(PL_THREADS), 0, s, tensorRes, transforms, base, nTensors);
+    if (capacity == 0) return hipGetLastError();
+    const dim3 g(tile_grid(capacity, nTensors)), b(PL_THREADS);
+    pl_for_elem(E, [&](auto eb) {
+        hipLaunchKernelGGL((k_planes_split_each<decltype(eb)::value>), g, b, 0, s, planes, src, base, transforms, srcOff, nTensors, capacity);
+    });
+    return hipGetLastError();
+}
+
+hipError_t launch_planes_merge_each(u8* dst, const u64* dstOff, size_t* results, const u8* planes, const u64* planeOff, const size_t* planeSizes, const u8* base,
+                                    const u8* transforms, size_t nTensors, unsigned E, u64 dstCapacity, hipStream_t s)
+{
+    if (nTensors == 0) return hipSuccess;
+    const hipError_t e0 = launch_planes_verdicts(results, dstOff, planeSizes, nTensors, E, dstCapacity, s);
+    if (e0 != hipSuccess) return e0;
+    hipLaunchKernelGGL(k_each_refuse, dim3(grid_for(nTensors)), dim3(PL_THREADS), 0, s, results, transforms, base, nTensors);
+    if (dstCapacity == 0) return hipGetLastError();
+    const dim3 g(tile_grid(dstCapacity, nTensors)), b(PL_THREADS);
+    pl_for_elem(E, [&](auto eb) {
+        hipLaunchKernelGGL((k_planes_merge_each<decltype(eb)::value>), g, b, 0, s, dst, dstOff, planes, planeOff, planeSizes, base, transforms, nTensors, dstCapacity);
+    });
+    return hipGetLastError();
+}

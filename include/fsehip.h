@@ -1370,6 +1370,79 @@ FSEHIP_API int FSEHIP_planes_estimate_dbatch(uint64_t* d_planeBits, uint64_t* d_
                                              const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes, uint64_t capacity, unsigned candidateMask,
                                              unsigned marginPermille, void* d_workspace, size_t workspaceBytes, void* stream);
 
+/* A transform per tensor (planes_each.hip, capi_each.hip): ONE SPLIT, ONE MERGE AND ONE COMPOSITE FOR A BATCH WHOSE TENSORS TAKE DIFFERENT
+ * TRANSFORMS.  Every call above takes one transform per call, so a caller of the estimate had to read the choices back, cut the batch by
+ * choice and call once per part.  These calls read the transform of tensor i from a device array, d_transforms[i] = FSEHIP_EST_PLAIN,
+ * _PRED, _XOR or _SUB -- the ids the estimate writes to d_choice -- given by the caller or chosen by the call itself and returned: choose
+ * once, then give, as the mixed writer treats d_codecs.  No transform is defined here and no frame byte differs.
+ *
+ *   The contract (normative; a numpy model in tests/planes_each_corpus.py): the planes of tensor i are byte for byte the planes that
+ *     FSEHIP_planes_split_dbatch (PLAIN), FSEHIP_planes_split_pred_dbatch (PRED), FSEHIP_planes_split_xor_dbatch (XOR) or
+ *     FSEHIP_planes_split_op_dbatch with FSEHIP_DELTA_SUB (SUB) writes for that tensor, the trailing n mod E bytes included, at the same
+ *     plane offsets and with the same result; the merge is the exact inverse.
+ *   Refused tensors: a transform byte that is none of the four (the estimate's 0xFF for a tensor it refused among them), or XOR / SUB where
+ *     d_base is NULL: the tensor's result is GENERIC and nothing of it is read or written -- merged in place, its old bytes stay.  Its plane
+ *     offsets are those of its size; a composite writes frames of whatever d_planes held there, and the tensor's result says to drop them.
+ *
+ *   FSEHIP_planes_split_each_dbatch   FSEHIP_planes_split_pred_dbatch with d_base (may be NULL; laid out as d_src is, read for XOR and SUB
+ *     tensors only) and d_transforms (nTensors bytes): the same arguments, offsets, results and refusals as the call it is named after.
+ *     d_planes and d_src are required for elemBytes == 1 too (a PLAIN tensor of one-byte elements is copied).  The flat ragged mapping of
+ *     "byte planes", chunks of 16 whole elements counted from the tensor's start; a workgroup has one tensor, so the branch on the
+ *     transform is uniform over it.
+ *   FSEHIP_planes_merge_each_dbatch   FSEHIP_planes_merge_pred_dbatch with d_base and d_transforms: the same arguments, verdicts and rules
+ *     for what is written.  Tiles relative to the tensor, as there; a PRED tensor takes the run scan, the others are element-wise in the
+ *     same rounds.  d_base may be exactly d_dst (in place, as in FSEHIP_planes_merge_xor_dbatch); a PLAIN or PRED tensor overwrites its
+ *     bytes.  d_dst must not overlap d_planes.
+ *   FSEHIP_tensor_compress_each_dbatch / FSEHIP_tensor_compress_seg_each_dbatch   FSEHIP_tensor_compress_pred_dbatch /
+ *     FSEHIP_tensor_compress_seg_pred_dbatch with d_base (may be NULL), d_transforms and transformPolicy; codec, d_codecs, policy and
+ *     tolerancePermille exactly as there.
+ *       FSEHIP_TRANSFORMS_GIVEN    d_transforms is an INPUT; candidateMask, marginPermille and d_estBytes are ignored.
+ *       FSEHIP_TRANSFORMS_CHOOSE   d_transforms is an OUTPUT: the call runs FSEHIP_planes_estimate_dbatch with candidateMask and marginPermille
+ *         (its rules) on the stream, writes d_choice to d_transforms, splits by it and runs the writer -- no host read in between.  d_estBytes
+ *         (may be NULL): nTensors * 4 entries, the estimate's d_estBytes.  The same inputs, mask and margin give the same bytes.
+ *     The workspace: FSEHIP_tensor_each_workspaceHead(nTensors, elemBytes, transformPolicy, candidateMask) bytes (host arithmetic, a multiple
+ *     of 256; 0 for GIVEN; GENERIC where the estimate's bound is) in front of the writer's own workspace, whose bound is that of the _pred_
+ *     composite.
+ *   FSEHIP_tensor_decompress_each_dbatch / FSEHIP_tensor_decompress_seg_each_dbatch   the _pred_ pair with d_base (may be NULL) and
+ *     d_transforms, always an input.
+ *   All six: launches only (capturable); nTensors == 0 is legal; every argument error is hipErrorInvalidValue before any device call, with
+ *     nothing written: a null mandatory pointer; elemBytes not 1, 2, 4 or 8; an unknown transformPolicy; with CHOOSE a candidateMask of 0
+ *     or with an unknown bit, XOR or SUB in it with d_base == NULL, marginPermille > 1000, 2^24 tensors; a workspace that is misaligned
+ *     (256) or short; a launch beyond the limits of "byte planes"; whatever the writer or the reader refuses.
+ *   Out of scope: sparse planes around these calls; digests and gating; windows and patches; a record of the transforms in frames or in
+ *   the archive head (the caller carries d_transforms as it carries a delta's op); new candidates or costs in the estimate. */
+#define FSEHIP_TRANSFORMS_GIVEN  0   /* d_transforms is an INPUT: nTensors bytes, FSEHIP_EST_PLAIN .. FSEHIP_EST_SUB */
+#define FSEHIP_TRANSFORMS_CHOOSE 1   /* d_transforms is an OUTPUT: the estimate's choice per tensor */
+FSEHIP_API size_t FSEHIP_tensor_each_workspaceHead(size_t nTensors, unsigned elemBytes, int transformPolicy, unsigned candidateMask);
+FSEHIP_API int FSEHIP_planes_split_each_dbatch(void* d_planes, uint64_t* d_planeOffsets, size_t* d_tensorResults, const void* d_src, const void* d_base,
+                                               const uint8_t* d_transforms, const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes, uint64_t capacity,
+                                               void* stream);
+FSEHIP_API int FSEHIP_planes_merge_each_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_planes, const uint64_t* d_planeOffsets,
+                                               const size_t* d_planeSizes, const void* d_base, const uint8_t* d_transforms, size_t nTensors, unsigned elemBytes,
+                                               uint64_t dstCapacity, void* stream);
+FSEHIP_API int FSEHIP_tensor_compress_each_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
+                                                  const void* d_src, const void* d_base, uint8_t* d_transforms, int transformPolicy, unsigned candidateMask,
+                                                  unsigned marginPermille, uint64_t* d_estBytes, const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes,
+                                                  uint64_t capacity, size_t maxTotalBlocks, unsigned blockSizeId, int codec, uint8_t* d_codecs, int policy,
+                                                  unsigned tolerancePermille, unsigned slotAlignLog, void* d_planes, uint64_t* d_planeOffsets, void* d_workspace,
+                                                  size_t workspaceBytes, void* stream);
+FSEHIP_API int FSEHIP_tensor_compress_seg_each_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
+                                                      const void* d_src, const void* d_base, uint8_t* d_transforms, int transformPolicy, unsigned candidateMask,
+                                                      unsigned marginPermille, uint64_t* d_estBytes, const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes,
+                                                      uint64_t capacity, const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, size_t maxTotalBlocks,
+                                                      unsigned blockSizeId, int codec, uint8_t* d_codecs, int policy, unsigned tolerancePermille, unsigned slotAlignLog,
+                                                      void* d_planes, uint64_t* d_planeOffsets, uint64_t* d_segOffsets, void* d_workspace, size_t workspaceBytes,
+                                                      void* stream);
+FSEHIP_API int FSEHIP_tensor_decompress_each_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base, const uint8_t* d_transforms,
+                                                    size_t* d_results, const void* d_frames, const uint64_t* d_frameOffsets, size_t nTensors, unsigned elemBytes,
+                                                    size_t maxTotalBlocks, void* d_planes, uint64_t planesCapacity, uint64_t* d_planeOffsets, size_t* d_planeResults,
+                                                    void* d_workspace, size_t workspaceBytes, void* stream);
+FSEHIP_API int FSEHIP_tensor_decompress_seg_each_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base, const uint8_t* d_transforms,
+                                                        size_t* d_results, const void* d_frames, const uint64_t* d_frameOffsets, size_t nTensors, unsigned elemBytes,
+                                                        const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, size_t maxTotalBlocks, void* d_planes,
+                                                        uint64_t planesCapacity, uint64_t* d_segOffsets, size_t* d_segResults, uint64_t* d_planeOffsets,
+                                                        size_t* d_planeSizes, void* d_workspace, size_t workspaceBytes, void* stream);
+
 /* ---- FSE for 16-bit symbols (lib/fseU16.h:62-80, lib/fseU16.c) -- SURVEY 8(f) rank 4.  Alphabets of up to
  * FSEHIP_FSEU16_MAX_SYMBOL_VALUE + 1 symbols, table logs up to 13 (default 12), ONE tANS state per stream: a different format from
  * the byte coder's.  Sizes of the uncompressed side are in SYMBOLS (as in the reference), strides in bytes.
