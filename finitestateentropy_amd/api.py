@@ -1995,7 +1995,17 @@ def _planes_methods():
         those sizes.  sel_first or max_total_blocks None: planes_window_first of the sizes and windows with `block_size_id` (both then need
         src_offsets and windows on the host).  planes: n_selected << segment_log bytes are always enough (the default).  sel_frame_offsets,
         sel_offsets (n_selected + 1), sel_results (n_selected), plane_offsets and plane_sizes (n * E) are outputs / scratch; the workspace is
-        the packed reader's for n_selected frames.  With everything given and on the device the call is launches only."""
+        the packed reader's for n_selected frames.  With everything given and on the device the call is launches only.  For frames of
+        compress_tensors_segmented with a codec and an optional base; frames written with a transform per tensor or with predicted planes
+        go to tensor_decompress_window_each_dbatch."""
+        return _window_read(self, "tensor_decompress_window_dbatch", None, frames, frame_offsets, src_offsets, windows, dst_offsets, elem_bytes, segment_log, seg_first,
+                            n_segments, sel_first, n_selected, base, dst, dst_capacity, max_total_blocks, block_size_id, planes, planes_capacity, sel_frame_offsets,
+                            sel_offsets, sel_results, plane_offsets, plane_sizes, workspace, results, delta_op)
+
+    def _window_read(self, what, transforms, frames, frame_offsets, src_offsets, windows, dst_offsets, elem_bytes, segment_log, seg_first, n_segments, sel_first,
+                     n_selected, base, dst, dst_capacity, max_total_blocks, block_size_id, planes, planes_capacity, sel_frame_offsets, sel_offsets, sel_results,
+                     plane_offsets, plane_sizes, workspace, results, delta_op):
+        """the two window composites: transforms None -- one op for the batch, delta_op -- or one transform per tensor"""
         E, L = _elem(elem_bytes), _seg_log(segment_log)
         self._flat(frames, "frames")
         foff, _ = self._offsets(frame_offsets, frames.device, False)
@@ -2013,7 +2023,7 @@ def _planes_methods():
             raise ValueError("frame_offsets: one entry per segment (%d) and one more" % nseg)
         if need_first:
             if whost is None:
-                raise ValueError("tensor_decompress_window_dbatch: windows on the device need sel_first, n_selected and max_total_blocks")
+                raise ValueError(what + ": windows on the device need sel_first, n_selected and max_total_blocks")
             first, blocks = planes_window_first(self, np.diff(shost.astype(np.int64)).clip(min=0), whost, E, L, block_size_id)
             sel_first = first if sel_first is None else sel_first
             max_total_blocks = blocks if max_total_blocks is None else max_total_blocks
@@ -2027,16 +2037,20 @@ def _planes_methods():
         psz = _i64(self, plane_sizes, n * E, frames.device, "plane_sizes")
         res = _i64(self, results, n, frames.device, "results")
         workspace = _reader_workspace(self, workspace, nsel, max_total_blocks, frames.device)
-        what = "tensor_decompress_window_dbatch"
         op = _delta_op(delta_op)
         _base(self, base, frames, dst_capacity, "dst")
+        tr = None if transforms is None else _transforms(transforms, n, frames.device)
 
         def some(t):                                             # (an array of no entries still needs an address)
             return t if t.numel() else t.new_zeros(1)
-        _check(_call_base(
-            self, "FSEHIP_tensor_decompress_window_dbatch", op, 3, _ptr(some(dst)), _ptr(doff), C.c_uint64(dst_capacity), _ptr(base), _ptr(some(res)), _ptr(some(frames)), _ptr(foff), _ptr(soff), _ptr(some(win)), SZ(n),
-            C.c_uint(E), _ptr(sf), SZ(nseg), C.c_uint(L), _ptr(wf), SZ(nsel), SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity), _ptr(sfo), _ptr(so),
-            _ptr(some(sres)), _ptr(some(poff)), _ptr(some(psz)), _ptr(workspace), SZ(workspace.numel()), _stream()), what)
+        head = (_ptr(some(dst)), _ptr(doff), C.c_uint64(dst_capacity), _ptr(base))
+        rest = (_ptr(some(res)), _ptr(some(frames)), _ptr(foff), _ptr(soff), _ptr(some(win)), SZ(n),
+                C.c_uint(E), _ptr(sf), SZ(nseg), C.c_uint(L), _ptr(wf), SZ(nsel), SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity), _ptr(sfo), _ptr(so),
+                _ptr(some(sres)), _ptr(some(poff)), _ptr(some(psz)), _ptr(workspace), SZ(workspace.numel()), _stream())
+        if tr is None:
+            _check(_call_base(self, "FSEHIP_tensor_decompress_window_dbatch", op, 3, *head, *rest), what)
+        else:
+            _check(self.lib.FSEHIP_tensor_decompress_window_each_dbatch(*head, VP(tr.data_ptr() or res.data_ptr()), *rest), what)
         if g is not None:
             g.check(what)
         return dst, res
@@ -3085,8 +3099,51 @@ def _planes_methods():
                                 n_segments, dst, dst_capacity, max_total_blocks, planes, planes_capacity, seg_offsets, seg_results, plane_offsets, plane_sizes, workspace,
                                 results)
 
+    # ---- windows of tensors with a transform per tensor (fsehip.h, the section of that name): the read side of the windows for frames of
+    # tensor_compress_seg_each_dbatch and tensor_compress_seg_pred_dbatch
+    def planes_merge_window_each_dbatch(self, planes, plane_offsets, plane_sizes, dst_offsets, windows, elem_bytes, transforms, base=None, dst=None, capacity=None,
+                                        results=None):
+        """-> (dst, results): planes_merge_each_dbatch of the windows (a, b), in elements, of every tensor: plane_offsets point at the window's
+        first byte of every plane and plane_sizes are b - a, as planes_fold_window_dbatch leaves them; slot i of dst_offsets receives
+        tensor_i[a * E : b * E].  For a "pred" tensor the a % 1024 plane bytes in front of each of its plane offsets must be the decoded bytes
+        in front of the window: they are summed and not stored.  Refused alone, results -1 and nothing written: a byte that is none of the
+        four, xor / sub without a base, a > b, a window that disagrees with the plane sizes, a pred tensor whose lead is larger than a
+        plane offset.  windows: host pairs or a CUDA int64 tensor of 2 n entries.  base: dst's layout, may be dst."""
+        E = _elem(elem_bytes)
+        self._flat(planes, "planes")
+        doff, dhost = self._offsets(dst_offsets, planes.device, dst is None)
+        n = doff.numel() - 1
+        poff = _i64(self, plane_offsets, n * E, planes.device, "plane_offsets")
+        psz = _i64(self, plane_sizes, n * E, planes.device, "plane_sizes")
+        win, _ = _windows(self, windows, planes.device, n)
+        dst, capacity, g = _dst_room(self, dst, capacity, dhost, planes.device)
+        _base(self, base, planes, capacity, "dst")
+        tr = _transforms(transforms, n, planes.device)
+        res = _i64(self, results, n, planes.device, "results")
+        what = "planes_merge_window_each_dbatch"
+        _check(self.lib.FSEHIP_planes_merge_window_each_dbatch(_ptr(_some(dst)), _ptr(doff), _ptr(_some(res)), _ptr(planes), _ptr(_some(poff)), _ptr(_some(psz)), _ptr(base),
+                                                               VP(tr.data_ptr() or doff.data_ptr()), _ptr(_some(win)), SZ(n), C.c_uint(E), C.c_uint64(capacity), _stream()),
+               what)
+        if g is not None:
+            g.check(what)
+        return dst, res
+
+    def tensor_decompress_window_each_dbatch(self, frames, frame_offsets, src_offsets, windows, dst_offsets, elem_bytes, segment_log, transforms, seg_first=None,
+                                             n_segments=None, sel_first=None, n_selected=None, base=None, dst=None, dst_capacity=None, max_total_blocks=None,
+                                             block_size_id=5, planes=None, planes_capacity=None, sel_frame_offsets=None, sel_offsets=None, sel_results=None,
+                                             plane_offsets=None, plane_sizes=None, workspace=None, results=None):
+        """tensor_decompress_window_dbatch for frames that tensor_compress_seg_each_dbatch wrote with these transforms (names, ids or a CUDA
+        uint8 tensor, as tensor_decompress_seg_each_dbatch takes them; all "pred": frames of tensor_compress_seg_pred_dbatch): the selection, the
+        packed reader over the selected extents, the window fold, then planes_merge_window_each_dbatch.  Every other argument, the scratch,
+        the workspace and the results are those of tensor_decompress_window_dbatch; the same segments are selected -- a pred window that
+        starts inside a run of 1024 elements finds the differences in front of it in its first selected segment.  base (dst's layout, may
+        be dst) is read for xor and sub tensors only; without one those are refused alone."""
+        return _window_read(self, "tensor_decompress_window_each_dbatch", transforms, frames, frame_offsets, src_offsets, windows, dst_offsets, elem_bytes, segment_log,
+                            seg_first, n_segments, sel_first, n_selected, base, dst, dst_capacity, max_total_blocks, block_size_id, planes, planes_capacity,
+                            sel_frame_offsets, sel_offsets, sel_results, plane_offsets, plane_sizes, workspace, results, 0)
+
     for f in (tensor_each_workspace_head, planes_split_each_dbatch, planes_merge_each_dbatch, tensor_compress_each_dbatch, tensor_compress_seg_each_dbatch,
-              tensor_decompress_each_dbatch, tensor_decompress_seg_each_dbatch):
+              tensor_decompress_each_dbatch, tensor_decompress_seg_each_dbatch, planes_merge_window_each_dbatch, tensor_decompress_window_each_dbatch):
         setattr(FseHip, f.__name__, f)
 
     # ---- tensor archives (csrc/planes_archive.hip; fsehip.h "tensor archives"): head | frames in one device buffer, sealed behind the frames a
@@ -3369,9 +3426,11 @@ def _planes_methods():
         if getattr(obj, "sparse_permille", None) is not None:
             raise ValueError(what + ": the object holds sparse planes (SparsePlanes); windows and patches of those are not supported")
         if getattr(obj, "predictor", None) is not None:
-            raise ValueError(what + ": the object holds predicted planes (PredictedPlanes); windows and patches of those are not supported")
+            raise ValueError(what + ": the object holds predicted planes (PredictedPlanes); decompress_tensor_windows_each reads windows of those, patches are not "
+                             "supported")
         if getattr(obj, "transforms", None) is not None:
-            raise ValueError(what + ": the object holds a transform per tensor (compress_tensors_each); windows and patches of those are not supported")
+            raise ValueError(what + ": the object holds a transform per tensor (compress_tensors_each); decompress_tensor_windows_each reads windows of those, "
+                             "patches are not supported")
 
     # ---- the user-facing pair
     def _read_base(obj, base, what):
@@ -3766,7 +3825,8 @@ def _planes_methods():
         base: a sequence matching `tensors` one to one (or a DeltaBase without check: its tensors); needed where a given name is "xor" or
         "sub".  codec: 0, 1 or an AutoCodec.  A tensor of 0 bytes takes the lowest candidate and needs no company.
         Out of scope, each a ValueError before any launch: a SparsePlanes or PredictedPlanes as codec, an earlier object as codec, a
-        DeltaBase(check=True); windows and patches of the object (decompress_tensor_windows, patch_tensor_windows)."""
+        DeltaBase(check=True); patches of the object (patch_tensor_windows).  Windows of a segmented object are read by
+        decompress_tensor_windows_each, not by decompress_tensor_windows."""
         what = "compress_tensors_each"
         margin = _margin(margin_permille, what)
         if isinstance(codec, bool) or not (isinstance(codec, AutoCodec) or (isinstance(codec, numbers.Integral) and codec in (0, 1))):
@@ -3874,23 +3934,11 @@ def _planes_methods():
 
     setattr(FseHip, "compress_tensors_each", compress_tensors_each)
 
-    def decompress_tensor_windows(self, obj, windows, base=None):
-        """-> per tensor of `obj` (a CompressedTensors of compress_tensors_segmented) the elements [start, stop) of the FLATTENED tensor as a 1-D
-        tensor of the recorded dtype that owns its memory: a row shard, a slice, a row range.  `windows` has one entry per tensor: None (the
-        tensor is skipped and None is returned in its place) or (start, stop) with 0 <= start <= stop <= numel.  Only the segment frames that
-        hold a window are decoded (tensor_decompress_window_dbatch): time and scratch follow the windows, not the tensors.
-        base: for an object with `delta` set, the WHOLE base tensors as decompress_tensors takes them; the call slices them and does not change
-        them.  ValueError for an object without segment_log, a window that is not one, a wrong number of windows, and a base / delta
-        mismatch as in decompress_tensors -- all before any launch.  `base_digests` of the object are NOT checked here: a digest covers a whole
-        base tensor and would cost more than the window saves."""
-        seg_log = getattr(obj, "segment_log", None)
-        if seg_log is None:
-            raise ValueError("decompress_tensor_windows: the object is not segmented (compress_tensors_segmented writes those)")
-        _not_sparse(obj, "decompress_tensor_windows")
-        base, op = _read_base(obj, base, "decompress_tensor_windows")
+    def _window_list(what, obj, windows):
+        """the `windows` of a user-facing window call -> per tensor None or (start, stop) as ints"""
         windows = list(windows)
         if len(windows) != len(obj.dtypes):
-            raise ValueError("decompress_tensor_windows: %d windows for %d tensors" % (len(windows), len(obj.dtypes)))
+            raise ValueError("%s: %d windows for %d tensors" % (what, len(windows), len(obj.dtypes)))
         wins = []
         for k, (w, sh) in enumerate(zip(windows, obj.shapes)):
             if w is None:
@@ -3899,9 +3947,13 @@ def _planes_methods():
             numel = int(np.prod(sh, dtype=np.int64))
             if (not isinstance(w, (tuple, list)) or len(w) != 2 or any(not isinstance(x, numbers.Integral) or isinstance(x, bool) for x in w)
                     or not 0 <= w[0] <= w[1] <= numel):
-                raise ValueError("decompress_tensor_windows: window %d is %r, (start, stop) with 0 <= start <= stop <= %d is needed" % (k, w, numel))
+                raise ValueError("%s: window %d is %r, (start, stop) with 0 <= start <= stop <= %d is needed" % (what, k, w, numel))
             wins.append((int(w[0]), int(w[1])))
-        braw = None if base is None else _bases(base, obj.dtypes, obj.shapes, obj.device)
+        return wins
+
+    def _read_windows(what, obj, wins, braw, read):
+        """the groups of `obj` through read(g, src_offsets, windows, dst_offsets, dst) -> (dst, results); dst: the windows of the bases (a
+        copy: rebuilt in place, the bases stay) where there are bases"""
         out = [None] * len(obj.dtypes)
         for g in obj.groups:
             E, sizes = g["elem_bytes"], g["sizes"]
@@ -3915,18 +3967,86 @@ def _planes_methods():
             doff = np.concatenate([[0], np.cumsum([E * (b - a) for a, b in gw])]).astype(np.uint64)
             dst = None
             if braw is not None:
-                dst = torch.cat([braw[i][E * a:E * b] for i, (a, b) in zip(g["index"], gw)])             # a copy: rebuilt in place, the bases stay
-            dst, res = self.tensor_decompress_window_dbatch(g["frames"], g["frame_offsets"], soff, gw, doff, E, seg_log, g["seg_first"], base=dst, dst=dst,
-                                                            block_size_id=obj.block_size_id, delta_op=op)
+                dst = torch.cat([braw[i][E * a:E * b] for i, (a, b) in zip(g["index"], gw)])
+            dst, res = read(g, soff, gw, doff, dst)
             got, want = res.cpu().tolist(), [E * (b - a) for a, b in gw]
             if got != want:
-                raise RuntimeError("decompress_tensor_windows: element size %d, results %s for windows of %s bytes" % (E, got[:8], want[:8]))
+                raise RuntimeError("%s: element size %d, results %s for windows of %s bytes" % (what, E, got[:8], want[:8]))
             for k, i in enumerate(g["index"]):
                 if wins[i] is not None:
                     out[i] = dst[int(doff[k]):int(doff[k + 1])].clone().view(obj.dtypes[i])
         return out
 
-    for f in (planes_window_first, planes_select_window_dbatch, planes_fold_window_dbatch, tensor_decompress_window_dbatch, decompress_tensor_windows):
+    def decompress_tensor_windows(self, obj, windows, base=None):
+        """-> per tensor of `obj` (a CompressedTensors of compress_tensors_segmented) the elements [start, stop) of the FLATTENED tensor as a 1-D
+        tensor of the recorded dtype that owns its memory: a row shard, a slice, a row range.  `windows` has one entry per tensor: None (the
+        tensor is skipped and None is returned in its place) or (start, stop) with 0 <= start <= stop <= numel.  Only the segment frames that
+        hold a window are decoded (tensor_decompress_window_dbatch): time and scratch follow the windows, not the tensors.
+        base: for an object with `delta` set, the WHOLE base tensors as decompress_tensors takes them; the call slices them and does not change
+        them.  ValueError for an object without segment_log, a window that is not one, a wrong number of windows, and a base / delta
+        mismatch as in decompress_tensors -- all before any launch.  `base_digests` of the object are NOT checked here: a digest covers a whole
+        base tensor and would cost more than the window saves.
+        Which call takes which object: this one takes plain and delta objects of compress_tensors_segmented and refuses (ValueError) objects
+        with a transform per tensor (compress_tensors_each), with predicted planes (PredictedPlanes) and with sparse planes;
+        decompress_tensor_windows_each takes all of these but the sparse ones."""
+        what = "decompress_tensor_windows"
+        seg_log = getattr(obj, "segment_log", None)
+        if seg_log is None:
+            raise ValueError(what + ": the object is not segmented (compress_tensors_segmented writes those)")
+        _not_sparse(obj, what)
+        base, op = _read_base(obj, base, what)
+        wins = _window_list(what, obj, windows)
+        braw = None if base is None else _bases(base, obj.dtypes, obj.shapes, obj.device)
+        return _read_windows(what, obj, wins, braw, lambda g, soff, gw, doff, dst: self.tensor_decompress_window_dbatch(
+            g["frames"], g["frame_offsets"], soff, gw, doff, g["elem_bytes"], seg_log, g["seg_first"], base=dst, dst=dst, block_size_id=obj.block_size_id, delta_op=op))
+
+    def decompress_tensor_windows_each(self, obj, windows, base=None):
+        """decompress_tensor_windows for ANY segmented object that is not sparse, with the same contract -- None entries, 1-D results of the
+        recorded dtype that own their memory, the whole base tensors sliced by the call and not changed, only the segment frames that hold a
+        window decoded (tensor_decompress_window_each_dbatch):
+          an object of compress_tensors_each(..., segment_log=...), also reopened from an archive: obj.transforms, per tensor; base where one
+            of them is "xor" or "sub";
+          an object written with PredictedPlanes (predictor "prev"): every tensor "pred", no base;
+          a plain or a delta object of compress_tensors_segmented: every tensor "plain", or "xor" / "sub" by the object's delta_op with its base.
+        A window of a "pred" tensor may start anywhere: the differences of its run in front of it lie in its first selected segment.
+        ValueError before any launch: no segment_log; a sparse object; a window that is not one or a wrong number of windows; a predictor
+        other than "prev"; "xor" / "sub" tensors without a base; a base for an object that holds neither.  base_digests are not checked."""
+        what = "decompress_tensor_windows_each"
+        seg_log = getattr(obj, "segment_log", None)
+        if seg_log is None:
+            raise ValueError(what + ": the object is not segmented (compress_tensors_each and compress_tensors_segmented write those with a segment_log)")
+        if getattr(obj, "sparse_permille", None) is not None:
+            raise ValueError(what + ": the object holds sparse planes (SparsePlanes); windows of those are not supported")
+        n = len(obj.dtypes)
+        names, predictor = getattr(obj, "transforms", None), getattr(obj, "predictor", None)
+        if names is not None:
+            names = list(names)
+            if len(names) != n or any(t not in EST_NAMES for t in names):
+                raise ValueError("%s: transforms %r; one name per tensor (%d) out of %r is needed" % (what, names[:8], n, EST_NAMES))
+            if predictor is not None:
+                raise ValueError(what + ": a predictor does not go with a transform per tensor")
+            if isinstance(base, DeltaBase):
+                base = base.tensors
+            if any(t in ("xor", "sub") for t in names) != (base is not None):
+                raise ValueError(what + ": the object holds \"xor\" or \"sub\" tensors and needs its base" if base is None else
+                                 what + ": the object holds no \"xor\" or \"sub\" tensor, a base does not belong to it")
+        elif predictor is not None:
+            if predictor != "prev":
+                raise ValueError("%s: predictor %r; only \"prev\" is known" % (what, predictor))
+            if base is not None:
+                raise ValueError(what + ": the object holds predicted planes, a base does not belong to it")
+            names = ["pred"] * n
+        else:
+            base, op = _read_base(obj, base, what)
+            names = [("plain" if base is None else "sub" if op else "xor")] * n
+        wins = _window_list(what, obj, windows)
+        braw = None if base is None else _bases(base, obj.dtypes, obj.shapes, obj.device)
+        return _read_windows(what, obj, wins, braw, lambda g, soff, gw, doff, dst: self.tensor_decompress_window_each_dbatch(
+            g["frames"], g["frame_offsets"], soff, gw, doff, g["elem_bytes"], seg_log, [names[i] for i in g["index"]], g["seg_first"], base=dst, dst=dst,
+            block_size_id=obj.block_size_id))
+
+    for f in (planes_window_first, planes_select_window_dbatch, planes_fold_window_dbatch, tensor_decompress_window_dbatch, decompress_tensor_windows,
+              decompress_tensor_windows_each):
         setattr(FseHip, f.__name__, f)
     for f in (estimate_tensors, compress_tensors_auto):
         setattr(FseHip, f.__name__, f)
@@ -3980,6 +4100,11 @@ def compress_tensors_each(tensors, transforms="auto", base=None, codec=0, block_
 def decompress_tensor_windows(obj, windows, base=None):
     """FseHip.decompress_tensor_windows on a library handle of the module's own"""
     return _default().decompress_tensor_windows(obj, windows, base)
+
+
+def decompress_tensor_windows_each(obj, windows, base=None):
+    """FseHip.decompress_tensor_windows_each on a library handle of the module's own"""
+    return _default().decompress_tensor_windows_each(obj, windows, base)
 
 
 def patch_tensor_windows(obj, tensors, windows, base=None):

@@ -4,6 +4,9 @@
 //   FSEHIP_tensor_compress(_seg)_each_dbatch   : [CHOOSE: FSEHIP_planes_estimate_dbatch, its choice into d_transforms] -> the split by d_transforms
 //                                                -> [the segments kernel] -> the packed (mixed) writer
 //   FSEHIP_tensor_decompress(_seg)_each_dbatch : the packed reader -> [the fold] -> the merge by d_transforms
+//   FSEHIP_planes_merge_window_each_dbatch     : the launcher of the window form of that merge
+//   FSEHIP_tensor_decompress_window_each_dbatch: the selection -> the packed reader over the extents -> the window fold (planes_win.hip, all
+//                                                three as they are) -> the window form of the merge
 //
 // The workspace of a CHOOSE call: the estimate's counters, plane costs, estimates and results (each a multiple of 256) in front of the
 // writer's workspace; FSEHIP_tensor_each_workspaceHead is their sum.
@@ -158,4 +161,44 @@ extern "C" int FSEHIP_tensor_decompress_seg_each_dbatch(void* d_dst, const uint6
     if (f != 0) return f;
     return (int)launch_planes_merge_each((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeSizes, (const u8*)d_base,
                                          d_transforms, nTensors, elemBytes, dstCapacity, (hipStream_t)stream);
+}
+
+// ---- windows of tensors with a transform per tensor ----
+extern "C" int FSEHIP_planes_merge_window_each_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_planes, const uint64_t* d_planeOffsets,
+                                                      const size_t* d_planeSizes, const void* d_base, const uint8_t* d_transforms, const uint64_t* d_windows,
+                                                      size_t nTensors, unsigned elemBytes, uint64_t dstCapacity, void* stream)
+{
+    if (bad_elem(elemBytes) || !d_dst || !d_dstOffsets || !d_results || !d_planes || !d_planeOffsets || !d_planeSizes || !d_transforms || !d_windows)
+        return (int)hipErrorInvalidValue;
+    if (bad_tensors(nTensors, elemBytes) || bad_grid(dstCapacity, 2 * nTensors)) return (int)hipErrorInvalidValue;
+    return (int)launch_planes_merge_window_each((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeSizes,
+                                                (const u8*)d_base, d_transforms, (const u64*)d_windows, nTensors, elemBytes, dstCapacity, (hipStream_t)stream);
+}
+
+// the argument checks of all four steps in front of the first launch (those of the selection and of the fold are among them)
+extern "C" int FSEHIP_tensor_decompress_window_each_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base,
+                                                           const uint8_t* d_transforms, size_t* d_results, const void* d_frames, const uint64_t* d_frameOffsets,
+                                                           const uint64_t* d_srcOffsets, const uint64_t* d_windows, size_t nTensors, unsigned elemBytes,
+                                                           const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, const uint64_t* d_selFirst, size_t nSelected,
+                                                           size_t maxTotalBlocks, void* d_planes, uint64_t planesCapacity, uint64_t* d_selFrameOffsets,
+                                                           uint64_t* d_selOffsets, size_t* d_selResults, uint64_t* d_planeOffsets, size_t* d_planeSizes,
+                                                           void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    if (bad_elem(elemBytes) || !d_dst || !d_dstOffsets || !d_transforms || !d_results || !d_frames || !d_frameOffsets || !d_srcOffsets || !d_windows || !d_segFirst ||
+        !d_selFirst || !d_planes || !d_selFrameOffsets || !d_selOffsets || !d_selResults || !d_planeOffsets || !d_planeSizes)
+        return (int)hipErrorInvalidValue;
+    if (bad_seg(segLog, 0) || bad_counts(nTensors, elemBytes, nSelected) || nSegments >= ((size_t)1 << 31) || nSelected > nSegments || bad_grid(dstCapacity, 2 * nTensors))
+        return (int)hipErrorInvalidValue;
+    if (bad_reader(d_workspace, workspaceBytes, nSelected, maxTotalBlocks)) return (int)hipErrorInvalidValue;
+    int r = FSEHIP_planes_select_window_dbatch(d_selFrameOffsets, d_frameOffsets, d_srcOffsets, d_windows, d_segFirst, d_selFirst, nTensors, elemBytes, nSegments, nSelected,
+                                               segLog, stream);
+    if (r != 0) return r;
+    r = FSEHIP_frame_decompress_packed_dbatch(d_planes, (size_t)planesCapacity, d_selOffsets, d_selResults, d_frames, d_selFrameOffsets, nSelected, maxTotalBlocks, 0,
+                                              d_workspace, workspaceBytes, stream);
+    if (r != 0) return r;
+    r = FSEHIP_planes_fold_window_dbatch(d_planeOffsets, d_planeSizes, d_selOffsets, d_selResults, d_srcOffsets, d_windows, d_segFirst, d_selFirst, nTensors, elemBytes,
+                                         nSelected, segLog, stream);
+    if (r != 0) return r;
+    return (int)launch_planes_merge_window_each((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeSizes,
+                                                (const u8*)d_base, d_transforms, (const u64*)d_windows, nTensors, elemBytes, dstCapacity, (hipStream_t)stream);
 }

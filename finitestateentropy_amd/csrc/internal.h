@@ -375,6 +375,10 @@ hipError_t launch_planes_split_each(u8* planes, u64* planeOff, size_t* tensorRes
                                     unsigned E, u64 capacity, hipStream_t s);
 hipError_t launch_planes_merge_each(u8* dst, const u64* dstOff, size_t* results, const u8* planes, const u64* planeOff, const size_t* planeSizes, const u8* base,
                                     const u8* transforms, size_t nTensors, unsigned E, u64 dstCapacity, hipStream_t s);
+// the window form of that merge (fsehip.h, "windows of tensors with a transform per tensor"): planeOff at the window's first byte of every
+// plane, windows (a, b) in elements; its grid has 2 * nTensors workgroups beyond the tiles of dstCapacity
+hipError_t launch_planes_merge_window_each(u8* dst, const u64* dstOff, size_t* results, const u8* planes, const u64* planeOff, const size_t* planeSizes, const u8* base,
+                                           const u8* transforms, const u64* windows, size_t nTensors, unsigned E, u64 dstCapacity, hipStream_t s);
 
 // ---- kernel timing probe (HIP events on the launch stream; used by bench.py for the live roofline figure) ----
 enum { PK_HIST = 0, PK_FSE_CPREP, PK_FSE_ENCODE, PK_FSE_DPREP, PK_FSE_DECODE, PK_HUF_CPREP, PK_HUF_ENCODE, PK_HUF_DPREP, PK_HUF_DECODE, PK_FSE_ENCODE_WAVE, PK_COUNT };

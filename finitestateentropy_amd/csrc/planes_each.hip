@@ -5,6 +5,7 @@
 //
 //   launch_planes_split_each : k_planes_offsets (planes.hip) -> k_each_refuse -> k_planes_split_each
 //   launch_planes_merge_each : k_planes_verdicts (planes.hip) -> k_each_refuse -> k_planes_merge_each
+//   launch_planes_merge_window_each : k_planes_verdicts -> k_each_refuse_window -> k_planes_merge_each<E, const u64*> (THE WINDOW FORM below)
 //
 // THE SPLIT has the frame of k_planes_split_pred: the flat ragged mapping (a workgroup per (tile, tensor) intersection, pl_find) and chunks
 // of 16 whole elements per lane counted from the TENSOR's start.  That frame serves all four: SUB and PRED need whole elements per dword,
@@ -18,8 +19,27 @@
 // same rounds.  IN PLACE (base == dst) as in the delta merge: a byte of dst is read as base and written by one thread, whose base loads
 // of a chunk stand in front of its stores.  A PLAIN or PRED tensor reads no base and overwrites its bytes.
 //
+// THE WINDOW FORM OF THE MERGE (fsehip.h, "windows of tensors with a transform per tensor"; WIN = true of the same templates): the planes hold
+// the elements [a, b) of the tensor, W[2 i] and W[2 i + 1], and PO points at the window's first byte of every plane, as the window fold of
+// planes_win.hip leaves it.  PLAIN, XOR and SUB are element-wise, so a window is a tensor of its own and they run as above.  PRED sums
+// differences inside runs of PP_RUN elements counted from the TENSOR's start: a window that starts inside a run needs the lead, the
+// L = a mod PP_RUN differences in front of it (0 for the other three, and for an empty window, of which nothing is read).  Such a tensor is
+// merged as a VIRTUAL tensor of n + L E bytes that begins L elements in front of its slot: plane pointers planes + PO - L, tiles and runs
+// relative to the virtual tensor -- a run is again one round of one wave, the scan is unchanged -- and every element with virtual index
+// below L is loaded and summed but never stored.  The lane whose chunk straddles L stores its elements from L on one by one.  No byte in
+// front of the slot is written; the stores at db + (e - L) E are off every alignment, as they are above.
+// The work mapping: the non-window key floor(D[i] / T) + i gives tensor i the items floor(D[i] / T) + i .. floor(D[i+1] / T) + i, which are
+// floor(D[i+1] / T) - floor(D[i] / T) + 1 >= ceil(n / T) of them and in the worst case no more (D[i] = 0, n = T - 1: one).  The virtual
+// tensor has ceil((n + L E) / T) <= ceil(n / T) + 1 tiles, because L E <= 1023 * 8 < T, so it can need one item more (E = 1, D[i] = 0,
+// n = T - 1, L = 1023: 33790 bytes, two tiles).  The window key is floor(D[i] / T) + 2 i: still strictly increasing in i, tensor i owns
+// the items from its key to below the next one's, floor(D[i+1] / T) - floor(D[i] / T) + 2 of them, and ceil(capacity / T) + 2 nTensors
+// workgroups are launched (the last tensor: ceil(capacity / T) - floor(D[i] / T) + 2 items).  A workgroup whose tile lies behind
+// n + L E returns.
+//
 // REFUSALS: a transform byte above FSEHIP_EST_SUB (the estimate's 0xFF among them), or XOR / SUB without a base: k_each_refuse writes GENERIC
-// over the tensor's result, and the data kernels return for it in front of every load and store.
+// over the tensor's result, and the data kernels return for it in front of every load and store.  The window form adds (pe_win_ok): a window
+// with a > b, a window whose E (b - a) is not the n of the merge's verdict, and a PRED tensor whose lead is larger than one of its plane
+// offsets -- it would lie in front of the planes buffer.
 #include "planes_dev.h"
 
 namespace {
@@ -29,6 +49,25 @@ __global__ void k_each_refuse(size_t* res, const u8* T, const u8* base, size_t n
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < nT && !pe_ok(T[i], base)) res[i] = FERR(GENERIC);
+}
+// The window rules of tensor i, whose transform is tr and whose verdict is n bytes, and its lead L in elements.  An empty window has none
+DEV bool pe_win_ok(const u64* W, const u64* PO, size_t i, u32 E, u32 tr, u64 n, u64& L)
+{
+    const u64 a = W[2 * i], b = W[2 * i + 1];
+    L = tr == FSEHIP_EST_PRED && n ? a & (PP_RUN - 1) : 0;
+    if (a > b || n % E || b - a != n / E) return false;
+    for (u32 p = 0; p < E; ++p) if (L > PO[i * E + p]) return false;
+    return true;
+}
+// behind k_planes_verdicts, whose verdict of tensor i stands in res[i]: an error there stays unless the transform is refused
+__global__ void k_each_refuse_window(size_t* res, const u8* T, const u8* base, const u64* W, const u64* PO, size_t nT, u32 E)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nT) return;
+    const size_t v = res[i];
+    const u32 tr = T[i];
+    u64 L;
+    if (!pe_ok(tr, base) || (!is_err(v) && !pe_win_ok(W, PO, i, E, tr, (u64)v, L))) res[i] = FERR(GENERIC);
 }
 
 // ---- split -------------------------------------------------------------------------------------------------------------------------------
@@ -95,8 +134,9 @@ __global__ __launch_bounds__(PL_THREADS) void k_planes_split_each(u8* planes, co
 }
 
 // ---- merge -------------------------------------------------------------------------------------------------------------------------------
-// the runs of tile t of the tensor at db (n bytes, base bb, plane p at planes + P[p]) under transform TR
-template <int E, int TR> DEV void pe_merge(u8* db, const u8* bb, const u8* planes, const u64* P, u64 n, u64 t)
+// the runs of tile t of the tensor at db (n bytes, base bb, plane p at planes + P[p]) under transform TR.  WIN: db, n and t are those of the
+// virtual tensor, whose planes start L bytes in front of P[p] and whose first L elements are not stored (n is a multiple of E there)
+template <int E, int TR, bool WIN = false> DEV void pe_merge(u8* db, const u8* bb, const u8* planes, const u64* P, u64 n, u64 t, u64 L = 0)
 {
     constexpr u32 RUNS = (u32)(PLANES_TILE / E / PP_RUN);         // whole runs of a tile
     const u64 m = n / E;
@@ -104,6 +144,10 @@ template <int E, int TR> DEV void pe_merge(u8* db, const u8* bb, const u8* plane
     const u8* pp[E];
 #pragma unroll
     for (int p = 0; p < E; ++p) pp[p] = planes + P[p];
+    if constexpr (WIN) {
+#pragma unroll
+        for (int p = 0; p < E; ++p) pp[p] -= L;
+    }
     for (u32 r = threadIdx.x / WAVE; r < RUNS; r += PL_THREADS / WAVE) {
         const u64 e0 = t * (PLANES_TILE / E) + r * PP_RUN, e = e0 + 16 * lane;
         if (e0 * E >= n) break;                                   // (uniform over the wave: the run lies behind the tensor)
@@ -126,8 +170,18 @@ template <int E, int TR> DEV void pe_merge(u8* db, const u8* bb, const u8* plane
             else carry = group_scan_incl<64, ScanAdd>((u32)total, lane) - (u32)total;
             if (full) {
                 pp_carry<E>(wv, carry);
+                bool whole = true;
+                if constexpr (WIN) whole = e >= L;
+                if (whole) {
 #pragma unroll
-                for (int k = 0; k < E; ++k) __builtin_memcpy(db + e * E + 16 * k, &wv[4 * k], 16);
+                    for (int k = 0; k < E; ++k) __builtin_memcpy(db + e * E + 16 * k, &wv[4 * k], 16);
+                } else {
+                    if constexpr (WIN) {                          // the chunk that straddles the lead: its elements from L on, one by one
+#pragma unroll
+                        for (int j = 0; j < 16; ++j)
+                            if (e + j >= L) __builtin_memcpy(db + (e + j) * E, (const u8*)wv + j * E, E);
+                    }
+                }
             } else if (e * E < n) {                               // the tensor's last chunk: fewer than 16 whole elements, then n mod E bytes
                 u64 acc = carry;
                 for (u64 j = e; j < m; ++j) {
@@ -135,10 +189,12 @@ template <int E, int TR> DEV void pe_merge(u8* db, const u8* bb, const u8* plane
 #pragma unroll
                     for (int p = 0; p < E; ++p) z |= (u64)pp[p][j] << (8 * p);
                     acc = pl_unzz<E>(z, acc);
+                    if (WIN && j < L) continue;                   // (the lead: summed, not stored)
 #pragma unroll
                     for (int p = 0; p < E; ++p) db[j * E + p] = (u8)(acc >> (8 * p));
                 }
-                for (u64 k = m * E; k < n; ++k) db[k] = planes[P[k - m * E] + m];
+                if constexpr (!WIN)
+                    for (u64 k = m * E; k < n; ++k) db[k] = planes[P[k - m * E] + m];
             }
         } else if (full) {
             u32 o[E][4];
@@ -168,26 +224,45 @@ template <int E, int TR> DEV void pe_merge(u8* db, const u8* bb, const u8* plane
     }
 }
 
-template <int E>
+// Win: empty -- the merge, launched as ever -- or the one more argument of the window form, const u64* W
+template <int E, class... Win>
 __global__ __launch_bounds__(PL_THREADS) void k_planes_merge_each(u8* dst, const u64* D, const u8* planes, const u64* PO, const size_t* PS, const u8* base, const u8* T,
-                                                                  size_t nT, u64 dstCapacity)
+                                                                  size_t nT, u64 dstCapacity, Win... win)
 {
+    constexpr bool WIN = sizeof...(Win) != 0;
     const u64 w = blockIdx.x;
     size_t i;
-    if (!pl_find(D, nT, w, i)) return;                            // (uniform, like every return below)
-    const u64 d0 = D[i], first = (d0 >> PL_TILE_LOG) + i;
+    if constexpr (WIN) {                                          // the key floor(D[j] / T) + 2 j: one more item per tensor
+        if (nT == 0 || (D[0] >> PL_TILE_LOG) > w) return;
+        i = pl_last_le(nT, w, [D](size_t j) { return (D[j] >> PL_TILE_LOG) + 2 * j; });
+    } else if (!pl_find(D, nT, w, i)) return;                     // (uniform, like every return below)
+    const u64 d0 = D[i], first = (d0 >> PL_TILE_LOG) + (WIN ? 2 : 1) * i;
     if (first > w) return;                                        // (offsets that decrease: the search found no tensor of this item)
     const u64 t = w - first;
     const u32 tr = T[i];
     if (!pe_ok(tr, base)) return;                                 // (a refused tensor: in place its old bytes stay)
     const size_t v = pm_verdict(D, PS, i, E, dstCapacity);
-    if (is_err(v) || (t << PL_TILE_LOG) >= (u64)v) return;        // (a good tensor: d0 + n <= D[i + 1] <= dstCapacity; t < 2^24)
-    u8* const db = dst + d0;
-    const u64* const P = PO + i * E;
-    if (tr == FSEHIP_EST_PLAIN) pe_merge<E, FSEHIP_EST_PLAIN>(db, nullptr, planes, P, v, t);
-    else if (tr == FSEHIP_EST_PRED) pe_merge<E, FSEHIP_EST_PRED>(db, nullptr, planes, P, v, t);
-    else if (tr == FSEHIP_EST_XOR) pe_merge<E, FSEHIP_EST_XOR>(db, base + d0, planes, P, v, t);
-    else pe_merge<E, FSEHIP_EST_SUB>(db, base + d0, planes, P, v, t);
+    if constexpr (WIN) {
+        const u64* const W = (win, ...);
+        u64 L;
+        if (is_err(v) || !pe_win_ok(W, PO, i, E, tr, (u64)v, L)) return;
+        const u64 nv = (u64)v + L * E;                            // the virtual tensor (an empty window: 0 bytes)
+        if ((t << PL_TILE_LOG) >= nv) return;
+        u8* const db = (u8*)((uintptr_t)(dst + d0) - L * E);      // where virtual element 0 would lie; nothing below dst + d0 is written
+        const u64* const P = PO + i * E;
+        if (tr == FSEHIP_EST_PLAIN) pe_merge<E, FSEHIP_EST_PLAIN, true>(db, nullptr, planes, P, nv, t, L);
+        else if (tr == FSEHIP_EST_PRED) pe_merge<E, FSEHIP_EST_PRED, true>(db, nullptr, planes, P, nv, t, L);
+        else if (tr == FSEHIP_EST_XOR) pe_merge<E, FSEHIP_EST_XOR, true>(db, base + d0, planes, P, nv, t, L);
+        else pe_merge<E, FSEHIP_EST_SUB, true>(db, base + d0, planes, P, nv, t, L);
+    } else {
+        if (is_err(v) || (t << PL_TILE_LOG) >= (u64)v) return;    // (a good tensor: d0 + n <= D[i + 1] <= dstCapacity; t < 2^24)
+        u8* const db = dst + d0;
+        const u64* const P = PO + i * E;
+        if (tr == FSEHIP_EST_PLAIN) pe_merge<E, FSEHIP_EST_PLAIN>(db, nullptr, planes, P, v, t);
+        else if (tr == FSEHIP_EST_PRED) pe_merge<E, FSEHIP_EST_PRED>(db, nullptr, planes, P, v, t);
+        else if (tr == FSEHIP_EST_XOR) pe_merge<E, FSEHIP_EST_XOR>(db, base + d0, planes, P, v, t);
+        else pe_merge<E, FSEHIP_EST_SUB>(db, base + d0, planes, P, v, t);
+    }
 }
 }   // namespace
 
@@ -217,6 +292,23 @@ hipError_t launch_planes_merge_each(u8* dst, const u64* dstOff, size_t* results,
     const dim3 g(tile_grid(dstCapacity, nTensors)), b(PL_THREADS);
     pl_for_elem(E, [&](auto eb) {
         hipLaunchKernelGGL((k_planes_merge_each<decltype(eb)::value>), g, b, 0, s, dst, dstOff, planes, planeOff, planeSizes, base, transforms, nTensors, dstCapacity);
+    });
+    return hipGetLastError();
+}
+
+// the window form: the verdicts, the refusals with the window rules, then ceil(dstCapacity / T) + 2 nTensors workgroups (bad_grid with 2 nTensors)
+hipError_t launch_planes_merge_window_each(u8* dst, const u64* dstOff, size_t* results, const u8* planes, const u64* planeOff, const size_t* planeSizes, const u8* base,
+                                           const u8* transforms, const u64* windows, size_t nTensors, unsigned E, u64 dstCapacity, hipStream_t s)
+{
+    if (nTensors == 0) return hipSuccess;
+    const hipError_t e0 = launch_planes_verdicts(results, dstOff, planeSizes, nTensors, E, dstCapacity, s);
+    if (e0 != hipSuccess) return e0;
+    hipLaunchKernelGGL(k_each_refuse_window, dim3(grid_for(nTensors)), dim3(PL_THREADS), 0, s, results, transforms, base, windows, planeOff, nTensors, (u32)E);
+    if (dstCapacity == 0) return hipGetLastError();
+    const dim3 g(tile_grid(dstCapacity, 2 * nTensors)), b(PL_THREADS);
+    pl_for_elem(E, [&](auto eb) {
+        hipLaunchKernelGGL((k_planes_merge_each<decltype(eb)::value, const u64*>), g, b, 0, s, dst, dstOff, planes, planeOff, planeSizes, base, transforms, nTensors, dstCapacity,
+                           windows);
     });
     return hipGetLastError();
 }

@@ -1287,7 +1287,7 @@ FSEHIP_API int FSEHIP_archive_open_dbatch(uint64_t* d_srcOffsets, uint64_t* d_fr
  *   All six: launches only (capturable); every argument error is hipErrorInvalidValue before any device call, with nothing written;
  *   workspaces are the writers' and readers' own.
  *   Out of scope: strides other than 1 (interleaved channels); higher-order or float-aware predictors; prediction combined with a base or
- *   with sparse planes; windows and patches of predicted tensors; a record of the predictor in frames or in the archive head. */
+ *   with sparse planes; patches of predicted tensors (their windows: "windows of tensors with a transform per tensor" below); a record of the predictor in frames or in the archive head. */
 #define FSEHIP_PRED_RUN_LOG 10
 FSEHIP_API int FSEHIP_planes_split_pred_dbatch(void* d_planes, uint64_t* d_planeOffsets, size_t* d_tensorResults, const void* d_src, const uint64_t* d_srcOffsets,
                                                size_t nTensors, unsigned elemBytes, uint64_t capacity, void* stream);
@@ -1409,7 +1409,7 @@ FSEHIP_API int FSEHIP_planes_estimate_dbatch(uint64_t* d_planeBits, uint64_t* d_
  *     nothing written: a null mandatory pointer; elemBytes not 1, 2, 4 or 8; an unknown transformPolicy; with CHOOSE a candidateMask of 0
  *     or with an unknown bit, XOR or SUB in it with d_base == NULL, marginPermille > 1000, 2^24 tensors; a workspace that is misaligned
  *     (256) or short; a launch beyond the limits of "byte planes"; whatever the writer or the reader refuses.
- *   Out of scope: sparse planes around these calls; digests and gating; windows and patches; a record of the transforms in frames or in
+ *   Out of scope: sparse planes around these calls; digests and gating; patches (windows: the next section); a record of the transforms in frames or in
  *   the archive head (the caller carries d_transforms as it carries a delta's op); new candidates or costs in the estimate. */
 #define FSEHIP_TRANSFORMS_GIVEN  0   /* d_transforms is an INPUT: nTensors bytes, FSEHIP_EST_PLAIN .. FSEHIP_EST_SUB */
 #define FSEHIP_TRANSFORMS_CHOOSE 1   /* d_transforms is an OUTPUT: the estimate's choice per tensor */
@@ -1442,6 +1442,53 @@ FSEHIP_API int FSEHIP_tensor_decompress_seg_each_dbatch(void* d_dst, const uint6
                                                         const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, size_t maxTotalBlocks, void* d_planes,
                                                         uint64_t planesCapacity, uint64_t* d_segOffsets, size_t* d_segResults, uint64_t* d_planeOffsets,
                                                         size_t* d_planeSizes, void* d_workspace, size_t workspaceBytes, void* stream);
+
+/* Windows of tensors with a transform per tensor (planes_each.hip, capi_each.hip): THE READ SIDE OF "windows of segmented tensors" FOR OBJECTS
+ * WRITTEN BY FSEHIP_tensor_compress_seg_each_dbatch -- and, with all bytes FSEHIP_EST_PRED, by FSEHIP_tensor_compress_seg_pred_dbatch: the
+ * elements [a, b) of every tensor, decoding only the segment frames that hold them.  No frame byte, reader, selection or fold changes:
+ * FSEHIP_planes_windowFirst, FSEHIP_planes_select_window_dbatch and FSEHIP_planes_fold_window_dbatch are used as they are.
+ *
+ *   Why one more merge.  For a window of whole elements every plane contributes the same plane-relative range.  PLAIN, XOR and SUB are
+ *     element-wise, so their window is merged like a tensor of its own.  PRED sums zigzag differences inside runs of 1 << FSEHIP_PRED_RUN_LOG
+ *     = 1024 elements counted from the TENSOR's start, each run's first element predicted by 0: a window with a % 1024 != 0 starts inside a
+ *     run, and its first element can only be rebuilt from the lead, the a % 1024 differences in front of it.
+ *   The lead is always decoded already, and costs no frame.  A segment is 1 << segLog bytes of a plane with segLog >= 10 + blockSizeId >=
+ *     FSEHIP_PRED_RUN_LOG, so every segment starts on a run boundary; the first selected segment starts at (a >> segLog) << segLog, which
+ *     is at or below a - a % 1024; and the fold writes d_planeOffsets[j] = off[selFirst[j]] + (a - ((a >> segLog) << segLog)), so the
+ *     a % 1024 bytes in front of d_planeOffsets[j] lie inside the decoded extent of plane j.  nSelected and the block count are those of
+ *     FSEHIP_planes_windowFirst: the lead selects nothing.
+ *
+ *   FSEHIP_planes_merge_window_each_dbatch   FSEHIP_planes_merge_each_dbatch with d_windows (2 * nTensors entries: a_i, b_i in elements, as
+ *     every window call takes them).  d_planeOffsets[i * E + p] points at the WINDOW's first byte of plane p, d_planeSizes are b - a (what the
+ *     window fold writes), the slot d_dstOffsets[i] .. [i + 1] receives the E * (b - a) bytes tensor_i[a * E .. b * E).  THE CALLER'S
+ *     CONTRACT for a PRED tensor with a < b: the a % 1024 bytes in front of every one of its plane offsets are the decoded plane bytes in
+ *     front of the window; they are read, summed and not stored.  The results are the merge's five rules with n = E * (b - a), then GENERIC,
+ *     with nothing of the tensor read or written (in place its old bytes stay), for: a transform byte that is none of the four; XOR or SUB
+ *     with d_base == NULL; a > b; E * (b - a) != n, the window and the plane sizes disagree; a PRED tensor with a < b and a % 1024 larger
+ *     than one of its plane offsets (the lead would lie in front of d_planes).  An error of the five rules -- a plane whose fold failed
+ *     among them -- stays the result.  No byte outside [d_dstOffsets[i], d_dstOffsets[i] + n) is written for tensor i.  d_base has the layout
+ *     of d_dst (the same windows of the base) and may be exactly d_dst.  Checked before the first launch: a null pointer other than d_base,
+ *     elemBytes not 1, 2, 4 or 8, 2^31 planes, a launch beyond the limits of "byte planes" counted with 2 * nTensors (the work mapping
+ *     gives every tensor one more item than the merge: a lead can add a tile).  It only launches.
+ *   FSEHIP_tensor_decompress_window_each_dbatch   the argument list of FSEHIP_tensor_decompress_window_op_dbatch with d_transforms (nTensors
+ *     bytes, an input) in place of deltaOp: the selection, FSEHIP_frame_decompress_packed_dbatch over the nSelected extents into d_planes, the
+ *     window fold, then the merge above.  d_base may be NULL -- the tensors whose byte says XOR or SUB are then refused alone -- and may be
+ *     d_dst (in place over resident window slices).  The workspace is the packed reader's for nSelected frames and nothing else.  Checked
+ *     before the first launch, for all four steps: a null pointer other than d_base and d_workspace's own rule, elemBytes, segLog outside
+ *     10 .. 30, 2^31 planes, segments or selected frames, nSelected > nSegments, the launch limit above, a workspace that is misaligned (256)
+ *     or short, maxTotalBlocks >= 2^31.  It only launches.  A refused tensor's slot is not written; other tensors are not affected.
+ *   Both: every argument error is hipErrorInvalidValue with nothing written; nTensors == 0 is legal; capturable into a graph.
+ *   Out of scope: patches of such objects; windows of sparse objects; windows finer than an element; other run lengths. */
+FSEHIP_API int FSEHIP_planes_merge_window_each_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_planes, const uint64_t* d_planeOffsets,
+                                                      const size_t* d_planeSizes, const void* d_base, const uint8_t* d_transforms, const uint64_t* d_windows,
+                                                      size_t nTensors, unsigned elemBytes, uint64_t dstCapacity, void* stream);
+FSEHIP_API int FSEHIP_tensor_decompress_window_each_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base,
+                                                           const uint8_t* d_transforms, size_t* d_results, const void* d_frames, const uint64_t* d_frameOffsets,
+                                                           const uint64_t* d_srcOffsets, const uint64_t* d_windows, size_t nTensors, unsigned elemBytes,
+                                                           const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, const uint64_t* d_selFirst, size_t nSelected,
+                                                           size_t maxTotalBlocks, void* d_planes, uint64_t planesCapacity, uint64_t* d_selFrameOffsets,
+                                                           uint64_t* d_selOffsets, size_t* d_selResults, uint64_t* d_planeOffsets, size_t* d_planeSizes,
+                                                           void* d_workspace, size_t workspaceBytes, void* stream);
 
 /* ---- FSE for 16-bit symbols (lib/fseU16.h:62-80, lib/fseU16.c) -- SURVEY 8(f) rank 4.  Alphabets of up to
  * FSEHIP_FSEU16_MAX_SYMBOL_VALUE + 1 symbols, table logs up to 13 (default 12), ONE tANS state per stream: a different format from
