@@ -9,7 +9,8 @@ library has not been built (``python -c 'import __graft_entry__ as g; g.build()'
 from ._lib import build_library, library_path  # noqa: F401
 
 _FROM_API = ("DeltaBase", "SparsePlanes", "PredictedPlanes", "tensor_digests", "archive_tensors", "open_archive", "save_tensors", "load_tensors", "estimate_tensors",
-             "compress_tensors_auto", "TensorBundle", "compress_tensors_each", "decompress_tensor_windows_each")
+             "compress_tensors_auto", "TensorBundle", "compress_tensors_each", "decompress_tensor_windows_each",
+             "patch_tensor_windows_each")
 __all__ = ["build_library", "library_path"] + list(_FROM_API)
 
 
@@ -19,8 +20,8 @@ def __getattr__(name):
     # CompressedTensors as one device buffer and back; save_tensors / load_tensors: the same through a file) live in .api, which needs torch
     # and the built library, as do estimate_tensors / compress_tensors_auto (the plane transform chosen per tensor from device estimates) and the
     # TensorBundle they return, and compress_tensors_each (the same choice without cutting the list: one CompressedTensors with a transform
-    # per tensor) and decompress_tensor_windows_each (element windows of such an object, of a predicted one and of a plain or delta one): on
-    # first use
+    # per tensor) and decompress_tensor_windows_each (element windows of such an object, of a predicted one and of a plain or delta one) and
+    # patch_tensor_windows_each (the write side of those windows: only the segment frames that hold a window are coded again): on first use
     if name in _FROM_API:
         from . import api
         return getattr(api, name)

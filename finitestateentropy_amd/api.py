@@ -73,7 +73,8 @@ class PredictedPlanes:
     elements taken as unsigned integers and the predecessor as 0 at the start of every run of 1024 elements (include/fsehip.h "predicted
     planes").  `codec` is what codes them: 0 (FSE), 1 (Huff0) or an AutoCodec.  For tensors whose neighbours are close -- sorted indices,
     offsets, position ids, sampled fields, audio; weights get worse.  Opt-in, never chosen automatically.  The object written carries
-    `predictor` ("prev"); decompress_tensors reads it.  Not combined with a base or with SparsePlanes; no windows, no patches."""
+    `predictor` ("prev"); decompress_tensors reads it.  Not combined with a base or with SparsePlanes; windows and patches of a
+    segmented object: decompress_tensor_windows_each and patch_tensor_windows_each."""
 
     def __init__(self, codec=0):
         if not isinstance(codec, AutoCodec) and (isinstance(codec, (bool, SparsePlanes, PredictedPlanes)) or codec not in (0, 1)):
@@ -1293,10 +1294,10 @@ class CompressedTensors:
     contents -- `codec` is then that SparsePlanes -- and decompress_tensors reads them as such; windows and patches of such an object are
     refused.  `transforms` (None, or one name per tensor out of "plain", "pred", "xor", "sub" where compress_tensors_each wrote the object): every
     tensor's planes are those of its own transform, and decompress_tensors merges each accordingly (a base only where a name is "xor" or
-    "sub"); windows and patches of such an object are refused.  `base_digests` (None, or one int per tensor in tensor order where the object was written against a DeltaBase(..., check=True)):
+    "sub"); decompress_tensor_windows_each and patch_tensor_windows_each take such an object.  `base_digests` (None, or one int per tensor in tensor order where the object was written against a DeltaBase(..., check=True)):
     the 64-bit digests of the base tensors; decompress_tensors refuses a base whose digests differ.  `predictor` (None, or "prev" where the
     object was written with a PredictedPlanes -- `codec` is then that PredictedPlanes): the frames hold the planes of the neighbour
-    differences, and decompress_tensors sums them back; windows and patches of such an object are refused."""
+    differences, and decompress_tensors sums them back; decompress_tensor_windows_each and patch_tensor_windows_each take such an object."""
     segment_log = None
     delta_op = "xor"
     sparse_permille = None
@@ -2076,22 +2077,20 @@ def _planes_methods():
         m = np.where(cnt > 0, np.minimum(n - at, (cnt << L) * E), 0)
         return np.concatenate([[0], np.cumsum(m, dtype=np.int64)]).astype(np.uint64)
 
-    def planes_split_window_dbatch(self, src, src_offsets, windows, elem_bytes, segment_log, stage_offsets=None, base=None, capacity=None, stage=None,
-                                   stage_capacity=None, plane_offsets=None, results=None, delta_op=0):
-        """-> (stage, plane_offsets, results): per tensor the planes of the bytes its selected segments cover (planes_stage_offsets), staged back to
-        back at stage_offsets -- plane p of staged tensor i = stage[plane_offsets[i*E+p] : plane_offsets[i*E+p+1]] is segments k0 .. k1 of plane
-        p of the tensor (of tensor XOR base where a base is given, of zigzag(tensor - base) with delta_op 1).  results[i] = the staged bytes, or -1 for a tensor with a bad window, one
-        that ends behind `capacity`, or a pair of stage offsets that does not hold exactly those bytes below stage_capacity.  stage_offsets
-        None: planes_stage_offsets (src_offsets and windows then on the host); on the device they need stage or stage_capacity."""
+    def _split_window(self, what, transforms, src, src_offsets, windows, elem_bytes, segment_log, stage_offsets, base, capacity, stage, stage_capacity, plane_offsets,
+                      results, delta_op):
+        """planes_split_window_dbatch (transforms None: one op for all) and planes_split_window_each_dbatch (a transform per tensor)"""
         E, L = _elem(elem_bytes), _seg_log(segment_log)
         soff, shost = self._offsets(src_offsets, src.device, stage_offsets is None)
         n = soff.numel() - 1
+        op = 0 if transforms is not None else _delta_op(delta_op)
+        tr = None if transforms is None else _transforms(transforms, n, src.device)
         capacity = _room(self, src, capacity, "src")
         _base(self, base, src, capacity, "src")
         win, whost = _windows(self, windows, src.device, n)
         if stage_offsets is None:
             if whost is None:
-                raise ValueError("planes_split_window_dbatch: windows on the device need stage_offsets")
+                raise ValueError(what + ": windows on the device need stage_offsets")
             stage_offsets = planes_stage_offsets(self, np.diff(shost.astype(np.int64)).clip(min=0), whost, E, L)
         toff, thost = self._offsets(stage_offsets, src.device, stage is None and stage_capacity is None)
         if toff.numel() != n + 1:
@@ -2105,12 +2104,25 @@ def _planes_methods():
             stage_capacity = _room(self, stage, stage_capacity, "stage")
         poff = _i64(self, plane_offsets, n * E + 1, src.device, "plane_offsets")
         res = _i64(self, results, n, src.device, "results")
-        what = "planes_split_window_dbatch"
-        _check(_call_base(self, "FSEHIP_planes_split_window_dbatch", _delta_op(delta_op), 4, _ptr(stage), _ptr(poff), _ptr(_some(res)), _ptr(_some(src)), _ptr(base),
-                          _ptr(soff), _ptr(_some(win)), _ptr(toff), SZ(n), C.c_uint(E), C.c_uint(L), C.c_uint64(capacity), C.c_uint64(stage_capacity), _stream()), what)
+        args = (_ptr(soff), _ptr(_some(win)), _ptr(toff), SZ(n), C.c_uint(E), C.c_uint(L), C.c_uint64(capacity), C.c_uint64(stage_capacity), _stream())
+        if tr is None:
+            _check(_call_base(self, "FSEHIP_planes_split_window_dbatch", op, 4, _ptr(stage), _ptr(poff), _ptr(_some(res)), _ptr(_some(src)), _ptr(base), *args), what)
+        else:
+            _check(self.lib.FSEHIP_planes_split_window_each_dbatch(_ptr(stage), _ptr(poff), _ptr(_some(res)), _ptr(_some(src)), _ptr(base),
+                                                                   VP(tr.data_ptr() or soff.data_ptr()), *args), what)
         if g is not None:
             g.check(what)
         return stage, poff, res
+
+    def planes_split_window_dbatch(self, src, src_offsets, windows, elem_bytes, segment_log, stage_offsets=None, base=None, capacity=None, stage=None,
+                                   stage_capacity=None, plane_offsets=None, results=None, delta_op=0):
+        """-> (stage, plane_offsets, results): per tensor the planes of the bytes its selected segments cover (planes_stage_offsets), staged back to
+        back at stage_offsets -- plane p of staged tensor i = stage[plane_offsets[i*E+p] : plane_offsets[i*E+p+1]] is segments k0 .. k1 of plane
+        p of the tensor (of tensor XOR base where a base is given, of zigzag(tensor - base) with delta_op 1).  results[i] = the staged bytes, or -1 for a tensor with a bad window, one
+        that ends behind `capacity`, or a pair of stage offsets that does not hold exactly those bytes below stage_capacity.  stage_offsets
+        None: planes_stage_offsets (src_offsets and windows then on the host); on the device they need stage or stage_capacity."""
+        return _split_window(self, "planes_split_window_dbatch", None, src, src_offsets, windows, elem_bytes, segment_log, stage_offsets, base, capacity, stage,
+                             stage_capacity, plane_offsets, results, delta_op)
 
     def planes_splice_scratch_bound(self, n_tensors, elem_bytes, n_segments):
         """bytes of scratch planes_splice_dbatch and tensor_patch_window_dbatch need.  Host arithmetic: needs no device."""
@@ -2204,25 +2216,11 @@ def _planes_methods():
             x.check(what)
         return out, ooff, ores, tres, (out_codecs[:nseg] if out_codecs is not None else None)
 
-    def tensor_patch_window_dbatch(self, frames, frame_offsets, frame_results, src, src_offsets, windows, elem_bytes, segment_log, seg_first=None, n_segments=None,
-                                   sel_first=None, n_selected=None, stage_offsets=None, base=None, codec=0, codecs=None, new_codecs=None, block_size_id=5,
-                                   capacity=None, frames_capacity=None, max_total_blocks=None, align_log=0, out=None, out_capacity=None, out_offsets=None,
-                                   out_results=None, out_codecs=None, tensor_results=None, stage=None, stage_capacity=None, stage_plane_offsets=None,
-                                   stage_seg_offsets=None, stage_results=None, new_frames=None, new_capacity=None, new_offsets=None, new_results=None, scratch=None,
-                                   workspace=None, delta_op=0):
-        """-> (out, out_offsets, out_results, tensor_results, out_codecs): the object (frames, frame_offsets, frame_results, codecs) of
-        tensor_compress_seg_dbatch brought up to date with `src`, the WHOLE current tensors in the layout src_offsets they were compressed in,
-        which changed inside one window (a, b) of elements each.  The segments a >> segment_log .. (b - 1) >> segment_log of every plane are
-        coded anew from src (XOR base, or zigzag(src - base) with delta_op 1), all other frames are the old ones byte for byte: planes_split_window_dbatch, planes_segments_dbatch
-        over the stage, the packed writer, planes_splice_dbatch.  WHOLE SEGMENTS are replaced: inside a selected segment the bytes of src win
-        outside the window too, elsewhere the old ones stay, so src must equal the object's content outside the windows (not checked).  For
-        tensors that differ inside the windows only, the result is tensor_compress_seg_dbatch of src, byte for byte.
-        codecs None: `codec` 0 / 1 for every new frame.  codecs the object's (one per segment): `codec` an AutoCodec -- the new frames' codecs
-        are chosen by size -- or new_codecs given (one per selected frame).  align_log: what the object was written with.  tensor_results
-        and capacity as planes_splice_dbatch; out_capacity None: frames_capacity + frame_packed_bound of the staged bytes.  sel_first,
-        stage_offsets or max_total_blocks None: planes_window_first / planes_stage_offsets (src_offsets and windows then on the host).  The
-        stage, its offsets and results, the new frames, the scratch and the writer's workspace for n_selected frames are scratch; with
-        everything given and on the device the call is launches only."""
+    def _patch_window(self, what, transforms, frames, frame_offsets, frame_results, src, src_offsets, windows, elem_bytes, segment_log, seg_first, n_segments, sel_first,
+                      n_selected, stage_offsets, base, codec, codecs, new_codecs, block_size_id, capacity, frames_capacity, max_total_blocks, align_log, out, out_capacity,
+                      out_offsets, out_results, out_codecs, tensor_results, stage, stage_capacity, stage_plane_offsets, stage_seg_offsets, stage_results, new_frames,
+                      new_capacity, new_offsets, new_results, scratch, workspace, delta_op):
+        """tensor_patch_window_dbatch (transforms None: one op for all) and tensor_patch_window_each_dbatch (a transform per tensor)"""
         E = _elem(elem_bytes)
         align_log = _align_log(align_log)
         L = _seg_log(segment_log, min(block_size_id, 6))
@@ -2231,12 +2229,12 @@ def _planes_methods():
         dev = frames.device
         if src.device != dev:
             raise ValueError("src is on %s, the frames on %s" % (src.device, dev))
-        what = "tensor_patch_window_dbatch"
-        op = _delta_op(delta_op)
+        op = 0 if transforms is not None else _delta_op(delta_op)
         foff, _ = self._offsets(frame_offsets, dev, False)
         need_first = sel_first is None or max_total_blocks is None or stage_offsets is None
         soff, shost = self._offsets(src_offsets, dev, seg_first is None or need_first)
         n = soff.numel() - 1
+        tr = None if transforms is None else _transforms(transforms, n, dev)
         capacity = _room(self, src, capacity, "src")
         _base(self, base, src, capacity, "src")
         frames_capacity = _room(self, frames, frames_capacity, "frames")
@@ -2293,17 +2291,44 @@ def _planes_methods():
             scratch = torch.empty(planes_splice_scratch_bound(self, n, E, nseg), dtype=torch.uint8, device=dev)
         workspace = _writer_workspace(self, workspace, nsel, max_total_blocks, block_size_id, codec, mixed, choose, dev)
         tol = codec.tolerance_permille if choose else 0
-        _check(_call_base(
-            self, "FSEHIP_tensor_patch_window_dbatch", op, 12, _ptr(out), C.c_uint64(out_capacity), _ptr(ooff), _ptr(_some(ores)), _ptr(_some(out_codecs)), _ptr(_some(tres)), _ptr(_some(frames)),
-            C.c_uint64(frames_capacity), _ptr(foff), _ptr(_some(fres)), _ptr(_some(codecs)), _ptr(_some(src)), _ptr(base), _ptr(soff), C.c_uint64(capacity),
-            _ptr(_some(win)), SZ(n), C.c_uint(E), _ptr(sf), SZ(nseg), C.c_uint(L), _ptr(wf), SZ(nsel), _ptr(toff), C.c_uint64(stage_capacity), SZ(max_total_blocks),
-            C.c_uint(block_size_id), C.c_int(0 if mixed else codec), _ptr(_some(new_codecs)), C.c_int(CODECS_CHOOSE if choose else CODECS_GIVEN), C.c_uint(tol),
-            C.c_uint(align_log), _ptr(stage), _ptr(spo), _ptr(sso), _ptr(_some(sres)), _ptr(new_frames), C.c_uint64(new_capacity), _ptr(noff), _ptr(_some(nres)),
-            _ptr(scratch), SZ(scratch.numel()), _ptr(workspace), SZ(workspace.numel()), _stream()), what)
+        front = (_ptr(out), C.c_uint64(out_capacity), _ptr(ooff), _ptr(_some(ores)), _ptr(_some(out_codecs)), _ptr(_some(tres)), _ptr(_some(frames)),
+                 C.c_uint64(frames_capacity), _ptr(foff), _ptr(_some(fres)), _ptr(_some(codecs)), _ptr(_some(src)), _ptr(base))
+        rest = (_ptr(soff), C.c_uint64(capacity), _ptr(_some(win)), SZ(n), C.c_uint(E), _ptr(sf), SZ(nseg), C.c_uint(L), _ptr(wf), SZ(nsel), _ptr(toff),
+                C.c_uint64(stage_capacity), SZ(max_total_blocks), C.c_uint(block_size_id), C.c_int(0 if mixed else codec), _ptr(_some(new_codecs)),
+                C.c_int(CODECS_CHOOSE if choose else CODECS_GIVEN), C.c_uint(tol), C.c_uint(align_log), _ptr(stage), _ptr(spo), _ptr(sso), _ptr(_some(sres)), _ptr(new_frames),
+                C.c_uint64(new_capacity), _ptr(noff), _ptr(_some(nres)), _ptr(scratch), SZ(scratch.numel()), _ptr(workspace), SZ(workspace.numel()), _stream())
+        if tr is None:
+            _check(_call_base(self, "FSEHIP_tensor_patch_window_dbatch", op, 12, *front, *rest), what)
+        else:
+            _check(self.lib.FSEHIP_tensor_patch_window_each_dbatch(*front, VP(tr.data_ptr() or soff.data_ptr()), *rest), what)
         _check_codecs(cgu, nsel, what)
         for x in guards:
             x.check(what)
         return out, ooff, ores, tres, (out_codecs[:nseg] if out_codecs is not None else None)
+
+    def tensor_patch_window_dbatch(self, frames, frame_offsets, frame_results, src, src_offsets, windows, elem_bytes, segment_log, seg_first=None, n_segments=None,
+                                   sel_first=None, n_selected=None, stage_offsets=None, base=None, codec=0, codecs=None, new_codecs=None, block_size_id=5,
+                                   capacity=None, frames_capacity=None, max_total_blocks=None, align_log=0, out=None, out_capacity=None, out_offsets=None,
+                                   out_results=None, out_codecs=None, tensor_results=None, stage=None, stage_capacity=None, stage_plane_offsets=None,
+                                   stage_seg_offsets=None, stage_results=None, new_frames=None, new_capacity=None, new_offsets=None, new_results=None, scratch=None,
+                                   workspace=None, delta_op=0):
+        """-> (out, out_offsets, out_results, tensor_results, out_codecs): the object (frames, frame_offsets, frame_results, codecs) of
+        tensor_compress_seg_dbatch brought up to date with `src`, the WHOLE current tensors in the layout src_offsets they were compressed in,
+        which changed inside one window (a, b) of elements each.  The segments a >> segment_log .. (b - 1) >> segment_log of every plane are
+        coded anew from src (XOR base, or zigzag(src - base) with delta_op 1), all other frames are the old ones byte for byte: planes_split_window_dbatch, planes_segments_dbatch
+        over the stage, the packed writer, planes_splice_dbatch.  WHOLE SEGMENTS are replaced: inside a selected segment the bytes of src win
+        outside the window too, elsewhere the old ones stay, so src must equal the object's content outside the windows (not checked).  For
+        tensors that differ inside the windows only, the result is tensor_compress_seg_dbatch of src, byte for byte.
+        codecs None: `codec` 0 / 1 for every new frame.  codecs the object's (one per segment): `codec` an AutoCodec -- the new frames' codecs
+        are chosen by size -- or new_codecs given (one per selected frame).  align_log: what the object was written with.  tensor_results
+        and capacity as planes_splice_dbatch; out_capacity None: frames_capacity + frame_packed_bound of the staged bytes.  sel_first,
+        stage_offsets or max_total_blocks None: planes_window_first / planes_stage_offsets (src_offsets and windows then on the host).  The
+        stage, its offsets and results, the new frames, the scratch and the writer's workspace for n_selected frames are scratch; with
+        everything given and on the device the call is launches only."""
+        return _patch_window(self, "tensor_patch_window_dbatch", None, frames, frame_offsets, frame_results, src, src_offsets, windows, elem_bytes, segment_log,
+                             seg_first, n_segments, sel_first, n_selected, stage_offsets, base, codec, codecs, new_codecs, block_size_id, capacity, frames_capacity,
+                             max_total_blocks, align_log, out, out_capacity, out_offsets, out_results, out_codecs, tensor_results, stage, stage_capacity, stage_plane_offsets,
+                             stage_seg_offsets, stage_results, new_frames, new_capacity, new_offsets, new_results, scratch, workspace, delta_op)
 
     def patch_tensor_windows(self, obj, tensors, windows, base=None):
         """-> a NEW CompressedTensors: `obj` (of compress_tensors_segmented) brought up to date with `tensors`, the WHOLE current CUDA tensors --
@@ -2372,7 +2397,128 @@ def _planes_methods():
         return _segmented(CompressedTensors(groups, list(obj.dtypes), list(obj.shapes), obj.device, obj.codec, obj.block_size_id, obj.delta), seg_log,
                           getattr(obj, "delta_op", "xor"), None, getattr(obj, "base_digests", None))
 
-    for f in (planes_stage_offsets, planes_split_window_dbatch, planes_splice_scratch_bound, planes_splice_dbatch, tensor_patch_window_dbatch, patch_tensor_windows):
+    # ---- patching tensors with a transform per tensor (fsehip.h, the section of that name): the write side of the windows for frames of
+    # tensor_compress_seg_each_dbatch and tensor_compress_seg_pred_dbatch
+    def planes_split_window_each_dbatch(self, src, src_offsets, windows, elem_bytes, segment_log, transforms, stage_offsets=None, base=None, capacity=None, stage=None,
+                                        stage_capacity=None, plane_offsets=None, results=None):
+        """planes_split_window_dbatch with tensor i staged as transforms[i] says (names, ids or a CUDA uint8 tensor, as planes_split_each_dbatch
+        takes them): for "plain", "xor" and "sub" byte for byte what planes_split_window_dbatch stages (no base, delta_op 0, delta_op 1), for
+        "pred" segments k0 .. k1 of the planes planes_split_pred_dbatch writes for the whole tensor -- a segment starts on a run of 1024
+        elements, so nothing in front of the staged bytes is read.  base: laid out as src, read for xor and sub tensors only.  results -1 and
+        all plane offsets the tensor's stage offset, nothing of it read or written, also for a byte that is none of the four and for xor /
+        sub without a base."""
+        return _split_window(self, "planes_split_window_each_dbatch", transforms, src, src_offsets, windows, elem_bytes, segment_log, stage_offsets, base, capacity, stage,
+                             stage_capacity, plane_offsets, results, 0)
+
+    def tensor_patch_window_each_dbatch(self, frames, frame_offsets, frame_results, src, src_offsets, windows, elem_bytes, segment_log, transforms, seg_first=None,
+                                        n_segments=None, sel_first=None, n_selected=None, stage_offsets=None, base=None, codec=0, codecs=None, new_codecs=None,
+                                        block_size_id=5, capacity=None, frames_capacity=None, max_total_blocks=None, align_log=0, out=None, out_capacity=None,
+                                        out_offsets=None, out_results=None, out_codecs=None, tensor_results=None, stage=None, stage_capacity=None,
+                                        stage_plane_offsets=None, stage_seg_offsets=None, stage_results=None, new_frames=None, new_capacity=None, new_offsets=None,
+                                        new_results=None, scratch=None, workspace=None):
+        """tensor_patch_window_dbatch for an object that tensor_compress_seg_each_dbatch wrote with these transforms (names, ids or a CUDA uint8
+        tensor; all "pred": an object of tensor_compress_seg_pred_dbatch): planes_split_window_each_dbatch, then the segments kernel, the packed
+        writer and the splice as they are.  Every other argument, the scratch, the workspace and the results are those of
+        tensor_patch_window_dbatch.  For tensors that differ inside the windows only, the result is tensor_compress_seg_each_dbatch of src with
+        the same transforms given, byte for byte.  The transforms are GIVEN: the patch never chooses again.  base is read for xor and sub
+        tensors only; without one those are refused alone (-1) and keep all their old frames, like a tensor whose byte is none of the four."""
+        return _patch_window(self, "tensor_patch_window_each_dbatch", transforms, frames, frame_offsets, frame_results, src, src_offsets, windows, elem_bytes, segment_log,
+                             seg_first, n_segments, sel_first, n_selected, stage_offsets, base, codec, codecs, new_codecs, block_size_id, capacity, frames_capacity,
+                             max_total_blocks, align_log, out, out_capacity, out_offsets, out_results, out_codecs, tensor_results, stage, stage_capacity, stage_plane_offsets,
+                             stage_seg_offsets, stage_results, new_frames, new_capacity, new_offsets, new_results, scratch, workspace, 0)
+
+    def patch_tensor_windows_each(self, obj, tensors, windows, base=None):
+        """patch_tensor_windows for ANY segmented object that is not sparse, with the same contract -- the WHOLE current CUDA tensors, one window
+        (start, stop) or None per tensor, whole segments replaced, a NEW object that shares nothing with `obj`, which is not changed; only the
+        segment frames that hold a window are coded again (tensor_patch_window_each_dbatch):
+          an object of compress_tensors_each(..., segment_log=...), also reopened from an archive: obj.transforms, per tensor, GIVEN -- the
+            patch never chooses a transform again; base (the base of the whole list) iff one of them is "xor" or "sub";
+          an object written with PredictedPlanes (predictor "prev"): every tensor "pred", no base;
+          a plain or a delta object of compress_tensors_segmented: every tensor "plain", or "xor" / "sub" by the object's delta_op with its base.
+        Where `tensors` equal the object's content outside the windows the result is what the compress call that wrote `obj` gives for
+        `tensors` (with obj.transforms given), byte for byte.  A window of a "pred" tensor may start anywhere: a segment starts on a run.
+        The new object carries transforms or predictor, segment_log, block_size_id, codec, delta, delta_op, base_digests and seg_first over;
+        with an AutoCodec the codecs of the new frames are chosen anew.  ValueError / TypeError before any launch: no segment_log; a sparse
+        object; a wrong number of tensors or windows; a tensor of another dtype, shape or device; a window that is not one; transforms that
+        are not names out of EST_NAMES, or together with a predictor; a predictor other than "prev"; "xor" / "sub" tensors without a base;
+        a base for an object that holds neither."""
+        what = "patch_tensor_windows_each"
+        seg_log = getattr(obj, "segment_log", None)
+        if seg_log is None:
+            raise ValueError(what + ": the object is not segmented (compress_tensors_each and compress_tensors_segmented write those with a segment_log)")
+        if getattr(obj, "sparse_permille", None) is not None:
+            raise ValueError(what + ": the object holds sparse planes (SparsePlanes); patches of those are not supported")
+        n = len(obj.dtypes)
+        names, predictor = getattr(obj, "transforms", None), getattr(obj, "predictor", None)
+        if names is not None:
+            names = list(names)
+            if len(names) != n or any(not isinstance(t, str) or t not in EST_NAMES for t in names):
+                raise ValueError("%s: transforms %r; one name per tensor (%d) out of %r is needed" % (what, names[:8], n, EST_NAMES))
+            if predictor is not None:
+                raise ValueError(what + ": a predictor does not go with a transform per tensor")
+            if isinstance(base, DeltaBase):
+                base = base.tensors
+            if any(t in ("xor", "sub") for t in names) != (base is not None):
+                raise ValueError(what + ": the object holds \"xor\" or \"sub\" tensors and needs its base" if base is None else
+                                 what + ": the object holds no \"xor\" or \"sub\" tensor, a base does not belong to it")
+        elif predictor is not None:
+            if predictor != "prev":
+                raise ValueError("%s: predictor %r; only \"prev\" is known" % (what, predictor))
+            if base is not None:
+                raise ValueError(what + ": the object holds predicted planes, a base does not belong to it")
+            names = ["pred"] * n
+        else:
+            base, op = _read_base(obj, base, what)
+            names = [("plain" if base is None else "sub" if op else "xor")] * n
+        tensors = list(tensors)
+        if len(tensors) != n:
+            raise ValueError("%s: %d tensors for %d tensors" % (what, len(tensors), n))
+        wins = [w or (0, 0) for w in _window_list(what, obj, windows)]
+        for k, (t, dt, sh) in enumerate(zip(tensors, obj.dtypes, obj.shapes)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != obj.device or t.dtype != dt:
+                raise TypeError("%s: tensor %d: a CUDA tensor of %s on %s is needed" % (what, k, dt, obj.device))
+            if tuple(t.shape) != tuple(sh):
+                raise ValueError("%s: tensor %d has shape %s, the object's has %s" % (what, k, tuple(t.shape), tuple(sh)))
+        braw = None if base is None else _bases(base, obj.dtypes, obj.shapes, obj.device)
+        inner = obj.codec.codec if isinstance(obj.codec, PredictedPlanes) else obj.codec
+        auto = isinstance(inner, AutoCodec)
+        groups = []
+        for g in obj.groups:
+            E, sizes, idx = g["elem_bytes"], g["sizes"], g["index"]
+            gw = [wins[i] for i in idx]
+            new = dict(g)
+            if any(b > a for a, b in gw):
+                raw = [tensors[i].contiguous().reshape(-1).view(torch.uint8) for i in idx]
+                offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
+                src = torch.cat(raw)
+                bsrc = None if braw is None else torch.cat([braw[i] for i in idx])
+                first, blocks = self.planes_window_first(sizes, gw, E, seg_log, obj.block_size_id)
+                toff = self.planes_stage_offsets(sizes, gw, E, seg_log)
+                cap = int(g["frames"].numel()) + self.frame_packed_bound(int(toff[-1]), int(first[-1]), blocks, 0)
+                out, ooff, ores, tres, ocod = tensor_patch_window_each_dbatch(
+                    self, g["frames"], g["frame_offsets"], g["frame_results"], src, offs, gw, E, seg_log, [names[i] for i in idx], g["seg_first"], sel_first=first,
+                    stage_offsets=toff, base=bsrc, codec=inner if auto or "codecs" not in g else 0, codecs=g.get("codecs"), block_size_id=obj.block_size_id,
+                    max_total_blocks=blocks, out_capacity=cap)
+                got = torch.cat([ooff[-1:], tres]).cpu().tolist()
+                if got[1:] != sizes or got[0] > cap:
+                    raise RuntimeError("%s: element size %d, results %s for tensors of %s bytes" % (what, E, got[1:9], sizes[:8]))
+                new.update(frames=out[:got[0]].clone(), frame_offsets=ooff, frame_results=ores, tensor_results=tres)
+                if ocod is not None:
+                    new["codecs"] = ocod.clone()
+            else:
+                new.update(frames=g["frames"].clone(), frame_offsets=g["frame_offsets"].clone(), frame_results=g["frame_results"].clone(),
+                           tensor_results=g["tensor_results"].clone())
+                if "codecs" in g:
+                    new["codecs"] = g["codecs"].clone()
+            groups.append(new)
+        got = _segmented(CompressedTensors(groups, list(obj.dtypes), list(obj.shapes), obj.device, obj.codec, obj.block_size_id, obj.delta), seg_log,
+                         getattr(obj, "delta_op", "xor"), None, getattr(obj, "base_digests", None), predictor)
+        if getattr(obj, "transforms", None) is not None:
+            got.transforms = list(names)
+        return got
+
+    for f in (planes_stage_offsets, planes_split_window_dbatch, planes_splice_scratch_bound, planes_splice_dbatch, tensor_patch_window_dbatch, patch_tensor_windows,
+              planes_split_window_each_dbatch, tensor_patch_window_each_dbatch, patch_tensor_windows_each):
         setattr(FseHip, f.__name__, f)
 
     # ---- sparse planes (csrc/planes_sparse.hip; fsehip.h "sparse planes"): a unit of n bytes as a zero mask of ceil(n / 8) bytes and its
@@ -3825,8 +3971,8 @@ def _planes_methods():
         base: a sequence matching `tensors` one to one (or a DeltaBase without check: its tensors); needed where a given name is "xor" or
         "sub".  codec: 0, 1 or an AutoCodec.  A tensor of 0 bytes takes the lowest candidate and needs no company.
         Out of scope, each a ValueError before any launch: a SparsePlanes or PredictedPlanes as codec, an earlier object as codec, a
-        DeltaBase(check=True); patches of the object (patch_tensor_windows).  Windows of a segmented object are read by
-        decompress_tensor_windows_each, not by decompress_tensor_windows."""
+        DeltaBase(check=True).  Windows of a segmented object are read by decompress_tensor_windows_each and written by
+        patch_tensor_windows_each, not by decompress_tensor_windows and patch_tensor_windows."""
         what = "compress_tensors_each"
         margin = _margin(margin_permille, what)
         if isinstance(codec, bool) or not (isinstance(codec, AutoCodec) or (isinstance(codec, numbers.Integral) and codec in (0, 1))):
@@ -4110,6 +4256,11 @@ def decompress_tensor_windows_each(obj, windows, base=None):
 def patch_tensor_windows(obj, tensors, windows, base=None):
     """FseHip.patch_tensor_windows on a library handle of the module's own"""
     return _default().patch_tensor_windows(obj, tensors, windows, base)
+
+
+def patch_tensor_windows_each(obj, tensors, windows, base=None):
+    """FseHip.patch_tensor_windows_each on a library handle of the module's own"""
+    return _default().patch_tensor_windows_each(obj, tensors, windows, base)
 
 
 def tensor_digests(tensors):

@@ -379,6 +379,9 @@ hipError_t launch_planes_merge_each(u8* dst, const u64* dstOff, size_t* results,
 // plane, windows (a, b) in elements; its grid has 2 * nTensors workgroups beyond the tiles of dstCapacity
 hipError_t launch_planes_merge_window_each(u8* dst, const u64* dstOff, size_t* results, const u8* planes, const u64* planeOff, const size_t* planeSizes, const u8* base,
                                            const u8* transforms, const u64* windows, size_t nTensors, unsigned E, u64 dstCapacity, hipStream_t s);
+// the window form of that split (fsehip.h, "patching tensors with a transform per tensor"): the stage of a patch, the transform read per tensor
+hipError_t launch_planes_split_window_each(u8* stage, u64* planeOff, size_t* stageRes, const u8* src, const u8* base, const u8* transforms, const u64* srcOff,
+                                           const u64* windows, const u64* stageOff, size_t nTensors, unsigned E, unsigned segLog, u64 capacity, u64 stageCapacity, hipStream_t s);
 
 // ---- kernel timing probe (HIP events on the launch stream; used by bench.py for the live roofline figure) ----
 enum { PK_HIST = 0, PK_FSE_CPREP, PK_FSE_ENCODE, PK_FSE_DPREP, PK_FSE_DECODE, PK_HUF_CPREP, PK_HUF_ENCODE, PK_HUF_DPREP, PK_HUF_DECODE, PK_FSE_ENCODE_WAVE, PK_COUNT };

@@ -372,6 +372,17 @@ HDEV PpSub pp_sub(u64 n, u64 k0, u64 cnt, u32 E, u32 segLog)
     const u64 at = (k0 << segLog) * E, full = (cnt << segLog) * E;
     return { at, cnt && at < n ? (n - at < full ? n - at : full) : 0 };
 }
+// what tensor i stages: the bytes [at, at + m) of it, accepted iff its slot in S lies below the capacity, its window is valid and its pair
+// of stage offsets holds exactly those m bytes below the stage's capacity
+struct PpStage { u64 at, m; bool ok; };
+DEV PpStage pp_stage(const u64* S, const u64* W, const u64* T, size_t i, u32 E, u32 segLog, u64 capacity, u64 stageCapacity)
+{
+    const u64 s0 = S[i], s1 = S[i + 1], n = s1 > s0 ? s1 - s0 : 0, a = W[2 * i], b = W[2 * i + 1], t0 = T[i], t1 = T[i + 1];
+    const bool valid = s0 <= s1 && s1 <= capacity && a <= b && b <= n / E;
+    const PwRange r = pw_range(a, b, valid, segLog);
+    const PpSub sub = pp_sub(n, r.k0, r.cnt, E, segLog);
+    return { sub.at, sub.m, valid && t0 <= t1 && t1 <= stageCapacity && t1 - t0 == sub.m };
+}
 // frame q of a packed batch lies inside its buffer and holds its result: 0 <= F[q] <= F[q + 1] <= capacity, R[q] <= F[q + 1] - F[q]
 DEV bool pp_extent_ok(const u64* F, const size_t* R, size_t q, u64 capacity)
 {

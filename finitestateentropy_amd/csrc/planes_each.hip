@@ -6,6 +6,7 @@
 //   launch_planes_split_each : k_planes_offsets (planes.hip) -> k_each_refuse -> k_planes_split_each
 //   launch_planes_merge_each : k_planes_verdicts (planes.hip) -> k_each_refuse -> k_planes_merge_each
 //   launch_planes_merge_window_each : k_planes_verdicts -> k_each_refuse_window -> k_planes_merge_each<E, const u64*> (THE WINDOW FORM below)
+//   launch_planes_split_window_each : k_each_stage_offsets -> k_planes_split_window_each (THE WINDOW FORM OF THE SPLIT below)
 //
 // THE SPLIT has the frame of k_planes_split_pred: the flat ragged mapping (a workgroup per (tile, tensor) intersection, pl_find) and chunks
 // of 16 whole elements per lane counted from the TENSOR's start.  That frame serves all four: SUB and PRED need whole elements per dword,
@@ -35,6 +36,13 @@
 // the items from its key to below the next one's, floor(D[i+1] / T) - floor(D[i] / T) + 2 of them, and ceil(capacity / T) + 2 nTensors
 // workgroups are launched (the last tensor: ceil(capacity / T) - floor(D[i] / T) + 2 items).  A workgroup whose tile lies behind
 // n + L E returns.
+//
+// THE WINDOW FORM OF THE SPLIT (fsehip.h, "patching tensors with a transform per tensor"; k_planes_split_window_each): the frame of
+// k_planes_split_window (planes_patch.hip) -- the STAGE offsets T are the axis, tensor i is accepted by pp_stage, its source and its base are
+// displaced by S[i] + at -- around pe_split, whose chunks and runs are counted from the staged SUB-TENSOR's start.  at = k0 seg E with
+// seg = 1 << segLog >= PP_RUN, so the sub-tensor starts at a multiple of PP_RUN elements of the tensor: its runs and its chunks are the
+// tensor's own, the PRED arm's run-start test on the relative index is the tensor's, and no difference reads an element in front of
+// src + S[i] + at.  No lead, no LDS, no workspace.  k_each_stage_offsets is k_planes_stage_offsets with the transform's refusal in rule 1.
 //
 // REFUSALS: a transform byte above FSEHIP_EST_SUB (the estimate's 0xFF among them), or XOR / SUB without a base: k_each_refuse writes GENERIC
 // over the tensor's result, and the data kernels return for it in front of every load and store.  The window form adds (pe_win_ok): a window
@@ -131,6 +139,46 @@ __global__ __launch_bounds__(PL_THREADS) void k_planes_split_each(u8* planes, co
     else if (tr == FSEHIP_EST_PRED) pe_split<E, FSEHIP_EST_PRED>(pb, sb, nullptr, s0, n, lo, tid);
     else if (tr == FSEHIP_EST_XOR) pe_split<E, FSEHIP_EST_XOR>(pb, sb, base + s0, s0, n, lo, tid);
     else pe_split<E, FSEHIP_EST_SUB>(pb, sb, base + s0, s0, n, lo, tid);
+}
+
+// ---- the window split (the patch's stage) ----------------------------------------------------------------------------------------------------
+// k_planes_stage_offsets (planes_patch.hip) with one more cause in its rule 1: per tensor (and one thread more for the last entry) its E
+// staged plane offsets and its result.  The entries of a tensor refused by pp_stage or by its transform are all its stage offset; no entry
+// lies behind the stage's capacity
+__global__ void k_each_stage_offsets(u64* P, size_t* res, const u8* TR, const u8* base, const u64* S, const u64* W, const u64* T, size_t nT, u32 E, u32 segLog, u64 capacity,
+                                     u64 stageCapacity)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > nT) return;
+    const u64 t0 = T[i] < stageCapacity ? T[i] : stageCapacity;
+    if (i == nT) { P[nT * E] = t0; return; }
+    const PpStage g = pp_stage(S, W, T, i, E, segLog, capacity, stageCapacity);
+    const bool ok = g.ok && pe_ok(TR[i], base);
+    for (u32 p = 0; p < E; ++p) P[i * E + p] = ok ? t0 + pl_start(g.m, p, E) : t0;
+    res[i] = ok ? (size_t)g.m : FERR(GENERIC);
+}
+// workgroup w takes tile w - i of the staged sub-tensor i under transform TR[i]: m bytes at src + S[i] + at, planes at stage + T[i]
+template <int E>
+__global__ __launch_bounds__(PL_THREADS) void k_planes_split_window_each(u8* stage, const u8* src, const u8* base, const u8* TR, const u64* S, const u64* W, const u64* T,
+                                                                         size_t nT, u32 segLog, u64 capacity, u64 stageCapacity)
+{
+    const u64 w = blockIdx.x;
+    size_t i;
+    if (!pl_find(T, nT, w, i)) return;                            // (uniform, like every return below)
+    const u64 t0 = T[i], t1 = T[i + 1], lo = (w - i) << PL_TILE_LOG;
+    if (!(t0 < t1) || lo >= t1 || lo + PLANES_TILE <= t0) return;
+    const u32 tr = TR[i];
+    if (!pe_ok(tr, base)) return;                                 // (a refused tensor: nothing of it is read or written)
+    const PpStage g = pp_stage(S, W, T, i, E, segLog, capacity, stageCapacity);
+    if (!g.ok) return;                                            // (accepted: t1 - t0 == m, t1 <= stageCapacity, S[i] + at + m <= S[i + 1] <= capacity)
+    const u32 tid = threadIdx.x;
+    const u64 at = S[i] + g.at;
+    const u8* const sb = src + at;
+    u8* const pb = stage + t0;
+    if (tr == FSEHIP_EST_PLAIN) pe_split<E, FSEHIP_EST_PLAIN>(pb, sb, nullptr, t0, g.m, lo, tid);
+    else if (tr == FSEHIP_EST_PRED) pe_split<E, FSEHIP_EST_PRED>(pb, sb, nullptr, t0, g.m, lo, tid);
+    else if (tr == FSEHIP_EST_XOR) pe_split<E, FSEHIP_EST_XOR>(pb, sb, base + at, t0, g.m, lo, tid);
+    else pe_split<E, FSEHIP_EST_SUB>(pb, sb, base + at, t0, g.m, lo, tid);
 }
 
 // ---- merge -------------------------------------------------------------------------------------------------------------------------------
@@ -277,6 +325,21 @@ hipError_t launch_planes_split_each(u8* planes, u64* planeOff, size_t* tensorRes
     const dim3 g(tile_grid(capacity, nTensors)), b(PL_THREADS);
     pl_for_elem(E, [&](auto eb) {
         hipLaunchKernelGGL((k_planes_split_each<decltype(eb)::value>), g, b, 0, s, planes, src, base, transforms, srcOff, nTensors, capacity);
+    });
+    return hipGetLastError();
+}
+
+// the window form: the offsets kernel runs even for no tensors (it writes the last entry), then ceil(stageCapacity / T) + nTensors workgroups
+hipError_t launch_planes_split_window_each(u8* stage, u64* planeOff, size_t* stageRes, const u8* src, const u8* base, const u8* transforms, const u64* srcOff,
+                                           const u64* windows, const u64* stageOff, size_t nTensors, unsigned E, unsigned segLog, u64 capacity, u64 stageCapacity, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_each_stage_offsets, dim3(grid_for(nTensors + 1)), dim3(PL_THREADS), 0, s, planeOff, stageRes, transforms, base, srcOff, windows, stageOff, nTensors,
+                       (u32)E, (u32)segLog, capacity, stageCapacity);
+    if (nTensors == 0 || stageCapacity == 0) return hipGetLastError();
+    const dim3 g(tile_grid(stageCapacity, nTensors)), b(PL_THREADS);
+    pl_for_elem(E, [&](auto eb) {
+        hipLaunchKernelGGL((k_planes_split_window_each<decltype(eb)::value>), g, b, 0, s, stage, src, base, transforms, srcOff, windows, stageOff, nTensors, (u32)segLog,
+                           capacity, stageCapacity);
     });
     return hipGetLastError();
 }

@@ -10,23 +10,14 @@
 //                                       result, codec) -> the exclusive scan of frame_dev.hip over the extents -> k_patch_results (per
 //                                       tensor) -> k_planes_splice (per (tile, frame) intersection of the new object: the copy)
 //   FSEHIP_tensor_patch_window_dbatch : the window split -> the segments kernel over the stage -> the packed (mixed) writer -> the splice
+//   FSEHIP_planes_split_window_each_dbatch, FSEHIP_tensor_patch_window_each_dbatch ("patching tensors with a transform per tensor"): the same
+//                                       two with the window split of planes_each.hip, which reads a transform per tensor; every later step as it is
 #include "planes_dev.h"
 
 namespace {
 #define PP_NEW ((u64)1 << 63)          // k_patch_entries' source word: the frame lies in the new frames buffer, at the low bits
 
 // ---- the window split ----------------------------------------------------------------------------------------------------------------------
-// what tensor i stages: the bytes [at, at + m) of it, accepted iff its slot in S lies below the capacity, its window is valid and its pair
-// of stage offsets holds exactly those m bytes below the stage's capacity
-struct PpStage { u64 at, m; bool ok; };
-DEV PpStage pp_stage(const u64* S, const u64* W, const u64* T, size_t i, u32 E, u32 segLog, u64 capacity, u64 stageCapacity)
-{
-    const u64 s0 = S[i], s1 = S[i + 1], n = s1 > s0 ? s1 - s0 : 0, a = W[2 * i], b = W[2 * i + 1], t0 = T[i], t1 = T[i + 1];
-    const bool valid = s0 <= s1 && s1 <= capacity && a <= b && b <= n / E;
-    const PwRange r = pw_range(a, b, valid, segLog);
-    const PpSub sub = pp_sub(n, r.k0, r.cnt, E, segLog);
-    return { sub.at, sub.m, valid && t0 <= t1 && t1 <= stageCapacity && t1 - t0 == sub.m };
-}
 // per tensor (and one thread more for the last entry): its E staged plane offsets and its result.  The entries of a refused tensor are all
 // its stage offset; no entry lies behind the stage's capacity
 __global__ void k_planes_stage_offsets(u64* P, size_t* res, const u64* S, const u64* W, const u64* T, size_t nT, u32 E, u32 segLog, u64 capacity, u64 stageCapacity)
@@ -329,16 +320,15 @@ extern "C" int FSEHIP_tensor_patch_window_dbatch(void* d_out, uint64_t outCapaci
                                                 policy, tolerancePermille, slotAlignLog, d_stage, d_stagePlaneOffsets, d_stageSegOffsets, d_stageResults, d_newFrames,
                                                 newCapacity, d_newOffsets, d_newResults, d_scratch, scratchBytes, d_workspace, workspaceBytes, stream);
 }
-extern "C" int FSEHIP_tensor_patch_window_op_dbatch(void* d_out, uint64_t outCapacity, uint64_t* d_outOffsets, size_t* d_outResults, uint8_t* d_outCodecs,
-                                                    size_t* d_tensorResults, const void* d_frames, uint64_t framesCapacity, const uint64_t* d_frameOffsets,
-                                                    const size_t* d_frameResults, const uint8_t* d_codecs, const void* d_src, const void* d_base, unsigned deltaOp,
-                                                    const uint64_t* d_srcOffsets, uint64_t capacity, const uint64_t* d_windows, size_t nTensors, unsigned elemBytes,
-                                                    const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, const uint64_t* d_selFirst, size_t nSelected,
-                                                    const uint64_t* d_stageOffsets, uint64_t stageCapacity, size_t maxTotalBlocks, unsigned blockSizeId, int codec,
-                                                    uint8_t* d_newCodecs, int policy, unsigned tolerancePermille, unsigned slotAlignLog, void* d_stage,
-                                                    uint64_t* d_stagePlaneOffsets, uint64_t* d_stageSegOffsets, size_t* d_stageResults, void* d_newFrames,
-                                                    uint64_t newCapacity, uint64_t* d_newOffsets, size_t* d_newResults, void* d_scratch, size_t scratchBytes,
-                                                    void* d_workspace, size_t workspaceBytes, void* stream)
+// the one composite: the window split by one op (d_transforms null) or by a transform per tensor, then the steps that both share
+static int patch_window(void* d_out, uint64_t outCapacity, uint64_t* d_outOffsets, size_t* d_outResults, uint8_t* d_outCodecs, size_t* d_tensorResults, const void* d_frames,
+                        uint64_t framesCapacity, const uint64_t* d_frameOffsets, const size_t* d_frameResults, const uint8_t* d_codecs, const void* d_src, const void* d_base,
+                        unsigned deltaOp, const uint8_t* d_transforms, const uint64_t* d_srcOffsets, uint64_t capacity, const uint64_t* d_windows, size_t nTensors,
+                        unsigned elemBytes, const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, const uint64_t* d_selFirst, size_t nSelected,
+                        const uint64_t* d_stageOffsets, uint64_t stageCapacity, size_t maxTotalBlocks, unsigned blockSizeId, int codec, uint8_t* d_newCodecs, int policy,
+                        unsigned tolerancePermille, unsigned slotAlignLog, void* d_stage, uint64_t* d_stagePlaneOffsets, uint64_t* d_stageSegOffsets, size_t* d_stageResults,
+                        void* d_newFrames, uint64_t newCapacity, uint64_t* d_newOffsets, size_t* d_newResults, void* d_scratch, size_t scratchBytes, void* d_workspace,
+                        size_t workspaceBytes, void* stream)
 {
     if (bad_op(deltaOp)) return (int)hipErrorInvalidValue;
     if (bad_splice(d_out, outCapacity, d_outOffsets, d_outResults, d_outCodecs, d_tensorResults, d_frames, d_frameOffsets, d_frameResults, d_codecs, d_newCodecs,
@@ -350,8 +340,12 @@ extern "C" int FSEHIP_tensor_patch_window_op_dbatch(void* d_out, uint64_t outCap
     const PlWriter wr = { maxTotalBlocks, blockSizeId, codec, d_newCodecs, policy, tolerancePermille, slotAlignLog, d_workspace, workspaceBytes };
     if (bad_seg(segLog, blockSizeId) || bad_grid(stageCapacity, nTensors) || bad_writer(wr, nSelected)) return (int)hipErrorInvalidValue;
     const hipStream_t s = (hipStream_t)stream;
-    hipError_t e = launch_split_window((u8*)d_stage, (u64*)d_stagePlaneOffsets, d_stageResults, (const u8*)d_src, (const u8*)d_base, deltaOp, (const u64*)d_srcOffsets,
-                                       (const u64*)d_windows, (const u64*)d_stageOffsets, nTensors, elemBytes, segLog, capacity, stageCapacity, s);
+    hipError_t e = d_transforms ? launch_planes_split_window_each((u8*)d_stage, (u64*)d_stagePlaneOffsets, d_stageResults, (const u8*)d_src, (const u8*)d_base, d_transforms,
+                                                                  (const u64*)d_srcOffsets, (const u64*)d_windows, (const u64*)d_stageOffsets, nTensors, elemBytes, segLog,
+                                                                  capacity, stageCapacity, s)
+                                : launch_split_window((u8*)d_stage, (u64*)d_stagePlaneOffsets, d_stageResults, (const u8*)d_src, (const u8*)d_base, deltaOp,
+                                                      (const u64*)d_srcOffsets, (const u64*)d_windows, (const u64*)d_stageOffsets, nTensors, elemBytes, segLog, capacity,
+                                                      stageCapacity, s);
     if (e != hipSuccess) return (int)e;
     if (nSelected) {                                             // (nothing selected: the splice alone, a copy of the object)
         // a staged sub-tensor has exactly cnt segments per plane: the segments kernel with the stage offsets as the tensors' and selFirst as
@@ -371,4 +365,52 @@ extern "C" int FSEHIP_tensor_patch_window_op_dbatch(void* d_out, uint64_t outCap
     const PpMap m = { (const u64*)d_srcOffsets, (const u64*)d_windows, (const u64*)d_segFirst, (const u64*)d_selFirst, d_stageResults, nTensors, elemBytes, nSegments,
                       nSelected, segLog };
     return (int)launch_splice((u8*)d_out, outCapacity, (u64*)d_outOffsets, d_outResults, d_outCodecs, d_tensorResults, old, nw, m, (u8*)d_scratch, (hipStream_t)stream);
+}
+extern "C" int FSEHIP_tensor_patch_window_op_dbatch(void* d_out, uint64_t outCapacity, uint64_t* d_outOffsets, size_t* d_outResults, uint8_t* d_outCodecs,
+                                                    size_t* d_tensorResults, const void* d_frames, uint64_t framesCapacity, const uint64_t* d_frameOffsets,
+                                                    const size_t* d_frameResults, const uint8_t* d_codecs, const void* d_src, const void* d_base, unsigned deltaOp,
+                                                    const uint64_t* d_srcOffsets, uint64_t capacity, const uint64_t* d_windows, size_t nTensors, unsigned elemBytes,
+                                                    const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, const uint64_t* d_selFirst, size_t nSelected,
+                                                    const uint64_t* d_stageOffsets, uint64_t stageCapacity, size_t maxTotalBlocks, unsigned blockSizeId, int codec,
+                                                    uint8_t* d_newCodecs, int policy, unsigned tolerancePermille, unsigned slotAlignLog, void* d_stage,
+                                                    uint64_t* d_stagePlaneOffsets, uint64_t* d_stageSegOffsets, size_t* d_stageResults, void* d_newFrames,
+                                                    uint64_t newCapacity, uint64_t* d_newOffsets, size_t* d_newResults, void* d_scratch, size_t scratchBytes,
+                                                    void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    return patch_window(d_out, outCapacity, d_outOffsets, d_outResults, d_outCodecs, d_tensorResults, d_frames, framesCapacity, d_frameOffsets, d_frameResults, d_codecs,
+                        d_src, d_base, deltaOp, nullptr, d_srcOffsets, capacity, d_windows, nTensors, elemBytes, d_segFirst, nSegments, segLog, d_selFirst, nSelected,
+                        d_stageOffsets, stageCapacity, maxTotalBlocks, blockSizeId, codec, d_newCodecs, policy, tolerancePermille, slotAlignLog, d_stage, d_stagePlaneOffsets,
+                        d_stageSegOffsets, d_stageResults, d_newFrames, newCapacity, d_newOffsets, d_newResults, d_scratch, scratchBytes, d_workspace, workspaceBytes, stream);
+}
+
+// ---- patching tensors with a transform per tensor ----
+extern "C" int FSEHIP_planes_split_window_each_dbatch(void* d_stage, uint64_t* d_stagePlaneOffsets, size_t* d_stageResults, const void* d_src, const void* d_base,
+                                                      const uint8_t* d_transforms, const uint64_t* d_srcOffsets, const uint64_t* d_windows, const uint64_t* d_stageOffsets,
+                                                      size_t nTensors, unsigned elemBytes, unsigned segLog, uint64_t capacity, uint64_t stageCapacity, void* stream)
+{
+    if (!d_transforms || bad_elem(elemBytes) || bad_seg(segLog, 0) || !d_stagePlaneOffsets || !d_stageResults || !d_srcOffsets || !d_windows || !d_stageOffsets ||
+        (stageCapacity && (!d_stage || !d_src)))
+        return (int)hipErrorInvalidValue;
+    if (bad_tensors(nTensors, elemBytes) || bad_grid(stageCapacity, nTensors)) return (int)hipErrorInvalidValue;
+    return (int)launch_planes_split_window_each((u8*)d_stage, (u64*)d_stagePlaneOffsets, d_stageResults, (const u8*)d_src, (const u8*)d_base, d_transforms,
+                                                (const u64*)d_srcOffsets, (const u64*)d_windows, (const u64*)d_stageOffsets, nTensors, elemBytes, segLog, capacity,
+                                                stageCapacity, (hipStream_t)stream);
+}
+extern "C" int FSEHIP_tensor_patch_window_each_dbatch(void* d_out, uint64_t outCapacity, uint64_t* d_outOffsets, size_t* d_outResults, uint8_t* d_outCodecs,
+                                                      size_t* d_tensorResults, const void* d_frames, uint64_t framesCapacity, const uint64_t* d_frameOffsets,
+                                                      const size_t* d_frameResults, const uint8_t* d_codecs, const void* d_src, const void* d_base,
+                                                      const uint8_t* d_transforms, const uint64_t* d_srcOffsets, uint64_t capacity, const uint64_t* d_windows, size_t nTensors,
+                                                      unsigned elemBytes,
+                                                      const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, const uint64_t* d_selFirst, size_t nSelected,
+                                                      const uint64_t* d_stageOffsets, uint64_t stageCapacity, size_t maxTotalBlocks, unsigned blockSizeId, int codec,
+                                                      uint8_t* d_newCodecs, int policy, unsigned tolerancePermille, unsigned slotAlignLog, void* d_stage,
+                                                      uint64_t* d_stagePlaneOffsets, uint64_t* d_stageSegOffsets, size_t* d_stageResults, void* d_newFrames,
+                                                      uint64_t newCapacity, uint64_t* d_newOffsets, size_t* d_newResults, void* d_scratch, size_t scratchBytes,
+                                                      void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    if (!d_transforms) return (int)hipErrorInvalidValue;
+    return patch_window(d_out, outCapacity, d_outOffsets, d_outResults, d_outCodecs, d_tensorResults, d_frames, framesCapacity, d_frameOffsets, d_frameResults, d_codecs,
+                        d_src, d_base, FSEHIP_DELTA_XOR, d_transforms, d_srcOffsets, capacity, d_windows, nTensors, elemBytes, d_segFirst, nSegments, segLog, d_selFirst,
+                        nSelected, d_stageOffsets, stageCapacity, maxTotalBlocks, blockSizeId, codec, d_newCodecs, policy, tolerancePermille, slotAlignLog, d_stage,
+                        d_stagePlaneOffsets, d_stageSegOffsets, d_stageResults, d_newFrames, newCapacity, d_newOffsets, d_newResults, d_scratch, scratchBytes, d_workspace, workspaceBytes, stream);
 }

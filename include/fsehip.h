@@ -1287,7 +1287,7 @@ FSEHIP_API int FSEHIP_archive_open_dbatch(uint64_t* d_srcOffsets, uint64_t* d_fr
  *   All six: launches only (capturable); every argument error is hipErrorInvalidValue before any device call, with nothing written;
  *   workspaces are the writers' and readers' own.
  *   Out of scope: strides other than 1 (interleaved channels); higher-order or float-aware predictors; prediction combined with a base or
- *   with sparse planes; patches of predicted tensors (their windows: "windows of tensors with a transform per tensor" below); a record of the predictor in frames or in the archive head. */
+ *   with sparse planes; (windows and patches of predicted tensors: "windows of" and "patching tensors with a transform per tensor" below); a record of the predictor in frames or in the archive head. */
 #define FSEHIP_PRED_RUN_LOG 10
 FSEHIP_API int FSEHIP_planes_split_pred_dbatch(void* d_planes, uint64_t* d_planeOffsets, size_t* d_tensorResults, const void* d_src, const uint64_t* d_srcOffsets,
                                                size_t nTensors, unsigned elemBytes, uint64_t capacity, void* stream);
@@ -1409,7 +1409,7 @@ FSEHIP_API int FSEHIP_planes_estimate_dbatch(uint64_t* d_planeBits, uint64_t* d_
  *     nothing written: a null mandatory pointer; elemBytes not 1, 2, 4 or 8; an unknown transformPolicy; with CHOOSE a candidateMask of 0
  *     or with an unknown bit, XOR or SUB in it with d_base == NULL, marginPermille > 1000, 2^24 tensors; a workspace that is misaligned
  *     (256) or short; a launch beyond the limits of "byte planes"; whatever the writer or the reader refuses.
- *   Out of scope: sparse planes around these calls; digests and gating; patches (windows: the next section); a record of the transforms in frames or in
+ *   Out of scope: sparse planes around these calls; digests and gating (windows and patches: the next two sections); a record of the transforms in frames or in
  *   the archive head (the caller carries d_transforms as it carries a delta's op); new candidates or costs in the estimate. */
 #define FSEHIP_TRANSFORMS_GIVEN  0   /* d_transforms is an INPUT: nTensors bytes, FSEHIP_EST_PLAIN .. FSEHIP_EST_SUB */
 #define FSEHIP_TRANSFORMS_CHOOSE 1   /* d_transforms is an OUTPUT: the estimate's choice per tensor */
@@ -1478,7 +1478,7 @@ FSEHIP_API int FSEHIP_tensor_decompress_seg_each_dbatch(void* d_dst, const uint6
  *     10 .. 30, 2^31 planes, segments or selected frames, nSelected > nSegments, the launch limit above, a workspace that is misaligned (256)
  *     or short, maxTotalBlocks >= 2^31.  It only launches.  A refused tensor's slot is not written; other tensors are not affected.
  *   Both: every argument error is hipErrorInvalidValue with nothing written; nTensors == 0 is legal; capturable into a graph.
- *   Out of scope: patches of such objects; windows of sparse objects; windows finer than an element; other run lengths. */
+ *   Out of scope: windows of sparse objects; windows finer than an element; other run lengths.  (Patches of such objects: the next section.) */
 FSEHIP_API int FSEHIP_planes_merge_window_each_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_planes, const uint64_t* d_planeOffsets,
                                                       const size_t* d_planeSizes, const void* d_base, const uint8_t* d_transforms, const uint64_t* d_windows,
                                                       size_t nTensors, unsigned elemBytes, uint64_t dstCapacity, void* stream);
@@ -1489,6 +1489,53 @@ FSEHIP_API int FSEHIP_tensor_decompress_window_each_dbatch(void* d_dst, const ui
                                                            size_t maxTotalBlocks, void* d_planes, uint64_t planesCapacity, uint64_t* d_selFrameOffsets,
                                                            uint64_t* d_selOffsets, size_t* d_selResults, uint64_t* d_planeOffsets, size_t* d_planeSizes,
                                                            void* d_workspace, size_t workspaceBytes, void* stream);
+
+/* Patching tensors with a transform per tensor (planes_each.hip, planes_patch.hip): THE WRITE SIDE OF "windows of tensors with a transform per
+ * tensor" -- "patching segmented tensors" FOR OBJECTS WRITTEN BY FSEHIP_tensor_compress_seg_each_dbatch and, with all bytes FSEHIP_EST_PRED, by
+ * FSEHIP_tensor_compress_seg_pred_dbatch.  The tensors changed inside an element window each; only the segment frames that hold the windows are
+ * coded anew, under the transform the tensor was written with.  No frame byte, writer, segments kernel or splice changes: one more split.
+ *
+ *   Why the patch needs no lead.  PLAIN, XOR and SUB are element-wise.  PRED takes differences inside runs of 1 << FSEHIP_PRED_RUN_LOG = 1024
+ *     elements counted from the TENSOR's start, each run's first element predicted by 0.  A segment is 1 << segLog bytes of a plane with
+ *     segLog >= 10 + blockSizeId >= FSEHIP_PRED_RUN_LOG, so every segment starts on a run boundary; the patch stages WHOLE segments k0 .. k1 of
+ *     every plane, the sub-tensor that starts at byte k0 * seg * E ("patching segmented tensors"), a multiple of 1024 elements.  Runs -- and
+ *     chunks of 16 elements -- counted from the sub-tensor's start are therefore the tensor's own: no difference inside a selected segment
+ *     reads an element in front of it, none outside reads an element inside.  The planes of transform(sub-tensor) ARE segments k0 .. k1 of the
+ *     planes of transform(tensor), byte for byte, for all four transforms -- unlike the window READ, which may start inside a run.
+ *   The identity of "patching segmented tensors" carries over: for tensors `old` and `new` that differ inside the windows only, the patch of
+ *     FSEHIP_tensor_compress_seg_each_dbatch(old, T) with `new` IS FSEHIP_tensor_compress_seg_each_dbatch(new, T given): offsets, results,
+ *     codecs and every frame byte.  The transforms are GIVEN only: choosing again would change a tensor's transform and with it every one of
+ *     its frames, which is a full compress.
+ *
+ *   FSEHIP_planes_split_window_each_dbatch   the argument list of FSEHIP_planes_split_window_op_dbatch with d_transforms (nTensors bytes, an
+ *     input, always given) in place of deltaOp.  The staged bytes, d_stagePlaneOffsets and d_stageResults of tensor i are byte for byte those
+ *     of FSEHIP_planes_split_window_op_dbatch for FSEHIP_EST_PLAIN (d_base NULL), _XOR and _SUB; for _PRED they are segments k0 .. k1 of what
+ *     FSEHIP_planes_split_pred_dbatch writes for the whole tensor.  d_base (laid out as d_src) is read for XOR and SUB tensors only and may be
+ *     NULL.  Rule 1 of "patching segmented tensors" gains one cause: a transform byte above FSEHIP_EST_SUB (the estimate's 0xFF among them), or
+ *     XOR / SUB with d_base == NULL -- GENERIC in d_stageResults[i], every d_stagePlaneOffsets entry of the tensor min(T[i], stageCapacity),
+ *     nothing of it read or written.  Checked before the first launch: NULL d_transforms, the pointers, elemBytes, segLog outside 10 .. 30,
+ *     2^31 planes and the launch limit of FSEHIP_planes_split_window_op_dbatch.  elemBytes == 1 is staged through the same kernel.
+ *   FSEHIP_tensor_patch_window_each_dbatch   the argument list of FSEHIP_tensor_patch_window_op_dbatch with d_transforms in place of deltaOp:
+ *     the split above, FSEHIP_planes_segments_dbatch over the stage, FSEHIP_frame_compress_packed_dbatch or _packed_mixed_dbatch, then
+ *     FSEHIP_planes_splice_dbatch, all on `stream`: launches only, capturable.  Every argument check of every step runs before the first
+ *     launch; argument errors are hipErrorInvalidValue with nothing written, a NULL d_transforms among them.  No *_workspaceSize of its own:
+ *     the workspace is the writer's for nSelected frames, the scratch FSEHIP_planes_spliceScratchBound.  The four rules "a tensor is patched
+ *     WHOLE OR NOT AT ALL" hold as written; a refused transform is a rule-1 GENERIC for that tensor alone, which keeps all its old frames.
+ *   Out of scope: patches of sparse objects; choosing transforms inside a patch; patching in place; tensors that grow or shrink; windows finer
+ *     than a segment; another segLog for the same object. */
+FSEHIP_API int FSEHIP_planes_split_window_each_dbatch(void* d_stage, uint64_t* d_stagePlaneOffsets, size_t* d_stageResults, const void* d_src, const void* d_base,
+                                                      const uint8_t* d_transforms, const uint64_t* d_srcOffsets, const uint64_t* d_windows, const uint64_t* d_stageOffsets,
+                                                      size_t nTensors, unsigned elemBytes, unsigned segLog, uint64_t capacity, uint64_t stageCapacity, void* stream);
+FSEHIP_API int FSEHIP_tensor_patch_window_each_dbatch(void* d_out, uint64_t outCapacity, uint64_t* d_outOffsets, size_t* d_outResults, uint8_t* d_outCodecs,
+                                                      size_t* d_tensorResults, const void* d_frames, uint64_t framesCapacity, const uint64_t* d_frameOffsets,
+                                                      const size_t* d_frameResults, const uint8_t* d_codecs, const void* d_src, const void* d_base,
+                                                      const uint8_t* d_transforms, const uint64_t* d_srcOffsets, uint64_t capacity, const uint64_t* d_windows, size_t nTensors,
+                                                      unsigned elemBytes, const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, const uint64_t* d_selFirst,
+                                                      size_t nSelected, const uint64_t* d_stageOffsets, uint64_t stageCapacity, size_t maxTotalBlocks, unsigned blockSizeId,
+                                                      int codec, uint8_t* d_newCodecs, int policy, unsigned tolerancePermille, unsigned slotAlignLog, void* d_stage,
+                                                      uint64_t* d_stagePlaneOffsets, uint64_t* d_stageSegOffsets, size_t* d_stageResults, void* d_newFrames,
+                                                      uint64_t newCapacity, uint64_t* d_newOffsets, size_t* d_newResults, void* d_scratch, size_t scratchBytes,
+                                                      void* d_workspace, size_t workspaceBytes, void* stream);
 
 /* ---- FSE for 16-bit symbols (lib/fseU16.h:62-80, lib/fseU16.c) -- SURVEY 8(f) rank 4.  Alphabets of up to
  * FSEHIP_FSEU16_MAX_SYMBOL_VALUE + 1 symbols, table logs up to 13 (default 12), ONE tANS state per stream: a different format from
