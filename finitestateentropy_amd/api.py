@@ -74,21 +74,50 @@ class PredictedPlanes:
     planes").  `codec` is what codes them: 0 (FSE), 1 (Huff0) or an AutoCodec.  For tensors whose neighbours are close -- sorted indices,
     offsets, position ids, sampled fields, audio; weights get worse.  Opt-in, never chosen automatically.  The object written carries
     `predictor` ("prev"); decompress_tensors reads it.  Not combined with a base or with SparsePlanes; windows and patches of a
-    segmented object: decompress_tensor_windows_each and patch_tensor_windows_each."""
+    segmented object: decompress_tensor_windows_each and patch_tensor_windows_each.
+    `stride` (1 .. 8, include/fsehip.h "strided predicted planes"): the predecessor is the element `stride` elements in front -- the same
+    channel of interleaved data: 2 for stereo samples or complex pairs, 3 for RGB or xyz, 4 for RGBA or boxes -- and 0 for the first
+    `stride` elements of every run.  The object then carries the predictor "prev<stride>" ("prev3"); windows and patches of such an
+    object are refused."""
 
-    def __init__(self, codec=0):
+    def __init__(self, codec=0, stride=1):
         if not isinstance(codec, AutoCodec) and (isinstance(codec, (bool, SparsePlanes, PredictedPlanes)) or codec not in (0, 1)):
             raise ValueError("PredictedPlanes: codec %r, 0 (FSE), 1 (Huff0) or an AutoCodec is needed" % (codec,))
+        if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or not 1 <= stride <= PRED_MAX_STRIDE:
+            raise ValueError("PredictedPlanes: stride %r, an integer 1 .. %d is needed" % (stride, PRED_MAX_STRIDE))
         self.codec = codec if isinstance(codec, AutoCodec) else int(codec)
+        self.stride = int(stride)
+
+    @property
+    def predictor(self):
+        return predictor_name(self.stride)
 
     def __repr__(self):
-        return "PredictedPlanes(%r)" % (self.codec,)
+        return "PredictedPlanes(%r)" % (self.codec,) if self.stride == 1 else "PredictedPlanes(%r, stride=%d)" % (self.codec, self.stride)
 
     def __eq__(self, other):
-        return isinstance(other, PredictedPlanes) and other.codec == self.codec
+        return isinstance(other, PredictedPlanes) and other.codec == self.codec and other.stride == self.stride
 
     def __hash__(self):
-        return hash(("PredictedPlanes", self.codec))
+        return hash(("PredictedPlanes", self.codec, self.stride))
+
+
+PRED_MAX_STRIDE = 8                     # FSEHIP_PRED_MAX_STRIDE (include/fsehip.h)
+
+
+def predictor_name(stride):
+    """the `predictor` of an object written with PredictedPlanes(codec, stride): "prev" for stride 1, "prev<stride>" above"""
+    return "prev" if stride == 1 else "prev%d" % stride
+
+
+def predictor_stride(predictor, what):
+    """the stride behind an object's `predictor`: "prev" -> 1, "prev2" .. "prev8" -> 2 .. 8; anything else ("prev0", "prev1", "prev9",
+    "next") is a ValueError -- a reader that does not know a predictor refuses it and never decodes wrongly"""
+    if predictor == "prev":
+        return 1
+    if isinstance(predictor, str) and len(predictor) == 5 and predictor.startswith("prev") and predictor[4] in "2345678":
+        return int(predictor[4])
+    raise ValueError("%s: predictor %r; \"prev\" and \"prev2\" .. \"prev%d\" are the ones there are" % (what, predictor, PRED_MAX_STRIDE))
 
 
 DELTA_OPS = {"xor": 0, "sub": 1}        # FSEHIP_DELTA_XOR / FSEHIP_DELTA_SUB (include/fsehip.h)
@@ -2741,15 +2770,23 @@ def _planes_methods():
 
     # ---- predicted planes (csrc/planes_pred.hip; fsehip.h "predicted planes"): the planes of zigzag(element - the element in front of it)
     # in runs of 1024 elements, the difference fused into the split and the run sums into the merge
-    def planes_split_pred_dbatch(self, src, src_offsets, elem_bytes, capacity=None, planes=None, plane_offsets=None, results=None):
+    _NO_STRIDE = object()                                    # the _pred_ exports take no stride; the _pred_stride_ ones take 1 .. 8
+
+    def _stride(stride, what):
+        if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or not 1 <= stride <= PRED_MAX_STRIDE:
+            raise ValueError("%s: stride %r, an integer 1 .. %d is needed" % (what, stride, PRED_MAX_STRIDE))
+        return (C.c_uint(int(stride)),)
+
+    def planes_split_pred_dbatch(self, src, src_offsets, elem_bytes, capacity=None, planes=None, plane_offsets=None, results=None, _stride_arg=_NO_STRIDE):
         """planes_split_dbatch of the neighbour differences: the same layout, offsets and results.  For every elem_bytes, 1 included, `planes`
         is a buffer of its own and is written; src is only read."""
+        what = "planes_split_pred_dbatch" if _stride_arg is _NO_STRIDE else "planes_split_pred_stride_dbatch"
+        st = () if _stride_arg is _NO_STRIDE else _stride(_stride_arg, what)      # (the _pred_ export takes none)
         E = _elem(elem_bytes)
         self._flat(src, "src")
         soff, _ = self._offsets(src_offsets, src.device, False)
         n = soff.numel() - 1
         capacity = _room(self, src, capacity, "src")
-        what = "planes_split_pred_dbatch"
         g = None
         if planes is None:
             planes, g = self._dst(1, src.numel(), src.device)
@@ -2758,15 +2795,17 @@ def _planes_methods():
             raise ValueError("planes holds %d bytes, the capacity is %d" % (planes.numel(), capacity))
         poff = _i64(self, plane_offsets, n * E + 1, src.device, "plane_offsets")
         res = _i64(self, results, n, src.device, "results")
-        _check(self.lib.FSEHIP_planes_split_pred_dbatch(_ptr(planes), _ptr(poff), _ptr(res), _ptr(src), _ptr(soff), SZ(n), C.c_uint(E), C.c_uint64(capacity), _stream()),
-               what)
+        call = self.lib.FSEHIP_planes_split_pred_dbatch if _stride_arg is _NO_STRIDE else self.lib.FSEHIP_planes_split_pred_stride_dbatch
+        _check(call(_ptr(planes), _ptr(poff), _ptr(res), _ptr(src), _ptr(soff), SZ(n), C.c_uint(E), C.c_uint64(capacity), *st, _stream()), what)
         if g is not None:
             g.check(what)
         return planes, poff, res
 
-    def planes_merge_pred_dbatch(self, planes, plane_offsets, plane_sizes, dst_offsets, elem_bytes, dst=None, capacity=None, results=None):
+    def planes_merge_pred_dbatch(self, planes, plane_offsets, plane_sizes, dst_offsets, elem_bytes, dst=None, capacity=None, results=None, _stride_arg=_NO_STRIDE):
         """planes_merge_dbatch, every run of a rebuilt tensor summed back: the inverse of planes_split_pred_dbatch, with the plain merge's
         results and rules.  dst must not overlap planes."""
+        what = "planes_merge_pred_dbatch" if _stride_arg is _NO_STRIDE else "planes_merge_pred_stride_dbatch"
+        st = () if _stride_arg is _NO_STRIDE else _stride(_stride_arg, what)      # (the _pred_ export takes none)
         E = _elem(elem_bytes)
         self._flat(planes, "planes")
         doff, dhost = self._offsets(dst_offsets, planes.device, dst is None)
@@ -2775,15 +2814,15 @@ def _planes_methods():
         psz = _i64(self, plane_sizes, n * E, planes.device, "plane_sizes")
         dst, capacity, g = _dst_room(self, dst, capacity, dhost, planes.device)
         res = _i64(self, results, n, planes.device, "results")
-        what = "planes_merge_pred_dbatch"
-        _check(self.lib.FSEHIP_planes_merge_pred_dbatch(_ptr(dst), _ptr(doff), _ptr(res), _ptr(planes), _ptr(poff), _ptr(psz), SZ(n), C.c_uint(E), C.c_uint64(capacity),
-                                                        _stream()), what)
+        call = self.lib.FSEHIP_planes_merge_pred_dbatch if _stride_arg is _NO_STRIDE else self.lib.FSEHIP_planes_merge_pred_stride_dbatch
+        _check(call(_ptr(dst), _ptr(doff), _ptr(res), _ptr(planes), _ptr(poff), _ptr(psz), SZ(n), C.c_uint(E), C.c_uint64(capacity), *st, _stream()), what)
         if g is not None:
             g.check(what)
         return dst, res
 
     def _compress_pred(self, what, src, src_offsets, elem_bytes, segment_log, seg_first, n_segments, codec, codecs, block_size_id, capacity, dst, dst_capacity,
-                       max_total_blocks, align_log, frame_offsets, frame_results, tensor_results, planes, plane_offsets, seg_offsets, workspace):
+                       max_total_blocks, align_log, frame_offsets, frame_results, tensor_results, planes, plane_offsets, seg_offsets, workspace, stride=_NO_STRIDE):
+        st = () if stride is _NO_STRIDE else _stride(stride, what)               # (the _pred_ exports take none)
         E = _elem(elem_bytes)
         align_log = _align_log(align_log)
         seg = segment_log is not None
@@ -2814,11 +2853,13 @@ def _planes_methods():
         writer = (SZ(max_total_blocks), C.c_uint(block_size_id), C.c_int(0 if mixed else codec),
                   _ptr((codecs if codecs.numel() else codecs.new_zeros(1)) if mixed else None), C.c_int(CODECS_CHOOSE if choose else CODECS_GIVEN), C.c_uint(tol),
                   C.c_uint(align_log), _ptr(planes), _ptr(poff))
-        tail = (_ptr(workspace), SZ(workspace.numel()), _stream())
+        tail = (_ptr(workspace), SZ(workspace.numel()), *st, _stream())
         if seg:
-            _check(self.lib.FSEHIP_tensor_compress_seg_pred_dbatch(*head, _ptr(sf), SZ(nf), C.c_uint(L), *writer, _ptr(so), *tail), what)
+            call = self.lib.FSEHIP_tensor_compress_seg_pred_dbatch if stride is _NO_STRIDE else self.lib.FSEHIP_tensor_compress_seg_pred_stride_dbatch
+            _check(call(*head, _ptr(sf), SZ(nf), C.c_uint(L), *writer, _ptr(so), *tail), what)
         else:
-            _check(self.lib.FSEHIP_tensor_compress_pred_dbatch(*head, *writer, *tail), what)
+            call = self.lib.FSEHIP_tensor_compress_pred_dbatch if stride is _NO_STRIDE else self.lib.FSEHIP_tensor_compress_pred_stride_dbatch
+            _check(call(*head, *writer, *tail), what)
         _check_codecs(cgu, nf, what)
         if g is not None:
             g.check(what)
@@ -2844,7 +2885,8 @@ def _planes_methods():
                               workspace)
 
     def _decompress_pred(self, what, frames, frame_offsets, dst_offsets, elem_bytes, segment_log, seg_first, n_segments, dst, dst_capacity, max_total_blocks, planes,
-                         planes_capacity, seg_offsets, seg_results, plane_offsets, plane_sizes, workspace, results):
+                         planes_capacity, seg_offsets, seg_results, plane_offsets, plane_sizes, workspace, results, stride=_NO_STRIDE):
+        st = () if stride is _NO_STRIDE else _stride(stride, what)               # (the _pred_ exports take none)
         E = _elem(elem_bytes)
         seg = segment_log is not None
         L = _seg_log(segment_log) if seg else 0
@@ -2870,14 +2912,15 @@ def _planes_methods():
         res = _i64(self, results, n, frames.device, "results")
         workspace = _reader_workspace(self, workspace, nf, max_total_blocks, frames.device)
         head = (_ptr(dst), _ptr(doff), C.c_uint64(dst_capacity), _ptr(res), _ptr(frames), _ptr(foff), SZ(n), C.c_uint(E))
-        tail = (_ptr(poff), _ptr(psz), _ptr(workspace), SZ(workspace.numel()), _stream())
+        tail = (_ptr(poff), _ptr(psz), _ptr(workspace), SZ(workspace.numel()), *st, _stream())
         if seg:
             so = _i64(self, seg_offsets, nf + 1, frames.device, "seg_offsets")
             sres = _i64(self, seg_results, nf, frames.device, "seg_results")
-            _check(self.lib.FSEHIP_tensor_decompress_seg_pred_dbatch(*head, _ptr(sf), SZ(nf), C.c_uint(L), SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity),
-                                                                     _ptr(so), _ptr(sres), *tail), what)
+            call = self.lib.FSEHIP_tensor_decompress_seg_pred_dbatch if stride is _NO_STRIDE else self.lib.FSEHIP_tensor_decompress_seg_pred_stride_dbatch
+            _check(call(*head, _ptr(sf), SZ(nf), C.c_uint(L), SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity), _ptr(so), _ptr(sres), *tail), what)
         else:
-            _check(self.lib.FSEHIP_tensor_decompress_pred_dbatch(*head, SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity), *tail), what)
+            call = self.lib.FSEHIP_tensor_decompress_pred_dbatch if stride is _NO_STRIDE else self.lib.FSEHIP_tensor_decompress_pred_stride_dbatch
+            _check(call(*head, SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity), *tail), what)
         if g is not None:
             g.check(what)
         return dst, res
@@ -2899,6 +2942,49 @@ def _planes_methods():
 
     for f in (planes_split_pred_dbatch, planes_merge_pred_dbatch, tensor_compress_pred_dbatch, tensor_decompress_pred_dbatch, tensor_compress_seg_pred_dbatch,
               tensor_decompress_seg_pred_dbatch):
+        setattr(FseHip, f.__name__, f)
+
+    # ---- strided predicted planes (csrc/planes_stride.hip; fsehip.h "strided predicted planes"): the predecessor `stride` elements back, the
+    # same channel of interleaved data.  The six calls above with `stride` (1 .. 8, required) behind elem_bytes; stride 1 is those calls
+    def planes_split_pred_stride_dbatch(self, src, src_offsets, elem_bytes, stride, capacity=None, planes=None, plane_offsets=None, results=None):
+        """planes_split_pred_dbatch with the predecessor `stride` elements in front, 0 for the first `stride` elements of every run."""
+        return planes_split_pred_dbatch(self, src, src_offsets, elem_bytes, capacity, planes, plane_offsets, results, _stride_arg=stride)
+
+    def planes_merge_pred_stride_dbatch(self, planes, plane_offsets, plane_sizes, dst_offsets, elem_bytes, stride, dst=None, capacity=None, results=None):
+        """planes_merge_pred_dbatch, the `stride` interleaved chains of every run summed back: the inverse of planes_split_pred_stride_dbatch."""
+        return planes_merge_pred_dbatch(self, planes, plane_offsets, plane_sizes, dst_offsets, elem_bytes, dst, capacity, results, _stride_arg=stride)
+
+    def tensor_compress_pred_stride_dbatch(self, src, src_offsets, elem_bytes, stride, codec=0, codecs=None, block_size_id=5, capacity=None, dst=None,
+                                           dst_capacity=None, max_total_blocks=None, align_log=0, frame_offsets=None, frame_results=None, tensor_results=None,
+                                           planes=None, plane_offsets=None, workspace=None):
+        """tensor_compress_pred_dbatch over planes_split_pred_stride_dbatch.  The frames do not record the stride; the caller carries it."""
+        return _compress_pred(self, "tensor_compress_pred_stride_dbatch", src, src_offsets, elem_bytes, None, None, None, codec, codecs, block_size_id, capacity, dst,
+                              dst_capacity, max_total_blocks, align_log, frame_offsets, frame_results, tensor_results, planes, plane_offsets, None, workspace, stride)
+
+    def tensor_compress_seg_pred_stride_dbatch(self, src, src_offsets, elem_bytes, stride, segment_log, seg_first=None, n_segments=None, codec=0, codecs=None,
+                                               block_size_id=5, capacity=None, dst=None, dst_capacity=None, max_total_blocks=None, align_log=0, frame_offsets=None,
+                                               frame_results=None, tensor_results=None, planes=None, plane_offsets=None, seg_offsets=None, workspace=None):
+        """tensor_compress_seg_pred_dbatch over planes_split_pred_stride_dbatch: runs stay 1024 elements whatever the stride, a segment starts on one."""
+        return _compress_pred(self, "tensor_compress_seg_pred_stride_dbatch", src, src_offsets, elem_bytes, segment_log, seg_first, n_segments, codec, codecs,
+                              block_size_id, capacity, dst, dst_capacity, max_total_blocks, align_log, frame_offsets, frame_results, tensor_results, planes, plane_offsets,
+                              seg_offsets, workspace, stride)
+
+    def tensor_decompress_pred_stride_dbatch(self, frames, frame_offsets, dst_offsets, elem_bytes, stride, dst=None, dst_capacity=None, max_total_blocks=None,
+                                             planes=None, planes_capacity=None, plane_offsets=None, plane_results=None, workspace=None, results=None):
+        """tensor_decompress_pred_dbatch of frames that tensor_compress_pred_stride_dbatch wrote with the same stride."""
+        return _decompress_pred(self, "tensor_decompress_pred_stride_dbatch", frames, frame_offsets, dst_offsets, elem_bytes, None, None, None, dst, dst_capacity,
+                                max_total_blocks, planes, planes_capacity, None, None, plane_offsets, plane_results, workspace, results, stride)
+
+    def tensor_decompress_seg_pred_stride_dbatch(self, frames, frame_offsets, dst_offsets, elem_bytes, stride, segment_log, seg_first=None, n_segments=None, dst=None,
+                                                 dst_capacity=None, max_total_blocks=None, planes=None, planes_capacity=None, seg_offsets=None, seg_results=None,
+                                                 plane_offsets=None, plane_sizes=None, workspace=None, results=None):
+        """tensor_decompress_seg_pred_dbatch of frames that tensor_compress_seg_pred_stride_dbatch wrote with the same stride."""
+        return _decompress_pred(self, "tensor_decompress_seg_pred_stride_dbatch", frames, frame_offsets, dst_offsets, elem_bytes, segment_log, seg_first, n_segments,
+                                dst, dst_capacity, max_total_blocks, planes, planes_capacity, seg_offsets, seg_results, plane_offsets, plane_sizes, workspace, results,
+                                stride)
+
+    for f in (planes_split_pred_stride_dbatch, planes_merge_pred_stride_dbatch, tensor_compress_pred_stride_dbatch, tensor_decompress_pred_stride_dbatch,
+              tensor_compress_seg_pred_stride_dbatch, tensor_decompress_seg_pred_stride_dbatch):
         setattr(FseHip, f.__name__, f)
 
     # ---- tensor digests and checked deltas (csrc/planes_digest.hip; fsehip.h "tensor digests and checked deltas"): a 64-bit digest per
@@ -3403,7 +3489,10 @@ def _planes_methods():
         if isinstance(codec, SparsePlanes):
             return {"sparse": _codec_to_json(codec.codec), "permille": codec.permille}
         if isinstance(codec, PredictedPlanes):
-            return {"pred": _codec_to_json(codec.codec)}
+            j = {"pred": _codec_to_json(codec.codec)}
+            if codec.stride != 1:
+                j["stride"] = codec.stride
+            return j
         if isinstance(codec, AutoCodec):
             return {"auto": codec.tolerance_permille}
         return int(codec)
@@ -3412,7 +3501,7 @@ def _planes_methods():
         if isinstance(j, dict) and "sparse" in j:
             return SparsePlanes(_codec_from_json(j["sparse"]), j["permille"])
         if isinstance(j, dict) and "pred" in j:
-            return PredictedPlanes(_codec_from_json(j["pred"]))
+            return PredictedPlanes(_codec_from_json(j["pred"]), j.get("stride", 1))
         if isinstance(j, dict) and "auto" in j:
             return AutoCodec(j["auto"])
         return int(j)
@@ -3549,7 +3638,7 @@ def _planes_methods():
         if transforms is not None:
             obj.transforms = transforms
         return _segmented(obj, int(first.segLog) if first.segLog else None, "sub" if delta and first.deltaOp else "xor",
-                          int(first.sparsePermille) if first.flags & ARCHIVE_SPARSE else None, digests, "prev" if isinstance(codec, PredictedPlanes) else None)
+                          int(first.sparsePermille) if first.flags & ARCHIVE_SPARSE else None, digests, codec.predictor if isinstance(codec, PredictedPlanes) else None)
 
     def save_tensors(self, obj, path):
         """archive_tensors(obj) written to the file `path` as it lies -> the number of bytes"""
@@ -3620,7 +3709,8 @@ def _planes_methods():
         AutoCodec) -- or a CompressedTensors an AutoCodec call returned for tensors of the same dtypes and shapes (ValueError otherwise, before
         any launch): its codecs are given again, nothing is tried twice.  An object compress_tensors_segmented wrote is refused here
         (ValueError): its codecs are per segment.  A SparsePlanes or a PredictedPlanes around 0, 1 or an AutoCodec: sparse contents, or the
-        planes of the neighbour differences (the object's `predictor` is "prev"; ValueError with a base, before any launch).  For tensors
+        planes of the neighbour differences (the object's `predictor` is "prev", or "prev<S>" for PredictedPlanes(codec, stride=S), the
+        predecessor S elements back for interleaved channels; ValueError with a base, before any launch).  For tensors
         above a few MiB use compress_tensors_segmented."""
         return _compress_tensors(self, tensors, codec, block_size_id, base, None)
 
@@ -3680,7 +3770,7 @@ def _planes_methods():
         if isinstance(codec, PredictedPlanes):              # the planes' codec inside; the differences need no base and take none
             if base is not None:
                 raise ValueError("compress_tensors: PredictedPlanes predicts from the tensor itself, a base does not go with it")
-            pred, codec = "prev", codec.codec
+            pred, stride, codec = codec.predictor, codec.stride, codec.codec
         if not tensors:
             if base is not None and len(list(base)):
                 raise ValueError("base: tensors for none")
@@ -3705,10 +3795,17 @@ def _planes_methods():
                 given = None if earlier is None else [g for g in earlier.groups if g["elem_bytes"] == E][0]["codecs"]
                 if segment_log is not None:
                     sfirst = self.planes_segment_first(np.diff(offs.astype(np.int64)), E, segment_log)
-                    dst, foff, fres, tres, codecs = self.tensor_compress_seg_pred_dbatch(src, offs, E, segment_log, sfirst, codec=codec, codecs=given,
-                                                                                         block_size_id=block_size_id)
-                else:
+                    if stride == 1:
+                        dst, foff, fres, tres, codecs = self.tensor_compress_seg_pred_dbatch(src, offs, E, segment_log, sfirst, codec=codec, codecs=given,
+                                                                                             block_size_id=block_size_id)
+                    else:
+                        dst, foff, fres, tres, codecs = self.tensor_compress_seg_pred_stride_dbatch(src, offs, E, stride, segment_log, sfirst, codec=codec,
+                                                                                                    codecs=given, block_size_id=block_size_id)
+                elif stride == 1:
                     dst, foff, fres, tres, codecs = self.tensor_compress_pred_dbatch(src, offs, E, codec=codec, codecs=given, block_size_id=block_size_id)
+                else:
+                    dst, foff, fres, tres, codecs = self.tensor_compress_pred_stride_dbatch(src, offs, E, stride, codec=codec, codecs=given,
+                                                                                            block_size_id=block_size_id)
             elif sparse is not None:
                 given = None if earlier is None else [g for g in earlier.groups if g["elem_bytes"] == E][0]["codecs"]
                 if segment_log is not None:
@@ -3793,8 +3890,7 @@ def _planes_methods():
         if getattr(obj, "transforms", None) is not None:     # compress_tensors_each's: one object, a transform per tensor
             return _decompress_each_obj(self, obj, base)
         base, op = _read_base(obj, base, "decompress_tensors")
-        if getattr(obj, "predictor", None) not in (None, "prev"):
-            raise ValueError("decompress_tensors: predictor %r, \"prev\" is the one there is" % (obj.predictor,))
+        stride = None if getattr(obj, "predictor", None) is None else predictor_stride(obj.predictor, "decompress_tensors")
         braw = None if base is None else _bases(base, obj.dtypes, obj.shapes, obj.device)
         checked = _gate_groups(self, obj, braw) if getattr(obj, "base_digests", None) is not None else None
         out = [None] * len(obj.dtypes)
@@ -3804,11 +3900,16 @@ def _planes_methods():
             blocks = self.planes_block_bound(sum(sizes), len(sizes), E, obj.block_size_id)
             seg_log = getattr(obj, "segment_log", None)
             held, foff = checked[gi] if checked is not None else (None, g["frame_offsets"])     # (checked: the copy that was digested, the gated offsets)
-            if getattr(obj, "predictor", None) is not None:
+            if stride == 1:
                 if seg_log is not None:
                     dst, res = self.tensor_decompress_seg_pred_dbatch(g["frames"], foff, offs, E, seg_log, g["seg_first"], max_total_blocks=blocks)
                 else:
                     dst, res = self.tensor_decompress_pred_dbatch(g["frames"], foff, offs, E, max_total_blocks=blocks)
+            elif stride is not None:
+                if seg_log is not None:
+                    dst, res = self.tensor_decompress_seg_pred_stride_dbatch(g["frames"], foff, offs, E, stride, seg_log, g["seg_first"], max_total_blocks=blocks)
+                else:
+                    dst, res = self.tensor_decompress_pred_stride_dbatch(g["frames"], foff, offs, E, stride, max_total_blocks=blocks)
             elif getattr(obj, "sparse_permille", None) is not None:
                 dst = None if braw is None else _base_copy(braw, g, obj.device, held)
                 if seg_log is not None:

@@ -357,17 +357,23 @@ size_t sparse_workspace(u64 capacity, size_t nUnits);
 bool bad_sparse(u64 capacity, size_t nUnits, const void* d_workspace, size_t workspaceBytes);
 hipError_t launch_sparse_pack(u8* contents, u64* contentOff, const u8* units, const u64* unitOff, size_t nUnits, u64 capacity, unsigned permille, u8* ws, hipStream_t s);
 // the compress path of all compress composites (planes.hip): argument checks, (delta) split, segments where d_segFirst is given, pack where
-// `sparse` is given, writer.  `pred` (no base with it): the predicted split in place of the plain one
+// `sparse` is given, writer.  `pred` != 0 (no base with it): the predicted split of that stride in place of the plain one
 int planes_compress(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults, const void* d_src, const void* d_base,
                     unsigned deltaOp, const uint64_t* d_srcOffsets, size_t nTensors, unsigned E, uint64_t capacity, const uint64_t* d_segFirst, size_t nSegments,
                     unsigned segLog, void* d_planes, uint64_t* d_planeOffsets, uint64_t* d_segOffsets, const PlWriter& w, void* stream, const PlSparse* sparse = nullptr,
-                    bool pred = false);
+                    unsigned pred = 0);
 // predicted planes (planes_pred.hip; fsehip.h, "predicted planes"): the split on zigzag(element - the element in front of it), every E, and
 // the merge that sums the runs back.  launch_planes_verdicts (planes.hip): the merge's first step by itself, a result per tensor
 hipError_t launch_planes_split_pred(u8* planes, u64* planeOff, size_t* tensorRes, const u8* src, const u64* srcOff, size_t nTensors, unsigned E, u64 capacity,
                                     hipStream_t s);
 hipError_t launch_planes_merge_pred(u8* dst, const u64* dstOff, size_t* results, const u8* planes, const u64* planeOff, const size_t* planeSizes, size_t nTensors,
                                     unsigned E, u64 dstCapacity, hipStream_t s);
+// strided predicted planes (planes_stride.hip; fsehip.h, "strided predicted planes"): the predecessor `stride` elements back, 1 <= stride <=
+// FSEHIP_PRED_MAX_STRIDE; stride 1 launches the two above
+hipError_t launch_planes_split_pred_stride(u8* planes, u64* planeOff, size_t* tensorRes, const u8* src, const u64* srcOff, size_t nTensors, unsigned E, u64 capacity,
+                                           unsigned stride, hipStream_t s);
+hipError_t launch_planes_merge_pred_stride(u8* dst, const u64* dstOff, size_t* results, const u8* planes, const u64* planeOff, const size_t* planeSizes, size_t nTensors,
+                                           unsigned E, u64 dstCapacity, unsigned stride, hipStream_t s);
 hipError_t launch_planes_verdicts(size_t* results, const u64* dstOff, const size_t* planeSizes, size_t nTensors, unsigned E, u64 dstCapacity, hipStream_t s);
 // a transform per tensor (planes_each.hip; fsehip.h, "a transform per tensor"): the split and the merge that read tensor i's transform, an
 // FSEHIP_EST_* id, from transforms[i]; base null: an XOR or SUB tensor is refused.  The C calls are in capi_each.hip

@@ -233,11 +233,11 @@ hipError_t launch_planes_merge(u8* dst, const u64* dstOff, size_t* results, cons
 // front of the first launch (fsehip.h: what the guarantee covers), the split (d_base given: the split of the delta by deltaOp), the segments kernel where
 // d_segFirst is given, then the packed writer -- a codec per frame where w.d_codecs is given -- over the planes or their segments, read
 // from d_src itself where the split moved nothing.  `sparse` given (planes_sparse.hip): pack stands between the units and the writer, which
-// then reads the contents; pack's workspace is the head of the caller's, the writer's the rest.  `pred` (planes_pred.hip): the predicted
-// split in place of the plain one, which moves every element size
+// then reads the contents; pack's workspace is the head of the caller's, the writer's the rest.  `pred` != 0 (planes_stride.hip): the predicted
+// split of that stride in place of the plain one, which moves every element size
 int planes_compress(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults, const void* d_src, const void* d_base,
                     unsigned deltaOp, const uint64_t* d_srcOffsets, size_t nTensors, unsigned E, uint64_t capacity, const uint64_t* d_segFirst, size_t nSegments,
-                    unsigned segLog, void* d_planes, uint64_t* d_planeOffsets, uint64_t* d_segOffsets, const PlWriter& writer, void* stream, const PlSparse* sparse, bool pred)
+                    unsigned segLog, void* d_planes, uint64_t* d_planeOffsets, uint64_t* d_segOffsets, const PlWriter& writer, void* stream, const PlSparse* sparse, unsigned pred)
 {
     if (bad_op(deltaOp) || (pred && d_base)) return (int)hipErrorInvalidValue;
     if (d_segFirst ? bad_seg(segLog, writer.blockSizeId) || bad_counts(nTensors, E, nSegments) : bad_tensors(nTensors, E)) return (int)hipErrorInvalidValue;
@@ -252,7 +252,8 @@ int planes_compress(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets,
     }
     if (bad_grid(capacity, nTensors) || bad_writer(w, nFrames)) return (int)hipErrorInvalidValue;
     const hipStream_t s = (hipStream_t)stream;
-    hipError_t e = pred ? launch_planes_split_pred((u8*)d_planes, (u64*)d_planeOffsets, d_tensorResults, (const u8*)d_src, (const u64*)d_srcOffsets, nTensors, E, capacity, s)
+    hipError_t e = pred ? launch_planes_split_pred_stride((u8*)d_planes, (u64*)d_planeOffsets, d_tensorResults, (const u8*)d_src, (const u64*)d_srcOffsets, nTensors, E, capacity,
+                                                             pred, s)
                         : launch_planes_split((u8*)d_planes, (u64*)d_planeOffsets, d_tensorResults, (const u8*)d_src, (const u8*)d_base, deltaOp, (const u64*)d_srcOffsets,
                                               nTensors, E, capacity, s);
     if (e == hipSuccess && d_segFirst)

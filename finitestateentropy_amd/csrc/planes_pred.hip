@@ -10,6 +10,7 @@
 //   FSEHIP_tensor_compress_seg_pred_dbatch   : the predicted split -> the segments kernel -> the writer    (the same)
 //   FSEHIP_tensor_decompress_pred_dbatch     : the packed reader into the planes buffer -> the predicted merge
 //   FSEHIP_tensor_decompress_seg_pred_dbatch : the packed reader -> the fold (planes_seg.hip) -> the predicted merge
+// each of them the _pred_stride_ call of planes_stride.hip with stride 1, which launches the kernels of this file.
 //
 // THE SPLIT is k_planes_split of planes.hip -- its tile mapping over the flat byte axis, its chunks of 16 elements per lane, its E loads,
 // byte shuffle and E stores -- with the chunks counted from the TENSOR's start (a chunk begins at an element index that is a multiple of
@@ -141,22 +142,18 @@ hipError_t launch_planes_merge_pred(u8* dst, const u64* dstOff, size_t* results,
     return hipGetLastError();
 }
 
+// The six C calls are those of planes_stride.hip with stride 1, which launches the kernels above: one set of argument checks, one chain of
+// launches per call
 extern "C" int FSEHIP_planes_split_pred_dbatch(void* d_planes, uint64_t* d_planeOffsets, size_t* d_tensorResults, const void* d_src, const uint64_t* d_srcOffsets,
                                                size_t nTensors, unsigned elemBytes, uint64_t capacity, void* stream)
 {
-    if (bad_elem(elemBytes) || !d_planes || !d_planeOffsets || !d_tensorResults || !d_src || !d_srcOffsets) return (int)hipErrorInvalidValue;
-    if (bad_tensors(nTensors, elemBytes) || bad_grid(capacity, nTensors)) return (int)hipErrorInvalidValue;
-    return (int)launch_planes_split_pred((u8*)d_planes, (u64*)d_planeOffsets, d_tensorResults, (const u8*)d_src, (const u64*)d_srcOffsets, nTensors, elemBytes, capacity,
-                                         (hipStream_t)stream);
+    return FSEHIP_planes_split_pred_stride_dbatch(d_planes, d_planeOffsets, d_tensorResults, d_src, d_srcOffsets, nTensors, elemBytes, capacity, 1, stream);
 }
 
 extern "C" int FSEHIP_planes_merge_pred_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_planes, const uint64_t* d_planeOffsets,
                                                const size_t* d_planeSizes, size_t nTensors, unsigned elemBytes, uint64_t dstCapacity, void* stream)
 {
-    if (bad_elem(elemBytes) || !d_dst || !d_dstOffsets || !d_results || !d_planes || !d_planeOffsets || !d_planeSizes) return (int)hipErrorInvalidValue;
-    if (bad_tensors(nTensors, elemBytes) || bad_grid(dstCapacity, nTensors)) return (int)hipErrorInvalidValue;
-    return (int)launch_planes_merge_pred((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeSizes, nTensors,
-                                         elemBytes, dstCapacity, (hipStream_t)stream);
+    return FSEHIP_planes_merge_pred_stride_dbatch(d_dst, d_dstOffsets, d_results, d_planes, d_planeOffsets, d_planeSizes, nTensors, elemBytes, dstCapacity, 1, stream);
 }
 
 extern "C" int FSEHIP_tensor_compress_pred_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
@@ -164,11 +161,9 @@ extern "C" int FSEHIP_tensor_compress_pred_dbatch(void* d_dst, uint64_t dstCapac
                                                   size_t maxTotalBlocks, unsigned blockSizeId, int codec, uint8_t* d_codecs, int policy, unsigned tolerancePermille,
                                                   unsigned slotAlignLog, void* d_planes, uint64_t* d_planeOffsets, void* d_workspace, size_t workspaceBytes, void* stream)
 {
-    if (bad_elem(elemBytes) || !d_frameOffsets || !d_frameResults || !d_tensorResults || !d_src || !d_srcOffsets || !d_planeOffsets || !d_planes)
-        return (int)hipErrorInvalidValue;
-    return planes_compress(d_dst, dstCapacity, d_frameOffsets, d_frameResults, d_tensorResults, d_src, nullptr, 0, d_srcOffsets, nTensors, elemBytes, capacity, nullptr, 0, 0,
-                           d_planes, d_planeOffsets, nullptr,
-                           PlWriter{ maxTotalBlocks, blockSizeId, codec, d_codecs, policy, tolerancePermille, slotAlignLog, d_workspace, workspaceBytes }, stream, nullptr, true);
+    return FSEHIP_tensor_compress_pred_stride_dbatch(d_dst, dstCapacity, d_frameOffsets, d_frameResults, d_tensorResults, d_src, d_srcOffsets, nTensors, elemBytes, capacity,
+                                                     maxTotalBlocks, blockSizeId, codec, d_codecs, policy, tolerancePermille, slotAlignLog, d_planes, d_planeOffsets,
+                                                     d_workspace, workspaceBytes, 1, stream);
 }
 
 extern "C" int FSEHIP_tensor_compress_seg_pred_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
@@ -177,29 +172,18 @@ extern "C" int FSEHIP_tensor_compress_seg_pred_dbatch(void* d_dst, uint64_t dstC
                                                       int codec, uint8_t* d_codecs, int policy, unsigned tolerancePermille, unsigned slotAlignLog, void* d_planes,
                                                       uint64_t* d_planeOffsets, uint64_t* d_segOffsets, void* d_workspace, size_t workspaceBytes, void* stream)
 {
-    if (bad_elem(elemBytes) || !d_frameOffsets || !d_frameResults || !d_tensorResults || !d_src || !d_srcOffsets || !d_segFirst || !d_planeOffsets || !d_segOffsets ||
-        !d_planes)
-        return (int)hipErrorInvalidValue;
-    return planes_compress(d_dst, dstCapacity, d_frameOffsets, d_frameResults, d_tensorResults, d_src, nullptr, 0, d_srcOffsets, nTensors, elemBytes, capacity, d_segFirst,
-                           nSegments, segLog, d_planes, d_planeOffsets, d_segOffsets,
-                           PlWriter{ maxTotalBlocks, blockSizeId, codec, d_codecs, policy, tolerancePermille, slotAlignLog, d_workspace, workspaceBytes }, stream, nullptr, true);
+    return FSEHIP_tensor_compress_seg_pred_stride_dbatch(d_dst, dstCapacity, d_frameOffsets, d_frameResults, d_tensorResults, d_src, d_srcOffsets, nTensors, elemBytes,
+                                                         capacity, d_segFirst, nSegments, segLog, maxTotalBlocks, blockSizeId, codec, d_codecs, policy, tolerancePermille,
+                                                         slotAlignLog, d_planes, d_planeOffsets, d_segOffsets, d_workspace, workspaceBytes, 1, stream);
 }
 
-// the argument checks of both steps in front of the first launch
 extern "C" int FSEHIP_tensor_decompress_pred_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, size_t* d_results, const void* d_frames,
                                                     const uint64_t* d_frameOffsets, size_t nTensors, unsigned elemBytes, size_t maxTotalBlocks, void* d_planes,
                                                     uint64_t planesCapacity, uint64_t* d_planeOffsets, size_t* d_planeResults, void* d_workspace, size_t workspaceBytes,
                                                     void* stream)
 {
-    if (bad_elem(elemBytes) || !d_dst || !d_dstOffsets || !d_results || !d_frames || !d_frameOffsets || !d_planes || !d_planeOffsets || !d_planeResults)
-        return (int)hipErrorInvalidValue;
-    if (bad_tensors(nTensors, elemBytes) || bad_grid(dstCapacity, nTensors) || bad_reader(d_workspace, workspaceBytes, nTensors * elemBytes, maxTotalBlocks))
-        return (int)hipErrorInvalidValue;
-    const int r = FSEHIP_frame_decompress_packed_dbatch(d_planes, (size_t)planesCapacity, d_planeOffsets, d_planeResults, d_frames, d_frameOffsets, nTensors * elemBytes,
-                                                        maxTotalBlocks, 0, d_workspace, workspaceBytes, stream);
-    if (r != 0) return r;
-    return (int)launch_planes_merge_pred((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeResults, nTensors,
-                                         elemBytes, dstCapacity, (hipStream_t)stream);
+    return FSEHIP_tensor_decompress_pred_stride_dbatch(d_dst, d_dstOffsets, dstCapacity, d_results, d_frames, d_frameOffsets, nTensors, elemBytes, maxTotalBlocks, d_planes,
+                                                       planesCapacity, d_planeOffsets, d_planeResults, d_workspace, workspaceBytes, 1, stream);
 }
 
 extern "C" int FSEHIP_tensor_decompress_seg_pred_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, size_t* d_results, const void* d_frames,
@@ -208,17 +192,7 @@ extern "C" int FSEHIP_tensor_decompress_seg_pred_dbatch(void* d_dst, const uint6
                                                         uint64_t* d_segOffsets, size_t* d_segResults, uint64_t* d_planeOffsets, size_t* d_planeSizes, void* d_workspace,
                                                         size_t workspaceBytes, void* stream)
 {
-    if (bad_elem(elemBytes) || !d_dst || !d_dstOffsets || !d_results || !d_frames || !d_frameOffsets || !d_segFirst || !d_planes || !d_segOffsets || !d_segResults ||
-        !d_planeOffsets || !d_planeSizes)
-        return (int)hipErrorInvalidValue;
-    if (bad_seg(segLog, 0) || bad_counts(nTensors, elemBytes, nSegments) || bad_grid(dstCapacity, nTensors) || bad_reader(d_workspace, workspaceBytes, nSegments, maxTotalBlocks))
-        return (int)hipErrorInvalidValue;
-    const int r = FSEHIP_frame_decompress_packed_dbatch(d_planes, (size_t)planesCapacity, d_segOffsets, d_segResults, d_frames, d_frameOffsets, nSegments, maxTotalBlocks, 0,
-                                                        d_workspace, workspaceBytes, stream);
-    if (r != 0) return r;
-    const int f = FSEHIP_planes_fold_segments_dbatch(d_planeOffsets, d_planeSizes, d_segOffsets, d_segResults, d_segFirst, (size_t)nTensors * elemBytes, nSegments, segLog,
-                                                     stream);
-    if (f != 0) return f;
-    return (int)launch_planes_merge_pred((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeSizes, nTensors,
-                                         elemBytes, dstCapacity, (hipStream_t)stream);
+    return FSEHIP_tensor_decompress_seg_pred_stride_dbatch(d_dst, d_dstOffsets, dstCapacity, d_results, d_frames, d_frameOffsets, nTensors, elemBytes, d_segFirst, nSegments,
+                                                           segLog, maxTotalBlocks, d_planes, planesCapacity, d_segOffsets, d_segResults, d_planeOffsets, d_planeSizes,
+                                                           d_workspace, workspaceBytes, 1, stream);
 }

@@ -1286,7 +1286,7 @@ FSEHIP_API int FSEHIP_archive_open_dbatch(uint64_t* d_srcOffsets, uint64_t* d_fr
  *     and deltaOp.
  *   All six: launches only (capturable); every argument error is hipErrorInvalidValue before any device call, with nothing written;
  *   workspaces are the writers' and readers' own.
- *   Out of scope: strides other than 1 (interleaved channels); higher-order or float-aware predictors; prediction combined with a base or
+ *   Out of scope: (strides 2 .. 8, interleaved channels: "strided predicted planes" below); higher-order or float-aware predictors; prediction combined with a base or
  *   with sparse planes; (windows and patches of predicted tensors: "windows of" and "patching tensors with a transform per tensor" below); a record of the predictor in frames or in the archive head. */
 #define FSEHIP_PRED_RUN_LOG 10
 FSEHIP_API int FSEHIP_planes_split_pred_dbatch(void* d_planes, uint64_t* d_planeOffsets, size_t* d_tensorResults, const void* d_src, const uint64_t* d_srcOffsets,
@@ -1312,6 +1312,58 @@ FSEHIP_API int FSEHIP_tensor_decompress_seg_pred_dbatch(void* d_dst, const uint6
                                                         size_t nSegments, unsigned segLog, size_t maxTotalBlocks, void* d_planes, uint64_t planesCapacity,
                                                         uint64_t* d_segOffsets, size_t* d_segResults, uint64_t* d_planeOffsets, size_t* d_planeSizes, void* d_workspace,
                                                         size_t workspaceBytes, void* stream);
+
+/* Strided predicted planes (planes_stride.hip): NEIGHBOUR DELTA ACROSS INTERLEAVED CHANNELS.  In stereo int16 audio, RGB / RGBA uint8
+ * pixels, [N, 3] coordinates, (x, y, w, h) boxes or complex64 seen as pairs of float32 the element in front of an element belongs to another
+ * channel: its difference is as wide as the values, and the predicted planes above compress worse than the plain ones.  These calls take the
+ * predecessor S elements back, the same channel.  Nothing in a frame changes: ordinary .fse frames of the planes of z, and the caller carries
+ * the stride as it carries the predictor.
+ *
+ *   The transform (normative; a numpy model in tests/planes_stride_corpus.py).  For a tensor of n bytes and elemBytes E in {1, 2, 4, 8}:
+ *   W = 8 E, m = floor(n / E) elements t[0 .. m), little-endian unsigned integers, R = 1 << FSEHIP_PRED_RUN_LOG = 1024 elements, and a
+ *   stride S, 1 <= S <= FSEHIP_PRED_MAX_STRIDE = 8.
+ *     forward:  p[j] = 0 where (j mod R) < S, else t[j - S];  z[j] = zigzag((t[j] - p[j]) mod 2^W), the zigzag of "arithmetic tensor deltas"
+ *     inverse:  d[j] = unzigzag(z[j]);  t[j] = the sum of d[k] over k = j, j - S, j - 2 S, .. while k >= R floor(j / R), mod 2^W
+ *   The trailing n mod E bytes pass unchanged.  A tensor of fewer than S elements is zigzag(t).  S = 1 is exactly "predicted planes".  Runs
+ *   stay 1024 elements counted from the tensor's start whatever S is, and every plane segment still starts on a run (segLog >= 10), so
+ *   segmented frames need no rule of their own; S of every 1024 elements are coded without a predecessor, the price of that independence.
+ *   The chain an element belongs to is (j mod R) mod S -- not j mod S: 1024 mod S != 0 for S = 3, 5, 6, 7 -- it starts again at every run,
+ *   and each of the first S elements of a run is its own chain head.
+ *
+ *   The six calls are the _pred_ calls they are named after with `stride` directly in front of `stream`: offsets, results, refusals and
+ *   the rules for what is written are those.  stride == 0 or stride > FSEHIP_PRED_MAX_STRIDE: hipErrorInvalidValue before any launch, nothing
+ *   written.  stride == 1 launches the kernels of the _pred_ calls (which are these calls with stride 1).  The split reads the S elements in
+ *   front of a chunk of 16 where it read one; the merge sums S chains per run in one round of one wave: an in-lane recurrence, S wave
+ *   scans of the lanes' per-chain totals, no LDS, no workspace, nothing crosses a workgroup.  Launches only (capturable); workspaces are the
+ *   writers' and readers' own.
+ *   Out of scope: strides above 8 (a row-above or 2-D predictor needs strides far beyond a run); a stride per tensor; strides in the
+ *   estimate and in "a transform per tensor" (their PRED is stride 1); windows and patches of strided objects; prediction combined with a
+ *   base or with sparse planes; a record of the stride in frames or in the archive head. */
+#define FSEHIP_PRED_MAX_STRIDE 8
+FSEHIP_API int FSEHIP_planes_split_pred_stride_dbatch(void* d_planes, uint64_t* d_planeOffsets, size_t* d_tensorResults, const void* d_src, const uint64_t* d_srcOffsets,
+                                                      size_t nTensors, unsigned elemBytes, uint64_t capacity, unsigned stride, void* stream);
+FSEHIP_API int FSEHIP_planes_merge_pred_stride_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_planes, const uint64_t* d_planeOffsets,
+                                                      const size_t* d_planeSizes, size_t nTensors, unsigned elemBytes, uint64_t dstCapacity, unsigned stride, void* stream);
+FSEHIP_API int FSEHIP_tensor_compress_pred_stride_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
+                                                         const void* d_src, const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes, uint64_t capacity,
+                                                         size_t maxTotalBlocks, unsigned blockSizeId, int codec, uint8_t* d_codecs, int policy,
+                                                         unsigned tolerancePermille, unsigned slotAlignLog, void* d_planes, uint64_t* d_planeOffsets, void* d_workspace,
+                                                         size_t workspaceBytes, unsigned stride, void* stream);
+FSEHIP_API int FSEHIP_tensor_decompress_pred_stride_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, size_t* d_results, const void* d_frames,
+                                                           const uint64_t* d_frameOffsets, size_t nTensors, unsigned elemBytes, size_t maxTotalBlocks, void* d_planes,
+                                                           uint64_t planesCapacity, uint64_t* d_planeOffsets, size_t* d_planeResults, void* d_workspace,
+                                                           size_t workspaceBytes, unsigned stride, void* stream);
+FSEHIP_API int FSEHIP_tensor_compress_seg_pred_stride_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
+                                                             const void* d_src, const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes, uint64_t capacity,
+                                                             const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, size_t maxTotalBlocks, unsigned blockSizeId,
+                                                             int codec, uint8_t* d_codecs, int policy, unsigned tolerancePermille, unsigned slotAlignLog, void* d_planes,
+                                                             uint64_t* d_planeOffsets, uint64_t* d_segOffsets, void* d_workspace, size_t workspaceBytes, unsigned stride,
+                                                             void* stream);
+FSEHIP_API int FSEHIP_tensor_decompress_seg_pred_stride_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, size_t* d_results, const void* d_frames,
+                                                               const uint64_t* d_frameOffsets, size_t nTensors, unsigned elemBytes, const uint64_t* d_segFirst,
+                                                               size_t nSegments, unsigned segLog, size_t maxTotalBlocks, void* d_planes, uint64_t planesCapacity,
+                                                               uint64_t* d_segOffsets, size_t* d_segResults, uint64_t* d_planeOffsets, size_t* d_planeSizes,
+                                                               void* d_workspace, size_t workspaceBytes, unsigned stride, void* stream);
 
 /* Plane estimates (planes_estimate.hip): THE TRANSFORM CHOSEN PER TENSOR FROM DEVICE HISTOGRAMS.  The tensor line has four ways to turn a
  * tensor into byte planes -- plain, predicted, XOR against a base, SUB against a base -- each opt-in and per call, and a wrong guess costs
