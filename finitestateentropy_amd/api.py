@@ -1323,7 +1323,9 @@ class CompressedTensors:
     contents -- `codec` is then that SparsePlanes -- and decompress_tensors reads them as such; windows and patches of such an object are
     refused.  `transforms` (None, or one name per tensor out of "plain", "pred", "xor", "sub" where compress_tensors_each wrote the object): every
     tensor's planes are those of its own transform, and decompress_tensors merges each accordingly (a base only where a name is "xor" or
-    "sub"); decompress_tensor_windows_each and patch_tensor_windows_each take such an object.  `base_digests` (None, or one int per tensor in tensor order where the object was written against a DeltaBase(..., check=True)):
+    "sub"); decompress_tensor_windows_each and patch_tensor_windows_each take such an object.  `strides` (None, or one integer 1 .. 8 per tensor where
+    compress_tensors_each was given `strides`): the stride of every "pred" tensor, 1 for the others; an object that holds one above 1 has no
+    windows and no patches.  `base_digests` (None, or one int per tensor in tensor order where the object was written against a DeltaBase(..., check=True)):
     the 64-bit digests of the base tensors; decompress_tensors refuses a base whose digests differ.  `predictor` (None, or "prev" where the
     object was written with a PredictedPlanes -- `codec` is then that PredictedPlanes): the frames hold the planes of the neighbour
     differences, and decompress_tensors sums them back; decompress_tensor_windows_each and patch_tensor_windows_each take such an object."""
@@ -1333,6 +1335,7 @@ class CompressedTensors:
     base_digests = None
     predictor = None
     transforms = None
+    strides = None
 
     def __init__(self, groups, dtypes, shapes, device, codec, block_size_id, delta=False):
         self.groups, self.dtypes, self.shapes, self.device, self.codec, self.block_size_id = groups, dtypes, shapes, device, codec, block_size_id
@@ -2477,6 +2480,8 @@ def _planes_methods():
             raise ValueError(what + ": the object is not segmented (compress_tensors_each and compress_tensors_segmented write those with a segment_log)")
         if getattr(obj, "sparse_permille", None) is not None:
             raise ValueError(what + ": the object holds sparse planes (SparsePlanes); patches of those are not supported")
+        if any(st != 1 for st in (getattr(obj, "strides", None) or ())):
+            raise ValueError(what + ": the object holds a stride above 1 (compress_tensors_each with strides); patches of those are not supported")
         n = len(obj.dtypes)
         names, predictor = getattr(obj, "transforms", None), getattr(obj, "predictor", None)
         if names is not None:
@@ -3138,6 +3143,41 @@ def _planes_methods():
             raise ValueError("transforms: %d names out of %r (or ids 0 .. 255) are needed" % (n, EST_NAMES))
         return torch.tensor(ids, dtype=torch.uint8).to(device) if n else torch.zeros(1, dtype=torch.uint8, device=device)[:0]
 
+    def _strides(strides, n, device):
+        """the `strides` of a call that takes them as given: None (stride 1 everywhere), a CUDA uint8 tensor of n bytes (handed on as it
+        is: the device refuses a pred tensor whose byte is 0 or above 8), or a sequence of n integers 0 .. 255 -> the CUDA uint8 tensor"""
+        if strides is None:
+            return None
+        if isinstance(strides, torch.Tensor):
+            return _u8(strides, n, device, "strides")
+        ids = list(strides)
+        if len(ids) != n or any(not isinstance(t, numbers.Integral) or isinstance(t, bool) or not 0 <= t <= 255 for t in ids):
+            raise ValueError("strides: %d integers (1 .. %d for a pred tensor) are needed" % (n, PRED_MAX_STRIDE))
+        return torch.tensor([int(t) for t in ids], dtype=torch.uint8).to(device) if n else torch.zeros(1, dtype=torch.uint8, device=device)[:0]
+
+    def _stride_mask(strides, what):
+        """a candidate set of strides, integers out of 1 .. 8 (or the mask itself, an integer 1 .. 255) -> the strideMask of the C calls"""
+        if isinstance(strides, numbers.Integral) and not isinstance(strides, bool):
+            if not 1 <= strides <= 255:
+                raise ValueError("%s: stride mask %r, bits 0 .. 7 and at least one are needed" % (what, strides))
+            return int(strides)
+        mask = 0
+        for st in ([] if isinstance(strides, str) else list(strides)):
+            _stride(st, what)
+            mask |= 1 << (int(st) - 1)
+        if not mask:
+            raise ValueError("%s: strides %r, integers out of 1 .. %d are needed" % (what, strides, PRED_MAX_STRIDE))
+        return mask
+
+    def tensor_each_stride_workspace_head(self, n_tensors, elem_bytes, choose, candidate_mask=3, stride_mask=1):
+        """tensor_each_workspace_head of the _each_stride_ composites: with stride_mask 1 the same number."""
+        self.lib.FSEHIP_tensor_each_stride_workspaceHead.restype = SZ
+        r = int(self.lib.FSEHIP_tensor_each_stride_workspaceHead(SZ(int(n_tensors)), C.c_uint(int(elem_bytes)), C.c_int(1 if choose else 0),
+                                                                 C.c_uint(int(candidate_mask) & 0xFFFFFFFF), C.c_uint(int(stride_mask) & 0xFFFFFFFF)))
+        if r >= (1 << 62):
+            raise ValueError("tensor_each_stride_workspace_head(%r, %r, %r, %r, %r)" % (n_tensors, elem_bytes, choose, candidate_mask, stride_mask))
+        return r
+
     def tensor_each_workspace_head(self, n_tensors, elem_bytes, choose, candidate_mask=3):
         """the bytes of a tensor_compress_each_dbatch workspace that lie in front of the writer's own: 0 with the transforms given, the
         estimate's counters and outputs where the call chooses.  Host arithmetic: needs no device."""
@@ -3148,7 +3188,8 @@ def _planes_methods():
             raise ValueError("tensor_each_workspace_head(%r, %r, %r, %r)" % (n_tensors, elem_bytes, choose, candidate_mask))
         return r
 
-    def planes_split_each_dbatch(self, src, src_offsets, elem_bytes, transforms, base=None, capacity=None, planes=None, plane_offsets=None, results=None):
+    def planes_split_each_dbatch(self, src, src_offsets, elem_bytes, transforms, base=None, capacity=None, planes=None, plane_offsets=None, results=None,
+                                 _strides_arg=_NO_STRIDE):
         """-> (planes, plane_offsets, results): tensor i split as transforms[i] says (0 plain, 1 pred, 2 xor, 3 sub; names or a CUDA uint8
         tensor) -- byte for byte what planes_split_dbatch, planes_split_pred_dbatch or planes_split_xor_dbatch (delta_op 0 / 1) writes for
         it.  base: laid out as src, read for xor and sub tensors only; a tensor whose byte is none of the four, or xor / sub without a
@@ -3160,7 +3201,9 @@ def _planes_methods():
         capacity = _room(self, src, capacity, "src")
         _base(self, base, src, capacity, "src")
         tr = _transforms(transforms, n, src.device)
-        what = "planes_split_each_dbatch"
+        what = "planes_split_each_dbatch" if _strides_arg is _NO_STRIDE else "planes_split_each_stride_dbatch"
+        held = None if _strides_arg is _NO_STRIDE else _strides(_strides_arg, n, src.device)
+        st = () if _strides_arg is _NO_STRIDE else (_ptr(held),)                               # (the _each_ export takes none)
         g = None
         if planes is None:
             planes, g = self._dst(1, src.numel(), src.device)
@@ -3169,13 +3212,15 @@ def _planes_methods():
             raise ValueError("planes holds %d bytes, the capacity is %d" % (planes.numel(), capacity))
         poff = _i64(self, plane_offsets, n * E + 1, src.device, "plane_offsets")
         res = _i64(self, results, n, src.device, "results")
-        _check(self.lib.FSEHIP_planes_split_each_dbatch(_ptr(planes), _ptr(poff), _ptr(res), _ptr(src), _ptr(base), VP(tr.data_ptr() or res.data_ptr()), _ptr(soff), SZ(n),
-                                                        C.c_uint(E), C.c_uint64(capacity), _stream()), what)
+        call = self.lib.FSEHIP_planes_split_each_dbatch if _strides_arg is _NO_STRIDE else self.lib.FSEHIP_planes_split_each_stride_dbatch
+        _check(call(_ptr(planes), _ptr(poff), _ptr(res), _ptr(src), _ptr(base), VP(tr.data_ptr() or res.data_ptr()), *st, _ptr(soff), SZ(n), C.c_uint(E),
+                    C.c_uint64(capacity), _stream()), what)
         if g is not None:
             g.check(what)
         return planes, poff, res
 
-    def planes_merge_each_dbatch(self, planes, plane_offsets, plane_sizes, dst_offsets, elem_bytes, transforms, base=None, dst=None, capacity=None, results=None):
+    def planes_merge_each_dbatch(self, planes, plane_offsets, plane_sizes, dst_offsets, elem_bytes, transforms, base=None, dst=None, capacity=None, results=None,
+                                 _strides_arg=_NO_STRIDE):
         """-> (dst, results): the inverse of planes_split_each_dbatch with the merges' results and rules.  base may be dst itself (the
         resident tensors are updated where they lie; a plain or pred tensor overwrites its bytes, a refused one keeps them).  dst must not
         overlap planes."""
@@ -3189,16 +3234,22 @@ def _planes_methods():
         _base(self, base, planes, capacity, "dst")
         tr = _transforms(transforms, n, planes.device)
         res = _i64(self, results, n, planes.device, "results")
-        what = "planes_merge_each_dbatch"
-        _check(self.lib.FSEHIP_planes_merge_each_dbatch(_ptr(dst), _ptr(doff), _ptr(res), _ptr(planes), _ptr(poff), _ptr(psz), _ptr(base),
-                                                        VP(tr.data_ptr() or res.data_ptr()), SZ(n), C.c_uint(E), C.c_uint64(capacity), _stream()), what)
+        what = "planes_merge_each_dbatch" if _strides_arg is _NO_STRIDE else "planes_merge_each_stride_dbatch"
+        held = None if _strides_arg is _NO_STRIDE else _strides(_strides_arg, n, planes.device)
+        st = () if _strides_arg is _NO_STRIDE else (_ptr(held),)                               # (the _each_ export takes none)
+        call = self.lib.FSEHIP_planes_merge_each_dbatch if _strides_arg is _NO_STRIDE else self.lib.FSEHIP_planes_merge_each_stride_dbatch
+        _check(call(_ptr(dst), _ptr(doff), _ptr(res), _ptr(planes), _ptr(poff), _ptr(psz), _ptr(base), VP(tr.data_ptr() or res.data_ptr()), *st, SZ(n), C.c_uint(E),
+                    C.c_uint64(capacity), _stream()), what)
         if g is not None:
             g.check(what)
         return dst, res
 
     def _compress_each(self, what, src, src_offsets, elem_bytes, transforms, base, candidate_mask, margin_permille, est_bytes, segment_log, seg_first, n_segments, codec,
                        codecs, block_size_id, capacity, dst, dst_capacity, max_total_blocks, align_log, frame_offsets, frame_results, tensor_results, planes,
-                       plane_offsets, seg_offsets, workspace, chosen):
+                       plane_offsets, seg_offsets, workspace, chosen, strides=_NO_STRIDE, stride_mask=None, chosen_strides=None):
+        """strides is _NO_STRIDE: the _each_ exports.  Else the _each_stride_ exports: `strides` as _strides takes them where the transforms are
+        given; where the call chooses, stride_mask is the candidate set and the chosen strides are returned (in chosen_strides where given)"""
+        each = strides is _NO_STRIDE
         E = _elem(elem_bytes)
         align_log = _align_log(align_log)
         seg = segment_log is not None
@@ -3216,6 +3267,14 @@ def _planes_methods():
         else:
             tr = torch.zeros(max(n, 1), dtype=torch.uint8, device=src.device)[:n] if chosen is None else _u8(chosen, n, src.device, "chosen")[:n]
         eb = None if est_bytes is None else _i64(self, est_bytes, n * 4, src.device, "est_bytes")
+        st, smask = None, 1
+        if not each and pick:
+            smask = _stride_mask(1 if stride_mask is None else stride_mask, what)
+            if smask != 1 and not (candidate_mask >> 1) & 1:
+                raise ValueError(what + ": strides are candidates of \"pred\", which is not among the candidates")
+            st = torch.ones(max(n, 1), dtype=torch.uint8, device=src.device)[:n] if chosen_strides is None else _u8(chosen_strides, n, src.device, "chosen_strides")[:n]
+        elif not each:
+            st = _strides(strides, n, src.device)
         if seg:
             if seg_first is None:
                 seg_first = planes_segment_first(self, np.diff(shost.astype(np.int64)).clip(min=0), E, L)
@@ -3233,23 +3292,30 @@ def _planes_methods():
         poff = _i64(self, plane_offsets, n * E + 1, src.device, "plane_offsets")
         so = _i64(self, seg_offsets, nf + 1, src.device, "seg_offsets") if seg else None
         if workspace is None:
-            need = tensor_each_workspace_head(self, n, E, pick, candidate_mask or 0) + _writer_need(self, nf, max_total_blocks, block_size_id, codec, mixed, choose)
+            need = (tensor_each_workspace_head(self, n, E, pick, candidate_mask or 0) if each else
+                    tensor_each_stride_workspace_head(self, n, E, pick, candidate_mask or 0, smask)) + _writer_need(self, nf, max_total_blocks, block_size_id, codec, mixed, choose)
             workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=src.device)
         tol = codec.tolerance_permille if choose and isinstance(codec, AutoCodec) else 0
-        head = (_ptr(dst), C.c_uint64(int(dst_capacity)), _ptr(foff), _ptr(fres), _ptr(tres), _ptr(src), _ptr(base), VP(tr.data_ptr() or tres.data_ptr()),
-                C.c_int(1 if pick else 0), C.c_uint(int(candidate_mask or 0)), C.c_uint(int(margin_permille)), _ptr(eb), _ptr(soff), SZ(n), C.c_uint(E), C.c_uint64(capacity))
+        sp = () if each else (VP((st.data_ptr() or tres.data_ptr()) if st is not None else None),)
+        sm = () if each else (C.c_uint(smask),)
+        head = (_ptr(dst), C.c_uint64(int(dst_capacity)), _ptr(foff), _ptr(fres), _ptr(tres), _ptr(src), _ptr(base), VP(tr.data_ptr() or tres.data_ptr()), *sp,
+                C.c_int(1 if pick else 0), C.c_uint(int(candidate_mask or 0)), *sm, C.c_uint(int(margin_permille)), _ptr(eb), _ptr(soff), SZ(n), C.c_uint(E),
+                C.c_uint64(capacity))
         writer = (SZ(max_total_blocks), C.c_uint(block_size_id), C.c_int(0 if mixed else codec),
                   _ptr((codecs if codecs.numel() else codecs.new_zeros(1)) if mixed else None), C.c_int(CODECS_CHOOSE if choose else CODECS_GIVEN), C.c_uint(tol),
                   C.c_uint(align_log), _ptr(planes), _ptr(poff))
         tail = (_ptr(workspace), SZ(workspace.numel()), _stream())
         if seg:
-            _check(self.lib.FSEHIP_tensor_compress_seg_each_dbatch(*head, _ptr(sf), SZ(nf), C.c_uint(L), *writer, _ptr(so), *tail), what)
+            call = self.lib.FSEHIP_tensor_compress_seg_each_dbatch if each else self.lib.FSEHIP_tensor_compress_seg_each_stride_dbatch
+            _check(call(*head, _ptr(sf), SZ(nf), C.c_uint(L), *writer, _ptr(so), *tail), what)
         else:
-            _check(self.lib.FSEHIP_tensor_compress_each_dbatch(*head, *writer, *tail), what)
+            call = self.lib.FSEHIP_tensor_compress_each_dbatch if each else self.lib.FSEHIP_tensor_compress_each_stride_dbatch
+            _check(call(*head, *writer, *tail), what)
         _check_codecs(cgu, nf, what)
         if g is not None:
             g.check(what)
-        return dst, foff, fres, tres, (codecs[:nf] if mixed else None), tr
+        out = (dst, foff, fres, tres, (codecs[:nf] if mixed else None), tr)
+        return out if each else out + (st,)
 
     def tensor_compress_each_dbatch(self, src, src_offsets, elem_bytes, transforms=None, base=None, candidate_mask=None, margin_permille=50, est_bytes=None, codec=0,
                                     codecs=None, block_size_id=5, capacity=None, dst=None, dst_capacity=None, max_total_blocks=None, align_log=0, frame_offsets=None,
@@ -3275,7 +3341,8 @@ def _planes_methods():
                               frame_results, tensor_results, planes, plane_offsets, seg_offsets, workspace, chosen)
 
     def _decompress_each(self, what, frames, frame_offsets, dst_offsets, elem_bytes, transforms, base, segment_log, seg_first, n_segments, dst, dst_capacity,
-                         max_total_blocks, planes, planes_capacity, seg_offsets, seg_results, plane_offsets, plane_sizes, workspace, results):
+                         max_total_blocks, planes, planes_capacity, seg_offsets, seg_results, plane_offsets, plane_sizes, workspace, results, strides=_NO_STRIDE):
+        each = strides is _NO_STRIDE                            # the _each_ exports take no strides
         E = _elem(elem_bytes)
         seg = segment_log is not None
         L = _seg_log(segment_log) if seg else 0
@@ -3302,15 +3369,19 @@ def _planes_methods():
         psz = _i64(self, plane_sizes, n * E, frames.device, "plane_sizes")
         res = _i64(self, results, n, frames.device, "results")
         workspace = _reader_workspace(self, workspace, nf, max_total_blocks, frames.device)
-        head = (_ptr(dst), _ptr(doff), C.c_uint64(dst_capacity), _ptr(base), VP(tr.data_ptr() or res.data_ptr()), _ptr(res), _ptr(frames), _ptr(foff), SZ(n), C.c_uint(E))
+        held = None if each else _strides(strides, n, frames.device)
+        sp = () if each else (_ptr(held),)
+        head = (_ptr(dst), _ptr(doff), C.c_uint64(dst_capacity), _ptr(base), VP(tr.data_ptr() or res.data_ptr()), *sp, _ptr(res), _ptr(frames), _ptr(foff), SZ(n),
+                C.c_uint(E))
         tail = (_ptr(poff), _ptr(psz), _ptr(workspace), SZ(workspace.numel()), _stream())
         if seg:
             so = _i64(self, seg_offsets, nf + 1, frames.device, "seg_offsets")
             sres = _i64(self, seg_results, nf, frames.device, "seg_results")
-            _check(self.lib.FSEHIP_tensor_decompress_seg_each_dbatch(*head, _ptr(sf), SZ(nf), C.c_uint(L), SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity),
-                                                                     _ptr(so), _ptr(sres), *tail), what)
+            call = self.lib.FSEHIP_tensor_decompress_seg_each_dbatch if each else self.lib.FSEHIP_tensor_decompress_seg_each_stride_dbatch
+            _check(call(*head, _ptr(sf), SZ(nf), C.c_uint(L), SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity), _ptr(so), _ptr(sres), *tail), what)
         else:
-            _check(self.lib.FSEHIP_tensor_decompress_each_dbatch(*head, SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity), *tail), what)
+            call = self.lib.FSEHIP_tensor_decompress_each_dbatch if each else self.lib.FSEHIP_tensor_decompress_each_stride_dbatch
+            _check(call(*head, SZ(max_total_blocks), _ptr(planes), C.c_uint64(planes_capacity), *tail), what)
         if g is not None:
             g.check(what)
         return dst, res
@@ -3330,6 +3401,97 @@ def _planes_methods():
         return _decompress_each(self, "tensor_decompress_seg_each_dbatch", frames, frame_offsets, dst_offsets, elem_bytes, transforms, base, segment_log, seg_first,
                                 n_segments, dst, dst_capacity, max_total_blocks, planes, planes_capacity, seg_offsets, seg_results, plane_offsets, plane_sizes, workspace,
                                 results)
+
+    # ---- a stride per tensor, strides in the estimate (csrc/planes_each_stride.hip, planes_estimate.hip; fsehip.h, the sections of those names)
+    def planes_estimate_stride_workspace_bound(self, n_tensors, elem_bytes, candidate_mask, stride_mask):
+        """the workspace of planes_estimate_stride_dbatch; with stride_mask 1 that of planes_estimate_dbatch.  Host arithmetic."""
+        self.lib.FSEHIP_planes_estimate_stride_workspaceBound.restype = SZ
+        r = int(self.lib.FSEHIP_planes_estimate_stride_workspaceBound(SZ(int(n_tensors)), C.c_uint(int(elem_bytes)), C.c_uint(int(candidate_mask) & 0xFFFFFFFF),
+                                                                      C.c_uint(int(stride_mask) & 0xFFFFFFFF)))
+        if r >= (1 << 62):
+            raise ValueError("planes_estimate_stride_workspace_bound(%r, %r, %r, %r)" % (n_tensors, elem_bytes, candidate_mask, stride_mask))
+        return r
+
+    def planes_estimate_stride_dbatch(self, src, src_offsets, elem_bytes, candidate_mask=3, stride_mask=1, margin_permille=50, base=None, capacity=None, plane_bits=None,
+                                      est_bytes=None, choice=None, results=None, stride_est_bytes=None, strides=None, workspace=None):
+        """-> (plane_bits, est_bytes, choice, results, stride_est_bytes, strides): planes_estimate_dbatch with the pred candidate at every stride
+        S whose bit 1 << (S - 1) is set in stride_mask.  stride_est_bytes[i*8+S-1] = the estimate of tensor i at stride S (-1: not
+        requested), strides[i] (uint8) = the stride chosen in rising order under margin_permille; the pred slots of plane_bits and
+        est_bytes hold the numbers of that stride, and choice is made over those.  A refused tensor: strides 0xFF."""
+        E = _elem(elem_bytes)
+        self._flat(src, "src")
+        soff, _ = self._offsets(src_offsets, src.device, False)
+        n = soff.numel() - 1
+        capacity = _room(self, src, capacity, "src")
+        _base(self, base, src, capacity, "src")
+        need = planes_estimate_stride_workspace_bound(self, n, E, candidate_mask, stride_mask)
+        pb = _i64(self, plane_bits, n * 4 * E, src.device, "plane_bits")
+        eb = _i64(self, est_bytes, n * 4, src.device, "est_bytes")
+        ch = torch.zeros(max(n, 1), dtype=torch.uint8, device=src.device)[:n] if choice is None else _u8(choice, n, src.device, "choice")
+        res = _i64(self, results, n, src.device, "results")
+        seb = _i64(self, stride_est_bytes, n * PRED_MAX_STRIDE, src.device, "stride_est_bytes")
+        st = torch.zeros(max(n, 1), dtype=torch.uint8, device=src.device)[:n] if strides is None else _u8(strides, n, src.device, "strides")
+        if workspace is None:
+            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=src.device)
+        _check(self.lib.FSEHIP_planes_estimate_stride_dbatch(_ptr(pb), _ptr(eb), _ptr(ch), _ptr(res), _ptr(seb), VP(st.data_ptr() or workspace.data_ptr()),
+                                                             VP(src.data_ptr() or workspace.data_ptr()), _ptr(base), _ptr(soff), SZ(n), C.c_uint(E), C.c_uint64(capacity),
+                                                             C.c_uint(int(candidate_mask)), C.c_uint(int(margin_permille)), _ptr(workspace), SZ(workspace.numel()),
+                                                             C.c_uint(int(stride_mask)), _stream()), "planes_estimate_stride_dbatch")
+        return pb, eb, ch, res, seb, st
+
+    def planes_split_each_stride_dbatch(self, src, src_offsets, elem_bytes, transforms, strides=None, base=None, capacity=None, planes=None, plane_offsets=None,
+                                        results=None):
+        """planes_split_each_dbatch with strides[i] (1 .. 8) the stride of tensor i where transforms[i] is pred -- the planes of
+        planes_split_pred_stride_dbatch at that stride; a 0 or a value above 8 there refuses that tensor alone (results -1).  For every
+        other transform the entry is ignored.  strides None: planes_split_each_dbatch."""
+        return planes_split_each_dbatch(self, src, src_offsets, elem_bytes, transforms, base, capacity, planes, plane_offsets, results, _strides_arg=strides)
+
+    def planes_merge_each_stride_dbatch(self, planes, plane_offsets, plane_sizes, dst_offsets, elem_bytes, transforms, strides=None, base=None, dst=None, capacity=None,
+                                        results=None):
+        """the inverse of planes_split_each_stride_dbatch, with the rules of planes_merge_each_dbatch."""
+        return planes_merge_each_dbatch(self, planes, plane_offsets, plane_sizes, dst_offsets, elem_bytes, transforms, base, dst, capacity, results, _strides_arg=strides)
+
+    def tensor_compress_each_stride_dbatch(self, src, src_offsets, elem_bytes, transforms=None, strides=None, base=None, candidate_mask=None, stride_mask=None,
+                                           margin_permille=50, est_bytes=None, codec=0, codecs=None, block_size_id=5, capacity=None, dst=None, dst_capacity=None,
+                                           max_total_blocks=None, align_log=0, frame_offsets=None, frame_results=None, tensor_results=None, planes=None,
+                                           plane_offsets=None, workspace=None, chosen=None, chosen_strides=None):
+        """-> (dst, frame_offsets, frame_results, tensor_results, codecs, transforms, strides): tensor_compress_each_dbatch with a stride per
+        pred tensor.  transforms given: `strides` is read with them (None: stride 1 everywhere).  transforms None: both are CHOSEN on the
+        device by planes_estimate_stride_dbatch with candidate_mask and stride_mask (a mask, or a sequence of strides; default stride 1 alone)
+        and returned -- strides 1 for the tensors that did not choose pred."""
+        return _compress_each(self, "tensor_compress_each_stride_dbatch", src, src_offsets, elem_bytes, transforms, base, candidate_mask, margin_permille, est_bytes, None,
+                              None, None, codec, codecs, block_size_id, capacity, dst, dst_capacity, max_total_blocks, align_log, frame_offsets, frame_results,
+                              tensor_results, planes, plane_offsets, None, workspace, chosen, strides, stride_mask, chosen_strides)
+
+    def tensor_compress_seg_each_stride_dbatch(self, src, src_offsets, elem_bytes, segment_log, transforms=None, strides=None, base=None, candidate_mask=None,
+                                               stride_mask=None, margin_permille=50, est_bytes=None, seg_first=None, n_segments=None, codec=0, codecs=None,
+                                               block_size_id=5, capacity=None, dst=None, dst_capacity=None, max_total_blocks=None, align_log=0, frame_offsets=None,
+                                               frame_results=None, tensor_results=None, planes=None, plane_offsets=None, seg_offsets=None, workspace=None, chosen=None,
+                                               chosen_strides=None):
+        """tensor_compress_each_stride_dbatch with a frame per segment of every plane."""
+        return _compress_each(self, "tensor_compress_seg_each_stride_dbatch", src, src_offsets, elem_bytes, transforms, base, candidate_mask, margin_permille, est_bytes,
+                              segment_log, seg_first, n_segments, codec, codecs, block_size_id, capacity, dst, dst_capacity, max_total_blocks, align_log, frame_offsets,
+                              frame_results, tensor_results, planes, plane_offsets, seg_offsets, workspace, chosen, strides, stride_mask, chosen_strides)
+
+    def tensor_decompress_each_stride_dbatch(self, frames, frame_offsets, dst_offsets, elem_bytes, transforms, strides=None, base=None, dst=None, dst_capacity=None,
+                                             max_total_blocks=None, planes=None, planes_capacity=None, plane_offsets=None, plane_results=None, workspace=None,
+                                             results=None):
+        """tensor_decompress_each_dbatch of frames that tensor_compress_each_stride_dbatch wrote with these transforms and strides."""
+        return _decompress_each(self, "tensor_decompress_each_stride_dbatch", frames, frame_offsets, dst_offsets, elem_bytes, transforms, base, None, None, None, dst,
+                                dst_capacity, max_total_blocks, planes, planes_capacity, None, None, plane_offsets, plane_results, workspace, results, strides)
+
+    def tensor_decompress_seg_each_stride_dbatch(self, frames, frame_offsets, dst_offsets, elem_bytes, segment_log, transforms, strides=None, base=None, seg_first=None,
+                                                 n_segments=None, dst=None, dst_capacity=None, max_total_blocks=None, planes=None, planes_capacity=None,
+                                                 seg_offsets=None, seg_results=None, plane_offsets=None, plane_sizes=None, workspace=None, results=None):
+        """tensor_decompress_seg_each_dbatch of frames that tensor_compress_seg_each_stride_dbatch wrote."""
+        return _decompress_each(self, "tensor_decompress_seg_each_stride_dbatch", frames, frame_offsets, dst_offsets, elem_bytes, transforms, base, segment_log, seg_first,
+                                n_segments, dst, dst_capacity, max_total_blocks, planes, planes_capacity, seg_offsets, seg_results, plane_offsets, plane_sizes, workspace,
+                                results, strides)
+
+    for f in (planes_estimate_stride_workspace_bound, planes_estimate_stride_dbatch, tensor_each_stride_workspace_head, planes_split_each_stride_dbatch,
+              planes_merge_each_stride_dbatch, tensor_compress_each_stride_dbatch, tensor_compress_seg_each_stride_dbatch, tensor_decompress_each_stride_dbatch,
+              tensor_decompress_seg_each_stride_dbatch):
+        setattr(FseHip, f.__name__, f)
 
     # ---- windows of tensors with a transform per tensor (fsehip.h, the section of that name): the read side of the windows for frames of
     # tensor_compress_seg_each_dbatch and tensor_compress_seg_pred_dbatch
@@ -3506,6 +3668,18 @@ def _planes_methods():
             return AutoCodec(j["auto"])
         return int(j)
 
+    def _archive_meta(obj, gi, n_groups, idx, device_index, codec):
+        """the meta record of group gi of `obj`, whose tensors are idx: what C has no notion of.  codec: the object's, as _codec_to_json gives it"""
+        fields = dict(v=1, group=gi, groups=n_groups, tensors=len(obj.dtypes), index=idx, dtypes=[str(obj.dtypes[i]).replace("torch.", "") for i in idx],
+                      shapes=[list(obj.shapes[i]) for i in idx], codec=codec, device_index=device_index)
+        if getattr(obj, "transforms", None) is not None:        # compress_tensors_each's: the names travel as the predictor does
+            fields["transforms"] = [obj.transforms[i] for i in idx]
+            if any(st != 1 for st in (getattr(obj, "strides", None) or ())):      # (only where one exceeds 1: every other object's meta bytes stay as they were)
+                fields["strides"] = [int(obj.strides[i]) for i in idx]
+        return fields
+
+    FseHip._archive_meta = staticmethod(_archive_meta)
+
     def archive_tensors(self, obj):
         """a CompressedTensors -> ONE flat CUDA uint8 tensor that holds all of it (include/fsehip.h "tensor archives"): one archive per group of
         obj.groups back to back, each at a multiple of 256 (an object without groups: one archive of no tensors), ready to be sent or written
@@ -3523,11 +3697,7 @@ def _planes_methods():
         parts = []
         for gi, g in enumerate(obj.groups or [None]):
             E, idx, sizes = (1, [], []) if g is None else (g["elem_bytes"], list(g["index"]), list(g["sizes"]))
-            fields = dict(v=1, group=gi, groups=n_groups, tensors=len(obj.dtypes), index=idx, dtypes=[str(obj.dtypes[i]).replace("torch.", "") for i in idx],
-                          shapes=[list(obj.shapes[i]) for i in idx], codec=_codec_to_json(obj.codec), device_index=device.index)
-            if getattr(obj, "transforms", None) is not None:    # compress_tensors_each's: the names travel as the predictor does, C has no notion of them
-                fields["transforms"] = [obj.transforms[i] for i in idx]
-            meta = json.dumps(fields, separators=(",", ":")).encode()
+            meta = json.dumps(_archive_meta(obj, gi, n_groups, idx, device.index, _codec_to_json(obj.codec)), separators=(",", ":")).encode()
             flags = (ARCHIVE_DELTA if obj.delta else 0) | (ARCHIVE_SPARSE if sparse is not None else 0)
             flags |= (ARCHIVE_CODECS if g is not None and "codecs" in g else 0) | (ARCHIVE_DIGESTS if digs is not None and obj.delta else 0)
             nF = 0 if g is None else g["frame_offsets"].numel() - 1
@@ -3631,12 +3801,24 @@ def _planes_methods():
                     raise ValueError("open_archive: the transforms in the meta bytes are not compress_tensors_each's (%r)" % (names,))
                 for i, t in zip(g["index"], names):
                     transforms[i] = t
+        strides = None
+        if any("strides" in g["_meta"] for g in groups):
+            strides = [1] * n
+            for g in groups:
+                sts = g["_meta"].get("strides")
+                if (transforms is None or not isinstance(sts, list) or len(sts) != len(g["index"])
+                        or any(isinstance(st, bool) or not isinstance(st, int) or not 1 <= st <= PRED_MAX_STRIDE for st in sts)):
+                    raise ValueError("open_archive: the strides in the meta bytes are not compress_tensors_each's (%r)" % (sts,))
+                for i, st in zip(g["index"], sts):
+                    strides[i] = st
         for g in groups:
             for k in ("_info", "_meta", "_dtypes", "_codec", "_digests"):
                 del g[k]
         obj = CompressedTensors(groups if m0["groups"] else [], dtypes, shapes, device if n else None, codec, int(first.blockSizeId), delta)
         if transforms is not None:
             obj.transforms = transforms
+        if strides is not None:
+            obj.strides = strides
         return _segmented(obj, int(first.segLog) if first.segLog else None, "sub" if delta and first.deltaOp else "xor",
                           int(first.sparsePermille) if first.flags & ARCHIVE_SPARSE else None, digests, codec.predictor if isinstance(codec, PredictedPlanes) else None)
 
@@ -3938,7 +4120,7 @@ def _planes_methods():
             raise ValueError("%s: margin_permille %r, 0 .. 1000 is needed" % (what, margin_permille))
         return int(margin_permille)
 
-    def estimate_tensors(self, tensors, base=None, candidates=None, margin_permille=50):
+    def estimate_tensors(self, tensors, base=None, candidates=None, margin_permille=50, strides=None):
         """CUDA tensors of one device and of 1, 2, 4 or 8 bytes per element -> one record per tensor, in input order: dict(bytes=its size,
         estimates={name: estimated bytes of its frames under that plane transform}, choice=name).  The names: "plain" (compress_tensors as
         it is), "pred" (PredictedPlanes), "xor" (base=...), "sub" (DeltaBase(..., "sub")).  One read of the tensors (and of the bases) on the
@@ -3949,8 +4131,12 @@ def _planes_methods():
         chosen).  candidates: names out of the four, default ("plain", "pred") without a base and all four with one; "xor" and "sub" need
         a base.  The choice: the first candidate in the order above, replaced by a later one only if that is more than margin_permille /
         1000 smaller than the best so far -- hysteresis towards the simpler form, a policy like AutoCodec's tolerance.  An estimate has
-        no term for frame headers or tables.  TypeError / ValueError as compress_tensors raises them, before any launch."""
+        no term for frame headers or tables.  TypeError / ValueError as compress_tensors raises them, before any launch.
+        strides: None, or a sequence of integers out of 1 .. 8, the strides at which "pred" is estimated (planes_estimate_stride_dbatch):
+        the records gain stride=the stride chosen among them in rising order under the same margin, and stride_estimates={S: bytes};
+        estimates["pred"] is the estimate at that stride.  "pred" must be among the candidates."""
         margin = _margin(margin_permille, "estimate_tensors")
+        smask = None if strides is None else _stride_mask(strides, "estimate_tensors")
         tensors = list(tensors)
         if isinstance(base, DeltaBase):
             base = base.tensors
@@ -3963,6 +4149,8 @@ def _planes_methods():
             mask |= 1 << EST_NAMES.index(c)
         if (mask & 12) and base is None:
             raise ValueError("estimate_tensors: \"xor\" and \"sub\" are deltas against a base, none was given")
+        if smask is not None and not mask & 2:
+            raise ValueError("estimate_tensors: strides are candidates of \"pred\", which is not among the candidates %r" % (tuple(candidates),))
         if not tensors:
             if base is not None and len(list(base)):
                 raise ValueError("base: tensors for none")
@@ -3986,14 +4174,21 @@ def _planes_methods():
                 one = len(raw) == 1 and raw[0].numel() > 0          # a single tensor is estimated where it lies
                 src = raw[0] if one else torch.cat(raw) if int(offs[-1]) else torch.zeros(1, dtype=torch.uint8, device=device)[:0]
                 bsrc = None if braw is None or not (mask & 12) else braw[idx[0]] if one else torch.cat([braw[i] for i in idx]) if int(offs[-1]) else src
-                _, eb, ch, res = planes_estimate_dbatch(self, src, offs, E, mask, margin, bsrc)
-                got = torch.cat([eb, ch.to(torch.int64), res]).cpu().tolist()
                 n = len(idx)
-                if got[5 * n:] != [int(x) for x in np.diff(offs.astype(np.int64))]:
+                if smask is None:
+                    _, eb, ch, res = planes_estimate_dbatch(self, src, offs, E, mask, margin, bsrc)
+                    got = torch.cat([eb, ch.to(torch.int64), res]).cpu().tolist()
+                else:
+                    _, eb, ch, res, seb, st = planes_estimate_stride_dbatch(self, src, offs, E, mask, smask, margin, bsrc)
+                    got = torch.cat([eb, ch.to(torch.int64), res, st.to(torch.int64), seb]).cpu().tolist()
+                if got[5 * n:6 * n] != [int(x) for x in np.diff(offs.astype(np.int64))]:
                     raise RuntimeError("estimate_tensors: element size %d, results %s" % (E, got[5 * n:5 * n + 8]))
                 for k, i in enumerate(idx):
                     out[i] = dict(bytes=got[5 * n + k], estimates={name: got[4 * k + c] for c, name in enumerate(EST_NAMES) if (mask >> c) & 1},
                                   choice=EST_NAMES[got[4 * n + k]])
+                    if smask is not None:
+                        out[i]["stride"] = got[6 * n + k]
+                        out[i]["stride_estimates"] = {S: got[7 * n + 8 * k + S - 1] for S in range(1, PRED_MAX_STRIDE + 1) if (smask >> (S - 1)) & 1}
         return out
 
     def compress_tensors_auto(self, tensors, base=None, codec=0, block_size_id=5, segment_log=None, margin_permille=50):
@@ -4061,7 +4256,7 @@ def _planes_methods():
                 out[i] = t
         return out
 
-    def compress_tensors_each(self, tensors, transforms="auto", base=None, codec=0, block_size_id=5, segment_log=None, margin_permille=50):
+    def compress_tensors_each(self, tensors, transforms="auto", base=None, codec=0, block_size_id=5, segment_log=None, margin_permille=50, strides=None):
         """A mixed list of CUDA tensors -> ONE CompressedTensors whose `transforms` lists the plane transform of every tensor ("plain", "pred",
         "xor", "sub"): what compress_tensors_auto chooses, without cutting the list -- per group of one element size one
         tensor_compress_each_dbatch (with segment_log: tensor_compress_seg_each_dbatch), which estimates, chooses, splits and writes on the
@@ -4071,8 +4266,13 @@ def _planes_methods():
         estimate_tensors takes it -- or one name per tensor, given ("choose once, then give": obj.transforms of an earlier call).
         base: a sequence matching `tensors` one to one (or a DeltaBase without check: its tensors); needed where a given name is "xor" or
         "sub".  codec: 0, 1 or an AutoCodec.  A tensor of 0 bytes takes the lowest candidate and needs no company.
+        strides: None -- "pred" is stride 1, as ever -- or, with "auto", the candidate strides of "pred" (integers out of 1 .. 8: the stride of
+        every tensor is chosen with its transform, interleaved channels find their channel count), or, with given names, one stride per
+        tensor (obj.strides of an earlier call; looked at for the "pred" ones).  The object's `strides` lists the stride of every tensor, 1
+        for those that are not "pred"; archives and files carry it where one exceeds 1.
         Out of scope, each a ValueError before any launch: a SparsePlanes or PredictedPlanes as codec, an earlier object as codec, a
-        DeltaBase(check=True).  Windows of a segmented object are read by decompress_tensor_windows_each and written by
+        DeltaBase(check=True); a stride outside 1 .. 8; strides with "auto" where "pred" is no candidate.  An object with a stride above 1 has
+        no windows and no patches.  Windows of a segmented object are read by decompress_tensor_windows_each and written by
         patch_tensor_windows_each, not by decompress_tensor_windows and patch_tensor_windows."""
         what = "compress_tensors_each"
         margin = _margin(margin_permille, what)
@@ -4096,11 +4296,23 @@ def _planes_methods():
                 raise ValueError("%s: transforms %r; \"auto\" or one name per tensor (%d) out of %r is needed" % (what, transforms[:8], len(tensors), EST_NAMES))
             if base is None and any(t in ("xor", "sub") for t in transforms):
                 raise ValueError(what + ": \"xor\" and \"sub\" are deltas against a base, none was given")
+        smask = None
+        if strides is not None and auto:
+            smask = _stride_mask(list(strides), what)             # ("pred" is a candidate of every "auto" call)
+        elif strides is not None:
+            strides = list(strides)
+            if len(strides) != len(tensors):
+                raise ValueError("%s: %d strides for %d tensors" % (what, len(strides), len(tensors)))
+            for st in strides:
+                _stride(st, what)
+            strides = [int(st) if t == "pred" else 1 for st, t in zip(strides, transforms)]
         if not tensors:
             if base is not None and len(base):
                 raise ValueError("base: tensors for none")
             obj = _segmented(CompressedTensors([], [], [], None, codec, block_size_id), segment_log)
             obj.transforms = []
+            if strides is not None:
+                obj.strides = []
             return obj
         device = tensors[0].device if isinstance(tensors[0], torch.Tensor) else None
         for k, t in enumerate(tensors):
@@ -4110,7 +4322,7 @@ def _planes_methods():
             if auto and t.numel() * t.element_size() >= 1 << 32:
                 raise ValueError("%s: tensor %d holds 2^32 bytes or more, the estimate's counts are 32 bits wide" % (what, k))
         braw = None if base is None else _bases(base, [t.dtype for t in tensors], [tuple(t.shape) for t in tensors], device)
-        names, groups = [None] * len(tensors), []
+        names, groups, chosen = [None] * len(tensors), [], [1] * len(tensors)
         with torch.cuda.device(device):
             for E in (1, 2, 4, 8):
                 idx = [i for i, t in enumerate(tensors) if t.element_size() == E]
@@ -4122,14 +4334,30 @@ def _planes_methods():
                 bsrc = None if braw is None else torch.cat([braw[i] for i in idx]) if int(offs[-1]) else src
                 given = None if auto else [transforms[i] for i in idx]
                 sfirst = None
+                st = None
                 if segment_log is not None:
                     sfirst = self.planes_segment_first(np.diff(offs.astype(np.int64)), E, segment_log)
+                if strides is not None:                         # the calls with a stride per tensor: given with the names, or chosen with them
+                    gs = None if auto else [strides[i] for i in idx]
+                    if segment_log is not None:
+                        dst, foff, fres, tres, codecs, tr, st = tensor_compress_seg_each_stride_dbatch(self, src, offs, E, segment_log, given, gs, bsrc, None, smask, margin,
+                                                                                                       seg_first=sfirst, codec=codec, block_size_id=block_size_id)
+                    else:
+                        dst, foff, fres, tres, codecs, tr, st = tensor_compress_each_stride_dbatch(self, src, offs, E, given, gs, bsrc, None, smask, margin, codec=codec,
+                                                                                                   block_size_id=block_size_id)
+                elif segment_log is not None:
                     dst, foff, fres, tres, codecs, tr = tensor_compress_seg_each_dbatch(self, src, offs, E, segment_log, given, bsrc, None, margin, seg_first=sfirst,
                                                                                         codec=codec, block_size_id=block_size_id)
                 else:
                     dst, foff, fres, tres, codecs, tr = tensor_compress_each_dbatch(self, src, offs, E, given, bsrc, None, margin, codec=codec, block_size_id=block_size_id)
-                got = torch.cat([foff[-1:], fres, tres, tr.to(torch.int64)]).cpu().tolist()      # the one read-back of the group
                 nf, n = fres.numel(), len(idx)
+                got = torch.cat([foff[-1:], fres, tres, tr.to(torch.int64)] + ([] if st is None else [st.to(torch.int64)])).cpu().tolist()      # the one read-back of the group
+                if st is not None:
+                    got, gst = got[:1 + nf + 2 * n], got[1 + nf + 2 * n:]
+                    if any(not 1 <= x <= PRED_MAX_STRIDE for x in gst):
+                        raise RuntimeError("%s: element size %d, strides %s" % (what, E, gst[:8]))
+                    for k, i in enumerate(idx):
+                        chosen[i] = gst[k]
                 if min(got[:1 + nf + n]) < 0 or max(got[1 + nf + n:]) > 3:
                     bad = [k for k, r in enumerate(got[1:1 + nf]) if r < 0]
                     raise RuntimeError("%s: element size %d, frames %s failed (%s), tensor results %s, transforms %s"
@@ -4144,7 +4372,21 @@ def _planes_methods():
                     groups[-1]["seg_first"] = sfirst
         obj = _segmented(CompressedTensors(groups, [t.dtype for t in tensors], [tuple(t.shape) for t in tensors], device, codec, block_size_id), segment_log)
         obj.transforms = names
+        if strides is not None:
+            obj.strides = chosen
         return obj
+
+    def _obj_strides(obj, what):
+        """the strides of an object with a transform per tensor: None (stride 1 everywhere), or one integer 1 .. 8 per tensor"""
+        strides = getattr(obj, "strides", None)
+        if strides is None:
+            return None
+        strides = list(strides)
+        if len(strides) != len(obj.dtypes):
+            raise ValueError("%s: %d strides for %d tensors" % (what, len(strides), len(obj.dtypes)))
+        for st in strides:
+            _stride(st, what)
+        return [int(st) for st in strides]
 
     def _decompress_each_obj(self, obj, base):
         what = "decompress_tensors"
@@ -4153,6 +4395,7 @@ def _planes_methods():
             raise ValueError("%s: transforms %r; one name per tensor (%d) out of %r is needed" % (what, names[:8], len(obj.dtypes), EST_NAMES))
         if getattr(obj, "sparse_permille", None) is not None or getattr(obj, "base_digests", None) is not None or getattr(obj, "predictor", None) is not None:
             raise ValueError(what + ": sparse planes, base digests and a predictor do not go with a transform per tensor")
+        strides = _obj_strides(obj, what)
         if isinstance(base, DeltaBase):
             base = base.tensors
         needs = any(t in ("xor", "sub") for t in names)
@@ -4167,7 +4410,13 @@ def _planes_methods():
             blocks = self.planes_block_bound(sum(sizes), len(sizes), E, obj.block_size_id)
             tr = [names[i] for i in g["index"]]
             dst = None if braw is None else _base_copy(braw, g, obj.device)       # (a copy: rebuilt in place, the bases stay)
-            if seg_log is not None:
+            if strides is not None and seg_log is not None:
+                dst, res = tensor_decompress_seg_each_stride_dbatch(self, g["frames"], g["frame_offsets"], offs, E, seg_log, tr, [strides[i] for i in g["index"]], dst,
+                                                                    g["seg_first"], dst=dst, max_total_blocks=blocks)
+            elif strides is not None:
+                dst, res = tensor_decompress_each_stride_dbatch(self, g["frames"], g["frame_offsets"], offs, E, tr, [strides[i] for i in g["index"]], dst, dst=dst,
+                                                                max_total_blocks=blocks)
+            elif seg_log is not None:
                 dst, res = tensor_decompress_seg_each_dbatch(self, g["frames"], g["frame_offsets"], offs, E, seg_log, tr, dst, g["seg_first"], dst=dst,
                                                              max_total_blocks=blocks)
             else:
@@ -4264,6 +4513,8 @@ def _planes_methods():
             raise ValueError(what + ": the object is not segmented (compress_tensors_each and compress_tensors_segmented write those with a segment_log)")
         if getattr(obj, "sparse_permille", None) is not None:
             raise ValueError(what + ": the object holds sparse planes (SparsePlanes); windows of those are not supported")
+        if any(st != 1 for st in (getattr(obj, "strides", None) or ())):
+            raise ValueError(what + ": the object holds a stride above 1 (compress_tensors_each with strides); windows of those are not supported")
         n = len(obj.dtypes)
         names, predictor = getattr(obj, "transforms", None), getattr(obj, "predictor", None)
         if names is not None:

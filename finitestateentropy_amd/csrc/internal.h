@@ -388,6 +388,17 @@ hipError_t launch_planes_merge_window_each(u8* dst, const u64* dstOff, size_t* r
 // the window form of that split (fsehip.h, "patching tensors with a transform per tensor"): the stage of a patch, the transform read per tensor
 hipError_t launch_planes_split_window_each(u8* stage, u64* planeOff, size_t* stageRes, const u8* src, const u8* base, const u8* transforms, const u64* srcOff,
                                            const u64* windows, const u64* stageOff, size_t nTensors, unsigned E, unsigned segLog, u64 capacity, u64 stageCapacity, hipStream_t s);
+// a stride per tensor (planes_each_stride.hip; fsehip.h, "a stride per tensor"): the two launchers above with strides[i], 1 ..
+// FSEHIP_PRED_MAX_STRIDE, read for the tensors whose transform is FSEHIP_EST_PRED; strides null: the two above
+hipError_t launch_planes_split_each_stride(u8* planes, u64* planeOff, size_t* tensorRes, const u8* src, const u8* base, const u8* transforms, const u8* strides,
+                                           const u64* srcOff, size_t nTensors, unsigned E, u64 capacity, hipStream_t s);
+hipError_t launch_planes_merge_each_stride(u8* dst, const u64* dstOff, size_t* results, const u8* planes, const u64* planeOff, const size_t* planeSizes, const u8* base,
+                                           const u8* transforms, const u8* strides, size_t nTensors, unsigned E, u64 dstCapacity, hipStream_t s);
+// the estimate over strides (planes_estimate.hip; fsehip.h, "strides in the estimate"): FSEHIP_planes_estimate_stride_dbatch with all its
+// argument checks; settle: d_strides[i] = 1 where the choice of an accepted tensor is not FSEHIP_EST_PRED (the CHOOSE composites)
+int planes_estimate_stride(uint64_t* d_planeBits, uint64_t* d_estBytes, uint8_t* d_choice, size_t* d_results, uint64_t* d_strideEstBytes, uint8_t* d_strides,
+                           const void* d_src, const void* d_base, const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes, uint64_t capacity,
+                           unsigned candidateMask, unsigned marginPermille, void* d_workspace, size_t workspaceBytes, unsigned strideMask, bool settle, void* stream);
 
 // ---- kernel timing probe (HIP events on the launch stream; used by bench.py for the live roofline figure) ----
 enum { PK_HIST = 0, PK_FSE_CPREP, PK_FSE_ENCODE, PK_FSE_DPREP, PK_FSE_DECODE, PK_HUF_CPREP, PK_HUF_ENCODE, PK_HUF_DPREP, PK_HUF_DECODE, PK_FSE_ENCODE_WAVE, PK_COUNT };

@@ -1,5 +1,5 @@
 // planes_dev.h -- what the plane files (planes.hip: byte planes of tensors and their delta forms; planes_seg.hip; planes_win.hip; planes_patch.hip) share: the byte
-// shuffle, the delta ops (XOR, subtract and zigzag), the register forms of the predicted planes (planes_pred.hip), the plane arithmetic, the search behind every work mapping, a workgroup's share of a tensor, the merge's verdict, the fold of a
+// shuffle, the delta ops (XOR, subtract and zigzag), the register forms of the predicted planes (planes_pred.hip) and of the strided ones (planes_stride.hip), the arms of the per-tensor kernels (planes_each.hip, planes_each_stride.hip), the plane arithmetic, the search behind every work mapping, a workgroup's share of a tensor, the merge's verdict, the fold of a
 // plane's segment results, the dispatch over the element size and the argument checks of the C calls.  Device helpers are inlined into the
 // kernels of the file that includes this; nothing here is a kernel.
 #pragma once
@@ -307,6 +307,320 @@ DEV size_t pm_verdict(const u64* D, const size_t* PS, size_t i, u32 E, u64 dstCa
     for (u32 p = 0; p < E; ++p) if ((u64)PS[i * E + p] != pl_size(n, p, E)) return FERR(corruption_detected);
     if (n > (d1 > d0 ? d1 - d0 : 0)) return FERR(dstSize_tooSmall);
     return (size_t)n;
+}
+
+// ---- strided predicted planes (planes_stride.hip, planes_each_stride.hip; fsehip.h, "strided predicted planes") ----
+// pv = the chunk w moved up by S elements: every element's predecessor.  Those of the first S are the S E bytes in front of `at` (where
+// the chunk lies in the source), or 0 where the chunk starts a run -- nothing in front of it is read then.  The bytes in front are loaded
+// as whole dwords, up to 3 bytes more than needed: a chunk that starts no run lies at least 16 elements inside its tensor, S E + 3 <= 16 E
+template <int E, int S> DEV void ps_prev(u32* pv, const u32* w, const u8* at, bool runStart)
+{
+    constexpr int FD = (S * E + 3) / 4, OFF = 4 * FD - S * E;
+    u32 x[FD + 4 * E];
+#pragma unroll
+    for (int j = 0; j < FD; ++j) x[j] = 0;
+    if (!runStart) __builtin_memcpy(x, at - 4 * FD, 4 * FD);
+#pragma unroll
+    for (int j = 0; j < 4 * E; ++j) x[FD + j] = w[j];
+#pragma unroll
+    for (int j = 0; j < 4 * E; ++j) {
+        if constexpr (OFF != 0) pv[j] = __builtin_amdgcn_alignbyte(x[j + 1], x[j], OFF);
+        else pv[j] = x[j];
+    }
+}
+// element e of the tensor at sb (n bytes) a thread per element, the split's head and tail (pp_elem_split with the predecessor S back)
+template <int E, int S> DEV void ps_elem_split(u8* pb, const u8* sb, u64 n, u64 e)
+{
+    const u64 k0 = e * E;
+    if (k0 + E <= n) {
+        u64 t = 0, b = 0;
+#pragma unroll
+        for (int p = 0; p < E; ++p) t |= (u64)sb[k0 + p] << (8 * p);
+        if ((e & (PP_RUN - 1)) >= (u64)S) {
+#pragma unroll
+            for (int p = 0; p < E; ++p) b |= (u64)sb[k0 - S * E + p] << (8 * p);
+        }
+        const u64 z = pl_zz<E>(t, b);
+#pragma unroll
+        for (int p = 0; p < E; ++p) pb[pl_start(n, p, E) + e] = (u8)(z >> (8 * p));
+    } else {
+        for (u64 k = k0; k < n; ++k) pb[pl_start(n, (u32)(k - k0), E) + e] = sb[k];
+    }
+}
+
+// the merge's arithmetic: an element per register, sums mod 2^32 (2^64 for E == 8).  For E < 4 the bits above the element are not kept
+// clean -- they never reach a bit below them -- and ps_pack drops them
+template <int E> using ps_t = std::conditional_t<E == 8, u64, u32>;
+template <int E> DEV void ps_unpack(ps_t<E>* x, const u32* w)
+{
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        if constexpr (E == 1) x[q] = w[q / 4] >> (8 * (q % 4));
+        else if constexpr (E == 2) x[q] = w[q / 2] >> (16 * (q % 2));
+        else if constexpr (E == 4) x[q] = w[q];
+        else x[q] = (u64)w[2 * q] | ((u64)w[2 * q + 1] << 32);
+    }
+}
+template <int E> DEV void ps_pack(u32* w, const ps_t<E>* x)
+{
+#pragma unroll
+    for (int k = 0; k < 4 * E; ++k) {
+        if constexpr (E == 1) w[k] = (x[4 * k] & 0xFFu) | ((x[4 * k + 1] & 0xFFu) << 8) | ((x[4 * k + 2] & 0xFFu) << 16) | (x[4 * k + 3] << 24);
+        else if constexpr (E == 2) w[k] = (x[2 * k] & 0xFFFFu) | (x[2 * k + 1] << 16);
+        else if constexpr (E == 4) w[k] = x[k];
+        else w[k] = (u32)(x[k / 2] >> (32 * (k % 2)));
+    }
+}
+// v[k] = v[(k + r) mod S] for a lane-dependent r < S: one round of selects per bit of r, static register indices throughout
+template <int S, class T> DEV void ps_rotate(T* v, u32 r)
+{
+#pragma unroll
+    for (int b = 1; b < S; b <<= 1) {
+        T t[S];
+#pragma unroll
+        for (int k = 0; k < S; ++k) t[k] = (r & (u32)b) ? v[(k + b) % S] : v[k];
+#pragma unroll
+        for (int k = 0; k < S; ++k) v[k] = t[k];
+    }
+}
+// A workgroup's share of the split of the tensor at sb (n bytes at flat position s0, planes at pb) at stride S: the body of
+// k_planes_split_pred_stride and of the strided PRED arms of k_planes_split_each_stride
+template <int E, int S> DEV void ps_split(u8* pb, const u8* sb, u64 s0, u64 n, u64 lo, u32 tid)
+{
+    const PlShare h = pl_share<E>(s0, n, lo, 0, 1);               // chunks at multiples of 16 elements of the tensor
+    for (u64 c = tid; c < h.nch; c += PL_THREADS) {
+        const u64 e = h.eb + 16 * c;
+        u32 wv[4 * E], pv[4 * E], o[E][4];
+#pragma unroll
+        for (int k = 0; k < E; ++k) __builtin_memcpy(&wv[4 * k], sb + e * E + 16 * k, 16);
+        ps_prev<E, S>(pv, wv, sb + e * E, (e & (PP_RUN - 1)) == 0);
+#pragma unroll
+        for (int k = 0; k < E; ++k) pl_sub4<E, false>(&wv[4 * k], &pv[4 * k]);
+        pl_deinterleave<E>(wv, o);
+#pragma unroll
+        for (int p = 0; p < E; ++p) __builtin_memcpy(pb + pl_start(n, p, E) + e, o[p], 16);
+    }
+    const u64 nHead = h.eb - h.e0, nTail = h.e1 - h.et;
+    for (u64 j = tid; j < nHead + nTail; j += PL_THREADS) ps_elem_split<E, S>(pb, sb, n, j < nHead ? h.e0 + j : h.et + (j - nHead));
+}
+// The runs of tile t of the merge of the tensor at db (n bytes, plane p at planes + P[p]) at stride S: the body of
+// k_planes_merge_pred_stride and of the strided PRED arms of k_planes_merge_each_stride.  All 64 lanes of a wave take every scan
+template <int E, int S> DEV void ps_merge(u8* db, const u8* planes, const u64* P, u64 n, u64 t)
+{
+    typedef ps_t<E> T;
+    constexpr u32 RUNS = (u32)(PLANES_TILE / E / PP_RUN);         // whole runs of a tile
+    constexpr bool ROT = 16 % S != 0;                             // the chain of a register depends on the lane
+    const u64 m = n / E;
+    const u32 lane = threadIdx.x % WAVE;
+    const u32 r0 = ROT ? (16 * lane) % S : 0;                     // register q of this lane lies in chain (r0 + q) mod S
+    const u32 rEnd = ROT ? (S - (r0 + 16) % S) % S : 0;           // chain a's last element is register 16 - S + (a + rEnd) mod S
+    const u8* pp[E];
+#pragma unroll
+    for (int p = 0; p < E; ++p) pp[p] = planes + P[p];
+    for (u32 r = threadIdx.x / WAVE; r < RUNS; r += PL_THREADS / WAVE) {
+        const u64 e0 = t * (PLANES_TILE / E) + r * PP_RUN, e = e0 + 16 * lane;
+        if (e0 * E >= n) break;                                   // (uniform over the wave: the run lies behind the tensor)
+        const bool full = e + 16 <= m;
+        T x[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) x[q] = 0;
+        if (full) {
+            u32 wv[4 * E], o[E][4];
+            const u32 zero[4] = { 0, 0, 0, 0 };
+#pragma unroll
+            for (int p = 0; p < E; ++p) __builtin_memcpy(o[p], pp[p] + e, 16);
+            pl_interleave<E>(wv, o);
+#pragma unroll
+            for (int k = 0; k < E; ++k) pl_sub4<E, true>(&wv[4 * k], zero);
+            ps_unpack<E>(x, wv);
+#pragma unroll
+            for (int q = S; q < 16; ++q) x[q] += x[q - S];
+        }
+        T c[S];                                                   // chain by chain, what the lanes in front of this one add up to: all 64 lanes scan
+#pragma unroll
+        for (int k = 0; k < S; ++k) c[k] = x[16 - S + k];
+        if constexpr (ROT) ps_rotate<S>(c, rEnd);
+#pragma unroll
+        for (int k = 0; k < S; ++k) {
+            if constexpr (E == 8) c[k] = group_scan_incl_add64<64>(c[k], lane) - c[k];
+            else c[k] = group_scan_incl<64, ScanAdd>(c[k], lane) - c[k];
+        }
+        if constexpr (ROT) ps_rotate<S>(c, r0);                   // c[k]: the carry-in of the registers q with q mod S == k
+        if (full) {
+            u32 wv[4 * E];
+#pragma unroll
+            for (int q = 0; q < 16; ++q) x[q] += c[q % S];
+            ps_pack<E>(wv, x);
+#pragma unroll
+            for (int k = 0; k < E; ++k) __builtin_memcpy(db + e * E + 16 * k, &wv[4 * k], 16);
+        } else if (e * E < n) {                                   // the tensor's last chunk: fewer than 16 whole elements, then n mod E bytes
+            u64 acc[S];
+#pragma unroll
+            for (int k = 0; k < S; ++k) acc[k] = c[k];
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const u64 j = e + q;
+                if (j < m) {
+                    u64 z = 0;
+#pragma unroll
+                    for (int p = 0; p < E; ++p) z |= (u64)pp[p][j] << (8 * p);
+                    acc[q % S] = pl_unzz<E>(z, acc[q % S]);
+#pragma unroll
+                    for (int p = 0; p < E; ++p) db[j * E + p] = (u8)(acc[q % S] >> (8 * p));
+                }
+            }
+            for (u64 k = m * E; k < n; ++k) db[k] = planes[P[k - m * E] + m];
+        }
+    }
+}
+// the dispatch over a stride above 1: f(std::integral_constant<int, S>) for 2 <= S <= FSEHIP_PRED_MAX_STRIDE (bad_stride has let it through; on
+// the device: the stride byte of an accepted tensor).  A switch, so that every body has its S as a constant and static register indices
+template <class F> HDEV void ps_for_stride(unsigned S, F f)
+{
+    switch (S) {
+    case 2: f(std::integral_constant<int, 2>()); break;
+    case 3: f(std::integral_constant<int, 3>()); break;
+    case 4: f(std::integral_constant<int, 4>()); break;
+    case 5: f(std::integral_constant<int, 5>()); break;
+    case 6: f(std::integral_constant<int, 6>()); break;
+    case 7: f(std::integral_constant<int, 7>()); break;
+    default: f(std::integral_constant<int, 8>()); break;
+    }
+}
+static_assert(FSEHIP_PRED_MAX_STRIDE == 8, "the strides the kernels are instantiated for");
+HDEV bool bad_stride(unsigned stride) { return stride == 0 || stride > FSEHIP_PRED_MAX_STRIDE; }
+
+// ---- a transform per tensor (planes_each.hip, planes_each_stride.hip; fsehip.h, "a transform per tensor") ----
+DEV bool pe_ok(u32 tr, const void* base) { return tr <= FSEHIP_EST_SUB && (tr < FSEHIP_EST_XOR || base); }
+// a workgroup's share of the tensor at sb (n bytes at flat position s0, base bb, planes at pb) under transform TR
+template <int E, int TR> DEV void pe_split(u8* pb, const u8* sb, const u8* bb, u64 s0, u64 n, u64 lo, u32 tid)
+{
+    const PlShare h = pl_share<E>(s0, n, lo, 0, 1);               // chunks at multiples of 16 elements of the tensor
+    for (u64 c = tid; c < h.nch; c += PL_THREADS) {
+        const u64 e = h.eb + 16 * c;
+        u32 wv[4 * E], o[E][4];
+#pragma unroll
+        for (int k = 0; k < E; ++k) __builtin_memcpy(&wv[4 * k], sb + e * E + 16 * k, 16);
+        if constexpr (TR == FSEHIP_EST_PRED) {
+            u32 pv[4 * E];
+            pp_prev<E>(pv, wv, sb + e * E, (e & (PP_RUN - 1)) == 0);
+#pragma unroll
+            for (int k = 0; k < E; ++k) pl_sub4<E, false>(&wv[4 * k], &pv[4 * k]);
+        } else if constexpr (TR != FSEHIP_EST_PLAIN) {
+#pragma unroll
+            for (int k = 0; k < E; ++k) pl_base16<E, TR == FSEHIP_EST_SUB ? PL_SUB : PL_XOR, false>(&wv[4 * k], bb + e * E + 16 * k);
+        }
+        pl_deinterleave<E>(wv, o);
+#pragma unroll
+        for (int p = 0; p < E; ++p) __builtin_memcpy(pb + pl_start(n, p, E) + e, o[p], 16);
+    }
+    // head and tail, an element per thread; the partial last element of the tensor byte by byte
+    const u64 nHead = h.eb - h.e0, nTail = h.e1 - h.et;
+    for (u64 j = tid; j < nHead + nTail; j += PL_THREADS) {
+        const u64 e = j < nHead ? h.e0 + j : h.et + (j - nHead);
+        if constexpr (TR == FSEHIP_EST_PRED) pp_elem_split<E>(pb, sb, n, e);
+        else if constexpr (TR == FSEHIP_EST_SUB) pl_sub_elem_split<E>(pb, sb, bb, n, e);
+        else {
+#pragma unroll
+            for (int p = 0; p < E; ++p) {
+                const u64 k = e * E + p;
+                if (k < n) {
+                    u8 v = sb[k];
+                    if constexpr (TR == FSEHIP_EST_XOR) v ^= bb[k];
+                    pb[pl_start(n, p, E) + e] = v;
+                }
+            }
+        }
+    }
+}
+// the runs of tile t of the tensor at db (n bytes, base bb, plane p at planes + P[p]) under transform TR.  WIN: db, n and t are those of the
+// virtual tensor, whose planes start L bytes in front of P[p] and whose first L elements are not stored (n is a multiple of E there)
+template <int E, int TR, bool WIN = false> DEV void pe_merge(u8* db, const u8* bb, const u8* planes, const u64* P, u64 n, u64 t, u64 L = 0)
+{
+    constexpr u32 RUNS = (u32)(PLANES_TILE / E / PP_RUN);         // whole runs of a tile
+    const u64 m = n / E;
+    const u32 lane = threadIdx.x % WAVE;
+    const u8* pp[E];
+#pragma unroll
+    for (int p = 0; p < E; ++p) pp[p] = planes + P[p];
+    if constexpr (WIN) {
+#pragma unroll
+        for (int p = 0; p < E; ++p) pp[p] -= L;
+    }
+    for (u32 r = threadIdx.x / WAVE; r < RUNS; r += PL_THREADS / WAVE) {
+        const u64 e0 = t * (PLANES_TILE / E) + r * PP_RUN, e = e0 + 16 * lane;
+        if (e0 * E >= n) break;                                   // (uniform over the wave: the run lies behind the tensor)
+        const bool full = e + 16 <= m;
+        u32 wv[4 * E];
+        if constexpr (TR == FSEHIP_EST_PRED) {
+            u64 total = 0;
+            if (full) {
+                u32 o[E][4];
+                const u32 zero[4] = { 0, 0, 0, 0 };
+#pragma unroll
+                for (int p = 0; p < E; ++p) __builtin_memcpy(o[p], pp[p] + e, 16);
+                pl_interleave<E>(wv, o);
+#pragma unroll
+                for (int k = 0; k < E; ++k) pl_sub4<E, true>(&wv[4 * k], zero);
+                total = pp_prefix<E>(wv);
+            }
+            u64 carry;                                            // what the lanes in front of this one add up to: all 64 lanes scan
+            if constexpr (E == 8) carry = group_scan_incl_add64<64>(total, lane) - total;
+            else carry = group_scan_incl<64, ScanAdd>((u32)total, lane) - (u32)total;
+            if (full) {
+                pp_carry<E>(wv, carry);
+                bool whole = true;
+                if constexpr (WIN) whole = e >= L;
+                if (whole) {
+#pragma unroll
+                    for (int k = 0; k < E; ++k) __builtin_memcpy(db + e * E + 16 * k, &wv[4 * k], 16);
+                } else {
+                    if constexpr (WIN) {                          // the chunk that straddles the lead: its elements from L on, one by one
+#pragma unroll
+                        for (int j = 0; j < 16; ++j)
+                            if (e + j >= L) __builtin_memcpy(db + (e + j) * E, (const u8*)wv + j * E, E);
+                    }
+                }
+            } else if (e * E < n) {                               // the tensor's last chunk: fewer than 16 whole elements, then n mod E bytes
+                u64 acc = carry;
+                for (u64 j = e; j < m; ++j) {
+                    u64 z = 0;
+#pragma unroll
+                    for (int p = 0; p < E; ++p) z |= (u64)pp[p][j] << (8 * p);
+                    acc = pl_unzz<E>(z, acc);
+                    if (WIN && j < L) continue;                   // (the lead: summed, not stored)
+#pragma unroll
+                    for (int p = 0; p < E; ++p) db[j * E + p] = (u8)(acc >> (8 * p));
+                }
+                if constexpr (!WIN)
+                    for (u64 k = m * E; k < n; ++k) db[k] = planes[P[k - m * E] + m];
+            }
+        } else if (full) {
+            u32 o[E][4];
+#pragma unroll
+            for (int p = 0; p < E; ++p) __builtin_memcpy(o[p], pp[p] + e, 16);
+            pl_interleave<E>(wv, o);
+            if constexpr (TR != FSEHIP_EST_PLAIN) {
+#pragma unroll
+                for (int k = 0; k < E; ++k)                       // (in place: these loads, then the stores below)
+                    pl_base16<E, TR == FSEHIP_EST_SUB ? PL_SUB : PL_XOR, true>(&wv[4 * k], bb + e * E + 16 * k);
+            }
+#pragma unroll
+            for (int k = 0; k < E; ++k) __builtin_memcpy(db + e * E + 16 * k, &wv[4 * k], 16);
+        } else if (e * E < n) {                                   // the tensor's last chunk, an element at a time (in place: its loads, then its stores)
+            if constexpr (TR == FSEHIP_EST_SUB) {
+                for (u64 j = e; j * E < n; ++j) pl_sub_elem_merge<E>(db, bb, n, j, [&](u32 p) { return planes + P[p]; });
+            } else {
+                for (u64 j = e; j * E < n; ++j) {
+                    for (u64 k = j * E; k < n && k < (j + 1) * E; ++k) {
+                        u8 v = planes[P[k - j * E] + j];
+                        if constexpr (TR == FSEHIP_EST_XOR) v ^= bb[k];
+                        db[k] = v;
+                    }
+                }
+            }
+        }
+    }
 }
 
 // ---- segmented planes (planes_seg.hip; fsehip.h, "segmented planes") ----

@@ -51,8 +51,7 @@
 #include "planes_dev.h"
 
 namespace {
-DEV bool pe_ok(u32 tr, const void* base) { return tr <= FSEHIP_EST_SUB && (tr < FSEHIP_EST_XOR || base); }
-
+// (pe_ok and the arms pe_split and pe_merge are in planes_dev.h: planes_each_stride.hip takes the same ones)
 __global__ void k_each_refuse(size_t* res, const u8* T, const u8* base, size_t nT)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -79,48 +78,6 @@ __global__ void k_each_refuse_window(size_t* res, const u8* T, const u8* base, c
 }
 
 // ---- split -------------------------------------------------------------------------------------------------------------------------------
-// a workgroup's share of the tensor at sb (n bytes at flat position s0, base bb, planes at pb) under transform TR
-template <int E, int TR> DEV void pe_split(u8* pb, const u8* sb, const u8* bb, u64 s0, u64 n, u64 lo, u32 tid)
-{
-    const PlShare h = pl_share<E>(s0, n, lo, 0, 1);               // chunks at multiples of 16 elements of the tensor
-    for (u64 c = tid; c < h.nch; c += PL_THREADS) {
-        const u64 e = h.eb + 16 * c;
-        u32 wv[4 * E], o[E][4];
-#pragma unroll
-        for (int k = 0; k < E; ++k) __builtin_memcpy(&wv[4 * k], sb + e * E + 16 * k, 16);
-        if constexpr (TR == FSEHIP_EST_PRED) {
-            u32 pv[4 * E];
-            pp_prev<E>(pv, wv, sb + e * E, (e & (PP_RUN - 1)) == 0);
-#pragma unroll
-            for (int k = 0; k < E; ++k) pl_sub4<E, false>(&wv[4 * k], &pv[4 * k]);
-        } else if constexpr (TR != FSEHIP_EST_PLAIN) {
-#pragma unroll
-            for (int k = 0; k < E; ++k) pl_base16<E, TR == FSEHIP_EST_SUB ? PL_SUB : PL_XOR, false>(&wv[4 * k], bb + e * E + 16 * k);
-        }
-        pl_deinterleave<E>(wv, o);
-#pragma unroll
-        for (int p = 0; p < E; ++p) __builtin_memcpy(pb + pl_start(n, p, E) + e, o[p], 16);
-    }
-    // head and tail, an element per thread; the partial last element of the tensor byte by byte
-    const u64 nHead = h.eb - h.e0, nTail = h.e1 - h.et;
-    for (u64 j = tid; j < nHead + nTail; j += PL_THREADS) {
-        const u64 e = j < nHead ? h.e0 + j : h.et + (j - nHead);
-        if constexpr (TR == FSEHIP_EST_PRED) pp_elem_split<E>(pb, sb, n, e);
-        else if constexpr (TR == FSEHIP_EST_SUB) pl_sub_elem_split<E>(pb, sb, bb, n, e);
-        else {
-#pragma unroll
-            for (int p = 0; p < E; ++p) {
-                const u64 k = e * E + p;
-                if (k < n) {
-                    u8 v = sb[k];
-                    if constexpr (TR == FSEHIP_EST_XOR) v ^= bb[k];
-                    pb[pl_start(n, p, E) + e] = v;
-                }
-            }
-        }
-    }
-}
-
 template <int E>
 __global__ __launch_bounds__(PL_THREADS) void k_planes_split_each(u8* planes, const u8* src, const u8* base, const u8* T, const u64* S, size_t nT, u64 capacity)
 {
@@ -182,96 +139,6 @@ __global__ __launch_bounds__(PL_THREADS) void k_planes_split_window_each(u8* sta
 }
 
 // ---- merge -------------------------------------------------------------------------------------------------------------------------------
-// the runs of tile t of the tensor at db (n bytes, base bb, plane p at planes + P[p]) under transform TR.  WIN: db, n and t are those of the
-// virtual tensor, whose planes start L bytes in front of P[p] and whose first L elements are not stored (n is a multiple of E there)
-template <int E, int TR, bool WIN = false> DEV void pe_merge(u8* db, const u8* bb, const u8* planes, const u64* P, u64 n, u64 t, u64 L = 0)
-{
-    constexpr u32 RUNS = (u32)(PLANES_TILE / E / PP_RUN);         // whole runs of a tile
-    const u64 m = n / E;
-    const u32 lane = threadIdx.x % WAVE;
-    const u8* pp[E];
-#pragma unroll
-    for (int p = 0; p < E; ++p) pp[p] = planes + P[p];
-    if constexpr (WIN) {
-#pragma unroll
-        for (int p = 0; p < E; ++p) pp[p] -= L;
-    }
-    for (u32 r = threadIdx.x / WAVE; r < RUNS; r += PL_THREADS / WAVE) {
-        const u64 e0 = t * (PLANES_TILE / E) + r * PP_RUN, e = e0 + 16 * lane;
-        if (e0 * E >= n) break;                                   // (uniform over the wave: the run lies behind the tensor)
-        const bool full = e + 16 <= m;
-        u32 wv[4 * E];
-        if constexpr (TR == FSEHIP_EST_PRED) {
-            u64 total = 0;
-            if (full) {
-                u32 o[E][4];
-                const u32 zero[4] = { 0, 0, 0, 0 };
-#pragma unroll
-                for (int p = 0; p < E; ++p) __builtin_memcpy(o[p], pp[p] + e, 16);
-                pl_interleave<E>(wv, o);
-#pragma unroll
-                for (int k = 0; k < E; ++k) pl_sub4<E, true>(&wv[4 * k], zero);
-                total = pp_prefix<E>(wv);
-            }
-            u64 carry;                                            // what the lanes in front of this one add up to: all 64 lanes scan
-            if constexpr (E == 8) carry = group_scan_incl_add64<64>(total, lane) - total;
-            else carry = group_scan_incl<64, ScanAdd>((u32)total, lane) - (u32)total;
-            if (full) {
-                pp_carry<E>(wv, carry);
-                bool whole = true;
-                if constexpr (WIN) whole = e >= L;
-                if (whole) {
-#pragma unroll
-                    for (int k = 0; k < E; ++k) __builtin_memcpy(db + e * E + 16 * k, &wv[4 * k], 16);
-                } else {
-                    if constexpr (WIN) {                          // the chunk that straddles the lead: its elements from L on, one by one
-#pragma unroll
-                        for (int j = 0; j < 16; ++j)
-                            if (e + j >= L) __builtin_memcpy(db + (e + j) * E, (const u8*)wv + j * E, E);
-                    }
-                }
-            } else if (e * E < n) {                               // the tensor's last chunk: fewer than 16 whole elements, then n mod E bytes
-                u64 acc = carry;
-                for (u64 j = e; j < m; ++j) {
-                    u64 z = 0;
-#pragma unroll
-                    for (int p = 0; p < E; ++p) z |= (u64)pp[p][j] << (8 * p);
-                    acc = pl_unzz<E>(z, acc);
-                    if (WIN && j < L) continue;                   // (the lead: summed, not stored)
-#pragma unroll
-                    for (int p = 0; p < E; ++p) db[j * E + p] = (u8)(acc >> (8 * p));
-                }
-                if constexpr (!WIN)
-                    for (u64 k = m * E; k < n; ++k) db[k] = planes[P[k - m * E] + m];
-            }
-        } else if (full) {
-            u32 o[E][4];
-#pragma unroll
-            for (int p = 0; p < E; ++p) __builtin_memcpy(o[p], pp[p] + e, 16);
-            pl_interleave<E>(wv, o);
-            if constexpr (TR != FSEHIP_EST_PLAIN) {
-#pragma unroll
-                for (int k = 0; k < E; ++k)                       // (in place: these loads, then the stores below)
-                    pl_base16<E, TR == FSEHIP_EST_SUB ? PL_SUB : PL_XOR, true>(&wv[4 * k], bb + e * E + 16 * k);
-            }
-#pragma unroll
-            for (int k = 0; k < E; ++k) __builtin_memcpy(db + e * E + 16 * k, &wv[4 * k], 16);
-        } else if (e * E < n) {                                   // the tensor's last chunk, an element at a time (in place: its loads, then its stores)
-            if constexpr (TR == FSEHIP_EST_SUB) {
-                for (u64 j = e; j * E < n; ++j) pl_sub_elem_merge<E>(db, bb, n, j, [&](u32 p) { return planes + P[p]; });
-            } else {
-                for (u64 j = e; j * E < n; ++j) {
-                    for (u64 k = j * E; k < n && k < (j + 1) * E; ++k) {
-                        u8 v = planes[P[k - j * E] + j];
-                        if constexpr (TR == FSEHIP_EST_XOR) v ^= bb[k];
-                        db[k] = v;
-                    }
-                }
-            }
-        }
-    }
-}
-
 // Win: empty -- the merge, launched as ever -- or the one more argument of the window form, const u64* W
 template <int E, class... Win>
 __global__ __launch_bounds__(PL_THREADS) void k_planes_merge_each(u8* dst, const u64* D, const u8* planes, const u64* PO, const size_t* PS, const u8* base, const u8* T,

@@ -6,6 +6,9 @@
 //   FSEHIP_planes_estimate_dbatch : k_est_zero (the counters of the workspace) -> k_est_count (a workgroup per (tile, tensor): LDS histograms
 //                                   per candidate and plane, flushed into the tensor's counters) -> k_est_finish (a wave per tensor: the cost
 //                                   of every plane, the estimates, the choice, the result)
+//   FSEHIP_planes_estimate_stride_dbatch : k_est_zero -> k_est_count (the candidates beside PRED) -> k_est_count_stride (PRED at every
+//                                   requested stride 1 .. 8) -> k_est_finish_stride (the stride choice in front of the transform choice):
+//                                   "strides in the estimate", below the kernels of the first call
 //
 // THE COUNT is k_planes_split_pred's frame (planes_pred.hip): the flat ragged mapping, chunks of 16 whole elements per lane counted from the
 // TENSOR's start (so a run starts only where a chunk does, and a chunk's dwords hold whole elements for the subtraction), head and tail an
@@ -231,6 +234,18 @@ __global__ __launch_bounds__(PL_THREADS) void k_est_count(u32* counters, const u
     }
 }
 
+// bits256 of the plane of N bytes whose counters are cp[0 .. 256): four bins per lane, all 64 lanes in the scan; the same on every lane
+DEV u64 est_plane_bits(const u32* cp, u64 N, u32 lane)
+{
+    const u32 LN = est_L(N);
+    u64 part = 0;
+#pragma unroll
+    for (u32 k = 0; k < 4; ++k) {
+        const u32 cnt = cp[lane + WAVE * k];
+        if (cnt) part += (u64)cnt * (LN - est_L(cnt));
+    }
+    return group_last64<64>(group_scan_incl_add64<64>(part, lane), lane);
+}
 // A wave per tensor.  Every branch in front of a scan depends on the tensor and the mask alone: all 64 lanes take it together
 __global__ __launch_bounds__(WAVE) void k_est_finish(u64* planeBits, u64* estBytes, u8* choice, size_t* results, const u32* counters, const u64* S, size_t nT, u32 E,
                                                      u64 capacity, u32 mask, u32 margin)
@@ -250,14 +265,7 @@ __global__ __launch_bounds__(WAVE) void k_est_finish(u64* planeBits, u64* estByt
             if (req) {
                 const u32* const cp = counters + (((u64)i * nReq + est_rank(mask, c)) * E + p) * 256;
                 const u64 N = pl_size(n, p, E);
-                const u32 LN = est_L(N);
-                u64 part = 0;
-#pragma unroll
-                for (u32 k = 0; k < 4; ++k) {
-                    const u32 cnt = cp[lane + WAVE * k];
-                    if (cnt) part += (u64)cnt * (LN - est_L(cnt));
-                }
-                bits = group_last64<64>(group_scan_incl_add64<64>(part, lane), lane);
+                bits = est_plane_bits(cp, N, lane);
                 const u64 b = (bits + 2047) >> 11;
                 sum += b < N ? b : N;
             }
@@ -275,6 +283,163 @@ __global__ __launch_bounds__(WAVE) void k_est_finish(u64* planeBits, u64* estByt
         }
     }
     choice[i] = (u8)best;
+    results[i] = ok ? (size_t)n : inside ? FERR(srcSize_wrong) : FERR(GENERIC);
+}
+
+// ---- strides in the estimate (fsehip.h, "strides in the estimate") ---------------------------------------------------------------------------
+// k_est_count_stride is k_est_count for the PRED candidate at every requested stride 1 .. 8: the same frame, the same columns and hot-bin
+// paths, one histogram set of E planes per REQUESTED stride in dynamic LDS -- 8 KB each for every E, so four strides take the 32 KB of
+// k_est_count and all eight 64 KB.  A lane loads its chunk once and the 8 elements in front of it (zeros where the chunk starts a run: the
+// chain heads of every stride), and every stride's predecessors are those 24 elements moved in registers (est_prev), as ps_prev moves
+// them.  The stride set is an argument that is uniform over the launch: a stride that is not asked for costs neither a load nor a branch
+// taken.  PLAIN, XOR and SUB are counted by k_est_count in a launch of its own (EXPERIMENTS.md: why not in this one).
+#define EST_STRIDES ((u32)FSEHIP_PRED_MAX_STRIDE)
+// y: the 8 elements in front of a chunk (2 E dwords), then the chunk (4 E dwords) -> pv: the chunk's predecessors at stride S
+template <int E, int S> DEV void est_prev(u32* pv, const u32* y)
+{
+    constexpr int B = (8 - S) * E, D = B / 4, OFF = B % 4;
+#pragma unroll
+    for (int j = 0; j < 4 * E; ++j) {
+        if constexpr (OFF != 0) pv[j] = __builtin_amdgcn_alignbyte(y[D + j + 1], y[D + j], OFF);
+        else pv[j] = y[D + j];
+    }
+}
+// the strides S .. 8 of a chunk, each into the histograms of its rank among the requested ones
+template <int E, int S> DEV void est_stride_chunks(u32* hist, u32 smask, const u32* y, u32 col)
+{
+    constexpr u32 HC = (E * 256) << EstCols<E>::LOG;
+    if (smask & (1u << (S - 1))) {
+        u32 pv[4 * E], t[4 * E];
+        est_prev<E, S>(pv, y);
+#pragma unroll
+        for (int j = 0; j < 4 * E; ++j) t[j] = y[2 * E + j];
+#pragma unroll
+        for (int k = 0; k < E; ++k) pl_sub4<E, false>(&t[4 * k], &pv[4 * k]);
+        est_count_chunk<E>(hist + est_rank(smask, S - 1) * HC, t, col);
+    }
+    if constexpr (S < (int)EST_STRIDES) est_stride_chunks<E, S + 1>(hist, smask, y, col);
+}
+// element e of the tensor at sb (n bytes) a thread per element, head and tail: every requested stride's bytes of it, as ps_elem_split places them
+template <int E> DEV void est_stride_elem(u32* hist, u32 smask, const u8* sb, u64 n, u64 e)
+{
+    constexpr u32 CL = EstCols<E>::LOG, HC = (E * 256) << CL;      // (head and tail: column 0)
+    const u64 k0 = e * E;
+    u64 t = 0;
+    if (k0 + E <= n) {
+#pragma unroll
+        for (int p = 0; p < E; ++p) t |= (u64)sb[k0 + p] << (8 * p);
+    }
+    u32 r = 0;
+    for (u32 s = 1; s <= EST_STRIDES; ++s) {
+        if (!((smask >> (s - 1)) & 1u)) continue;
+        u32* const hc = hist + r++ * HC;
+        if (k0 + E <= n) {
+            u64 pr = 0;
+            if ((e & (PP_RUN - 1)) >= s) {
+#pragma unroll
+                for (int p = 0; p < E; ++p) pr |= (u64)sb[k0 - (u64)s * E + p] << (8 * p);
+            }
+            est_count_elem<E>(hc, pl_zz<E>(t, pr));
+        } else {
+            for (u64 k = k0; k < n; ++k) atomicAdd(&hc[(256u * (u32)(k - k0) + sb[k]) << CL], 1u);
+        }
+    }
+}
+
+// counters: per tensor popcount(smask) x E x 256 words, the requested strides in rising order.  `smask` is uniform over the launch
+template <int E>
+__global__ __launch_bounds__(PL_THREADS) void k_est_count_stride(u32* counters, const u8* src, const u64* S, size_t nT, u64 capacity, u32 smask)
+{
+    constexpr u32 CL = EstCols<E>::LOG, HC = (E * 256) << CL;      // words per stride: 8 KB
+    extern __shared__ __attribute__((aligned(16))) u32 shist[];   // popcount(smask) x HC words
+    const u64 w = blockIdx.x;
+    size_t i;
+    if (!pl_find(S, nT, w, i)) return;                            // (uniform, like every return below)
+    const u64 s0 = S[i], s1 = S[i + 1], lo = (w - i) << PL_TILE_LOG;
+    if (!(s0 < s1) || s1 > capacity || s1 - s0 >= EST_MAX || lo >= s1 || lo + PLANES_TILE <= s0) return;
+    const u64 n = s1 - s0;
+    const u32 tid = threadIdx.x, col = tid & (EstCols<E>::N - 1u), nReq = (u32)__builtin_popcount(smask);
+    const u8* const sb = src + s0;
+    for (u32 k = tid; k < nReq * (HC / 4); k += PL_THREADS) ((uint4*)shist)[k] = make_uint4(0, 0, 0, 0);
+    __syncthreads();
+    const PlShare h = pl_share<E>(s0, n, lo, 0, 1);               // chunks at multiples of 16 elements of the tensor
+    for (u64 c = tid; c < h.nch; c += PL_THREADS) {
+        const u64 e = h.eb + 16 * c;
+        u32 y[6 * E];
+#pragma unroll
+        for (int j = 0; j < 2 * E; ++j) y[j] = 0;
+        if (e & (PP_RUN - 1)) __builtin_memcpy(y, sb + e * E - 8 * E, 8 * E);      // (no run starts here: at least 16 elements lie in front)
+#pragma unroll
+        for (int k = 0; k < E; ++k) __builtin_memcpy(&y[2 * E + 4 * k], sb + e * E + 16 * k, 16);
+        est_stride_chunks<E, 1>(shist, smask, y, col);
+    }
+    const u64 nHead = h.eb - h.e0, nTail = h.e1 - h.et;
+    for (u64 j = tid; j < nHead + nTail; j += PL_THREADS) est_stride_elem<E>(shist, smask, sb, n, j < nHead ? h.e0 + j : h.et + (j - nHead));
+    __syncthreads();
+    u32* const ct = counters + (u64)i * nReq * (E * 256);          // the flush: this tile's non-zero bins into the tensor's counters
+    for (u32 k = tid; k < nReq * (E * 256); k += PL_THREADS) {
+        u32 v = 0;
+#pragma unroll
+        for (u32 j = 0; j < EstCols<E>::N; ++j) v += shist[(k << CL) + j];
+        if (v) atomicAdd(&ct[k], v);
+    }
+}
+
+// k_est_finish with the stride choice in front of the transform choice.  cA: the counters of k_est_count for mask & ~PRED; cB: those of
+// k_est_count_stride (PRED requested: nS = popcount(smask) sets per tensor, else none).  The PRED slots hold the numbers of the chosen
+// stride.  Every branch in front of a scan depends on the tensor, the masks and numbers that are the same on every lane
+__global__ __launch_bounds__(WAVE) void k_est_finish_stride(u64* planeBits, u64* estBytes, u8* choice, size_t* results, u64* strideEst, u8* strides, const u32* cA,
+                                                            const u32* cB, const u64* S, size_t nT, u32 E, u64 capacity, u32 mask, u32 smask, u32 margin, u32 settle)
+{
+    const size_t i = blockIdx.x;
+    const u32 lane = threadIdx.x;
+    const u64 s0 = S[i], s1 = S[i + 1];
+    const bool inside = s0 <= s1 && s1 <= capacity, ok = inside && s1 - s0 < EST_MAX;
+    const u64 n = ok ? s1 - s0 : 0;
+    const u32 maskA = mask & ~(u32)EST_M_PRED, nA = (u32)__builtin_popcount(maskA), nS = (mask & EST_M_PRED) ? (u32)__builtin_popcount(smask) : 0;
+    const u32* const tB = cB + (u64)i * nS * E * 256;
+    u32 bs = 0xFFu;                                               // the best stride so far, as its bit number
+    u64 estBs = 0;
+    for (u32 s = 0; s < EST_STRIDES; ++s) {
+        const bool req = ok && nS && ((smask >> s) & 1u);
+        u64 sum = req ? 0 : ~(u64)0;
+        if (req) {
+            for (u32 p = 0; p < E; ++p) {
+                const u64 N = pl_size(n, p, E), b = (est_plane_bits(tB + (est_rank(smask, s) * E + p) * 256, N, lane) + 2047) >> 11;
+                sum += b < N ? b : N;
+            }
+            if (bs == 0xFFu || sum * 1000 < estBs * (1000 - margin)) { bs = s; estBs = sum; }
+        }
+        if (lane == 0 && strideEst) strideEst[(u64)i * EST_STRIDES + s] = sum;
+    }
+    u64 est[EST_CANDS];
+    for (u32 c = 0; c < EST_CANDS; ++c) {
+        const bool req = ok && ((mask >> c) & 1u);
+        u64 sum = req ? 0 : ~(u64)0;
+        for (u32 p = 0; p < E; ++p) {
+            u64 bits = ~(u64)0;
+            if (req) {
+                const u32* const cp = c == FSEHIP_EST_PRED ? tB + (est_rank(smask, bs) * E + p) * 256 : cA + (((u64)i * nA + est_rank(maskA, c)) * E + p) * 256;
+                const u64 N = pl_size(n, p, E);
+                bits = est_plane_bits(cp, N, lane);
+                const u64 b = (bits + 2047) >> 11;
+                sum += b < N ? b : N;
+            }
+            if (lane == 0) planeBits[((u64)i * EST_CANDS + c) * E + p] = bits;
+        }
+        est[c] = sum;
+        if (lane == 0) estBytes[(u64)i * EST_CANDS + c] = sum;
+    }
+    if (lane != 0) return;
+    u32 best = 0xFFu;
+    if (ok) {
+        for (u32 c = 0; c < EST_CANDS; ++c) {
+            if (!((mask >> c) & 1u)) continue;
+            if (best == 0xFFu || est[c] * 1000 < est[best] * (1000 - margin)) best = c;
+        }
+    }
+    choice[i] = (u8)best;
+    strides[i] = !ok ? (u8)0xFF : (bs == 0xFFu || (settle && best != FSEHIP_EST_PRED)) ? (u8)1 : (u8)(bs + 1);
     results[i] = ok ? (size_t)n : inside ? FERR(srcSize_wrong) : FERR(GENERIC);
 }
 
@@ -316,4 +481,63 @@ extern "C" int FSEHIP_planes_estimate_dbatch(uint64_t* d_planeBits, uint64_t* d_
     hipLaunchKernelGGL(k_est_finish, dim3((unsigned)nTensors), dim3(WAVE), 0, s, (u64*)d_planeBits, (u64*)d_estBytes, d_choice, d_results, (const u32*)d_workspace, S,
                        nTensors, (u32)elemBytes, (u64)capacity, (u32)candidateMask, (u32)marginPermille);
     return (int)hipGetLastError();
+}
+
+// ---- strides in the estimate: the C calls ----
+namespace {
+// a stride set of 0 or beyond stride 8, or more than stride 1 where PRED is no candidate
+inline bool bad_smask(unsigned mask, unsigned smask) { return smask == 0 || (smask & ~0xFFu) || (smask != 1 && !(mask & EST_M_PRED)); }
+inline unsigned est_stride_sets(unsigned mask, unsigned smask) { return (mask & EST_M_PRED) ? (unsigned)__builtin_popcount(smask) : 0; }
+// the counters of k_est_count for the candidates beside PRED, then those of k_est_count_stride: per tensor and requested stride E histograms
+inline size_t est_stride_workspace(size_t nTensors, unsigned E, unsigned mask, unsigned smask)
+{
+    return r256(nTensors * (size_t)(__builtin_popcount(mask & ~(unsigned)EST_M_PRED) + est_stride_sets(mask, smask)) * E * 1024);
+}
+}   // namespace
+
+extern "C" size_t FSEHIP_planes_estimate_stride_workspaceBound(size_t nTensors, unsigned elemBytes, unsigned candidateMask, unsigned strideMask)
+{
+    if (bad_estimate(nTensors, elemBytes, candidateMask) || bad_smask(candidateMask, strideMask)) return FSEHIP_ERROR(GENERIC);
+    return est_stride_workspace(nTensors, elemBytes, candidateMask, strideMask);
+}
+
+int planes_estimate_stride(uint64_t* d_planeBits, uint64_t* d_estBytes, uint8_t* d_choice, size_t* d_results, uint64_t* d_strideEstBytes, uint8_t* d_strides,
+                           const void* d_src, const void* d_base, const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes, uint64_t capacity,
+                           unsigned candidateMask, unsigned marginPermille, void* d_workspace, size_t workspaceBytes, unsigned strideMask, bool settle, void* stream)
+{
+    if (!d_planeBits || !d_estBytes || !d_choice || !d_results || !d_strides || !d_src || !d_srcOffsets || bad_estimate(nTensors, elemBytes, candidateMask) ||
+        bad_smask(candidateMask, strideMask) || bad_grid(capacity, nTensors) || ((candidateMask & EST_M_BASE) && !d_base) || marginPermille > 1000)
+        return (int)hipErrorInvalidValue;
+    const size_t need = est_stride_workspace(nTensors, elemBytes, candidateMask, strideMask);
+    if ((need && !d_workspace) || ((uintptr_t)d_workspace & 255u) || workspaceBytes < need) return (int)hipErrorInvalidValue;
+    if (nTensors == 0) return (int)hipSuccess;
+    const hipStream_t s = (hipStream_t)stream;
+    const u64* const S = (const u64*)d_srcOffsets;
+    const unsigned maskA = candidateMask & ~(unsigned)EST_M_PRED, nS = est_stride_sets(candidateMask, strideMask);
+    u32* const cA = (u32*)d_workspace;
+    u32* const cB = cA + nTensors * (size_t)__builtin_popcount(maskA) * elemBytes * 256;
+    const u64 n16 = need / 16;
+    const u64 zb = (n16 + PL_THREADS - 1) / PL_THREADS;
+    hipLaunchKernelGGL(k_est_zero, dim3((unsigned)(zb < 65536 ? zb : 65536)), dim3(PL_THREADS), 0, s, (uint4*)d_workspace, n16);
+    if (capacity) {
+        const dim3 g(tile_grid(capacity, nTensors)), b(PL_THREADS);
+        pl_for_elem(elemBytes, [&](auto eb) {
+            constexpr int E = decltype(eb)::value;
+            if (maskA) hipLaunchKernelGGL((k_est_count<E>), g, b, 0, s, cA, (const u8*)d_src, (const u8*)d_base, S, nTensors, (u64)capacity, (u32)maskA);
+            if (nS) hipLaunchKernelGGL((k_est_count_stride<E>), g, b, nS * (((E * 256u) << EstCols<E>::LOG) * 4u), s, cB, (const u8*)d_src, S, nTensors, (u64)capacity, (u32)strideMask);
+        });
+    }
+    hipLaunchKernelGGL(k_est_finish_stride, dim3((unsigned)nTensors), dim3(WAVE), 0, s, (u64*)d_planeBits, (u64*)d_estBytes, d_choice, d_results, (u64*)d_strideEstBytes,
+                       d_strides, (const u32*)cA, (const u32*)cB, S, nTensors, (u32)elemBytes, (u64)capacity, (u32)candidateMask, (u32)strideMask, (u32)marginPermille,
+                       (u32)settle);
+    return (int)hipGetLastError();
+}
+
+extern "C" int FSEHIP_planes_estimate_stride_dbatch(uint64_t* d_planeBits, uint64_t* d_estBytes, uint8_t* d_choice, size_t* d_results, uint64_t* d_strideEstBytes,
+                                                    uint8_t* d_strides, const void* d_src, const void* d_base, const uint64_t* d_srcOffsets, size_t nTensors,
+                                                    unsigned elemBytes, uint64_t capacity, unsigned candidateMask, unsigned marginPermille, void* d_workspace,
+                                                    size_t workspaceBytes, unsigned strideMask, void* stream)
+{
+    return planes_estimate_stride(d_planeBits, d_estBytes, d_choice, d_results, d_strideEstBytes, d_strides, d_src, d_base, d_srcOffsets, nTensors, elemBytes, capacity,
+                                  candidateMask, marginPermille, d_workspace, workspaceBytes, strideMask, false, stream);
 }

@@ -12,6 +12,7 @@
 //   FSEHIP_tensor_decompress_seg_pred_stride_dbatch : the packed reader -> the fold (planes_seg.hip) -> the strided merge
 // stride == 1 launches the kernels of planes_pred.hip: the six _pred_ calls are these with stride 1.
 //
+// The bodies of both kernels, ps_split and ps_merge, and their helpers are in planes_dev.h: planes_each_stride.hip takes the same ones.
 // THE SPLIT is k_planes_split_pred with the predecessors S elements back: the chunk moved up by S elements in registers behind the S
 // elements in front of it (ps_prev), which are 0 where the chunk starts a run -- a run starts only where a chunk does and S <= 16, so the
 // S chain heads of a run are the first S elements of one chunk.  The source is only read; no scan, no workspace.
@@ -28,80 +29,6 @@
 #include "planes_dev.h"
 
 namespace {
-// pv = the chunk w moved up by S elements: every element's predecessor.  Those of the first S are the S E bytes in front of `at` (where
-// the chunk lies in the source), or 0 where the chunk starts a run -- nothing in front of it is read then.  The bytes in front are loaded
-// as whole dwords, up to 3 bytes more than needed: a chunk that starts no run lies at least 16 elements inside its tensor, S E + 3 <= 16 E
-template <int E, int S> DEV void ps_prev(u32* pv, const u32* w, const u8* at, bool runStart)
-{
-    constexpr int FD = (S * E + 3) / 4, OFF = 4 * FD - S * E;
-    u32 x[FD + 4 * E];
-#pragma unroll
-    for (int j = 0; j < FD; ++j) x[j] = 0;
-    if (!runStart) __builtin_memcpy(x, at - 4 * FD, 4 * FD);
-#pragma unroll
-    for (int j = 0; j < 4 * E; ++j) x[FD + j] = w[j];
-#pragma unroll
-    for (int j = 0; j < 4 * E; ++j) {
-        if constexpr (OFF != 0) pv[j] = __builtin_amdgcn_alignbyte(x[j + 1], x[j], OFF);
-        else pv[j] = x[j];
-    }
-}
-// element e of the tensor at sb (n bytes) a thread per element, the split's head and tail (pp_elem_split with the predecessor S back)
-template <int E, int S> DEV void ps_elem_split(u8* pb, const u8* sb, u64 n, u64 e)
-{
-    const u64 k0 = e * E;
-    if (k0 + E <= n) {
-        u64 t = 0, b = 0;
-#pragma unroll
-        for (int p = 0; p < E; ++p) t |= (u64)sb[k0 + p] << (8 * p);
-        if ((e & (PP_RUN - 1)) >= (u64)S) {
-#pragma unroll
-            for (int p = 0; p < E; ++p) b |= (u64)sb[k0 - S * E + p] << (8 * p);
-        }
-        const u64 z = pl_zz<E>(t, b);
-#pragma unroll
-        for (int p = 0; p < E; ++p) pb[pl_start(n, p, E) + e] = (u8)(z >> (8 * p));
-    } else {
-        for (u64 k = k0; k < n; ++k) pb[pl_start(n, (u32)(k - k0), E) + e] = sb[k];
-    }
-}
-
-// the merge's arithmetic: an element per register, sums mod 2^32 (2^64 for E == 8).  For E < 4 the bits above the element are not kept
-// clean -- they never reach a bit below them -- and ps_pack drops them
-template <int E> using ps_t = std::conditional_t<E == 8, u64, u32>;
-template <int E> DEV void ps_unpack(ps_t<E>* x, const u32* w)
-{
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        if constexpr (E == 1) x[q] = w[q / 4] >> (8 * (q % 4));
-        else if constexpr (E == 2) x[q] = w[q / 2] >> (16 * (q % 2));
-        else if constexpr (E == 4) x[q] = w[q];
-        else x[q] = (u64)w[2 * q] | ((u64)w[2 * q + 1] << 32);
-    }
-}
-template <int E> DEV void ps_pack(u32* w, const ps_t<E>* x)
-{
-#pragma unroll
-    for (int k = 0; k < 4 * E; ++k) {
-        if constexpr (E == 1) w[k] = (x[4 * k] & 0xFFu) | ((x[4 * k + 1] & 0xFFu) << 8) | ((x[4 * k + 2] & 0xFFu) << 16) | (x[4 * k + 3] << 24);
-        else if constexpr (E == 2) w[k] = (x[2 * k] & 0xFFFFu) | (x[2 * k + 1] << 16);
-        else if constexpr (E == 4) w[k] = x[k];
-        else w[k] = (u32)(x[k / 2] >> (32 * (k % 2)));
-    }
-}
-// v[k] = v[(k + r) mod S] for a lane-dependent r < S: one round of selects per bit of r, static register indices throughout
-template <int S, class T> DEV void ps_rotate(T* v, u32 r)
-{
-#pragma unroll
-    for (int b = 1; b < S; b <<= 1) {
-        T t[S];
-#pragma unroll
-        for (int k = 0; k < S; ++k) t[k] = (r & (u32)b) ? v[(k + b) % S] : v[k];
-#pragma unroll
-        for (int k = 0; k < S; ++k) v[k] = t[k];
-    }
-}
-
 template <int E, int S>
 __global__ __launch_bounds__(PL_THREADS) void k_planes_split_pred_stride(u8* planes, const u8* src, const u64* SO, size_t nT, u64 capacity)
 {
@@ -110,33 +37,12 @@ __global__ __launch_bounds__(PL_THREADS) void k_planes_split_pred_stride(u8* pla
     if (!pl_find(SO, nT, w, i)) return;                           // (uniform, like every return below)
     const u64 s0 = SO[i], s1 = SO[i + 1], lo = (w - i) << PL_TILE_LOG;
     if (!(s0 < s1) || s1 > capacity || lo >= s1 || lo + PLANES_TILE <= s0) return;
-    const u64 n = s1 - s0;
-    const u32 tid = threadIdx.x;
-    const u8* const sb = src + s0;
-    u8* const pb = planes + s0;
-    const PlShare h = pl_share<E>(s0, n, lo, 0, 1);               // chunks at multiples of 16 elements of the tensor
-    for (u64 c = tid; c < h.nch; c += PL_THREADS) {
-        const u64 e = h.eb + 16 * c;
-        u32 wv[4 * E], pv[4 * E], o[E][4];
-#pragma unroll
-        for (int k = 0; k < E; ++k) __builtin_memcpy(&wv[4 * k], sb + e * E + 16 * k, 16);
-        ps_prev<E, S>(pv, wv, sb + e * E, (e & (PP_RUN - 1)) == 0);
-#pragma unroll
-        for (int k = 0; k < E; ++k) pl_sub4<E, false>(&wv[4 * k], &pv[4 * k]);
-        pl_deinterleave<E>(wv, o);
-#pragma unroll
-        for (int p = 0; p < E; ++p) __builtin_memcpy(pb + pl_start(n, p, E) + e, o[p], 16);
-    }
-    const u64 nHead = h.eb - h.e0, nTail = h.e1 - h.et;
-    for (u64 j = tid; j < nHead + nTail; j += PL_THREADS) ps_elem_split<E, S>(pb, sb, n, j < nHead ? h.e0 + j : h.et + (j - nHead));
+    ps_split<E, S>(planes + s0, src + s0, s0, s1 - s0, lo, threadIdx.x);
 }
 
 template <int E, int S>
 __global__ __launch_bounds__(PL_THREADS) void k_planes_merge_pred_stride(u8* dst, const u64* D, const u8* planes, const u64* PO, const size_t* PS, size_t nT, u64 dstCapacity)
 {
-    typedef ps_t<E> T;
-    constexpr u32 RUNS = (u32)(PLANES_TILE / E / PP_RUN);         // whole runs of a tile
-    constexpr bool ROT = 16 % S != 0;                             // the chain of a register depends on the lane
     const u64 w = blockIdx.x;
     size_t i;
     if (!pl_find(D, nT, w, i)) return;                            // (uniform, like every return below)
@@ -145,86 +51,8 @@ __global__ __launch_bounds__(PL_THREADS) void k_planes_merge_pred_stride(u8* dst
     const u64 t = w - first;
     const size_t v = pm_verdict(D, PS, i, E, dstCapacity);
     if (is_err(v) || (t << PL_TILE_LOG) >= (u64)v) return;        // (a good tensor: d0 + n <= D[i + 1] <= dstCapacity; t < 2^24)
-    const u64 n = v, m = n / E;
-    const u32 lane = threadIdx.x % WAVE;
-    const u32 r0 = ROT ? (16 * lane) % S : 0;                     // register q of this lane lies in chain (r0 + q) mod S
-    const u32 rEnd = ROT ? (S - (r0 + 16) % S) % S : 0;           // chain a's last element is register 16 - S + (a + rEnd) mod S
-    u8* const db = dst + d0;
-    const u8* pp[E];
-#pragma unroll
-    for (int p = 0; p < E; ++p) pp[p] = planes + PO[i * E + p];
-    for (u32 r = threadIdx.x / WAVE; r < RUNS; r += PL_THREADS / WAVE) {
-        const u64 e0 = t * (PLANES_TILE / E) + r * PP_RUN, e = e0 + 16 * lane;
-        if (e0 * E >= n) break;                                   // (uniform over the wave: the run lies behind the tensor)
-        const bool full = e + 16 <= m;
-        T x[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) x[q] = 0;
-        if (full) {
-            u32 wv[4 * E], o[E][4];
-            const u32 zero[4] = { 0, 0, 0, 0 };
-#pragma unroll
-            for (int p = 0; p < E; ++p) __builtin_memcpy(o[p], pp[p] + e, 16);
-            pl_interleave<E>(wv, o);
-#pragma unroll
-            for (int k = 0; k < E; ++k) pl_sub4<E, true>(&wv[4 * k], zero);
-            ps_unpack<E>(x, wv);
-#pragma unroll
-            for (int q = S; q < 16; ++q) x[q] += x[q - S];
-        }
-        T c[S];                                                   // chain by chain, what the lanes in front of this one add up to: all 64 lanes scan
-#pragma unroll
-        for (int k = 0; k < S; ++k) c[k] = x[16 - S + k];
-        if constexpr (ROT) ps_rotate<S>(c, rEnd);
-#pragma unroll
-        for (int k = 0; k < S; ++k) {
-            if constexpr (E == 8) c[k] = group_scan_incl_add64<64>(c[k], lane) - c[k];
-            else c[k] = group_scan_incl<64, ScanAdd>(c[k], lane) - c[k];
-        }
-        if constexpr (ROT) ps_rotate<S>(c, r0);                   // c[k]: the carry-in of the registers q with q mod S == k
-        if (full) {
-            u32 wv[4 * E];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) x[q] += c[q % S];
-            ps_pack<E>(wv, x);
-#pragma unroll
-            for (int k = 0; k < E; ++k) __builtin_memcpy(db + e * E + 16 * k, &wv[4 * k], 16);
-        } else if (e * E < n) {                                   // the tensor's last chunk: fewer than 16 whole elements, then n mod E bytes
-            u64 acc[S];
-#pragma unroll
-            for (int k = 0; k < S; ++k) acc[k] = c[k];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const u64 j = e + q;
-                if (j < m) {
-                    u64 z = 0;
-#pragma unroll
-                    for (int p = 0; p < E; ++p) z |= (u64)pp[p][j] << (8 * p);
-                    acc[q % S] = pl_unzz<E>(z, acc[q % S]);
-#pragma unroll
-                    for (int p = 0; p < E; ++p) db[j * E + p] = (u8)(acc[q % S] >> (8 * p));
-                }
-            }
-            for (u64 k = m * E; k < n; ++k) db[k] = planes[PO[i * E + (k - m * E)] + m];
-        }
-    }
+    ps_merge<E, S>(dst + d0, planes, PO + i * E, v, t);
 }
-
-// the dispatch over the stride: f(std::integral_constant<int, S>) for 2 <= S <= FSEHIP_PRED_MAX_STRIDE (bad_stride has let it through)
-template <class F> inline void ps_for_stride(unsigned S, F f)
-{
-    switch (S) {
-    case 2: f(std::integral_constant<int, 2>()); break;
-    case 3: f(std::integral_constant<int, 3>()); break;
-    case 4: f(std::integral_constant<int, 4>()); break;
-    case 5: f(std::integral_constant<int, 5>()); break;
-    case 6: f(std::integral_constant<int, 6>()); break;
-    case 7: f(std::integral_constant<int, 7>()); break;
-    default: f(std::integral_constant<int, 8>()); break;
-    }
-}
-static_assert(FSEHIP_PRED_MAX_STRIDE == 8, "the strides the kernels are instantiated for");
-inline bool bad_stride(unsigned stride) { return stride == 0 || stride > FSEHIP_PRED_MAX_STRIDE; }
 }   // namespace
 
 // stride 1: the kernels of planes_pred.hip.  The offsets kernel runs even for no tensors (it writes the last entry)

@@ -1336,8 +1336,8 @@ FSEHIP_API int FSEHIP_tensor_decompress_seg_pred_dbatch(void* d_dst, const uint6
  *   front of a chunk of 16 where it read one; the merge sums S chains per run in one round of one wave: an in-lane recurrence, S wave
  *   scans of the lanes' per-chain totals, no LDS, no workspace, nothing crosses a workgroup.  Launches only (capturable); workspaces are the
  *   writers' and readers' own.
- *   Out of scope: strides above 8 (a row-above or 2-D predictor needs strides far beyond a run); a stride per tensor; strides in the
- *   estimate and in "a transform per tensor" (their PRED is stride 1); windows and patches of strided objects; prediction combined with a
+ *   Out of scope: strides above 8 (a row-above or 2-D predictor needs strides far beyond a run); (a stride per tensor and strides in the
+ *   estimate: "strides in the estimate" and "a stride per tensor" below); windows and patches of strided objects; prediction combined with a
  *   base or with sparse planes; a record of the stride in frames or in the archive head. */
 #define FSEHIP_PRED_MAX_STRIDE 8
 FSEHIP_API int FSEHIP_planes_split_pred_stride_dbatch(void* d_planes, uint64_t* d_planeOffsets, size_t* d_tensorResults, const void* d_src, const uint64_t* d_srcOffsets,
@@ -1588,6 +1588,106 @@ FSEHIP_API int FSEHIP_tensor_patch_window_each_dbatch(void* d_out, uint64_t outC
                                                       uint64_t* d_stagePlaneOffsets, uint64_t* d_stageSegOffsets, size_t* d_stageResults, void* d_newFrames,
                                                       uint64_t newCapacity, uint64_t* d_newOffsets, size_t* d_newResults, void* d_scratch, size_t scratchBytes,
                                                       void* d_workspace, size_t workspaceBytes, void* stream);
+
+/* Strides in the estimate (planes_estimate.hip): THE PRED STRIDE CHOSEN PER TENSOR FROM DEVICE HISTOGRAMS.  "Plane estimates" knows PRED at
+ * stride 1 only, so it chooses plain planes for every interleaved tensor -- stereo int16, RGB, xyz, boxes -- and leaves the factor of two of
+ * "strided predicted planes" on the table.  This call is FSEHIP_planes_estimate_dbatch with a SET of strides for the PRED candidate: per
+ * tensor an estimate for every requested stride, the stride chosen among them, and the four-candidate outputs with PRED at that stride.
+ *
+ *   Meaning (normative, in integers; a numpy model in tests/planes_each_stride_corpus.py).  T, L, bits256 and estBytes are those of "plane
+ *     estimates", unchanged.  The planes of stride candidate S are exactly what FSEHIP_planes_split_pred_stride_dbatch writes at that stride:
+ *     the trailing n mod E bytes, a tensor of fewer than S elements and the chain heads (j mod 1024) < S included.
+ *   strideMask: bit S - 1 requests stride S, 1 <= S <= FSEHIP_PRED_MAX_STRIDE.
+ *   The stride of a tensor: best = the lowest requested stride; every further requested S, in rising order, replaces it iff
+ *     est[S] * 1000 < est[best] * (1000 - marginPermille) -- the margin, rule and direction of the transform choice.  The multiples of the
+ *     channel count cost a little more than the channel count itself (every run has more chain heads), so rising order lands on it.
+ *
+ *   FSEHIP_planes_estimate_stride_workspaceBound   host arithmetic, a multiple of 256: per tensor E histograms of 256 32-bit counters for
+ *     every requested candidate beside PRED and, where PRED is requested, for every requested stride.  GENERIC where
+ *     FSEHIP_planes_estimate_workspaceBound is, and for a strideMask the call refuses.  With strideMask == 1 it is that bound.
+ *   FSEHIP_planes_estimate_stride_dbatch   the arguments of FSEHIP_planes_estimate_dbatch, strideMask in front of stream, two outputs behind
+ *     d_results:
+ *       d_strideEstBytes[i * 8 + (S - 1)]  estBytes of tensor i under PRED at stride S; all-ones for a stride that was not requested, and
+ *                                          everywhere where PRED is no candidate.  May be NULL.
+ *       d_strides[i]                       the chosen stride (1 where PRED is no candidate).  It is the best stride found also where
+ *                                          d_choice[i] is another transform.
+ *     d_planeBits, d_estBytes, d_choice and d_results are laid out as there; the PRED slots hold the numbers of the CHOSEN stride and
+ *     d_choice is made by the rule of "plane estimates" over those.  A refused tensor (offsets, 2^32 bytes) is refused as there, its
+ *     d_strideEstBytes entries all-ones and d_strides[i] = 0xFF.
+ *     IDENTITY: with strideMask == 1 every output the two calls share is that of FSEHIP_planes_estimate_dbatch, and the entries of stride 1
+ *     are its PRED numbers bit for bit under every strideMask.
+ *     The work: the zeroing launch; k_est_count of "plane estimates" for the candidates beside PRED; the stride counting kernel in the same
+ *     frame -- a lane loads its chunk ONCE and the 8 elements in front of it (zeros where a run starts), derives every requested stride's
+ *     differences in registers and counts into LDS histograms per (requested stride, plane), 8 / E columns per bin, 8 KB per stride: 32 KB
+ *     for four strides, 64 KB for all eight; a stride that is not requested costs neither a load nor a branch taken -- then a wave per
+ *     tensor for the costs and both choices.  Launches only (capturable); the counters are zeroed by the call every time.
+ *     Argument errors (hipErrorInvalidValue before any device call, nothing written): those of FSEHIP_planes_estimate_dbatch; a null
+ *     d_strides; strideMask == 0 or with a bit above bit 7; a strideMask other than 1 where FSEHIP_EST_PRED is not in candidateMask.
+ *   Out of scope: strides above 8 and 2-D predictors; costs beyond order 0. */
+FSEHIP_API size_t FSEHIP_planes_estimate_stride_workspaceBound(size_t nTensors, unsigned elemBytes, unsigned candidateMask, unsigned strideMask);
+FSEHIP_API int FSEHIP_planes_estimate_stride_dbatch(uint64_t* d_planeBits, uint64_t* d_estBytes, uint8_t* d_choice, size_t* d_results, uint64_t* d_strideEstBytes,
+                                                    uint8_t* d_strides, const void* d_src, const void* d_base, const uint64_t* d_srcOffsets, size_t nTensors,
+                                                    unsigned elemBytes, uint64_t capacity, unsigned candidateMask, unsigned marginPermille, void* d_workspace,
+                                                    size_t workspaceBytes, unsigned strideMask, void* stream);
+
+/* A stride per tensor (planes_each_stride.hip, capi_each.hip): THE SIX CALLS OF "a transform per tensor" WITH A STRIDE BYTE BESIDE THE
+ * TRANSFORM BYTE.  A state dict that holds audio (stride 2), [N, 3] coordinates (3), boxes (4) and bf16 weights (plain) goes through one
+ * call.  Each call has the argument list of the _each_ call it is named after with d_strides directly behind d_transforms -- const where
+ * d_transforms is const, an output beside it in the compress composites, which also take strideMask behind candidateMask.  No transform is
+ * defined here and no frame byte differs; the caller carries d_strides as it carries d_transforms.
+ *
+ *   The contract (normative; a numpy model in tests/planes_each_stride_corpus.py): the planes and frames of tensor i are byte for byte those
+ *     of the dedicated call for d_transforms[i]; for FSEHIP_EST_PRED those of the _pred_stride_ call at stride d_strides[i].  The merge is
+ *     the exact inverse, in place over the base as in "a transform per tensor".
+ *   d_strides[i] is read only where d_transforms[i] == FSEHIP_EST_PRED.  A value of 0 or above FSEHIP_PRED_MAX_STRIDE there refuses that
+ *     tensor alone, as a bad transform byte does: result GENERIC, nothing of it read or written, merged in place its bytes stay.  Under
+ *     every other transform the byte is ignored, whatever it holds.
+ *   d_strides == NULL: stride 1 everywhere; the call then is the _each_ call (in a CHOOSE composite only with strideMask == 1).
+ *   FSEHIP_TRANSFORMS_GIVEN    d_transforms and d_strides are INPUTS; candidateMask, strideMask, marginPermille and d_estBytes are ignored.
+ *   FSEHIP_TRANSFORMS_CHOOSE   both are OUTPUTS of FSEHIP_planes_estimate_stride_dbatch with candidateMask, strideMask and marginPermille, run
+ *     on the stream with no host read in between; d_strides[i] is 1 for an accepted tensor whose choice is not PRED.  d_estBytes as in
+ *     the _each_ composites (PRED at the chosen stride).
+ *   FSEHIP_tensor_each_stride_workspaceHead   the bytes in front of the writer's workspace: 0 for GIVEN; for CHOOSE
+ *     FSEHIP_planes_estimate_stride_workspaceBound and the estimate's outputs, a multiple of 256, GENERIC where that bound is or for
+ *     strideMask == 0.
+ *   The kernels have the frames of the _each_ kernels, a workgroup has one tensor, the branch on the transform and inside PRED on the stride
+ *     is uniform over the workgroup; the bodies are those of the dedicated kernels.  No LDS, no workspace of their own.
+ *   All six: launches only (capturable); nTensors == 0 is legal; the argument errors of the _each_ calls, and with CHOOSE those of
+ *     FSEHIP_planes_estimate_stride_dbatch: hipErrorInvalidValue before any device call, nothing written.
+ *   Out of scope: windows and patches of objects with a stride above 1 (the window forms of "a transform per tensor" take stride 1); strides
+ *     above 8; prediction combined with a base or with sparse planes; a record of the strides in frames or in the archive head. */
+FSEHIP_API size_t FSEHIP_tensor_each_stride_workspaceHead(size_t nTensors, unsigned elemBytes, int transformPolicy, unsigned candidateMask, unsigned strideMask);
+FSEHIP_API int FSEHIP_planes_split_each_stride_dbatch(void* d_planes, uint64_t* d_planeOffsets, size_t* d_tensorResults, const void* d_src, const void* d_base,
+                                                      const uint8_t* d_transforms, const uint8_t* d_strides, const uint64_t* d_srcOffsets, size_t nTensors,
+                                                      unsigned elemBytes, uint64_t capacity, void* stream);
+FSEHIP_API int FSEHIP_planes_merge_each_stride_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_planes, const uint64_t* d_planeOffsets,
+                                                      const size_t* d_planeSizes, const void* d_base, const uint8_t* d_transforms, const uint8_t* d_strides,
+                                                      size_t nTensors, unsigned elemBytes, uint64_t dstCapacity, void* stream);
+FSEHIP_API int FSEHIP_tensor_compress_each_stride_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
+                                                         const void* d_src, const void* d_base, uint8_t* d_transforms, uint8_t* d_strides, int transformPolicy,
+                                                         unsigned candidateMask, unsigned strideMask, unsigned marginPermille, uint64_t* d_estBytes,
+                                                         const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes, uint64_t capacity, size_t maxTotalBlocks,
+                                                         unsigned blockSizeId, int codec, uint8_t* d_codecs, int policy, unsigned tolerancePermille,
+                                                         unsigned slotAlignLog, void* d_planes, uint64_t* d_planeOffsets, void* d_workspace, size_t workspaceBytes,
+                                                         void* stream);
+FSEHIP_API int FSEHIP_tensor_compress_seg_each_stride_dbatch(void* d_dst, uint64_t dstCapacity, uint64_t* d_frameOffsets, size_t* d_frameResults, size_t* d_tensorResults,
+                                                             const void* d_src, const void* d_base, uint8_t* d_transforms, uint8_t* d_strides, int transformPolicy,
+                                                             unsigned candidateMask, unsigned strideMask, unsigned marginPermille, uint64_t* d_estBytes,
+                                                             const uint64_t* d_srcOffsets, size_t nTensors, unsigned elemBytes, uint64_t capacity,
+                                                             const uint64_t* d_segFirst, size_t nSegments, unsigned segLog, size_t maxTotalBlocks, unsigned blockSizeId,
+                                                             int codec, uint8_t* d_codecs, int policy, unsigned tolerancePermille, unsigned slotAlignLog, void* d_planes,
+                                                             uint64_t* d_planeOffsets, uint64_t* d_segOffsets, void* d_workspace, size_t workspaceBytes, void* stream);
+FSEHIP_API int FSEHIP_tensor_decompress_each_stride_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base,
+                                                           const uint8_t* d_transforms, const uint8_t* d_strides, size_t* d_results, const void* d_frames,
+                                                           const uint64_t* d_frameOffsets, size_t nTensors, unsigned elemBytes, size_t maxTotalBlocks, void* d_planes,
+                                                           uint64_t planesCapacity, uint64_t* d_planeOffsets, size_t* d_planeResults, void* d_workspace,
+                                                           size_t workspaceBytes, void* stream);
+FSEHIP_API int FSEHIP_tensor_decompress_seg_each_stride_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base,
+                                                               const uint8_t* d_transforms, const uint8_t* d_strides, size_t* d_results, const void* d_frames,
+                                                               const uint64_t* d_frameOffsets, size_t nTensors, unsigned elemBytes, const uint64_t* d_segFirst,
+                                                               size_t nSegments, unsigned segLog, size_t maxTotalBlocks, void* d_planes, uint64_t planesCapacity,
+                                                               uint64_t* d_segOffsets, size_t* d_segResults, uint64_t* d_planeOffsets, size_t* d_planeSizes,
+                                                               void* d_workspace, size_t workspaceBytes, void* stream);
 
 /* ---- FSE for 16-bit symbols (lib/fseU16.h:62-80, lib/fseU16.c) -- SURVEY 8(f) rank 4.  Alphabets of up to
  * FSEHIP_FSEU16_MAX_SYMBOL_VALUE + 1 symbols, table logs up to 13 (default 12), ONE tANS state per stream: a different format from
