@@ -67,7 +67,13 @@ template <int W, class Op> DEV u32 group_scan_incl(u32 v, u32 sub)
     (void)sub;
     return v;
 }
-// the last lane's inclusive value = the group's total, in every lane of the group
+// PRECONDITION of everything from here to wave_max_i32, and of the wg_* primitives of wave_glue.h: a FULL wave -- all 64 lanes active -- in uniform
+// control flow.  A DPP move, v_readlane, ds_bpermute and the permlane swaps read the register of their source lane whether that lane is active
+// or not, and an inactive lane's register holds whatever it held before.  Otherwise: group_last / group_last64 return the stale register of the
+// group's last lane (W == 64: of lane 63) where that lane is inactive; the scans and reductions fold stale values of inactive source lanes in
+// (for a row the step cannot read at all, the identity); lane_xor returns the partner's stale value.  Nothing faults and nothing is asserted on
+// the device: the callers keep all 64 lanes in, and mask their operands, not their calls.
+// the last lane's inclusive value = the group's total, in every lane of the group (full wave: see above)
 template <int W> DEV u32 group_last(u32 incl, u32 lane)
 {
     if (W == 64) return (u32)__builtin_amdgcn_readlane((int)incl, 63);
@@ -86,6 +92,7 @@ template <int W> DEV u64 group_scan_incl_add64(u64 v, u32 sub)
     (void)sub;
     return v;
 }
+// (full wave, as group_last: two v_readlane of lane 63, or one 64-bit shuffle from the group's last lane -- stale halves where that lane is inactive)
 template <int W> DEV u64 group_last64(u64 incl, u32 lane)
 {
     if (W == 64) return (u64)(u32)__builtin_amdgcn_readlane((int)(u32)incl, 63) | ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(incl >> 32), 63) << 32);
@@ -93,7 +100,10 @@ template <int W> DEV u64 group_last64(u64 incl, u32 lane)
 }
 
 // the value of lane (lane ^ D), D a power of two, without the LDS pipe: quad_perm for 1 and 2, two row shifts by 4 under bank masks, row_ror:8, and gfx950's
-// v_permlane16_swap / v_permlane32_swap (rows / wave halves exchanged between two registers) with one select for 16 and 32
+// v_permlane16_swap / v_permlane32_swap (rows / wave halves exchanged between two registers) with one select for 16 and 32.
+// lane_xor<16> and lane_xor<32> need those two instructions, which gfx950 has and gfx942 and older do not: the DPP build compiles for gfx950 only
+// (FSEHIP_NO_DPP_SCANS: a shuffle, any target).  Full wave in uniform control flow, as above: with its partner (lane ^ D) inactive a lane gets no
+// defined value -- the partner's stale register (the shuffle, the DPP moves of D < 16) or whatever the swap leaves of an inactive lane's half.
 template <int D> DEV u32 lane_xor(u32 v, u32 lane)
 {
     static_assert(D == 1 || D == 2 || D == 4 || D == 8 || D == 16 || D == 32, "power-of-two lane distances");
@@ -125,7 +135,8 @@ DEV u32 lane_xor_any(u32 v, u32 d, u32 lane)           // d: a constant once the
     }
 }
 
-// 64-lane reductions
+// 64-lane reductions.  Full wave in uniform control flow: the result is read from lane 63 (v_readlane), so with lane 63 or any lane in front of it
+// inactive it is the maximum over stale registers -- a lane that has nothing to contribute passes 0 (wave_max_i32: INT_MIN), it does not sit out
 DEV u32 wave_max_u32(u32 v)
 {
 #if FSEHIP_DPP_SCANS

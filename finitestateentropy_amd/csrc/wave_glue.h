@@ -12,7 +12,7 @@
 //     threshold = 2^floor(log2(remaining)), so each lane forms its symbols' (value, nbBits) chunks directly; a run of zero
 //     counters is coded by the lane holding its first zero (its length comes from a suffix-min scan of the non-zero
 //     positions); bit offsets are one more scan and the chunks are OR-ed into an LDS image of the header.
-// All functions are templated on the group width W (a power of two, 4 .. 64): the wave is split into 64 / W groups of W lanes,
+// All functions are templated on the group width W (8, 16, 32 or 64 -- group_scan_incl refuses any other at compile time): the wave is split into 64 / W groups of W lanes,
 // each working on its own table (lane `sub` of a group holds symbols 4*sub .. 4*sub+3, so a group covers alphabets of up to
 // 4*W symbols); scalar arguments and results are uniform per group.  W = 64 is one table per wave (the FSE block tables),
 // W = 8 is eight tables at once (the 13-symbol weight alphabets of eight Huffman headers, huf_prep.hip).
@@ -27,6 +27,11 @@
 template <int W> DEV u32 wg_sub(u32 lane) { return lane & (u32)(W - 1); }
 // (lane-invariant callers pass no lane: these primitives are called by all lanes of the wave in uniform control flow, and a group's lanes are
 //  lane & ~(W - 1) .. | (W - 1); the DPP forms need the lane id only for groups smaller than the wave)
+// PRECONDITION of wg_sum, wg_sum64, wg_max, wg_min, wg_any, wg_scan_excl, wg_scan_excl64 and wg_suffix_min_excl: a FULL wave (all 64 lanes active) in
+// uniform control flow, in a block whose waves start at multiples of 64 of threadIdx.x (wg_lane), W one of 8, 16, 32, 64.  Otherwise (dev_common.h,
+// at group_last): the reductions read the group's last lane and fold every lane in front of it in, active or not, so an inactive lane contributes
+// the stale content of its register and an inactive last lane makes the result stale altogether; wg_any sees inactive lanes as false (__ballot);
+// wg_suffix_min_excl folds stale values from above.  A lane with nothing to contribute passes the identity (0; for a minimum 0xFFFFFFFF; false).
 DEV u32 wg_lane() { return (u32)threadIdx.x & 63u; }
 template <int W> DEV u32 wg_sum(u32 v)
 {
