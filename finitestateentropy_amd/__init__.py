@@ -10,7 +10,7 @@ from ._lib import build_library, library_path  # noqa: F401
 
 _FROM_API = ("DeltaBase", "SparsePlanes", "PredictedPlanes", "tensor_digests", "archive_tensors", "open_archive", "save_tensors", "load_tensors", "estimate_tensors",
              "compress_tensors_auto", "TensorBundle", "compress_tensors_each", "decompress_tensor_windows_each",
-             "patch_tensor_windows_each")
+             "patch_tensor_windows_each", "decompress_tensor_windows_each_stride", "patch_tensor_windows_each_stride")
 __all__ = ["build_library", "library_path"] + list(_FROM_API)
 
 
@@ -21,7 +21,8 @@ def __getattr__(name):
     # and the built library, as do estimate_tensors / compress_tensors_auto (the plane transform chosen per tensor from device estimates) and the
     # TensorBundle they return, and compress_tensors_each (the same choice without cutting the list: one CompressedTensors with a transform
     # per tensor) and decompress_tensor_windows_each (element windows of such an object, of a predicted one and of a plain or delta one) and
-    # patch_tensor_windows_each (the write side of those windows: only the segment frames that hold a window are coded again): on first use
+    # patch_tensor_windows_each (the write side of those windows: only the segment frames that hold a window are coded again), and their
+    # _stride namesakes, which also take objects that hold a stride above 1: on first use
     if name in _FROM_API:
         from . import api
         return getattr(api, name)

@@ -77,8 +77,8 @@ class PredictedPlanes:
     segmented object: decompress_tensor_windows_each and patch_tensor_windows_each.
     `stride` (1 .. 8, include/fsehip.h "strided predicted planes"): the predecessor is the element `stride` elements in front -- the same
     channel of interleaved data: 2 for stereo samples or complex pairs, 3 for RGB or xyz, 4 for RGBA or boxes -- and 0 for the first
-    `stride` elements of every run.  The object then carries the predictor "prev<stride>" ("prev3"); windows and patches of such an
-    object are refused."""
+    `stride` elements of every run.  The object then carries the predictor "prev<stride>" ("prev3"); windows and patches of such a
+    segmented object: decompress_tensor_windows_each_stride and patch_tensor_windows_each_stride (the calls without _stride refuse it)."""
 
     def __init__(self, codec=0, stride=1):
         if not isinstance(codec, AutoCodec) and (isinstance(codec, (bool, SparsePlanes, PredictedPlanes)) or codec not in (0, 1)):
@@ -2037,8 +2037,9 @@ def _planes_methods():
 
     def _window_read(self, what, transforms, frames, frame_offsets, src_offsets, windows, dst_offsets, elem_bytes, segment_log, seg_first, n_segments, sel_first,
                      n_selected, base, dst, dst_capacity, max_total_blocks, block_size_id, planes, planes_capacity, sel_frame_offsets, sel_offsets, sel_results,
-                     plane_offsets, plane_sizes, workspace, results, delta_op):
-        """the two window composites: transforms None -- one op for the batch, delta_op -- or one transform per tensor"""
+                     plane_offsets, plane_sizes, workspace, results, delta_op, stride_call=False, strides=None):
+        """the window composites: transforms None -- one op for the batch, delta_op -- or one transform per tensor; stride_call: the
+        _each_stride_ export, `strides` as _strides takes them (None: stride 1 everywhere)"""
         E, L = _elem(elem_bytes), _seg_log(segment_log)
         self._flat(frames, "frames")
         foff, _ = self._offsets(frame_offsets, frames.device, False)
@@ -2073,6 +2074,7 @@ def _planes_methods():
         op = _delta_op(delta_op)
         _base(self, base, frames, dst_capacity, "dst")
         tr = None if transforms is None else _transforms(transforms, n, frames.device)
+        held = _strides(strides, n, frames.device) if stride_call else None
 
         def some(t):                                             # (an array of no entries still needs an address)
             return t if t.numel() else t.new_zeros(1)
@@ -2082,6 +2084,8 @@ def _planes_methods():
                 _ptr(some(sres)), _ptr(some(poff)), _ptr(some(psz)), _ptr(workspace), SZ(workspace.numel()), _stream())
         if tr is None:
             _check(_call_base(self, "FSEHIP_tensor_decompress_window_dbatch", op, 3, *head, *rest), what)
+        elif stride_call:
+            _check(self.lib.FSEHIP_tensor_decompress_window_each_stride_dbatch(*head, VP(tr.data_ptr() or res.data_ptr()), _ptr(held), *rest), what)
         else:
             _check(self.lib.FSEHIP_tensor_decompress_window_each_dbatch(*head, VP(tr.data_ptr() or res.data_ptr()), *rest), what)
         if g is not None:
@@ -2110,13 +2114,15 @@ def _planes_methods():
         return np.concatenate([[0], np.cumsum(m, dtype=np.int64)]).astype(np.uint64)
 
     def _split_window(self, what, transforms, src, src_offsets, windows, elem_bytes, segment_log, stage_offsets, base, capacity, stage, stage_capacity, plane_offsets,
-                      results, delta_op):
-        """planes_split_window_dbatch (transforms None: one op for all) and planes_split_window_each_dbatch (a transform per tensor)"""
+                      results, delta_op, stride_call=False, strides=None):
+        """planes_split_window_dbatch (transforms None: one op for all), planes_split_window_each_dbatch (a transform per tensor) and, with
+        stride_call, planes_split_window_each_stride_dbatch (`strides` as _strides takes them)"""
         E, L = _elem(elem_bytes), _seg_log(segment_log)
         soff, shost = self._offsets(src_offsets, src.device, stage_offsets is None)
         n = soff.numel() - 1
         op = 0 if transforms is not None else _delta_op(delta_op)
         tr = None if transforms is None else _transforms(transforms, n, src.device)
+        held = _strides(strides, n, src.device) if stride_call else None
         capacity = _room(self, src, capacity, "src")
         _base(self, base, src, capacity, "src")
         win, whost = _windows(self, windows, src.device, n)
@@ -2139,6 +2145,9 @@ def _planes_methods():
         args = (_ptr(soff), _ptr(_some(win)), _ptr(toff), SZ(n), C.c_uint(E), C.c_uint(L), C.c_uint64(capacity), C.c_uint64(stage_capacity), _stream())
         if tr is None:
             _check(_call_base(self, "FSEHIP_planes_split_window_dbatch", op, 4, _ptr(stage), _ptr(poff), _ptr(_some(res)), _ptr(_some(src)), _ptr(base), *args), what)
+        elif stride_call:
+            _check(self.lib.FSEHIP_planes_split_window_each_stride_dbatch(_ptr(stage), _ptr(poff), _ptr(_some(res)), _ptr(_some(src)), _ptr(base),
+                                                                          VP(tr.data_ptr() or soff.data_ptr()), _ptr(held), *args), what)
         else:
             _check(self.lib.FSEHIP_planes_split_window_each_dbatch(_ptr(stage), _ptr(poff), _ptr(_some(res)), _ptr(_some(src)), _ptr(base),
                                                                    VP(tr.data_ptr() or soff.data_ptr()), *args), what)
@@ -2251,8 +2260,9 @@ def _planes_methods():
     def _patch_window(self, what, transforms, frames, frame_offsets, frame_results, src, src_offsets, windows, elem_bytes, segment_log, seg_first, n_segments, sel_first,
                       n_selected, stage_offsets, base, codec, codecs, new_codecs, block_size_id, capacity, frames_capacity, max_total_blocks, align_log, out, out_capacity,
                       out_offsets, out_results, out_codecs, tensor_results, stage, stage_capacity, stage_plane_offsets, stage_seg_offsets, stage_results, new_frames,
-                      new_capacity, new_offsets, new_results, scratch, workspace, delta_op):
-        """tensor_patch_window_dbatch (transforms None: one op for all) and tensor_patch_window_each_dbatch (a transform per tensor)"""
+                      new_capacity, new_offsets, new_results, scratch, workspace, delta_op, stride_call=False, strides=None):
+        """tensor_patch_window_dbatch (transforms None: one op for all), tensor_patch_window_each_dbatch (a transform per tensor) and, with
+        stride_call, tensor_patch_window_each_stride_dbatch (`strides` as _strides takes them)"""
         E = _elem(elem_bytes)
         align_log = _align_log(align_log)
         L = _seg_log(segment_log, min(block_size_id, 6))
@@ -2267,6 +2277,7 @@ def _planes_methods():
         soff, shost = self._offsets(src_offsets, dev, seg_first is None or need_first)
         n = soff.numel() - 1
         tr = None if transforms is None else _transforms(transforms, n, dev)
+        held = _strides(strides, n, dev) if stride_call else None
         capacity = _room(self, src, capacity, "src")
         _base(self, base, src, capacity, "src")
         frames_capacity = _room(self, frames, frames_capacity, "frames")
@@ -2331,6 +2342,8 @@ def _planes_methods():
                 C.c_uint64(new_capacity), _ptr(noff), _ptr(_some(nres)), _ptr(scratch), SZ(scratch.numel()), _ptr(workspace), SZ(workspace.numel()), _stream())
         if tr is None:
             _check(_call_base(self, "FSEHIP_tensor_patch_window_dbatch", op, 12, *front, *rest), what)
+        elif stride_call:
+            _check(self.lib.FSEHIP_tensor_patch_window_each_stride_dbatch(*front, VP(tr.data_ptr() or soff.data_ptr()), _ptr(held), *rest), what)
         else:
             _check(self.lib.FSEHIP_tensor_patch_window_each_dbatch(*front, VP(tr.data_ptr() or soff.data_ptr()), *rest), what)
         _check_codecs(cgu, nsel, what)
@@ -2474,14 +2487,34 @@ def _planes_methods():
         object; a wrong number of tensors or windows; a tensor of another dtype, shape or device; a window that is not one; transforms that
         are not names out of EST_NAMES, or together with a predictor; a predictor other than "prev"; "xor" / "sub" tensors without a base;
         a base for an object that holds neither."""
-        what = "patch_tensor_windows_each"
+        return _patch_windows_each(self, "patch_tensor_windows_each", obj, tensors, windows, base, False)
+
+    def patch_tensor_windows_each_stride(self, obj, tensors, windows, base=None):
+        """patch_tensor_windows_each for objects that hold a stride above 1 as well, with the same contract and the same refusals but that one
+        (tensor_patch_window_each_stride_dbatch).  It takes everything patch_tensor_windows_each takes -- the stride is then 1 everywhere -- and
+          an object of compress_tensors_each(..., strides=..., segment_log=...): obj.strides, one integer 1 .. 8 per tensor, GIVEN beside
+            obj.transforms -- the patch chooses neither again;
+          a segmented object written with PredictedPlanes(codec, stride=S) (predictor "prev<S>"): every tensor "pred" at stride S;
+          all of these reopened from an archive or a file.
+        A staged segment starts a run of 1024 elements for every one of the S chains, so a window may start anywhere and no element in front
+        of a segment is read.  Where `tensors` equal the object's content outside the windows the result is what the compress call that
+        wrote `obj` gives for `tensors` with obj.transforms and obj.strides given, byte for byte.  The new object carries strides or predictor
+        over, together with what patch_tensor_windows_each carries.  ValueError / TypeError before any launch: those of
+        patch_tensor_windows_each; strides that are not one integer 1 .. 8 per tensor; a predictor that predictor_stride does not know."""
+        return _patch_windows_each(self, "patch_tensor_windows_each_stride", obj, tensors, windows, base, True)
+
+    def _patch_windows_each(self, what, obj, tensors, windows, base, strided):
+        """the body of patch_tensor_windows_each (strided False: an object with a stride above 1 is refused) and of
+        patch_tensor_windows_each_stride"""
         seg_log = getattr(obj, "segment_log", None)
         if seg_log is None:
             raise ValueError(what + ": the object is not segmented (compress_tensors_each and compress_tensors_segmented write those with a segment_log)")
         if getattr(obj, "sparse_permille", None) is not None:
             raise ValueError(what + ": the object holds sparse planes (SparsePlanes); patches of those are not supported")
-        if any(st != 1 for st in (getattr(obj, "strides", None) or ())):
-            raise ValueError(what + ": the object holds a stride above 1 (compress_tensors_each with strides); patches of those are not supported")
+        if not strided and any(st != 1 for st in (getattr(obj, "strides", None) or ())):
+            raise ValueError(what + ": the object holds a stride above 1 (compress_tensors_each with strides); patches of those are not supported here, "
+                             "patch_tensor_windows_each_stride takes them")
+        strides = _obj_strides(obj, what) if strided else None
         n = len(obj.dtypes)
         names, predictor = getattr(obj, "transforms", None), getattr(obj, "predictor", None)
         if names is not None:
@@ -2496,8 +2529,11 @@ def _planes_methods():
                 raise ValueError(what + ": the object holds \"xor\" or \"sub\" tensors and needs its base" if base is None else
                                  what + ": the object holds no \"xor\" or \"sub\" tensor, a base does not belong to it")
         elif predictor is not None:
-            if predictor != "prev":
-                raise ValueError("%s: predictor %r; only \"prev\" is known" % (what, predictor))
+            if strided:
+                strides = [predictor_stride(predictor, what)] * n
+            elif predictor != "prev":
+                raise ValueError("%s: predictor %r; only \"prev\" is known (patch_tensor_windows_each_stride takes \"prev2\" .. \"prev%d\")" %
+                                 (what, predictor, PRED_MAX_STRIDE))
             if base is not None:
                 raise ValueError(what + ": the object holds predicted planes, a base does not belong to it")
             names = ["pred"] * n
@@ -2529,10 +2565,15 @@ def _planes_methods():
                 first, blocks = self.planes_window_first(sizes, gw, E, seg_log, obj.block_size_id)
                 toff = self.planes_stage_offsets(sizes, gw, E, seg_log)
                 cap = int(g["frames"].numel()) + self.frame_packed_bound(int(toff[-1]), int(first[-1]), blocks, 0)
-                out, ooff, ores, tres, ocod = tensor_patch_window_each_dbatch(
-                    self, g["frames"], g["frame_offsets"], g["frame_results"], src, offs, gw, E, seg_log, [names[i] for i in idx], g["seg_first"], sel_first=first,
-                    stage_offsets=toff, base=bsrc, codec=inner if auto or "codecs" not in g else 0, codecs=g.get("codecs"), block_size_id=obj.block_size_id,
-                    max_total_blocks=blocks, out_capacity=cap)
+                more = dict(sel_first=first, stage_offsets=toff, base=bsrc, codec=inner if auto or "codecs" not in g else 0, codecs=g.get("codecs"),
+                            block_size_id=obj.block_size_id, max_total_blocks=blocks, out_capacity=cap)
+                if strided:
+                    out, ooff, ores, tres, ocod = self.tensor_patch_window_each_stride_dbatch(
+                        g["frames"], g["frame_offsets"], g["frame_results"], src, offs, gw, E, seg_log, [names[i] for i in idx],
+                        None if strides is None else [strides[i] for i in idx], g["seg_first"], **more)
+                else:
+                    out, ooff, ores, tres, ocod = tensor_patch_window_each_dbatch(
+                        self, g["frames"], g["frame_offsets"], g["frame_results"], src, offs, gw, E, seg_log, [names[i] for i in idx], g["seg_first"], **more)
                 got = torch.cat([ooff[-1:], tres]).cpu().tolist()
                 if got[1:] != sizes or got[0] > cap:
                     raise RuntimeError("%s: element size %d, results %s for tensors of %s bytes" % (what, E, got[1:9], sizes[:8]))
@@ -2549,10 +2590,12 @@ def _planes_methods():
                          getattr(obj, "delta_op", "xor"), None, getattr(obj, "base_digests", None), predictor)
         if getattr(obj, "transforms", None) is not None:
             got.transforms = list(names)
+        if getattr(obj, "strides", None) is not None:
+            got.strides = [int(st) for st in obj.strides]
         return got
 
     for f in (planes_stage_offsets, planes_split_window_dbatch, planes_splice_scratch_bound, planes_splice_dbatch, tensor_patch_window_dbatch, patch_tensor_windows,
-              planes_split_window_each_dbatch, tensor_patch_window_each_dbatch, patch_tensor_windows_each):
+              planes_split_window_each_dbatch, tensor_patch_window_each_dbatch, patch_tensor_windows_each, patch_tensor_windows_each_stride):
         setattr(FseHip, f.__name__, f)
 
     # ---- sparse planes (csrc/planes_sparse.hip; fsehip.h "sparse planes"): a unit of n bytes as a zero mask of ceil(n / 8) bytes and its
@@ -3496,7 +3539,7 @@ def _planes_methods():
     # ---- windows of tensors with a transform per tensor (fsehip.h, the section of that name): the read side of the windows for frames of
     # tensor_compress_seg_each_dbatch and tensor_compress_seg_pred_dbatch
     def planes_merge_window_each_dbatch(self, planes, plane_offsets, plane_sizes, dst_offsets, windows, elem_bytes, transforms, base=None, dst=None, capacity=None,
-                                        results=None):
+                                        results=None, _strides_arg=_NO_STRIDE):
         """-> (dst, results): planes_merge_each_dbatch of the windows (a, b), in elements, of every tensor: plane_offsets point at the window's
         first byte of every plane and plane_sizes are b - a, as planes_fold_window_dbatch leaves them; slot i of dst_offsets receives
         tensor_i[a * E : b * E].  For a "pred" tensor the a % 1024 plane bytes in front of each of its plane offsets must be the decoded bytes
@@ -3514,10 +3557,13 @@ def _planes_methods():
         _base(self, base, planes, capacity, "dst")
         tr = _transforms(transforms, n, planes.device)
         res = _i64(self, results, n, planes.device, "results")
-        what = "planes_merge_window_each_dbatch"
-        _check(self.lib.FSEHIP_planes_merge_window_each_dbatch(_ptr(_some(dst)), _ptr(doff), _ptr(_some(res)), _ptr(planes), _ptr(_some(poff)), _ptr(_some(psz)), _ptr(base),
-                                                               VP(tr.data_ptr() or doff.data_ptr()), _ptr(_some(win)), SZ(n), C.c_uint(E), C.c_uint64(capacity), _stream()),
-               what)
+        each = _strides_arg is _NO_STRIDE
+        what = "planes_merge_window_each_dbatch" if each else "planes_merge_window_each_stride_dbatch"
+        held = None if each else _strides(_strides_arg, n, planes.device)
+        st = () if each else (_ptr(held),)                                                       # (the _each_ export takes none)
+        call = self.lib.FSEHIP_planes_merge_window_each_dbatch if each else self.lib.FSEHIP_planes_merge_window_each_stride_dbatch
+        _check(call(_ptr(_some(dst)), _ptr(doff), _ptr(_some(res)), _ptr(planes), _ptr(_some(poff)), _ptr(_some(psz)), _ptr(base), VP(tr.data_ptr() or doff.data_ptr()), *st,
+                    _ptr(_some(win)), SZ(n), C.c_uint(E), C.c_uint64(capacity), _stream()), what)
         if g is not None:
             g.check(what)
         return dst, res
@@ -3538,6 +3584,57 @@ def _planes_methods():
 
     for f in (tensor_each_workspace_head, planes_split_each_dbatch, planes_merge_each_dbatch, tensor_compress_each_dbatch, tensor_compress_seg_each_dbatch,
               tensor_decompress_each_dbatch, tensor_decompress_seg_each_dbatch, planes_merge_window_each_dbatch, tensor_decompress_window_each_dbatch):
+        setattr(FseHip, f.__name__, f)
+
+    # ---- windows and patches of tensors with a stride per tensor (csrc/planes_each_stride_win.hip; fsehip.h, the section of that name): the four
+    # window calls above and of "patching tensors with a transform per tensor" with `strides` behind `transforms`
+    def planes_merge_window_each_stride_dbatch(self, planes, plane_offsets, plane_sizes, dst_offsets, windows, elem_bytes, transforms, strides=None, base=None, dst=None,
+                                               capacity=None, results=None):
+        """planes_merge_window_each_dbatch with strides[i] (1 .. 8) the stride of tensor i where transforms[i] is pred: the lead is a % 1024
+        elements at every stride, and all strides[i] chains are summed through it.  A 0 or a value above 8 there refuses that tensor alone
+        (results -1, nothing of it read or written); for every other transform the entry is ignored.  strides: None (stride 1 everywhere:
+        planes_merge_window_each_dbatch byte for byte), integers, or a CUDA uint8 tensor."""
+        return planes_merge_window_each_dbatch(self, planes, plane_offsets, plane_sizes, dst_offsets, windows, elem_bytes, transforms, base, dst, capacity, results,
+                                               _strides_arg=strides)
+
+    def tensor_decompress_window_each_stride_dbatch(self, frames, frame_offsets, src_offsets, windows, dst_offsets, elem_bytes, segment_log, transforms, strides=None,
+                                                    seg_first=None, n_segments=None, sel_first=None, n_selected=None, base=None, dst=None, dst_capacity=None,
+                                                    max_total_blocks=None, block_size_id=5, planes=None, planes_capacity=None, sel_frame_offsets=None, sel_offsets=None,
+                                                    sel_results=None, plane_offsets=None, plane_sizes=None, workspace=None, results=None):
+        """tensor_decompress_window_each_dbatch for frames that tensor_compress_seg_each_stride_dbatch wrote with these transforms and strides
+        (all "pred" and one stride: frames of tensor_compress_seg_pred_stride_dbatch): the same selection, reader and fold, then
+        planes_merge_window_each_stride_dbatch.  strides None: tensor_decompress_window_each_dbatch byte for byte."""
+        return _window_read(self, "tensor_decompress_window_each_stride_dbatch", transforms, frames, frame_offsets, src_offsets, windows, dst_offsets, elem_bytes,
+                            segment_log, seg_first, n_segments, sel_first, n_selected, base, dst, dst_capacity, max_total_blocks, block_size_id, planes, planes_capacity,
+                            sel_frame_offsets, sel_offsets, sel_results, plane_offsets, plane_sizes, workspace, results, 0, True, strides)
+
+    def planes_split_window_each_stride_dbatch(self, src, src_offsets, windows, elem_bytes, segment_log, transforms, strides=None, stage_offsets=None, base=None,
+                                               capacity=None, stage=None, stage_capacity=None, plane_offsets=None, results=None):
+        """planes_split_window_each_dbatch with strides[i] (1 .. 8) the stride of tensor i where transforms[i] is pred: segments k0 .. k1 of the
+        planes planes_split_each_stride_dbatch writes for the whole tensor -- a segment starts a run for every chain, so nothing in front of
+        the staged bytes is read.  A 0 or a value above 8 there refuses that tensor alone (results -1, all its plane offsets its stage
+        offset).  strides None: planes_split_window_each_dbatch byte for byte."""
+        return _split_window(self, "planes_split_window_each_stride_dbatch", transforms, src, src_offsets, windows, elem_bytes, segment_log, stage_offsets, base, capacity,
+                             stage, stage_capacity, plane_offsets, results, 0, True, strides)
+
+    def tensor_patch_window_each_stride_dbatch(self, frames, frame_offsets, frame_results, src, src_offsets, windows, elem_bytes, segment_log, transforms, strides=None,
+                                               seg_first=None, n_segments=None, sel_first=None, n_selected=None, stage_offsets=None, base=None, codec=0, codecs=None,
+                                               new_codecs=None, block_size_id=5, capacity=None, frames_capacity=None, max_total_blocks=None, align_log=0, out=None,
+                                               out_capacity=None, out_offsets=None, out_results=None, out_codecs=None, tensor_results=None, stage=None,
+                                               stage_capacity=None, stage_plane_offsets=None, stage_seg_offsets=None, stage_results=None, new_frames=None,
+                                               new_capacity=None, new_offsets=None, new_results=None, scratch=None, workspace=None):
+        """tensor_patch_window_each_dbatch for an object that tensor_compress_seg_each_stride_dbatch wrote with these transforms and strides:
+        planes_split_window_each_stride_dbatch, then the segments kernel, the packed writer and the splice as they are.  For tensors that differ
+        inside the windows only, the result is tensor_compress_seg_each_stride_dbatch of src with the same transforms and strides given, byte
+        for byte.  Both are GIVEN: the patch never chooses.  A pred tensor whose stride is 0 or above 8 is refused alone (-1) and keeps all
+        its old frames.  strides None: tensor_patch_window_each_dbatch byte for byte."""
+        return _patch_window(self, "tensor_patch_window_each_stride_dbatch", transforms, frames, frame_offsets, frame_results, src, src_offsets, windows, elem_bytes,
+                             segment_log, seg_first, n_segments, sel_first, n_selected, stage_offsets, base, codec, codecs, new_codecs, block_size_id, capacity,
+                             frames_capacity, max_total_blocks, align_log, out, out_capacity, out_offsets, out_results, out_codecs, tensor_results, stage, stage_capacity,
+                             stage_plane_offsets, stage_seg_offsets, stage_results, new_frames, new_capacity, new_offsets, new_results, scratch, workspace, 0, True, strides)
+
+    for f in (planes_merge_window_each_stride_dbatch, tensor_decompress_window_each_stride_dbatch, planes_split_window_each_stride_dbatch,
+              tensor_patch_window_each_stride_dbatch):
         setattr(FseHip, f.__name__, f)
 
     # ---- tensor archives (csrc/planes_archive.hip; fsehip.h "tensor archives"): head | frames in one device buffer, sealed behind the frames a
@@ -4271,9 +4368,9 @@ def _planes_methods():
         tensor (obj.strides of an earlier call; looked at for the "pred" ones).  The object's `strides` lists the stride of every tensor, 1
         for those that are not "pred"; archives and files carry it where one exceeds 1.
         Out of scope, each a ValueError before any launch: a SparsePlanes or PredictedPlanes as codec, an earlier object as codec, a
-        DeltaBase(check=True); a stride outside 1 .. 8; strides with "auto" where "pred" is no candidate.  An object with a stride above 1 has
-        no windows and no patches.  Windows of a segmented object are read by decompress_tensor_windows_each and written by
-        patch_tensor_windows_each, not by decompress_tensor_windows and patch_tensor_windows."""
+        DeltaBase(check=True); a stride outside 1 .. 8; strides with "auto" where "pred" is no candidate.  Windows of a segmented object are read by
+        decompress_tensor_windows_each and written by patch_tensor_windows_each, not by decompress_tensor_windows and patch_tensor_windows; those
+        of an object with a stride above 1 by decompress_tensor_windows_each_stride and patch_tensor_windows_each_stride alone."""
         what = "compress_tensors_each"
         margin = _margin(margin_permille, what)
         if isinstance(codec, bool) or not (isinstance(codec, AutoCodec) or (isinstance(codec, numbers.Integral) and codec in (0, 1))):
@@ -4507,14 +4604,33 @@ def _planes_methods():
         A window of a "pred" tensor may start anywhere: the differences of its run in front of it lie in its first selected segment.
         ValueError before any launch: no segment_log; a sparse object; a window that is not one or a wrong number of windows; a predictor
         other than "prev"; "xor" / "sub" tensors without a base; a base for an object that holds neither.  base_digests are not checked."""
-        what = "decompress_tensor_windows_each"
+        return _read_windows_each(self, "decompress_tensor_windows_each", obj, windows, base, False)
+
+    def decompress_tensor_windows_each_stride(self, obj, windows, base=None):
+        """decompress_tensor_windows_each for objects that hold a stride above 1 as well, with the same contract and the same refusals but that
+        one (tensor_decompress_window_each_stride_dbatch).  It takes everything decompress_tensor_windows_each takes -- the stride is then 1
+        everywhere -- and
+          an object of compress_tensors_each(..., strides=..., segment_log=...): obj.strides, one integer 1 .. 8 per tensor, validated as
+            decompress_tensors validates them;
+          a segmented object written with PredictedPlanes(codec, stride=S) (predictor "prev<S>"): every tensor "pred" at stride S;
+          all of these reopened from an archive or a file.
+        A window may start anywhere: a run is 1024 elements counted from the tensor's start at every stride, and the differences of all S
+        chains in front of the window lie in its first selected segment.  ValueError before any launch: those of
+        decompress_tensor_windows_each; strides that are not one integer 1 .. 8 per tensor; a predictor that predictor_stride does not know."""
+        return _read_windows_each(self, "decompress_tensor_windows_each_stride", obj, windows, base, True)
+
+    def _read_windows_each(self, what, obj, windows, base, strided):
+        """the body of decompress_tensor_windows_each (strided False: an object with a stride above 1 is refused) and of
+        decompress_tensor_windows_each_stride"""
         seg_log = getattr(obj, "segment_log", None)
         if seg_log is None:
             raise ValueError(what + ": the object is not segmented (compress_tensors_each and compress_tensors_segmented write those with a segment_log)")
         if getattr(obj, "sparse_permille", None) is not None:
             raise ValueError(what + ": the object holds sparse planes (SparsePlanes); windows of those are not supported")
-        if any(st != 1 for st in (getattr(obj, "strides", None) or ())):
-            raise ValueError(what + ": the object holds a stride above 1 (compress_tensors_each with strides); windows of those are not supported")
+        if not strided and any(st != 1 for st in (getattr(obj, "strides", None) or ())):
+            raise ValueError(what + ": the object holds a stride above 1 (compress_tensors_each with strides); windows of those are not supported here, "
+                             "decompress_tensor_windows_each_stride takes them")
+        strides = _obj_strides(obj, what) if strided else None
         n = len(obj.dtypes)
         names, predictor = getattr(obj, "transforms", None), getattr(obj, "predictor", None)
         if names is not None:
@@ -4529,8 +4645,11 @@ def _planes_methods():
                 raise ValueError(what + ": the object holds \"xor\" or \"sub\" tensors and needs its base" if base is None else
                                  what + ": the object holds no \"xor\" or \"sub\" tensor, a base does not belong to it")
         elif predictor is not None:
-            if predictor != "prev":
-                raise ValueError("%s: predictor %r; only \"prev\" is known" % (what, predictor))
+            if strided:
+                strides = [predictor_stride(predictor, what)] * n
+            elif predictor != "prev":
+                raise ValueError("%s: predictor %r; only \"prev\" is known (decompress_tensor_windows_each_stride takes \"prev2\" .. \"prev%d\")" %
+                                 (what, predictor, PRED_MAX_STRIDE))
             if base is not None:
                 raise ValueError(what + ": the object holds predicted planes, a base does not belong to it")
             names = ["pred"] * n
@@ -4539,12 +4658,16 @@ def _planes_methods():
             names = [("plain" if base is None else "sub" if op else "xor")] * n
         wins = _window_list(what, obj, windows)
         braw = None if base is None else _bases(base, obj.dtypes, obj.shapes, obj.device)
+        if strided:
+            return _read_windows(what, obj, wins, braw, lambda g, soff, gw, doff, dst: self.tensor_decompress_window_each_stride_dbatch(
+                g["frames"], g["frame_offsets"], soff, gw, doff, g["elem_bytes"], seg_log, [names[i] for i in g["index"]],
+                None if strides is None else [strides[i] for i in g["index"]], g["seg_first"], base=dst, dst=dst, block_size_id=obj.block_size_id))
         return _read_windows(what, obj, wins, braw, lambda g, soff, gw, doff, dst: self.tensor_decompress_window_each_dbatch(
             g["frames"], g["frame_offsets"], soff, gw, doff, g["elem_bytes"], seg_log, [names[i] for i in g["index"]], g["seg_first"], base=dst, dst=dst,
             block_size_id=obj.block_size_id))
 
     for f in (planes_window_first, planes_select_window_dbatch, planes_fold_window_dbatch, tensor_decompress_window_dbatch, decompress_tensor_windows,
-              decompress_tensor_windows_each):
+              decompress_tensor_windows_each, decompress_tensor_windows_each_stride):
         setattr(FseHip, f.__name__, f)
     for f in (estimate_tensors, compress_tensors_auto):
         setattr(FseHip, f.__name__, f)
@@ -4605,6 +4728,11 @@ def decompress_tensor_windows_each(obj, windows, base=None):
     return _default().decompress_tensor_windows_each(obj, windows, base)
 
 
+def decompress_tensor_windows_each_stride(obj, windows, base=None):
+    """FseHip.decompress_tensor_windows_each_stride on a library handle of the module's own"""
+    return _default().decompress_tensor_windows_each_stride(obj, windows, base)
+
+
 def patch_tensor_windows(obj, tensors, windows, base=None):
     """FseHip.patch_tensor_windows on a library handle of the module's own"""
     return _default().patch_tensor_windows(obj, tensors, windows, base)
@@ -4613,6 +4741,11 @@ def patch_tensor_windows(obj, tensors, windows, base=None):
 def patch_tensor_windows_each(obj, tensors, windows, base=None):
     """FseHip.patch_tensor_windows_each on a library handle of the module's own"""
     return _default().patch_tensor_windows_each(obj, tensors, windows, base)
+
+
+def patch_tensor_windows_each_stride(obj, tensors, windows, base=None):
+    """FseHip.patch_tensor_windows_each_stride on a library handle of the module's own"""
+    return _default().patch_tensor_windows_each_stride(obj, tensors, windows, base)
 
 
 def tensor_digests(tensors):

@@ -10,6 +10,8 @@
 //
 //   the seven calls of "a stride per tensor" (at the end): the six above with d_strides behind d_transforms -- the launchers of
 //                                                planes_each_stride.hip, and with CHOOSE the estimate over strides (planes_estimate.hip)
+//   the two window calls with d_strides (at the very end): FSEHIP_planes_merge_window_each_stride_dbatch and
+//                                                FSEHIP_tensor_decompress_window_each_stride_dbatch, the launcher of planes_each_stride_win.hip
 //
 // The workspace of a CHOOSE call: the estimate's counters, plane costs, estimates and results (each a multiple of 256) in front of the
 // writer's workspace; FSEHIP_tensor_each_workspaceHead is their sum.
@@ -316,4 +318,48 @@ extern "C" int FSEHIP_tensor_decompress_seg_each_stride_dbatch(void* d_dst, cons
     if (f != 0) return f;
     return (int)launch_planes_merge_each_stride((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeSizes,
                                                 (const u8*)d_base, d_transforms, d_strides, nTensors, elemBytes, dstCapacity, (hipStream_t)stream);
+}
+
+// ---- windows of tensors with a stride per tensor (fsehip.h, "windows and patches of tensors with a stride per tensor"; the write side is in
+// planes_patch.hip): the two window calls above with d_strides behind d_transforms, null: stride 1 everywhere ----
+extern "C" int FSEHIP_planes_merge_window_each_stride_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_planes,
+                                                             const uint64_t* d_planeOffsets, const size_t* d_planeSizes, const void* d_base, const uint8_t* d_transforms,
+                                                             const uint8_t* d_strides, const uint64_t* d_windows, size_t nTensors, unsigned elemBytes, uint64_t dstCapacity,
+                                                             void* stream)
+{
+    if (bad_elem(elemBytes) || !d_dst || !d_dstOffsets || !d_results || !d_planes || !d_planeOffsets || !d_planeSizes || !d_transforms || !d_windows)
+        return (int)hipErrorInvalidValue;
+    if (bad_tensors(nTensors, elemBytes) || bad_grid(dstCapacity, 2 * nTensors)) return (int)hipErrorInvalidValue;
+    return (int)launch_planes_merge_window_each_stride((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeSizes,
+                                                       (const u8*)d_base, d_transforms, d_strides, (const u64*)d_windows, nTensors, elemBytes, dstCapacity,
+                                                       (hipStream_t)stream);
+}
+
+// the argument checks of all four steps in front of the first launch (those of the selection and of the fold are among them)
+extern "C" int FSEHIP_tensor_decompress_window_each_stride_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base,
+                                                                  const uint8_t* d_transforms, const uint8_t* d_strides, size_t* d_results, const void* d_frames,
+                                                                  const uint64_t* d_frameOffsets, const uint64_t* d_srcOffsets, const uint64_t* d_windows, size_t nTensors,
+                                                                  unsigned elemBytes, const uint64_t* d_segFirst, size_t nSegments, unsigned segLog,
+                                                                  const uint64_t* d_selFirst, size_t nSelected, size_t maxTotalBlocks, void* d_planes, uint64_t planesCapacity,
+                                                                  uint64_t* d_selFrameOffsets, uint64_t* d_selOffsets, size_t* d_selResults, uint64_t* d_planeOffsets,
+                                                                  size_t* d_planeSizes, void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    if (bad_elem(elemBytes) || !d_dst || !d_dstOffsets || !d_transforms || !d_results || !d_frames || !d_frameOffsets || !d_srcOffsets || !d_windows || !d_segFirst ||
+        !d_selFirst || !d_planes || !d_selFrameOffsets || !d_selOffsets || !d_selResults || !d_planeOffsets || !d_planeSizes)
+        return (int)hipErrorInvalidValue;
+    if (bad_seg(segLog, 0) || bad_counts(nTensors, elemBytes, nSelected) || nSegments >= ((size_t)1 << 31) || nSelected > nSegments || bad_grid(dstCapacity, 2 * nTensors))
+        return (int)hipErrorInvalidValue;
+    if (bad_reader(d_workspace, workspaceBytes, nSelected, maxTotalBlocks)) return (int)hipErrorInvalidValue;
+    int r = FSEHIP_planes_select_window_dbatch(d_selFrameOffsets, d_frameOffsets, d_srcOffsets, d_windows, d_segFirst, d_selFirst, nTensors, elemBytes, nSegments, nSelected,
+                                               segLog, stream);
+    if (r != 0) return r;
+    r = FSEHIP_frame_decompress_packed_dbatch(d_planes, (size_t)planesCapacity, d_selOffsets, d_selResults, d_frames, d_selFrameOffsets, nSelected, maxTotalBlocks, 0,
+                                              d_workspace, workspaceBytes, stream);
+    if (r != 0) return r;
+    r = FSEHIP_planes_fold_window_dbatch(d_planeOffsets, d_planeSizes, d_selOffsets, d_selResults, d_srcOffsets, d_windows, d_segFirst, d_selFirst, nTensors, elemBytes,
+                                         nSelected, segLog, stream);
+    if (r != 0) return r;
+    return (int)launch_planes_merge_window_each_stride((u8*)d_dst, (const u64*)d_dstOffsets, d_results, (const u8*)d_planes, (const u64*)d_planeOffsets, d_planeSizes,
+                                                       (const u8*)d_base, d_transforms, d_strides, (const u64*)d_windows, nTensors, elemBytes, dstCapacity,
+                                                       (hipStream_t)stream);
 }

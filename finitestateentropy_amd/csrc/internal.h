@@ -394,6 +394,13 @@ hipError_t launch_planes_split_each_stride(u8* planes, u64* planeOff, size_t* te
                                            const u64* srcOff, size_t nTensors, unsigned E, u64 capacity, hipStream_t s);
 hipError_t launch_planes_merge_each_stride(u8* dst, const u64* dstOff, size_t* results, const u8* planes, const u64* planeOff, const size_t* planeSizes, const u8* base,
                                            const u8* transforms, const u8* strides, size_t nTensors, unsigned E, u64 dstCapacity, hipStream_t s);
+// the window forms with a stride per tensor (planes_each_stride_win.hip; fsehip.h, "windows and patches of tensors with a stride per
+// tensor"): the two _window_each launchers above with strides[i] read for the PRED tensors; strides null: those two
+hipError_t launch_planes_merge_window_each_stride(u8* dst, const u64* dstOff, size_t* results, const u8* planes, const u64* planeOff, const size_t* planeSizes, const u8* base,
+                                                  const u8* transforms, const u8* strides, const u64* windows, size_t nTensors, unsigned E, u64 dstCapacity, hipStream_t s);
+hipError_t launch_planes_split_window_each_stride(u8* stage, u64* planeOff, size_t* stageRes, const u8* src, const u8* base, const u8* transforms, const u8* strides,
+                                                  const u64* srcOff, const u64* windows, const u64* stageOff, size_t nTensors, unsigned E, unsigned segLog, u64 capacity,
+                                                  u64 stageCapacity, hipStream_t s);
 // the estimate over strides (planes_estimate.hip; fsehip.h, "strides in the estimate"): FSEHIP_planes_estimate_stride_dbatch with all its
 // argument checks; settle: d_strides[i] = 1 where the choice of an accepted tensor is not FSEHIP_EST_PRED (the CHOOSE composites)
 int planes_estimate_stride(uint64_t* d_planeBits, uint64_t* d_estBytes, uint8_t* d_choice, size_t* d_results, uint64_t* d_strideEstBytes, uint8_t* d_strides,

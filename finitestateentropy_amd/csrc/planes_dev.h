@@ -404,8 +404,11 @@ template <int E, int S> DEV void ps_split(u8* pb, const u8* sb, u64 s0, u64 n, u
     for (u64 j = tid; j < nHead + nTail; j += PL_THREADS) ps_elem_split<E, S>(pb, sb, n, j < nHead ? h.e0 + j : h.et + (j - nHead));
 }
 // The runs of tile t of the merge of the tensor at db (n bytes, plane p at planes + P[p]) at stride S: the body of
-// k_planes_merge_pred_stride and of the strided PRED arms of k_planes_merge_each_stride.  All 64 lanes of a wave take every scan
-template <int E, int S> DEV void ps_merge(u8* db, const u8* planes, const u64* P, u64 n, u64 t)
+// k_planes_merge_pred_stride and of the strided PRED arms of k_planes_merge_each_stride.  All 64 lanes of a wave take every scan.  WIN (the
+// window form, as in pe_merge): db, n and t are those of the virtual tensor, whose planes start L bytes in front of P[p] and whose first L
+// elements are summed into their chains but not stored (n is a multiple of E there).  The virtual tensor starts on a run, so r0 and rEnd,
+// which depend on the lane only, are the tensor's own
+template <int E, int S, bool WIN = false> DEV void ps_merge(u8* db, const u8* planes, const u64* P, u64 n, u64 t, u64 L = 0)
 {
     typedef ps_t<E> T;
     constexpr u32 RUNS = (u32)(PLANES_TILE / E / PP_RUN);         // whole runs of a tile
@@ -417,6 +420,10 @@ template <int E, int S> DEV void ps_merge(u8* db, const u8* planes, const u64* P
     const u8* pp[E];
 #pragma unroll
     for (int p = 0; p < E; ++p) pp[p] = planes + P[p];
+    if constexpr (WIN) {
+#pragma unroll
+        for (int p = 0; p < E; ++p) pp[p] -= L;
+    }
     for (u32 r = threadIdx.x / WAVE; r < RUNS; r += PL_THREADS / WAVE) {
         const u64 e0 = t * (PLANES_TILE / E) + r * PP_RUN, e = e0 + 16 * lane;
         if (e0 * E >= n) break;                                   // (uniform over the wave: the run lies behind the tensor)
@@ -451,8 +458,18 @@ template <int E, int S> DEV void ps_merge(u8* db, const u8* planes, const u64* P
 #pragma unroll
             for (int q = 0; q < 16; ++q) x[q] += c[q % S];
             ps_pack<E>(wv, x);
+            bool whole = true;
+            if constexpr (WIN) whole = e >= L;
+            if (whole) {
 #pragma unroll
-            for (int k = 0; k < E; ++k) __builtin_memcpy(db + e * E + 16 * k, &wv[4 * k], 16);
+                for (int k = 0; k < E; ++k) __builtin_memcpy(db + e * E + 16 * k, &wv[4 * k], 16);
+            } else {
+                if constexpr (WIN) {                              // the chunk that straddles the lead: its elements from L on, one by one
+#pragma unroll
+                    for (int j = 0; j < 16; ++j)
+                        if (e + j >= L) __builtin_memcpy(db + (e + j) * E, (const u8*)wv + j * E, E);
+                }
+            }
         } else if (e * E < n) {                                   // the tensor's last chunk: fewer than 16 whole elements, then n mod E bytes
             u64 acc[S];
 #pragma unroll
@@ -465,11 +482,14 @@ template <int E, int S> DEV void ps_merge(u8* db, const u8* planes, const u64* P
 #pragma unroll
                     for (int p = 0; p < E; ++p) z |= (u64)pp[p][j] << (8 * p);
                     acc[q % S] = pl_unzz<E>(z, acc[q % S]);
+                    if (!WIN || j >= L) {                         // (the lead: summed, not stored)
 #pragma unroll
-                    for (int p = 0; p < E; ++p) db[j * E + p] = (u8)(acc[q % S] >> (8 * p));
+                        for (int p = 0; p < E; ++p) db[j * E + p] = (u8)(acc[q % S] >> (8 * p));
+                    }
                 }
             }
-            for (u64 k = m * E; k < n; ++k) db[k] = planes[P[k - m * E] + m];
+            if constexpr (!WIN)
+                for (u64 k = m * E; k < n; ++k) db[k] = planes[P[k - m * E] + m];
         }
     }
 }
@@ -492,6 +512,19 @@ HDEV bool bad_stride(unsigned stride) { return stride == 0 || stride > FSEHIP_PR
 
 // ---- a transform per tensor (planes_each.hip, planes_each_stride.hip; fsehip.h, "a transform per tensor") ----
 DEV bool pe_ok(u32 tr, const void* base) { return tr <= FSEHIP_EST_SUB && (tr < FSEHIP_EST_XOR || base); }
+// the stride of tensor i under transform tr (1 for every transform that has none: its stride byte is not read), and whether the pair is accepted
+DEV u32 pes_stride(u32 tr, const u8* ST, size_t i) { return tr == FSEHIP_EST_PRED ? ST[i] : 1u; }
+DEV bool pes_ok(u32 tr, u32 st, const void* base) { return pe_ok(tr, base) && !bad_stride(st); }
+// The window rules of tensor i, whose transform is tr and whose verdict is n bytes, and its lead L in elements (at every stride: a run is
+// PP_RUN elements counted from the tensor's start).  An empty window has none
+DEV bool pe_win_ok(const u64* W, const u64* PO, size_t i, u32 E, u32 tr, u64 n, u64& L)
+{
+    const u64 a = W[2 * i], b = W[2 * i + 1];
+    L = tr == FSEHIP_EST_PRED && n ? a & (PP_RUN - 1) : 0;
+    if (a > b || n % E || b - a != n / E) return false;
+    for (u32 p = 0; p < E; ++p) if (L > PO[i * E + p]) return false;
+    return true;
+}
 // a workgroup's share of the tensor at sb (n bytes at flat position s0, base bb, planes at pb) under transform TR
 template <int E, int TR> DEV void pe_split(u8* pb, const u8* sb, const u8* bb, u64 s0, u64 n, u64 lo, u32 tid)
 {

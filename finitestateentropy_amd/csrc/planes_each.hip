@@ -51,20 +51,11 @@
 #include "planes_dev.h"
 
 namespace {
-// (pe_ok and the arms pe_split and pe_merge are in planes_dev.h: planes_each_stride.hip takes the same ones)
+// (pe_ok, pe_win_ok and the arms pe_split and pe_merge are in planes_dev.h: planes_each_stride.hip and planes_each_stride_win.hip take the same ones)
 __global__ void k_each_refuse(size_t* res, const u8* T, const u8* base, size_t nT)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < nT && !pe_ok(T[i], base)) res[i] = FERR(GENERIC);
-}
-// The window rules of tensor i, whose transform is tr and whose verdict is n bytes, and its lead L in elements.  An empty window has none
-DEV bool pe_win_ok(const u64* W, const u64* PO, size_t i, u32 E, u32 tr, u64 n, u64& L)
-{
-    const u64 a = W[2 * i], b = W[2 * i + 1];
-    L = tr == FSEHIP_EST_PRED && n ? a & (PP_RUN - 1) : 0;
-    if (a > b || n % E || b - a != n / E) return false;
-    for (u32 p = 0; p < E; ++p) if (L > PO[i * E + p]) return false;
-    return true;
 }
 // behind k_planes_verdicts, whose verdict of tensor i stands in res[i]: an error there stays unless the transform is refused
 __global__ void k_each_refuse_window(size_t* res, const u8* T, const u8* base, const u64* W, const u64* PO, size_t nT, u32 E)

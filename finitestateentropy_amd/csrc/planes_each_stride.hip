@@ -20,10 +20,7 @@
 #include "planes_dev.h"
 
 namespace {
-// the stride of tensor i under transform tr (1 for every transform that has none), and whether the pair is accepted
-DEV u32 pes_stride(u32 tr, const u8* ST, size_t i) { return tr == FSEHIP_EST_PRED ? ST[i] : 1u; }
-DEV bool pes_ok(u32 tr, u32 st, const void* base) { return pe_ok(tr, base) && !bad_stride(st); }
-
+// (pes_stride and pes_ok are in planes_dev.h: planes_each_stride_win.hip takes the same ones)
 __global__ void k_each_stride_refuse(size_t* res, const u8* T, const u8* ST, const u8* base, size_t nT)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -12,6 +12,8 @@
 //   FSEHIP_tensor_patch_window_dbatch : the window split -> the segments kernel over the stage -> the packed (mixed) writer -> the splice
 //   FSEHIP_planes_split_window_each_dbatch, FSEHIP_tensor_patch_window_each_dbatch ("patching tensors with a transform per tensor"): the same
 //                                       two with the window split of planes_each.hip, which reads a transform per tensor; every later step as it is
+//   FSEHIP_planes_split_window_each_stride_dbatch, FSEHIP_tensor_patch_window_each_stride_dbatch ("windows and patches of tensors with a stride
+//                                       per tensor"): those two with d_strides, the window split of planes_each_stride_win.hip
 #include "planes_dev.h"
 
 namespace {
@@ -320,7 +322,8 @@ extern "C" int FSEHIP_tensor_patch_window_dbatch(void* d_out, uint64_t outCapaci
                                                 policy, tolerancePermille, slotAlignLog, d_stage, d_stagePlaneOffsets, d_stageSegOffsets, d_stageResults, d_newFrames,
                                                 newCapacity, d_newOffsets, d_newResults, d_scratch, scratchBytes, d_workspace, workspaceBytes, stream);
 }
-// the one composite: the window split by one op (d_transforms null) or by a transform per tensor, then the steps that both share
+// the one composite: the window split by one op (d_transforms null) or by a transform per tensor (d_strides: and a stride per PRED tensor;
+// null: stride 1 everywhere), then the steps that all share
 static int patch_window(void* d_out, uint64_t outCapacity, uint64_t* d_outOffsets, size_t* d_outResults, uint8_t* d_outCodecs, size_t* d_tensorResults, const void* d_frames,
                         uint64_t framesCapacity, const uint64_t* d_frameOffsets, const size_t* d_frameResults, const uint8_t* d_codecs, const void* d_src, const void* d_base,
                         unsigned deltaOp, const uint8_t* d_transforms, const uint64_t* d_srcOffsets, uint64_t capacity, const uint64_t* d_windows, size_t nTensors,
@@ -328,7 +331,7 @@ static int patch_window(void* d_out, uint64_t outCapacity, uint64_t* d_outOffset
                         const uint64_t* d_stageOffsets, uint64_t stageCapacity, size_t maxTotalBlocks, unsigned blockSizeId, int codec, uint8_t* d_newCodecs, int policy,
                         unsigned tolerancePermille, unsigned slotAlignLog, void* d_stage, uint64_t* d_stagePlaneOffsets, uint64_t* d_stageSegOffsets, size_t* d_stageResults,
                         void* d_newFrames, uint64_t newCapacity, uint64_t* d_newOffsets, size_t* d_newResults, void* d_scratch, size_t scratchBytes, void* d_workspace,
-                        size_t workspaceBytes, void* stream)
+                        size_t workspaceBytes, void* stream, const uint8_t* d_strides = nullptr)
 {
     if (bad_op(deltaOp)) return (int)hipErrorInvalidValue;
     if (bad_splice(d_out, outCapacity, d_outOffsets, d_outResults, d_outCodecs, d_tensorResults, d_frames, d_frameOffsets, d_frameResults, d_codecs, d_newCodecs,
@@ -340,9 +343,9 @@ static int patch_window(void* d_out, uint64_t outCapacity, uint64_t* d_outOffset
     const PlWriter wr = { maxTotalBlocks, blockSizeId, codec, d_newCodecs, policy, tolerancePermille, slotAlignLog, d_workspace, workspaceBytes };
     if (bad_seg(segLog, blockSizeId) || bad_grid(stageCapacity, nTensors) || bad_writer(wr, nSelected)) return (int)hipErrorInvalidValue;
     const hipStream_t s = (hipStream_t)stream;
-    hipError_t e = d_transforms ? launch_planes_split_window_each((u8*)d_stage, (u64*)d_stagePlaneOffsets, d_stageResults, (const u8*)d_src, (const u8*)d_base, d_transforms,
-                                                                  (const u64*)d_srcOffsets, (const u64*)d_windows, (const u64*)d_stageOffsets, nTensors, elemBytes, segLog,
-                                                                  capacity, stageCapacity, s)
+    hipError_t e = d_transforms ? launch_planes_split_window_each_stride((u8*)d_stage, (u64*)d_stagePlaneOffsets, d_stageResults, (const u8*)d_src, (const u8*)d_base,
+                                                                         d_transforms, d_strides, (const u64*)d_srcOffsets, (const u64*)d_windows,
+                                                                         (const u64*)d_stageOffsets, nTensors, elemBytes, segLog, capacity, stageCapacity, s)
                                 : launch_split_window((u8*)d_stage, (u64*)d_stagePlaneOffsets, d_stageResults, (const u8*)d_src, (const u8*)d_base, deltaOp,
                                                       (const u64*)d_srcOffsets, (const u64*)d_windows, (const u64*)d_stageOffsets, nTensors, elemBytes, segLog, capacity,
                                                       stageCapacity, s);
@@ -413,4 +416,39 @@ extern "C" int FSEHIP_tensor_patch_window_each_dbatch(void* d_out, uint64_t outC
                         d_src, d_base, FSEHIP_DELTA_XOR, d_transforms, d_srcOffsets, capacity, d_windows, nTensors, elemBytes, d_segFirst, nSegments, segLog, d_selFirst,
                         nSelected, d_stageOffsets, stageCapacity, maxTotalBlocks, blockSizeId, codec, d_newCodecs, policy, tolerancePermille, slotAlignLog, d_stage,
                         d_stagePlaneOffsets, d_stageSegOffsets, d_stageResults, d_newFrames, newCapacity, d_newOffsets, d_newResults, d_scratch, scratchBytes, d_workspace, workspaceBytes, stream);
+}
+
+// ---- patching tensors with a stride per tensor (fsehip.h, "windows and patches of tensors with a stride per tensor"): the two calls above
+// with d_strides behind d_transforms, null: stride 1 everywhere ----
+extern "C" int FSEHIP_planes_split_window_each_stride_dbatch(void* d_stage, uint64_t* d_stagePlaneOffsets, size_t* d_stageResults, const void* d_src, const void* d_base,
+                                                             const uint8_t* d_transforms, const uint8_t* d_strides, const uint64_t* d_srcOffsets, const uint64_t* d_windows,
+                                                             const uint64_t* d_stageOffsets, size_t nTensors, unsigned elemBytes, unsigned segLog, uint64_t capacity,
+                                                             uint64_t stageCapacity, void* stream)
+{
+    if (!d_transforms || bad_elem(elemBytes) || bad_seg(segLog, 0) || !d_stagePlaneOffsets || !d_stageResults || !d_srcOffsets || !d_windows || !d_stageOffsets ||
+        (stageCapacity && (!d_stage || !d_src)))
+        return (int)hipErrorInvalidValue;
+    if (bad_tensors(nTensors, elemBytes) || bad_grid(stageCapacity, nTensors)) return (int)hipErrorInvalidValue;
+    return (int)launch_planes_split_window_each_stride((u8*)d_stage, (u64*)d_stagePlaneOffsets, d_stageResults, (const u8*)d_src, (const u8*)d_base, d_transforms, d_strides,
+                                                       (const u64*)d_srcOffsets, (const u64*)d_windows, (const u64*)d_stageOffsets, nTensors, elemBytes, segLog, capacity,
+                                                       stageCapacity, (hipStream_t)stream);
+}
+extern "C" int FSEHIP_tensor_patch_window_each_stride_dbatch(void* d_out, uint64_t outCapacity, uint64_t* d_outOffsets, size_t* d_outResults, uint8_t* d_outCodecs,
+                                                             size_t* d_tensorResults, const void* d_frames, uint64_t framesCapacity, const uint64_t* d_frameOffsets,
+                                                             const size_t* d_frameResults, const uint8_t* d_codecs, const void* d_src, const void* d_base,
+                                                             const uint8_t* d_transforms, const uint8_t* d_strides, const uint64_t* d_srcOffsets, uint64_t capacity,
+                                                             const uint64_t* d_windows, size_t nTensors, unsigned elemBytes, const uint64_t* d_segFirst, size_t nSegments,
+                                                             unsigned segLog, const uint64_t* d_selFirst, size_t nSelected, const uint64_t* d_stageOffsets,
+                                                             uint64_t stageCapacity, size_t maxTotalBlocks, unsigned blockSizeId, int codec, uint8_t* d_newCodecs, int policy,
+                                                             unsigned tolerancePermille, unsigned slotAlignLog, void* d_stage, uint64_t* d_stagePlaneOffsets,
+                                                             uint64_t* d_stageSegOffsets, size_t* d_stageResults, void* d_newFrames, uint64_t newCapacity,
+                                                             uint64_t* d_newOffsets, size_t* d_newResults, void* d_scratch, size_t scratchBytes, void* d_workspace,
+                                                             size_t workspaceBytes, void* stream)
+{
+    if (!d_transforms) return (int)hipErrorInvalidValue;
+    return patch_window(d_out, outCapacity, d_outOffsets, d_outResults, d_outCodecs, d_tensorResults, d_frames, framesCapacity, d_frameOffsets, d_frameResults, d_codecs,
+                        d_src, d_base, FSEHIP_DELTA_XOR, d_transforms, d_srcOffsets, capacity, d_windows, nTensors, elemBytes, d_segFirst, nSegments, segLog, d_selFirst,
+                        nSelected, d_stageOffsets, stageCapacity, maxTotalBlocks, blockSizeId, codec, d_newCodecs, policy, tolerancePermille, slotAlignLog, d_stage,
+                        d_stagePlaneOffsets, d_stageSegOffsets, d_stageResults, d_newFrames, newCapacity, d_newOffsets, d_newResults, d_scratch, scratchBytes, d_workspace,
+                        workspaceBytes, stream, d_strides);
 }

@@ -1654,8 +1654,8 @@ FSEHIP_API int FSEHIP_planes_estimate_stride_dbatch(uint64_t* d_planeBits, uint6
  *     is uniform over the workgroup; the bodies are those of the dedicated kernels.  No LDS, no workspace of their own.
  *   All six: launches only (capturable); nTensors == 0 is legal; the argument errors of the _each_ calls, and with CHOOSE those of
  *     FSEHIP_planes_estimate_stride_dbatch: hipErrorInvalidValue before any device call, nothing written.
- *   Out of scope: windows and patches of objects with a stride above 1 (the window forms of "a transform per tensor" take stride 1); strides
- *     above 8; prediction combined with a base or with sparse planes; a record of the strides in frames or in the archive head. */
+ *   Windows and patches of objects with a stride above 1: "windows and patches of tensors with a stride per tensor", below (the window forms
+ *     of "a transform per tensor" take stride 1).  Out of scope: strides above 8; prediction combined with a base or with sparse planes; a record of the strides in frames or in the archive head. */
 FSEHIP_API size_t FSEHIP_tensor_each_stride_workspaceHead(size_t nTensors, unsigned elemBytes, int transformPolicy, unsigned candidateMask, unsigned strideMask);
 FSEHIP_API int FSEHIP_planes_split_each_stride_dbatch(void* d_planes, uint64_t* d_planeOffsets, size_t* d_tensorResults, const void* d_src, const void* d_base,
                                                       const uint8_t* d_transforms, const uint8_t* d_strides, const uint64_t* d_srcOffsets, size_t nTensors,
@@ -1688,6 +1688,63 @@ FSEHIP_API int FSEHIP_tensor_decompress_seg_each_stride_dbatch(void* d_dst, cons
                                                                size_t nSegments, unsigned segLog, size_t maxTotalBlocks, void* d_planes, uint64_t planesCapacity,
                                                                uint64_t* d_segOffsets, size_t* d_segResults, uint64_t* d_planeOffsets, size_t* d_planeSizes,
                                                                void* d_workspace, size_t workspaceBytes, void* stream);
+
+/* Windows and patches of tensors with a stride per tensor (planes_each_stride_win.hip, capi_each.hip, planes_patch.hip): THE FOUR WINDOW CALLS
+ * OF "windows of tensors with a transform per tensor" AND "patching tensors with a transform per tensor" WITH THE STRIDE BYTE OF "a stride per
+ * tensor".  An object written by FSEHIP_tensor_compress_seg_each_stride_dbatch, or by FSEHIP_tensor_compress_seg_pred_stride_dbatch with all
+ * transform bytes FSEHIP_EST_PRED and all stride bytes its stride, is read and rewritten by element windows.  Each call has the argument
+ * list of its _window_each_ sibling with const uint8_t* d_strides directly behind d_transforms.  No frame byte, selection, reader, fold,
+ * segments kernel, writer or splice changes.
+ *
+ *   The arithmetic.  A run is 1 << FSEHIP_PRED_RUN_LOG = 1024 elements counted from the TENSOR's start at every stride; element j lies in
+ *     chain (j % 1024) % S and is predicted by element j - S, the first S elements of a run by 0.  A segment starts on a multiple of 1024
+ *     elements (1 << segLog >= 1024 plane bytes).
+ *   Window.  [a, b) with a % 1024 != 0 needs the lead L = a % 1024, exactly as at stride 1 and whatever S is: the virtual tensor that starts
+ *     L elements in front of the slot starts on a run, so its runs and its chains are the tensor's own.  All S chains are summed through
+ *     the lead -- also where L < S or L % S != 0, when the chains have different lengths inside it -- and nothing of the lead is stored.
+ *     THE CALLER'S CONTRACT is that of "windows of tensors with a transform per tensor": the a % 1024 bytes in front of every plane offset of
+ *     a PRED tensor with a < b are the decoded plane bytes in front of the window, which the window fold guarantees.
+ *   Patch.  A staged sub-tensor starts on a run, hence on a run FOR EVERY CHAIN: the planes of the strided transform of the sub-tensor are
+ *     segments k0 .. k1 of the planes of the strided transform of the tensor, byte for byte.  No lead.  The identity carries over: the patch
+ *     of FSEHIP_tensor_compress_seg_each_stride_dbatch(old, T, ST) with `new` IS that call on new with T and ST given.  The patch never
+ *     chooses: transforms and strides are GIVEN.
+ *
+ *   d_strides[i] is read only where d_transforms[i] == FSEHIP_EST_PRED.  A value of 0 or above FSEHIP_PRED_MAX_STRIDE there refuses that
+ *     tensor alone -- GENERIC, one more cause beside a bad transform byte in the refusals of the sibling (the merge's GENERIC; rule 1 of
+ *     the stage) -- with nothing of it read or written: in place its old bytes stay, in the patch it keeps all its old frames.  Under every
+ *     other transform the byte is ignored, whatever it holds.
+ *   d_strides == NULL: stride 1 everywhere; the call then IS its _window_each_ sibling, byte for byte.
+ *   FSEHIP_planes_merge_window_each_stride_dbatch, FSEHIP_tensor_decompress_window_each_stride_dbatch, FSEHIP_planes_split_window_each_stride_dbatch,
+ *     FSEHIP_tensor_patch_window_each_stride_dbatch: results, rules, workspaces, scratch and argument errors are those of the sibling; every
+ *     argument check of every step stands in front of the first launch; launches only, capturable; nTensors == 0 is legal.  The merge has
+ *     the sibling's work mapping, 2 * nTensors workgroups beyond the tiles of dstCapacity; no LDS, no workspace of the kernels' own.
+ *   Out of scope: windows and patches of sparse objects; digest checks on windows; choosing a stride inside a patch. */
+FSEHIP_API int FSEHIP_planes_merge_window_each_stride_dbatch(void* d_dst, const uint64_t* d_dstOffsets, size_t* d_results, const void* d_planes,
+                                                             const uint64_t* d_planeOffsets, const size_t* d_planeSizes, const void* d_base, const uint8_t* d_transforms,
+                                                             const uint8_t* d_strides, const uint64_t* d_windows, size_t nTensors, unsigned elemBytes, uint64_t dstCapacity,
+                                                             void* stream);
+FSEHIP_API int FSEHIP_tensor_decompress_window_each_stride_dbatch(void* d_dst, const uint64_t* d_dstOffsets, uint64_t dstCapacity, const void* d_base,
+                                                                  const uint8_t* d_transforms, const uint8_t* d_strides, size_t* d_results, const void* d_frames,
+                                                                  const uint64_t* d_frameOffsets, const uint64_t* d_srcOffsets, const uint64_t* d_windows, size_t nTensors,
+                                                                  unsigned elemBytes, const uint64_t* d_segFirst, size_t nSegments, unsigned segLog,
+                                                                  const uint64_t* d_selFirst, size_t nSelected, size_t maxTotalBlocks, void* d_planes, uint64_t planesCapacity,
+                                                                  uint64_t* d_selFrameOffsets, uint64_t* d_selOffsets, size_t* d_selResults, uint64_t* d_planeOffsets,
+                                                                  size_t* d_planeSizes, void* d_workspace, size_t workspaceBytes, void* stream);
+FSEHIP_API int FSEHIP_planes_split_window_each_stride_dbatch(void* d_stage, uint64_t* d_stagePlaneOffsets, size_t* d_stageResults, const void* d_src, const void* d_base,
+                                                             const uint8_t* d_transforms, const uint8_t* d_strides, const uint64_t* d_srcOffsets, const uint64_t* d_windows,
+                                                             const uint64_t* d_stageOffsets, size_t nTensors, unsigned elemBytes, unsigned segLog, uint64_t capacity,
+                                                             uint64_t stageCapacity, void* stream);
+FSEHIP_API int FSEHIP_tensor_patch_window_each_stride_dbatch(void* d_out, uint64_t outCapacity, uint64_t* d_outOffsets, size_t* d_outResults, uint8_t* d_outCodecs,
+                                                             size_t* d_tensorResults, const void* d_frames, uint64_t framesCapacity, const uint64_t* d_frameOffsets,
+                                                             const size_t* d_frameResults, const uint8_t* d_codecs, const void* d_src, const void* d_base,
+                                                             const uint8_t* d_transforms, const uint8_t* d_strides, const uint64_t* d_srcOffsets, uint64_t capacity,
+                                                             const uint64_t* d_windows, size_t nTensors, unsigned elemBytes, const uint64_t* d_segFirst, size_t nSegments,
+                                                             unsigned segLog, const uint64_t* d_selFirst, size_t nSelected, const uint64_t* d_stageOffsets,
+                                                             uint64_t stageCapacity, size_t maxTotalBlocks, unsigned blockSizeId, int codec, uint8_t* d_newCodecs, int policy,
+                                                             unsigned tolerancePermille, unsigned slotAlignLog, void* d_stage, uint64_t* d_stagePlaneOffsets,
+                                                             uint64_t* d_stageSegOffsets, size_t* d_stageResults, void* d_newFrames, uint64_t newCapacity,
+                                                             uint64_t* d_newOffsets, size_t* d_newResults, void* d_scratch, size_t scratchBytes, void* d_workspace,
+                                                             size_t workspaceBytes, void* stream);
 
 /* ---- FSE for 16-bit symbols (lib/fseU16.h:62-80, lib/fseU16.c) -- SURVEY 8(f) rank 4.  Alphabets of up to
  * FSEHIP_FSEU16_MAX_SYMBOL_VALUE + 1 symbols, table logs up to 13 (default 12), ONE tANS state per stream: a different format from
